@@ -9,6 +9,15 @@ step summed over all ranks / max-over-ranks wall time.
 
   python bench.py [--config deit_base|dit_xl2|pixart_cross] [--steps K] [--warmup W]
   python bench.py --gpus N [--scaling weak|strong] ...
+  python bench.py ... --dump-outputs DIR     the last timed step's out / idx (a sample) as .npy
+  python bench.py ... --full [--lines ...]   everything below "Besides the contract fields"
+
+A plain run does what the headline figure needs and no more: it makes the inputs, warms
+up, times the K steps and prints the result line (metric, value, unit, ms_per_step, ...).
+The stage breakdown (a pass of its own through the *_timed twin), the roofline, the CPU
+baseline, the parity check and the secondary lines run only with --full; the options that
+shape them (--lines, --no-cpu-baseline, --no-parity, --no-secondary, --cpu-images,
+--parity-images, --traffic-json, --pmc-json) belong to --full.
 
 Multi-GPU: images are independent, so the batch is sharded over one
 process per GPU (RCCL over xGMI; `--gpus N` without WORLD_SIZE starts the N ranks
@@ -18,7 +27,7 @@ split over the ranks.  The only data-path collective is the rank-0 all_gather of
 sample of every rank's indices / outputs for the parity check after timing; the
 timed region is bracketed by barriers and its time is the MAX over ranks.
 
-Besides the contract fields the JSON line carries
+Besides the contract fields the JSON line of a --full run carries
   roofline      the dominant kernel's algorithmic bytes / its mean duration (HIP events
                 on the launch stream inside the timed region), plus
                 qa_pass: SURVEY §8d Bytes_qa over the quantize + approx + top-k kernels,
@@ -332,9 +341,11 @@ def profile_of(prof, stage, ms, ach_gbs):
     return traffic, lim
 
 
-def run_config(c, images, steps, warmup, device, world, prof=None):
+def run_config(c, images, steps, warmup, device, world, prof=None, breakdown=True):
     """Time `steps` calls of the op on this rank's images; returns the elapsed time
-    (max over ranks), the stage times, the roofline block and the outputs."""
+    (max over ranks), the stage times, the roofline block and the outputs of the last
+    timed step.  breakdown=False (a plain run) stops after the timed steps: the stage
+    times, the roofline and the e2e block, which take a pass of their own, are None."""
     import torch
     import mx_quantization_amd as M
     from mx_quantization_amd import _native as N
@@ -346,8 +357,8 @@ def run_config(c, images, steps, warmup, device, world, prof=None):
                                        flush_subnormals=c["bias"], out=out)
     torch.cuda.synchronize()
 
-    # the same call through the C entry point: K steps timed (the value), then its timed twin
-    # (HIP events between the kernels) for the stage breakdown
+    # the same call through the C entry point: K steps timed (the value), then, for the stage
+    # breakdown, its timed twin (HIP events between the kernels)
     B = len(images)
     p = N.AttnParams()
     p.q, p.k, p.v = q.data_ptr(), k.data_ptr(), v.data_ptr()
@@ -368,10 +379,15 @@ def run_config(c, images, steps, warmup, device, world, prof=None):
     p.workspace, p.workspace_bytes = ws.data_ptr(), ws.numel()
     stage_ms = (ctypes.c_float * 5)()
     stream = torch.cuda.current_stream(device).cuda_stream
-    elapsed = timed_product(
-        lambda: N.check(N.lib().mxa_attention(ctypes.byref(p), stream), "mxa_attention"),
-        lambda: N.check(N.lib().mxa_attention_timed(ctypes.byref(p), stream, steps, stage_ms), "mxa_attention_timed"),
-        steps, world, device)
+    call = lambda: N.check(N.lib().mxa_attention(ctypes.byref(p), stream), "mxa_attention")
+    elapsed = timed_region(lambda: [call() for _ in range(steps)], world, torch.cuda.synchronize, device)
+    if not breakdown:  # a plain run: the timed steps and what they left in out / idx
+        return elapsed, None, None, None, out, idx
+    # the stage breakdown, outside the timed region as in timed_product; the twin writes p.out and
+    # p.idx_out again, so what the timed steps left there is copied first
+    out, idx = out.clone(), idx.clone()
+    N.check(N.lib().mxa_attention_timed(ctypes.byref(p), stream, steps, stage_ms), "mxa_attention_timed")
+    torch.cuda.synchronize()
     path = N.PATH_NAMES.get(N.lib().mxa_attention_path(ctypes.byref(p)), "?")
     fin = fin_engines(p)
     stages = {name: float(stage_ms[slot]) for name, slot in zip(STAGES, STAGE_SLOTS)}
@@ -669,6 +685,27 @@ def run_secondary(args, c, rank, world, images, lines, run, device, res=None):
     return res
 
 
+DUMP_BYTES = 48 << 20  # --dump-outputs: all files of all ranks together stay under this
+
+
+def dump_outputs(dirname, out, idx, images, rank, world):
+    """--dump-outputs: what the last timed step left in out (B,H,N,D) and idx (B,H,N,k), as
+    float32 .npy files (key indices are far below 2^24, so float32 holds them exactly).  The
+    whole batch when it fits the rank's share of DUMP_BYTES, else a fixed, seeded sample of
+    its images; images.npy names the global image (the seed of its inputs) of each entry.
+    Every rank writes its own files (suffix _rank<r> when there are several)."""
+    import torch
+    per_image = (out[0].numel() + idx[0].numel()) * 4 + 8
+    n = max(1, min(len(images), DUMP_BYTES // world // per_image))
+    sel = np.sort(np.random.default_rng(2024).choice(len(images), n, replace=False))
+    pick = torch.from_numpy(sel).to(out.device)
+    os.makedirs(dirname, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    np.save(os.path.join(dirname, f"out{sfx}.npy"), out[pick].to(torch.float32).cpu().numpy())
+    np.save(os.path.join(dirname, f"idx{sfx}.npy"), idx[pick].to(torch.float32).cpu().numpy())
+    np.save(os.path.join(dirname, f"images{sfx}.npy"), np.asarray(images, dtype=np.float64)[sel])
+
+
 def launch_ranks(args):
     """--gpus N without WORLD_SIZE: start the N ranks (one process per GPU) through
     torch.distributed.run from this process, which has not touched the GPU, and exit
@@ -702,11 +739,21 @@ def main(argv=None, run=run_config):
     ap.add_argument("--pmc-json", default=None,
                     help="PMC instruction counters per kernel (tools/pmc_summary.py --json; default: the "
                          "committed profiles/<PROFILE_TAG>_pmc_<config>.json)")
-    ap.add_argument("--lines", default="main,qkv,qkvproj,dense,dropin,dit",
-                    help="which lines to run: main (the config), qkv (its fused qkv-Linear line), qkvproj (x -> "
-                         "qkv Linear -> attention -> proj Linear), dense (the top_k=False branch at the config's "
-                         "shape), dropin (the drop-in modules' path), dit (the DiT-XL/2 secondary of deit_base)")
+    ap.add_argument("--lines", default=None,
+                    help="which lines to run (default: main,qkv,qkvproj,dense,dropin,dit): main (the config), qkv (its "
+                         "fused qkv-Linear line), qkvproj (x -> qkv Linear -> attention -> proj Linear), dense (the "
+                         "top_k=False branch at the config's shape), dropin (the drop-in modules' path), dit (the "
+                         "DiT-XL/2 secondary of deit_base)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: the stage breakdown and roofline, the CPU baseline, the "
+                         "parity check and the secondary lines (--lines)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's out / idx (a seeded sample of the images when the batch is "
+                         "large) to DIR/<name>.npy")
     args = ap.parse_args(argv)
+    if not args.full and (args.lines or args.traffic_json or args.pmc_json):
+        raise SystemExit("bench.py: --lines, --traffic-json and --pmc-json need --full")
+    args.lines = args.lines or "main,qkv,qkvproj,dense,dropin,dit"
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus and args.gpus > 1:
@@ -719,7 +766,7 @@ def main(argv=None, run=run_config):
     c = CONFIGS[args.config] if args.k is None else dict(CONFIGS[args.config], k=args.k)
 
     cpu = None  # before any HIP call: the pool forks
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(c, c["B"] if args.cpu_images < 0 else args.cpu_images)
 
     import torch
@@ -740,8 +787,15 @@ def main(argv=None, run=run_config):
     prof = {"traffic": args.traffic_json or os.path.join(ROOT, "profiles", f"{PROFILE_TAG}_traffic_{args.config}.json"),
             "pmc": args.pmc_json or os.path.join(ROOT, "profiles", f"{PROFILE_TAG}_pmc_{args.config}.json")}
     if "main" not in lines:  # profiling the secondary lines alone
+        if args.dump_outputs:
+            raise SystemExit("bench.py: --dump-outputs writes the main line's outputs (--lines without main)")
         return run_secondary(args, c, rank, world, images, lines, run, device)
-    elapsed, stages, roof, e2e, out, idx = run(c, images, args.steps, args.warmup, device, world, prof)
+    if args.full:
+        elapsed, stages, roof, e2e, out, idx = run(c, images, args.steps, args.warmup, device, world, prof)
+    else:  # the timed steps alone: no pass through the timed twin, no roofline
+        elapsed, _, _, _, out, idx = run(c, images, args.steps, args.warmup, device, world, breakdown=False)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, idx, images, rank, world)
     tokens = (world * c["B"] if args.scaling == "weak" else c["B"]) * c["N"] * args.steps
     res = {
         "metric": METRIC,
@@ -759,17 +813,15 @@ def main(argv=None, run=run_config):
         "config": {"workload": c["workload"], "global_batch": world * c["B"] if args.scaling == "weak" else c["B"],
                    "batch_per_gpu": len(images), "heads": c["H"], "seq": c["N"], "keys": c["T"],
                    "head_dim": c["D"], "k": c["k"], "pred_mode": c["mode"], "parallelism": f"dp{world}"},
-        "roofline": roof,
-        "stages_ms": stages,
-        "e2e": e2e,
-        "cpu_baseline": cpu,
-        # what torch.distributed saw (a SCALE record shows RCCL ran N ranks)
-        "dist": {"initialized": dist.is_initialized(),
-                 "world_size": dist.get_world_size() if dist.is_initialized() else 1,
-                 "backend": dist.get_backend() if dist.is_initialized() else None},
     }
+    if args.full:
+        res.update(roofline=roof, stages_ms=stages, e2e=e2e, cpu_baseline=cpu)
+    # what torch.distributed saw (a SCALE record shows RCCL ran N ranks)
+    res["dist"] = {"initialized": dist.is_initialized(),
+                   "world_size": dist.get_world_size() if dist.is_initialized() else 1,
+                   "backend": dist.get_backend() if dist.is_initialized() else None}
 
-    if not args.no_parity:  # a sample of every rank's shard, gathered to rank 0
+    if args.full and not args.no_parity:  # a sample of every rank's shard, gathered to rank 0
         # the same sample size on every rank (all_gather needs equal shapes)
         npar = min([args.parity_images] + [len(shard(c, r, world, args.scaling)) for r in range(world)])
         sel = sorted({0, len(images) - 1})[:npar] if npar > 1 else [0]
@@ -790,7 +842,8 @@ def main(argv=None, run=run_config):
                                          torch.cat(gm).cpu().tolist())
             res["parity"]["ranks_checked"] = world
 
-    run_secondary(args, c, rank, world, images, lines, run, device, res)
+    if args.full:
+        run_secondary(args, c, rank, world, images, lines, run, device, res)
 
     if rank == 0:
         print(json.dumps(res), flush=True)

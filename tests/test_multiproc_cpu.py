@@ -65,7 +65,7 @@ def _run_world(argv, world=2):
 
 @pytest.mark.parametrize("scaling", ["weak", "strong"])
 def test_bench_main_two_ranks_gathers_and_checks_every_shard(scaling):
-    res = _run_world(["--gpus", "2", "--steps", "3", "--warmup", "1", "--no-secondary", "--scaling", scaling,
+    res = _run_world(["--full", "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-secondary", "--scaling", scaling,
                       "--parity-images", "2"])
     assert res["n_gpus"] == 2 and res["scaling"] == scaling
     assert res["config"]["parallelism"] == "dp2"
@@ -229,7 +229,7 @@ def test_bench_dit_strong_scaling_two_ranks_shard_boundaries():
     port = _free_port()
     mgr = mp.Manager()
     out = mgr.dict()
-    argv = ["--config", "dit_xl2", "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-secondary",
+    argv = ["--full", "--config", "dit_xl2", "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-secondary",
             "--scaling", "strong", "--parity-images", "1", "--no-cpu-baseline"]
     mp.spawn(_dit_worker, args=(2, port, argv, out), nprocs=2, join=True)
     assert out["images0"] == list(range(32)) and out["images1"] == list(range(32, 64))

@@ -9,7 +9,7 @@ pmc() {  # pmc <dir> <counters...>
   local d=$1; shift
   rm -rf $O/$d
   timeout -k 10 -s KILL 120 rocprofv3 --pmc "$@" -d $O/$d -o p --output-format csv -- \
-    python bench.py --config $cfg --steps 3 --warmup 1 --no-cpu-baseline --no-parity --lines $L > $O/$d.log 2>&1
+    python bench.py --full --config $cfg --steps 3 --warmup 1 --no-cpu-baseline --no-parity --lines $L > $O/$d.log 2>&1
 }
 pmc ${T}k1 SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY || exit $?
 pmc ${T}k2 SQ_WAIT_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_LDS_BANK_CONFLICT SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_I8 SQ_ACTIVE_INST_ANY || exit $?

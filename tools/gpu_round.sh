@@ -20,12 +20,12 @@ pmc() {  # pmc <dir> <lines> <counters...>
   local d=$1 l=$2; shift 2
   rm -rf $O/$d
   timeout -k 10 -s KILL 120 rocprofv3 --pmc "$@" -d $O/$d -o p --output-format csv -- \
-    python bench.py --config $cfg --steps 3 --warmup 1 --no-cpu-baseline --no-parity --lines $l > $O/$d.log 2>&1
+    python bench.py --full --config $cfg --steps 3 --warmup 1 --no-cpu-baseline --no-parity --lines $l > $O/$d.log 2>&1
 }
 for cfg in ${BENCH_CONFIGS:-deit_base dit_xl2 pixart_cross}; do
   rm -rf $O/prof_$cfg
   timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/prof_$cfg -o run --output-format csv -- \
-    python bench.py --config $cfg --steps 10 --warmup 2 --no-cpu-baseline --no-parity --lines main \
+    python bench.py --full --config $cfg --steps 10 --warmup 2 --no-cpu-baseline --no-parity --lines main \
     > $O/prof_bench_$cfg.json 2> $O/prof_$cfg.err || exit $?
   find $O/prof_$cfg -name "*kernel_stats.csv" -exec cp {} $O/${T}_rocprof_$cfg.csv \;
   pmc pf_$cfg main FETCH_SIZE || exit $?
@@ -37,7 +37,7 @@ for cfg in ${BENCH_CONFIGS:-deit_base dit_xl2 pixart_cross}; do
   python tools/pmc_summary.py "$O/pi[123]_$cfg/**/*counter_collection.csv" --json $O/${T}_pmc_$cfg.json > $O/${T}_pmc_$cfg.txt || exit $?
   if [ "$cfg" != pixart_cross ] && [ -z "${NOQKV:-}" ]; then
     timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/profq_$cfg -o run --output-format csv -- \
-      python bench.py --config $cfg --steps 6 --warmup 2 --no-cpu-baseline --no-parity --lines qkv \
+      python bench.py --full --config $cfg --steps 6 --warmup 2 --no-cpu-baseline --no-parity --lines qkv \
       > $O/profq_bench_$cfg.json 2> $O/profq_$cfg.err || exit $?
     find $O/profq_$cfg -name "*kernel_stats.csv" -exec cp {} $O/${T}_rocprof_qkv_$cfg.csv \;
     pmc pqf_$cfg qkv FETCH_SIZE || exit $?
@@ -47,7 +47,7 @@ for cfg in ${BENCH_CONFIGS:-deit_base dit_xl2 pixart_cross}; do
     python tools/pmc_summary.py "$O/pq1_$cfg/**/*counter_collection.csv" --json $O/${T}_pmc_qkv_$cfg.json > $O/${T}_pmc_qkv_$cfg.txt || exit $?
     # x -> qkv Linear -> attention -> proj Linear (the GEMM kernel's own passes)
     timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $O/profp_$cfg -o run --output-format csv -- \
-      python bench.py --config $cfg --steps 6 --warmup 2 --no-cpu-baseline --no-parity --lines qkvproj \
+      python bench.py --full --config $cfg --steps 6 --warmup 2 --no-cpu-baseline --no-parity --lines qkvproj \
       > $O/profp_bench_$cfg.json 2> $O/profp_$cfg.err || exit $?
     find $O/profp_$cfg -name "*kernel_stats.csv" -exec cp {} $O/${T}_rocprof_qkvproj_$cfg.csv \;
     pmc ppf_$cfg qkvproj FETCH_SIZE || exit $?
@@ -56,7 +56,7 @@ for cfg in ${BENCH_CONFIGS:-deit_base dit_xl2 pixart_cross}; do
     pmc pp1_$cfg qkvproj SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_VALU_MFMA_I8 SQ_WAVE_CYCLES SQ_WAIT_ANY || exit $?
     python tools/pmc_summary.py "$O/pp1_$cfg/**/*counter_collection.csv" --json $O/${T}_pmc_qkvproj_$cfg.json > $O/${T}_pmc_qkvproj_$cfg.txt || exit $?
   fi
-  timeout -k 10 300 python bench.py --config $cfg --traffic-json $O/${T}_traffic_$cfg.json --pmc-json $O/${T}_pmc_$cfg.json \
+  timeout -k 10 300 python bench.py --full --config $cfg --traffic-json $O/${T}_traffic_$cfg.json --pmc-json $O/${T}_pmc_$cfg.json \
     > $O/${T}_bench_$cfg.json 2> $O/${T}_bench_$cfg.err
   brc=$?; echo "bench $cfg rc=$brc"; tail -c 600 $O/${T}_bench_$cfg.json; [ $brc -eq 0 ] || exit $brc
 done
