@@ -301,10 +301,12 @@ struct TStack {
 constexpr int kTailWaves = 1;
 constexpr int kTailMaxK = 33;  // k handed to the tail (k - 1 <= 32: the final rank's width)
 // the record's positions the tail reads: [0, l) of an introselect hand-over (nothing past the
-// range is read again: the window loads beyond l are masked out of the stop masks), [0, k - 1)
-// of a sort hand-over
+// range is read again: the window loads beyond l are masked out of the stop masks), [0, k) of
+// a sort hand-over: the sort works on [0, k - 1), and position k - 1 holds the k-th element the
+// group kernel's heap_select left there, which the final loop reads with the sorted prefix (a
+// length of k - 1 dropped it whenever (k - 1) % 4 == 0: its 4-word group was never loaded)
 __device__ __forceinline__ int tail_rec_len(uint32_t state, int k) {
-  return ((state >> 24) & 3u) ? k - 1 : (int)((state >> 8) & 0xFFu);
+  return ((state >> 24) & 3u) ? k : (int)((state >> 8) & 0xFFu);
 }
 template <int TW>
 __global__ __launch_bounds__(64 * kTailWaves) void topk_tail_kernel(TailArgs a) {

@@ -387,17 +387,38 @@ def _lib():
                                         ctypes.c_void_p, ctypes.c_void_p]
         lib.oracle_antiqsort.restype = ctypes.c_int
         lib.oracle_antiqsort.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_void_p]
+        lib.oracle_antiqsort_dir.restype = ctypes.c_int
+        lib.oracle_antiqsort_dir.argtypes = [ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+        lib.oracle_introselect_probe.restype = ctypes.c_int
+        lib.oracle_introselect_probe.argtypes = [ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                                 ctypes.c_void_p]
         _LIB = lib
     return _LIB
 
 
-def antiqsort_row(n: int, k: int) -> np.ndarray:
+def antiqsort_row(n: int, k: int, high: bool = False) -> np.ndarray:
     """A row that exhausts introselect/introsort's depth limit (McIlroy adversary run
-    against libstdc++, oracle/topk_ref.cpp) -- exercises the heap fallbacks."""
+    against libstdc++, oracle/topk_ref.cpp) -- exercises the heap fallbacks.  The default
+    row is peeled from the front (the range soon collapses for small k); high=True plays
+    the adversary against "greater" itself, the row is peeled from the back and the depth
+    limit is reached for every small k (introselect_probe says where)."""
     out = np.zeros(n, dtype=F32)
-    if _lib().oracle_antiqsort(n, k, 1, out.ctypes.data) != 0:
+    if _lib().oracle_antiqsort_dir(n, k, 1, int(bool(high)), out.ctypes.data) != 0:
         raise ValueError("oracle_antiqsort failed")
     return out
+
+
+def introselect_probe(row: np.ndarray, k: int, tw: int = 48) -> dict:
+    """Where torch's nth_element(k-1) goes on `row` (libstdc++'s introselect loop, restated
+    in oracle/topk_ref.cpp): depth_limit -- d reached 0 with l - f > 3; (f, l) there;
+    hand -- (l, d) the first time l <= tw at the loop top (None: never), where the device's
+    group kernel hands the row to its one-lane tail."""
+    row = np.ascontiguousarray(row, dtype=F32)
+    res = np.zeros(6, dtype=np.int64)
+    if _lib().oracle_introselect_probe(row.ctypes.data, row.shape[0], k, tw, res.ctypes.data) != 0:
+        raise ValueError("oracle_introselect_probe failed")
+    return {"depth_limit": bool(res[0]), "f": int(res[1]), "l": int(res[2]),
+            "hand": None if res[3] < 0 else (int(res[3]), int(res[4])), "steps": int(res[5])}
 
 
 def topk(vals: np.ndarray, k: int, largest=True, sorted=True):

@@ -99,15 +99,72 @@ struct Adversary {
 };
 }  // namespace
 
-extern "C" int oracle_antiqsort(int64_t n, int64_t k, int with_sort, float* out) {
+// high = 0: the adversary plays against "less" and the row is negated for torch's
+// "greater" (the selection peels the row from the front).  high = 1: the adversary plays
+// against the reversed comparison, comp(x, y) = less(y, x), i.e. "greater" itself, and the
+// row is +val: the selection then peels from the back (f stays 0, l shrinks by about two a
+// step), so the depth limit is reached with the k-th position still inside the range for
+// every small k.  All n values come out distinct.
+extern "C" int oracle_antiqsort_dir(int64_t n, int64_t k, int with_sort, int high, float* out) {
   if (k < 1 || k > n) return -1;
   Adversary adv(n);
   std::vector<int64_t> ids(n);
   for (int64_t i = 0; i < n; ++i) ids[i] = i;
+  if (high) {
+    auto cmp = [&](int64_t x, int64_t y) { return adv.less(y, x); };
+    std::nth_element(ids.begin(), ids.begin() + k - 1, ids.end(), cmp);
+    if (with_sort) std::sort(ids.begin(), ids.begin() + k - 1, cmp);
+    for (int64_t i = 0; i < n; ++i) out[i] = static_cast<float>(adv.val[i]);
+    return 0;
+  }
   auto cmp = [&](int64_t x, int64_t y) { return adv.less(x, y); };
   std::nth_element(ids.begin(), ids.begin() + k - 1, ids.end(), cmp);
   if (with_sort) std::sort(ids.begin(), ids.begin() + k - 1, cmp);
   // the adversary built an input bad for "less"; negate for torch's "greater"
   for (int64_t i = 0; i < n; ++i) out[i] = -static_cast<float>(adv.val[i]);
+  return 0;
+}
+
+extern "C" int oracle_antiqsort(int64_t n, int64_t k, int with_sort, float* out) {
+  return oracle_antiqsort_dir(n, k, with_sort, 0, out);
+}
+
+// ---------------------------------------------------------------------------
+// Probe: which branch of the selection does a row reach?  libstdc++'s
+// std::__introselect loop (stl_algo.h) restated on pair<double, int64> with torch's
+// comparator, the same std::__unguarded_partition_pivot and the same 2 * lg(n) depth
+// that std::nth_element passes.  res[0] = 1 when the depth limit was reached with
+// l - f > 3 (the __heap_select fallback), res[1], res[2] = (f, l) there; res[3], res[4] =
+// (l, d) the first time l <= tw held at the top of the loop (-1, -1: never), which is
+// where the device's group kernel hands a row over to its one-lane tail; res[5] = the
+// partition steps taken.
+extern "C" int oracle_introselect_probe(const float* row, int64_t n, int64_t k, int64_t tw, int64_t* res) {
+  if (k < 1 || k > n) return -1;
+  std::vector<elem_t> q(n);
+  for (int64_t j = 0; j < n; ++j) q[j] = elem_t(row[j], j);
+  auto comp = __gnu_cxx::__ops::__iter_comp_iter(cmp_largest);
+  auto first = q.begin(), last = q.end(), nth = q.begin() + (k - 1);
+  int64_t d = 2 * std::__lg(n), steps = 0;
+  res[0] = 0;
+  res[1] = res[2] = res[3] = res[4] = -1;
+  while (true) {
+    if (res[3] < 0 && last - q.begin() <= tw) {
+      res[3] = last - q.begin();
+      res[4] = d;
+    }
+    if (last - first <= 3) break;
+    if (d == 0) {
+      res[0] = 1;
+      res[1] = first - q.begin();
+      res[2] = last - q.begin();
+      break;
+    }
+    --d;
+    ++steps;
+    auto cut = std::__unguarded_partition_pivot(first, last, comp);
+    if (cut <= nth) first = cut;
+    else last = cut;
+  }
+  res[5] = steps;
   return 0;
 }

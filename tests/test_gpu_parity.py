@@ -11,6 +11,8 @@ import numpy as np
 import pytest
 import torch
 
+import gate_cases as GC
+import topk_cases as TC
 from oracle import mx_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -142,6 +144,13 @@ def test_topk_adversarial_rows(M, n):
 
 @pytest.mark.parametrize("n,k", [(197, 30), (197, 154), (256, 77), (256, 154), (512, 300), (120, 20), (300, 4)])
 def test_topk_depth_limit_fallbacks_and_partial_sort(M, n, k):
+    """The front-peeled adversary row O.antiqsort_row(n, k) next to small-alphabet rows.  Per
+    the oracle's introselect probe (test_topk_depth_limit_cpu.py::test_existing_depth_limit_pairs)
+    the row reaches introselect's depth limit (heap_select fallback) at (197, 30), (197, 154),
+    (256, 77), (256, 154) and (512, 300); at (120, 20) it does not (two elements leave the front
+    per step, f passes k - 1 after ten of the twelve levels), and (300, 4) is std::partial_sort
+    (k * 64 <= n), which has no depth limit.  The row holds a -0, so the packed pass leaves it to
+    the 64-bit pass: the hand-overs to the one-lane tail are test_topk_depth_limit_handovers'."""
     rows = np.stack([O.antiqsort_row(n, k)] + [np.random.default_rng(i).integers(0, 3, n).astype(np.float32)
                                                 for i in range(7)])
     _, want = O.topk(rows, k)
@@ -203,6 +212,73 @@ def test_topk_rows_up_to_1024(M, n, k):
     _, idx, words = M.topk(dev(rows), k, return_mask=True)
     same(host(idx), want, f"n{n} k{k}")
     same(host(M.unpack_mask(words, n)), O.prune_mask(want, n), f"n{n} k{k} mask")
+
+
+def _check_topk_both_passes(M, rows_t, rows, n, k, what):
+    """idx, prune-mask words and returned values of M.topk, packed pass (+ one-lane tail) and
+    64-bit pass, bit-exact against libstdc++ on the float32 values of the rows."""
+    _, want = O.topk(rows, k)
+    want_mask = O.prune_mask(want, n)
+    for packed in (True, False):
+        vals, idx, words = M.topk(rows_t, k, return_mask=True, packed=packed)
+        idx_h = host(idx)
+        if not np.array_equal(idx_h, want):
+            bad = np.argwhere(idx_h != want)
+            print(f"{what} packed={packed}: idx mismatches at (row, position) {bad[:8].tolist()}, "
+                  f"got {idx_h[tuple(bad[0])]} want {want[tuple(bad[0])]}")
+        same(idx_h, want, f"{what} packed={packed} idx")
+        same(host(M.unpack_mask(words, n)), want_mask, f"{what} packed={packed} mask")
+        same(host(vals.float()), np.take_along_axis(rows, idx_h, -1), f"{what} packed={packed} vals")
+
+
+@pytest.mark.parametrize("n,k,branch", TC.STANDALONE, ids=TC.case_id)
+def test_topk_depth_limit_handovers(M, n, k, branch):
+    """Rows that exhaust introselect's depth limit on the packed path (tests/topk_cases.py;
+    which branch each reaches is pinned on the CPU by test_topk_depth_limit_cpu.py): in the
+    group kernel with l > 48, which heap-selects and hands [0, k) to the one-lane tail for the
+    sort (mxa_topk_grp.hpp grp_topk, state 1 << 24), or inside the tail after a phase-0
+    hand-over (mxa_tail.hpp, its own heap_select).  70 rows: two tail waves, handed-over rows
+    next to rows the group kernel finishes and a -0 row the 64-bit pass redoes."""
+    rows = TC.standalone_batch(n, k)
+    _check_topk_both_passes(M, dev(rows), rows, n, k, f"n{n} k{k} ({branch})")
+
+
+@pytest.mark.parametrize("dtype", [torch.float16, torch.bfloat16])
+def test_topk_depth_limit_handover_16bit_values(M, dtype):
+    """The sort hand-over at (197, 21) with 16-bit inputs: the row's integers are exact in both
+    types; the tail writes the values back through store_dt."""
+    n, k, _ = TC.DTYPE_CASE
+    rows = TC.standalone_batch(n, k)
+    t = dev(rows).to(dtype)
+    same(host(t.float()), rows, "exact in the 16-bit type")
+    _check_topk_both_passes(M, t, rows, n, k, f"n{n} k{k} {dtype}")
+
+
+@pytest.mark.parametrize("T,k,mode,branch", TC.FUSED, ids=TC.case_id)
+def test_fused_depth_limit_handover(M, T, k, mode, branch):
+    """The depth-limit row as approximate scores of the fused op: two MX blocks of sign counts
+    (topk_cases.fused_inputs) make an adversarial query's scores a strictly increasing function
+    of the adversary row's rank, so the selection kernel's packed pass meets the same row; a
+    few such query rows among random ones in head 0, head 1 random.  pred, idx and prune mask
+    bit-exact against the oracle, out within tolerance."""
+    q, kk, v, rank, qrows = TC.fused_inputs(T, k)
+    aq, ak = O.approx_operands(q, kk, mode)
+    pred_o = O.exact_matmul_f32(aq, np.swapaxes(ak, -1, -2))
+    for r in qrows:  # on the CPU, before any GPU call
+        same(np.argsort(np.argsort(pred_o[0, 0, r], kind="stable"), kind="stable"), rank, "score order")
+    out, idx, _, pred_s, mask = M.mx_topk_attention(dev(q), dev(kk), dev(v), 0.125, k_top=k, pred_mode=mode,
+                                                    return_scores=True, return_mask=True)
+    same(host(pred_s), pred_o, "pred")
+    _, want = O.topk(pred_o.reshape(-1, T), k)
+    idx_h = host(idx).reshape(-1, k)
+    if not np.array_equal(idx_h, want):
+        bad = np.argwhere(idx_h != want)
+        print(f"T{T} k{k} {mode}: idx mismatches at (row, position) {bad[:8].tolist()}, got {idx_h[tuple(bad[0])]}")
+    same(idx_h, want, "idx")
+    same(host(M.unpack_mask(mask, T)).reshape(-1, T), O.prune_mask(want, T), "mask")
+    ro = O.attention(q, kk, v, 0.125, k_top=k, pred_mode=mode)
+    same(ro["idx"].reshape(-1, k), want, "oracle idx")
+    assert O.normwise_rel_err(host(out), ro["out"]) <= OUT_TOL
 
 
 # ------------------------------------------------------------------ approximators
@@ -715,6 +791,70 @@ def test_qkv_projection_spread_paths(M, H):
     out, idx, qkv = M.mx_qkv_attention(dev(x), wq, dev(bias), H, D ** -0.5, k_top=10, return_qkv=True)
     torch.cuda.synchronize()
     same(host(qkv), O.mx_linear(x, W, bias), "qkv across the accumulation paths")
+    q, kk, v = (dev(np.ascontiguousarray(t)) for t in O.qkv_split(host(qkv), H))
+    o2, i2 = M.mx_topk_attention(q, kk, v, D ** -0.5, k_top=10)
+    same(host(idx), host(i2), "idx vs unfused op")
+    same(host(out), host(o2), "out vs unfused op")
+
+
+@pytest.mark.parametrize("regime", ["first_f64", "subnormal"])
+@pytest.mark.parametrize("H", [4, 2])
+def test_qkv_projection_digit_subnormal_gate(M, H, regime):
+    """The fused projection's digit path behind its subnormal gate (mxa_proj.hpp: dig &&
+    !fast_ok -> run_f64 rebuilding the block sums from the digit tile; the gate's quantity is
+    restated in tests/gate_cases.py).  The first 32-token tile as in
+    test_qkv_projection_spread_paths (row spreads <= 8, no wide weight columns: digits), x and
+    W scaled by powers of two so that in that tile every head's gate fires: the nearest head
+    one below the gate (normal results, a tiny bias), and x, W times 2^-70 (subnormal results;
+    H = 4 a tiny bias, H = 2 none).  Asserted on the CPU from the oracle's block exponents;
+    qkv bit-exact against the oracle, idx and out against the unfused op on the same qkv."""
+    B, N, C = 2, 70, 256
+    D = C // H
+    rng = np.random.default_rng(23 + H)
+    x = rng.standard_normal((B, N, C), dtype=np.float32)
+    W = (rng.standard_normal((3 * C, C), dtype=np.float32) * np.float32(0.05)).astype(np.float32)
+    odd = (np.arange(C) // 32) % 2 == 1
+    blk = x[:, :32].reshape(B, 32, C // 32, 32)
+    e = np.floor(np.log2(np.abs(blk).max(-1, keepdims=True)))
+    x[:, :32] = (blk * np.float32(2.0) ** -e).reshape(B, 32, C).astype(np.float32)  # block max in [1, 2)
+    shifts = [0, 3, 8, 9, 12, 20, 30]
+    for t in range(N):
+        s = shifts[(t // 5) % 3] if t < 32 else shifts[(t // 5) % len(shifts)]  # first tile: s <= 8
+        x[:, t, odd] *= np.float32(2.0 ** s)
+    if regime == "subnormal":
+        sx = sw = -70
+    else:
+        q0 = max(GC.qkv_gate(x[b, :32], W, H)[0].max() for b in range(B))
+        t = int(GC.GATE - 1 - q0)
+        sx = t // 2
+        sw = t - sx
+    x = (x * GC.pow2(sx)).astype(np.float32)
+    W = (W * GC.pow2(sw)).astype(np.float32)
+    qs = []
+    for b in range(B):
+        q, smx, gsp = GC.qkv_gate(x[b, :32], W, H)
+        assert smx <= GC.DIGIT_SPREAD and (gsp <= GC.DIGIT_SPREAD).all(), (smx, gsp)
+        qs.append(q)
+    qs = np.array(qs)
+    want = O.mx_linear(x, W)
+    sub = np.isfinite(want) & (want != 0) & (np.abs(want) < np.float32(2.0 ** -126))
+    if regime == "first_f64":
+        assert qs.max() == GC.GATE - 1, qs
+        assert sub.mean() < 0.01
+    else:
+        assert (qs <= GC.GATE - 20).all(), qs
+        assert sub[:, :32].mean() > 0.9
+    print(f"H={H} {regime}: gate quantity per (image, head) {qs.tolist()}, subnormal {int(sub.sum())}/{sub.size}")
+    bias = None
+    if regime == "first_f64" or H == 4:
+        mag = np.abs(want[:, :32][want[:, :32] != 0]).astype(np.float64)
+        bias = (rng.standard_normal(3 * C) * np.exp2(np.floor(np.log2(np.median(mag))))).astype(np.float32)
+        want = O.mx_linear(x, W, bias)
+    wq = M.LinearWeightMX(dev(W), D)
+    out, idx, qkv = M.mx_qkv_attention(dev(x), wq, None if bias is None else dev(bias), H, D ** -0.5, k_top=10,
+                                       return_qkv=True)
+    torch.cuda.synchronize()
+    same(host(qkv), want, "qkv behind the subnormal gate")
     q, kk, v = (dev(np.ascontiguousarray(t)) for t in O.qkv_split(host(qkv), H))
     o2, i2 = M.mx_topk_attention(q, kk, v, D ** -0.5, k_top=10)
     same(host(idx), host(i2), "idx vs unfused op")
