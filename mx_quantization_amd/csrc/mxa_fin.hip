@@ -1,9 +1,6 @@
 // Row-kernel launches: the finishing kernel of the top-k path (mxa_finish.hpp) and the
 // dense (top_k=False) branch: the MFMA finishing kernel with every key kept
 // (mxa_finish_qk.hpp, T <= 256), else the row kernel (mxa_rows2.hpp).
-#include <algorithm>
-#include <atomic>
-
 #include "mxa_finish.hpp"
 #include "mxa_launch.hpp"
 
@@ -56,77 +53,41 @@ static int launch_dense_s(const Rows2Args& ra0, int BH, hipStream_t stream, bool
 #endif  // MXA_FIN_PART == 0
 
 // ---- finishing kernel (mxa_finish.hpp): 32-row MFMA tiles, one per wave ------------
-// two lanes per query row (one pass per tile) when every row's kept keys fit 2 x 16 slots
-static bool finish_pair(const Rows2Args& ra) { return ra.k_top <= 32; }
+// (wave cap 12: the kernel's register use is not looked up)
 static int finish_plan(const Rows2Args& ra, int BH, int* waves, int* rows_per_wg) {
-  const int tiles = (ra.N + kFinTile - 1) / kFinTile;
-  const bool pair = finish_pair(ra);
   const bool xo = ra.xo_codes != nullptr;
-  auto lds = [&](int w) { return fin_lds(ra.T, ra.D, ra.kst, ra.nbd, ra.vst, ra.ntb, w, pair, xo).total; };
-  if (lds(1) > 160 * 1024) return MXA_ERR_UNSUPPORTED;
-  // a head's tiles round-robin over the waves of one workgroup (the K / V tables
-  // staged once per head); few heads (PixArt cross-attention): the tiles split over
-  // grid.y so that the grid still has ~2 workgroups per CU
-  int chunks = 1;
-  while ((int64_t)BH * chunks < 512 && chunks < tiles) ++chunks;
-  // waves per workgroup: the fewest sequential tile rounds per CU -- workgroups per
-  // CU over the LDS-limited concurrency, times each workgroup's rounds over its
-  // tiles; ties to the smaller workgroup (measured: DeiT-base 4 waves, 2 workgroups
-  // per CU, 0.29 ms vs 0.36 ms with 5; DiT 8 waves, 0.36 ms vs 0.61 ms with 4)
-  const int tpc = (tiles + chunks - 1) / chunks;
-  const int64_t wgs_per_cu = ((int64_t)BH * chunks + 255) / 256;
-  int w = 1;
-  int64_t best = -1;
-  for (int c = 1; c <= std::min(8, tpc); ++c) {
-    const size_t t = lds(c);
-    if (t > 160 * 1024) break;
-    const int64_t conc = std::min<int64_t>(160 * 1024 / t, 12 / c > 0 ? 12 / c : 1);
-    const int64_t score = (wgs_per_cu + conc - 1) / conc * ((tpc + c - 1) / c);
-    if (best < 0 || score < best) best = score, w = c;
-  }
-  *waves = w;
-  *rows_per_wg = kFinTile * ((tiles + chunks - 1) / chunks);
-  return MXA_OK;
+  auto lds = [&](int w) { return fin_lds(ra.T, ra.D, ra.kst, ra.nbd, ra.vst, ra.ntb, w, xo).total; };
+  return finish_tile_plan(kFinTile, ra.N, BH, lds, 12, waves, rows_per_wg);
 }
-template <int NB, int KS, bool PAIR, bool XDT, bool XO = false>
+template <int NB, int KS, bool XDT, bool XO = false>
 static int launch_finish_xdt(const Rows2Args& ra0, int BH, hipStream_t stream) {
   Rows2Args ra = ra0;
   int rc = finish_plan(ra, BH, &ra.waves, &ra.rows_per_wg);
   if (rc) return rc;
-  const size_t lds = fin_lds(ra.T, ra.D, ra.kst, ra.nbd, ra.vst, ra.ntb, ra.waves, PAIR, XO).total;
-  if (hipFuncSetAttribute(reinterpret_cast<const void*>(&finish_kernel<NB, KS, PAIR, XDT, XO>),
-                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-    return MXA_ERR_LAUNCH;
-  const unsigned gy = (unsigned)((ra.N + ra.rows_per_wg - 1) / ra.rows_per_wg);
-  hipLaunchKernelGGL((finish_kernel<NB, KS, PAIR, XDT, XO>), dim3((unsigned)BH, gy), dim3(64 * ra.waves), lds, stream, ra);
-  return hipGetLastError() == hipSuccess ? MXA_OK : MXA_ERR_LAUNCH;
+  const size_t lds = fin_lds(ra.T, ra.D, ra.kst, ra.nbd, ra.vst, ra.ntb, ra.waves, XO).total;
+  return launch_finish_tiles<&finish_kernel<NB, KS, XDT, XO>>(ra, BH, lds, stream);
 }
-template <int NB, int KS, bool PAIR>
+template <int NB, int KS>
 static int launch_finish_ks(const Rows2Args& ra, int BH, hipStream_t stream) {
   if (ra.xo_codes) {  // output MX codes for the proj Linear: float32, D % 32 == 0
     if (ra.s_dt != kF32 || ra.in_dt != kF32 || ra.D % 32) return MXA_ERR_UNSUPPORTED;
-    return launch_finish_xdt<NB, KS, PAIR, false, true>(ra, BH, stream);
+    return launch_finish_xdt<NB, KS, false, true>(ra, BH, stream);
   }
-  if (ra.s_dt != kF32 || ra.in_dt != kF32) return launch_finish_xdt<NB, KS, PAIR, true>(ra, BH, stream);
-  return launch_finish_xdt<NB, KS, PAIR, false>(ra, BH, stream);
+  if constexpr (KS >= 8) {
+    if (ra.s_dt != kF32 || ra.in_dt != kF32) return launch_finish_xdt<NB, KS, true>(ra, BH, stream);
+    return launch_finish_xdt<NB, KS, false>(ra, BH, stream);
+  }
+  return MXA_ERR_UNSUPPORTED;  // k <= 64 without xo: the 16-row kernel
 }
 template <int NB>
 static int launch_finish_nb(const Rows2Args& ra, int BH, hipStream_t stream) {
-  if (finish_pair(ra)) {  // slots per lane: ceil(k / 2)
-    const int kp = (ra.k_top + 1) / 2;
-    if (kp <= 2) return launch_finish_ks<NB, 2, true>(ra, BH, stream);
-    if (kp <= 4) return launch_finish_ks<NB, 4, true>(ra, BH, stream);
-    if (kp <= 8) return launch_finish_ks<NB, 8, true>(ra, BH, stream);
-    if (kp <= 12) return launch_finish_ks<NB, 12, true>(ra, BH, stream);
-    return launch_finish_ks<NB, 16, true>(ra, BH, stream);
-  }
-  const int ks = (ra.k_top + 15) / 16;
-  if (ks <= 1) return launch_finish_ks<NB, 1, false>(ra, BH, stream);
-  if (ks <= 2) return launch_finish_ks<NB, 2, false>(ra, BH, stream);
-  if (ks <= 4) return launch_finish_ks<NB, 4, false>(ra, BH, stream);
-  if (ks <= 8) return launch_finish_ks<NB, 8, false>(ra, BH, stream);
-  if (ks <= 16) return launch_finish_ks<NB, 16, false>(ra, BH, stream);
-  return launch_finish_ks<NB, 32, false>(ra, BH, stream);
+  // k <= 64 (k <= 32 with the proj's codes) is the 16-row kernel's (mxa_fin16.hip)
+  if (ra.k_top <= (ra.xo_codes ? 32 : 64)) return MXA_ERR_UNSUPPORTED;
+  const int ks = (ra.k_top + 15) / 16;  // slots per lane: 16 lanes per row
+  if (ks <= 4) return launch_finish_ks<NB, 4>(ra, BH, stream);
+  if (ks <= 8) return launch_finish_ks<NB, 8>(ra, BH, stream);
+  if (ks <= 16) return launch_finish_ks<NB, 16>(ra, BH, stream);
+  return launch_finish_ks<NB, 32>(ra, BH, stream);
 }
 #if MXA_FIN_PART > 0
 #define MXA_FIN_FN2(i) launch_finish32_p##i

@@ -21,8 +21,8 @@
 // scores key 0 and writes its code to a pad column), so the per-slot work has no branches.
 // exp / divide: the softmax on v_exp_f32 (2^((v - mx) log2 e)) and a corrected reciprocal
 // (P is a tolerance-only operand, as in mxa_finish_qk.hpp).
-// (The proj Linear's MX input codes stay on the 32-row kernel, whose 32 x 32 output blocks
-// are whole MX blocks of the rows.)
+// (The proj Linear's MX input codes, XO: here for k <= 32; for larger k they stay on the
+// 32-row kernel, whose 32 x 32 output blocks are whole MX blocks of the rows.)
 // Reference: microxscaling/mx/matmul.py:68-76 (MX P.V), callers
 // workloads/deit/scripts/main.py:124-152, workloads/DiT/models.py:195-225,
 // workloads/PixArt/models/MX_transformer_block.py:679-717, :826-859.
@@ -124,13 +124,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NB <= 2 && 
   // ---- stage the head's K table and V block scales; clear the code tile ---------------
   const int64_t kb = (int64_t)bh * T;
   {
-    const int cpr = a.dpad / 16;
-    for (int i = threadIdx.x; i < T * cpr; i += blockDim.x) {
-      const int j = i / cpr, c = i - j * cpr;
-      *reinterpret_cast<uint4*>(tkc + (size_t)j * kst + 16 * c) =
-          *reinterpret_cast<const uint4*>(a.kc + (kb + j) * a.dpad + 16 * c);
-    }
-    for (int i = threadIdx.x; i < T * nbd; i += blockDim.x) tke[i] = a.ksT[kb * nbd + i];
+    stage_k_table<NB>(a, kb, tkc, tke);
     const int16_t* vssrc = a.vs + (int64_t)bh * ntb * D;
     for (int i = threadIdx.x; i < ntb * D; i += blockDim.x) tvs[i] = scale_f(exp_from16(vssrc[i]));
     for (int i = lane; i < kFin16 * vst / 16; i += 64) reinterpret_cast<uint4*>(ptile)[i] = make_uint4(0, 0, 0, 0);
@@ -149,15 +143,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NB <= 2 && 
     // the row's query codes / exponents and its kept indices
     uint4 qv[2 * NB];
     int qe[NB];
-    {
-      const int8_t* qsrc = a.qc + grow * a.dpad;
-#pragma unroll
-      for (int b = 0; b < NB; ++b) {
-        qv[2 * b] = *reinterpret_cast<const uint4*>(qsrc + 32 * b);
-        qv[2 * b + 1] = *reinterpret_cast<const uint4*>(qsrc + 32 * b + 16);
-        qe[b] = exp_from16(a.qsT[grow * nbd + b]);
-      }
-    }
+    load_query_row<NB>(a, grow, qv, qe);
     int ix[KS];
     bool on[KS];
 #pragma unroll
@@ -165,13 +151,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NB <= 2 && 
       on[t] = valid && ph + 4 * t < k;
       ix[t] = ixn[t];
     }
-    auto true_of = [&](int j) -> float {  // true = quantize_elemwise(fl32(QK^T)) * scale (+ bias)
+    auto true_of = [&](int j) -> float {  // the true score of key j (+ bias: EXTRA only)
       const float acc = true_dot<NB>(qv, qe, tkc + (size_t)j * kst, tke + j * nbd);
-      if (!kRound) return acc * a.scale;
-      float t = round_bfloat(round_dt(acc, sdt), a.bfloat, kRoundNearest, 1, sdt);
-      t = round_dt(t * a.scale, sdt);
-      if (brow >= 0) t = round_dt(t + load_dt(a.bias, brow + (int64_t)j * a.bs3, idt), sdt);
-      return t;
+      const float t = true_score<kRound>(acc, a.scale, a.bfloat, sdt);
+      return kRound && brow >= 0 ? true_score_bias(t, a.bias, brow + (int64_t)j * a.bs3, idt, sdt) : t;
     };
     if (EXTRA && a.true_out && valid)  // debug output: every key's true score
       for (int j = ph; j < T; j += 4) a.true_out[grow * T + j] = true_of(j);
@@ -207,12 +190,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NB <= 2 && 
       sum += v[t];
     }
     sum = qsum(sum);
-    // p = v / sum from y = RN(1 / sum): q = RN(v y), r = v - q sum exact by fma, RN(q + r y)
     const float rs = 1.0f / sum;
 #pragma unroll
     for (int t = 0; t < KS; ++t) {
-      const float q0 = v[t] * rs;
-      float p = __builtin_fmaf(__builtin_fmaf(-q0, sum, v[t]), rs, q0);
+      float p = div_by_sum(v[t], sum, rs);
       if (kRound) p = round_dt(round_bfloat(p, a.bfloat, kRoundNearest, 1, sdt), sdt);
       v[t] = p;
       // zeros.scatter_(idx, softmax) -> MXINT8 along keys: the block maxima (an unused slot
@@ -222,6 +203,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NB <= 2 && 
     wave_lds_sync();
     // per block: the scale sP (NaN for a NaN block) and the code multiplier 2^-es (0 for a NaN
     // or flushed block: its codes 0; XDT: es + 1024 and the flush flag, round_code at run time)
+    // (p_block's rule, mxa_finish.hpp, written out: see there)
     for (int bk = ph; bk < ntb; bk += 4) {
       int e_raw;
       const int es = scale_exponent_dt(bm[bk], 127, sdt, &e_raw);
@@ -234,18 +216,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NB <= 2 && 
 #pragma unroll
     for (int t = 0; t < KS; ++t) {
       const uint32_t e = bm[ix[t] >> 5];
-      int code;
-      if (XDT) {
-        code = 0;
-        if (e & 0xFFFFu) {
-          const int es = (int)(e & 0xFFFFu) - 1024;
-          const float x = (e & 0x10000u) ? v[t] * 0.0f : v[t];
-          code = (int)round_code(x, es, 8, kRoundNearest, sdt);
-        }
-      } else {  // round_code for p >= 0: floor(p 2^-es 64 + 0.5), <= 127 (a NaN block: sP is NaN)
-        const float y = (v[t] * __uint_as_float(e)) * 64.0f;
-        code = (int)fminf(floorf(y + 0.5f), 127.0f);
-      }
+      // (float32: a NaN block's codes do not matter, its sP is NaN)
+      const int code = XDT ? p_code_word(v[t], e, sdt) : (int)p_code_f32(v[t], __uint_as_float(e));
       ptile[pr * vst + (on[t] ? ix[t] : pad)] = (int8_t)code;
     }
     wave_lds_sync();
@@ -294,11 +266,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NB <= 2 && 
         for (int i = 0; i < 4; ++i)
           if (16 * u + ln < D) ot[(4 * kg + i) * ost + 16 * u + ln] = round_bfloat(acc[u][i], a.bfloat, kRoundNearest, 1);
       wave_lds_sync();
-      RowsPrepArgs ro{};
-      ro.codes = a.xo_codes; ro.sT = a.xo_exps;
-      ro.dpad = a.H * D; ro.nb = a.H * nbd; ro.D = a.H * D;
-      ro.op_kind = MXA_OP_MXINT8; ro.flush = a.flush_p; ro.bfloat = a.bfloat; ro.dt = kF32;
-      ro.mfma_rows = 1;  // the MX GEMM's A layout
+      const RowsPrepArgs ro = xo_rows_args(a.xo_codes, a.xo_exps, a.H * D, a.H * nbd, a.flush_p, a.bfloat);
       const int row = (lane & 31) >> 1, sub = lane & 1, rr = r0 + row;
       const int64_t orow = (int64_t)b_ * a.N + (rr < r_end ? rr : r0);
 #pragma unroll
@@ -307,9 +275,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NB <= 2 && 
         float xv[16];
 #pragma unroll
         for (int j = 0; j < 16; ++j) xv[j] = ot[row * ost + 32 * blc + 16 * sub + j];
-        const int blk = h_ * nbd + blc, c0 = h_ * D + 32 * blc + 16 * sub;
-        if (rows_prep_plain(ro)) rows_prep_block_plain<16, kF32>(ro, orow, blk, sub, c0, xv, rr < r_end && bl < NB);
-        else rows_prep_block<16>(ro, orow, blk, sub, c0, xv, rr < r_end && bl < NB);
+        xo_block(ro, orow, h_ * nbd + blc, sub, h_ * D + 32 * blc + 16 * sub, xv, rr < r_end && bl < NB);
       }
       wave_lds_sync();
       // the area back to a clear code tile and zero block maxima (sP is rewritten per tile)

@@ -312,16 +312,10 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
           }
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
-            float s = sc[i];
-            if (kRound) {
-              s = round_bfloat(round_dt(s, sdt), a.bfloat, kRoundNearest, 1, sdt);
-              s = round_dt(s * a.scale, sdt);
-            } else {
-              s = s * a.scale;
-            }
+            float s = true_score<kRound>(sc[i], a.scale, a.bfloat, sdt);
             const int key = key0 + i;
             if (EXTRA) {
-              if (brow >= 0 && key < T) s = round_dt(s + load_dt(a.bias, brow + (int64_t)key * a.bs3, idt), sdt);
+              if (brow >= 0 && key < T) s = true_score_bias(s, a.bias, brow + (int64_t)key * a.bs3, idt, sdt);
               if (a.true_out && valid && key < T) a.true_out[grow * T + key] = s;
             }
             // a dropped key: -inf (the kept bit as an all-ones / zero mask, one bit select)
@@ -374,10 +368,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
     sum = fq_fsum4(sum);
     const bool nan_sum = sum != sum;
     const bool any_nan = __builtin_amdgcn_ballot_w64(nan_sum) != 0;  // wave-uniform: rare rows only
-    // p = v / sum correctly rounded without a division per element (Markstein: y = RN(1/sum),
-    // q = RN(v y), r = v - q sum exact by fma, RN(q + r y) = RN(v / sum); v in [0, 1],
-    // sum in [1, T]: no overflow, and subnormal p only where the block is negligible)
-    const float rs = 1.0f / sum;
+    const float rs = 1.0f / sum;  // p = v / sum by div_by_sum
     // ---- 3. per key block: P codes, then P.V: O^T = V^T . P^T, one MFMA per (16 columns,
     // block); A[m][k] = V^T[dt + m][32 blk + 8 g ..]: m = lane % 16; C[m][n]: m = 4 g + i
     // (column dt + 4 g + i), n = lane % 16 = q.  Block-outer: a block's scores die once its
@@ -391,8 +382,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
       if (blk < ntb) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          const float q0 = v[blk][j] * rs;
-          const float q1 = __builtin_fmaf(__builtin_fmaf(-q0, sum, v[blk][j]), rs, q0);
+          const float q1 = div_by_sum(v[blk][j], sum, rs);
           v[blk][j] = kRound ? round_dt(round_bfloat(q1, a.bfloat, kRoundNearest, 1, sdt), sdt) : q1;
         }
         if (any_nan)
@@ -403,22 +393,18 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
 #pragma unroll
         for (int j = 0; j < 8; ++j) bm = max(bm, __float_as_uint(v[blk][j]) & 0x7FFFFFFFu);
         bm = fq_umax4(bm);
-        int e_raw;
-        const int es = scale_exponent_dt(bm, 127, sdt, &e_raw);
-        const bool fl = a.flush_p && !(e_raw != kExpNaN && e_raw > -127);
-        const float sP = scale_f(es == kExpNaN ? kExpNaN : es - 6);
+        const PBlock pb = p_block(bm, a.flush_p, sdt);
+        const int es = pb.es;
+        const bool fl = pb.flush;
+        const float sP = pb.sP;
         uint32_t lo = 0u, hi = 0u;
-        if (es != kExpNaN) {
+        if (es != kExpNaN) {  // (a NaN block has no codes; p_code_word's rule from registers)
 #pragma unroll
           for (int j = 0; j < 8; ++j) {
-            const float x = fl ? v[blk][j] * 0.0f : v[blk][j];
             uint32_t code;
-            if (XDT) {
-              code = (uint32_t)(int)round_code(x, es, 8, kRoundNearest, sdt) & 0xFFu;
-            } else {  // round_code for x >= 0, finite (a NaN block has no codes): floor(x 2^-es 64 + 0.5), <= 127
-              const float y = (x * pow2f(-es)) * 64.0f;
-              code = (uint32_t)fminf(floorf(y + 0.5f), 127.0f);
-            }
+            const float x = fl ? v[blk][j] * 0.0f : v[blk][j];
+            if (XDT) code = (uint32_t)(int)round_code(x, es, 8, kRoundNearest, sdt) & 0xFFu;
+            else code = (uint32_t)p_code_f32(x, pow2f(-es));
             if (j < 4) lo |= code << (8 * j);
             else hi |= code << (8 * (j - 4));
           }

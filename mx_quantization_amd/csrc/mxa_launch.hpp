@@ -1,6 +1,9 @@
 // Host-side launchers shared across the library's translation units (one TU per
 // kernel family, so that hipcc compiles them in parallel).
 #pragma once
+#include <algorithm>
+#include <atomic>
+
 #include "mxa_proj_args.hpp"
 #include "mxa_rows2.hpp"
 
@@ -73,7 +76,69 @@ inline int rows_kernel_kind(bool topk, int k, int T, int nbd, bool xo) {
   // MX input codes: k <= 32); larger k: the 32-row kernel
   return k <= (xo ? 32 : 64) ? MXA_FIN_GATHER16 : MXA_FIN_GATHER32;
 }
-// its launches (mxa_fin_qk.hip): float32 inputs and scores (x0), float16 / bfloat16 (x1)
+
+// ---- what the three finishing kernels' launches share (mxa_fin.hip, mxa_fin16.hip,
+// mxa_fin_qk.hip): tiles of tile_rows query rows, one tile per wave at a time --------------
+// Waves per workgroup and query rows per workgroup.  lds(w): the LDS bytes of a workgroup
+// of w waves; wave_cap: the waves per CU the kernel's registers allow.  A head's tiles
+// round-robin over the waves of one workgroup (the K / V tables staged once per head); few
+// heads (PixArt cross-attention): the tiles split over grid.y so that the grid still has ~2
+// workgroups per CU.  Waves per workgroup: the fewest sequential tile rounds per CU --
+// workgroups per CU over the concurrency the LDS and the registers allow, times each
+// workgroup's rounds over its tiles; ties to the smaller workgroup (measured on the 32-row
+// kernel, wave_cap 12: DeiT-base 4 waves, 2 workgroups per CU, 0.29 ms vs 0.36 ms with 5;
+// DiT 8 waves, 0.36 ms vs 0.61 ms with 4).  MXA_ERR_UNSUPPORTED: one wave does not fit
+// the 160 KB.
+template <class LdsFn>
+inline int finish_tile_plan(int tile_rows, int N, int BH, LdsFn lds, int wave_cap, int* waves, int* rows_per_wg) {
+  const int tiles = (N + tile_rows - 1) / tile_rows;
+  if (lds(1) > 160 * 1024) return MXA_ERR_UNSUPPORTED;
+  int chunks = 1;
+  while ((int64_t)BH * chunks < 512 && chunks < tiles) ++chunks;
+  const int tpc = (tiles + chunks - 1) / chunks;
+  const int64_t wgs_per_cu = ((int64_t)BH * chunks + 255) / 256;
+  int w = 1;
+  int64_t best = -1;
+  for (int c = 1; c <= std::min(8, tpc); ++c) {
+    const size_t t = lds(c);
+    if (t > 160 * 1024) break;
+    const int64_t conc = std::max<int64_t>(1, std::min<int64_t>(160 * 1024 / t, wave_cap / c));
+    const int64_t score = (wgs_per_cu + conc - 1) / conc * ((tpc + c - 1) / c);
+    if (best < 0 || score < best) best = score, w = c;
+  }
+  *waves = w;
+  *rows_per_wg = tile_rows * tpc;
+  return MXA_OK;
+}
+// the wave cap of a kernel whose registers allow wps waves per SIMD (plan = true, before any
+// code object is looked at: 2)
+inline int finish_wave_cap(int wps) { return 4 * std::max(1, std::min(8, wps)); }
+// waves per SIMD the kernel's registers allow: a property of the code object (gfx950
+// only), cached per kernel function; concurrent first launches compute the same value
+template <auto Kernel>
+inline int kernel_waves_per_simd() {
+  static std::atomic<int> cached{0};
+  int wps = cached.load(std::memory_order_relaxed);
+  if (!wps) {
+    hipFuncAttributes fa{};
+    wps = hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(Kernel)) == hipSuccess && fa.numRegs > 0
+              ? 512 / ((fa.numRegs + 7) / 8 * 8) : 2;
+    cached.store(wps, std::memory_order_relaxed);
+  }
+  return wps;
+}
+// the launch of a planned finishing kernel (ra.waves, ra.rows_per_wg) with lds bytes of LDS
+template <auto Kernel>
+inline int launch_finish_tiles(const Rows2Args& ra, int BH, size_t lds, hipStream_t stream) {
+  if (hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) !=
+      hipSuccess)
+    return MXA_ERR_LAUNCH;
+  const unsigned gy = (unsigned)((ra.N + ra.rows_per_wg - 1) / ra.rows_per_wg);
+  hipLaunchKernelGGL(Kernel, dim3((unsigned)BH, gy), dim3(64 * ra.waves), lds, stream, ra);
+  return hipGetLastError() == hipSuccess ? MXA_OK : MXA_ERR_LAUNCH;
+}
+
+// the MFMA finishing kernel's launches (mxa_fin_qk.hip): float32 inputs and scores (x0), float16 / bfloat16 (x1)
 int launch_finish_qk_x0(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 int launch_finish_qk_x1(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 // the 16-row finishing kernel (mxa_fin16.hip): float32 (x0), float16 / bfloat16 (x1)

@@ -523,6 +523,23 @@ def gen_dtype():
     print("wrote attn_dtype")
 
 
+def gen_dtype_fin32():
+    """attn_dtype_fin32.npz: the attention glue on float16 tensors at a shape the 32-row
+    finishing kernel takes (k = 129 > 64 of T = 300 > 256 keys; N = 40: a full and a partial
+    32-row tile; D = 72: three MX blocks, the last partial)."""
+    s = specs()
+    B, H, N, T, D, k_top = 2, 2, 40, 300, 72, 129
+    q = torch.from_numpy(rnd((B, H, N, D), 60)).to(torch.float16)
+    kk = torch.from_numpy(rnd((B, H, T, D), 61)).to(torch.float16)
+    v = torch.from_numpy(rnd((B, H, T, D), 62)).to(torch.float16)
+    out = {"f16/q": _bits(q), "f16/k": _bits(kk), "f16/v": _bits(v), "k_top": np.int64(k_top)}
+    r = attention_glue_t(q, kk, v, s, D ** -0.5, k_top, "ex_pred")
+    for key in ("true", "pred", "idx", "out"):
+        out[f"f16/ex_pred/{key}"] = r[key]
+    np.savez_compressed(os.path.join(OUT, "attn_dtype_fin32.npz"), **out)
+    print("wrote attn_dtype_fin32")
+
+
 def attention_glue_t(q, k, v, s, scale, k_top, mode, top_k=True):
     """attention_glue for float16 / bfloat16 / autocast: the same glue, outputs as float32
     arrays of the dtype's values (idx int64)."""
@@ -549,6 +566,6 @@ def attention_glue_t(q, k, v, s, scale, k_top, mode, top_k=True):
 
 if __name__ == "__main__":
     which = sys.argv[1:] or ["quant_kat", "topk_ties", "attention", "attention_extra", "linear_qkv", "linear_proj", "analysis",
-                             "dtype"]
+                             "dtype", "dtype_fin32"]
     for w in which:
         globals()["gen_" + w]()

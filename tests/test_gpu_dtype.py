@@ -113,6 +113,26 @@ def test_attention_dtype_inputs(M, D, dt, tag, mode, k_top):
     out_close(host(out), to_f32(D[f"{pre}/out"], dt), TOL[dt], pre + " out")
 
 
+def test_attention_dtype_finish32(M):
+    """float16 inputs on the 32-row finishing kernel (its XDT instantiation: the dtype
+    roundings at run time): k = 129 of T = 300 keys, N = 40 rows, D = 72, against the
+    reference's own run (gen_golden.py gen_dtype_fin32 -> attn_dtype_fin32.npz)."""
+    import ctypes
+    F = np.load(os.path.join(G, "attn_dtype_fin32.npz"))
+    q, k, v = (from_bits(F[f"f16/{n}"], "f16") for n in "qkv")
+    k_top, sc = int(F["k_top"]), q.shape[-1] ** -0.5
+    p, _, _, _ = M.ops._attn_params(q, k, v, sc, k_top, "ex_pred", True, True, None, False, 0, None)
+    p.out = 16  # the query launches nothing
+    assert M._native.lib().mxa_attention_finish_kernel(ctypes.byref(p)) == 2  # MXA_FIN_GATHER32
+    out, idx, true_s, pred_s = M.mx_topk_attention(q, k, v, sc, k_top=k_top, return_scores=True)
+    assert out.dtype == torch.float16
+    pre = "f16/ex_pred"
+    same(host(true_s), to_f32(F[f"{pre}/true"], "f16"), pre + " true")
+    same(host(pred_s), to_f32(F[f"{pre}/pred"], "f16"), pre + " pred")
+    same(host(idx), F[f"{pre}/idx"].astype(np.int64), pre + " idx")
+    out_close(host(out), to_f32(F[f"{pre}/out"], "f16"), TOL["f16"], pre + " out")
+
+
 @pytest.mark.parametrize("dt", ["f16", "bf16"])
 @pytest.mark.parametrize("tag", ["deit", "dit"])
 def test_attention_dtype_dense(M, D, dt, tag):

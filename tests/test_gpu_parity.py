@@ -583,6 +583,40 @@ def test_dense_branch_vs_oracle(M, D, N, T):
         assert fk(ctypes.byref(p)) == 4  # MXA_FIN_DENSE_MFMA
 
 
+@pytest.mark.parametrize("D,k", [(32, 65), (72, 129), (128, 257)])
+def test_finish32_paths_vs_oracle(M, D, k):
+    """The 32-row finishing kernel (finish_kernel, mxa_finish.hpp: k > 64 with rows of more
+    than 256 keys) on the device: N = 40 is one full 32-row tile and a partial one of 8 rows,
+    T = 300 ten key blocks with a ragged last one; D = 32 / 72 / 128 are 1 / 3 / 4 MX blocks
+    per head dim (72: the P.V column clamp), k = 65 / 129 / 257 need 8 / 16 / 32 kept slots
+    per lane.  Special rows as in test_dense_branch_vs_oracle: a NaN query element, an
+    all-zero key row, a key row whose blocks spread 2^30.  With and without a bias of -10000
+    on the upper half of the keys.  idx, prune mask and true scores bit-exact, the output
+    within tolerance; the dispatch is pinned to MXA_FIN_GATHER32."""
+    import ctypes
+    rng = np.random.default_rng(D * 7 + k)
+    B, H, N, T = 2, 2, 40, 300
+    q = rng.standard_normal((B, H, N, D), dtype=np.float32)
+    kk = rng.standard_normal((B, H, T, D), dtype=np.float32)
+    v = rng.standard_normal((B, H, T, D), dtype=np.float32)
+    q[0, 0, 3, 1] = np.nan
+    kk[1, 0, 2, :] = 0.0
+    kk[1, 1, 1, D // 2:] *= np.float32(2.0 ** 30)
+    bias = np.zeros((B, 1, N, T), np.float32)
+    bias[:, :, :, T // 2:] = -10000.0
+    fk = M._native.lib().mxa_attention_finish_kernel
+    for bb in (None, bias):
+        bd = None if bb is None else dev(bb)
+        p, _, _, _ = M.ops._attn_params(dev(q), dev(kk), dev(v), D ** -0.5, k, "ex_pred", True, True, bd, False, 0, None)
+        p.out = 16  # the query launches nothing
+        assert fk(ctypes.byref(p)) == 2  # MXA_FIN_GATHER32
+        (got,) = _attn_all_paths(M, q, kk, v, D ** -0.5, k_top=k, bias=bd, return_mask=True)
+        r = O.attention(q, kk, v, D ** -0.5, k_top=k, bias=bb)
+        what = f"D{D} k{k} bias={bb is not None}"
+        _check_vs_oracle(got[:4], r, what)
+        same(host(M.unpack_mask(torch.from_numpy(got[4]), T)), O.prune_mask(r["idx"], T), what + " mask")
+
+
 @pytest.mark.parametrize("mode,k", [("ex_pred", 20), ("ex_pred", 100), ("MXINT4", 20)])
 def test_packed_pass_fallback_rows(M, mode, k):
     """Scattered query rows whose approximate scores do not pack into 32-bit elements (the

@@ -125,7 +125,7 @@ def test_hbm_traffic_kernel_names_map_to_bench_stages():
     assert ht.stage_of("void mxa::select_kernel<256, 3, 2, unsigned long, 0, 0>(mxa::Rows2Args)") == "select_fb"
     assert ht.stage_of("void mxa::topk_tail_kernel<64>(mxa::TailArgs)") == "select_tail"
     assert ht.stage_of("void mxa::finish_qk_kernel<3, 8, false>(mxa::Rows2Args)") == "finish"
-    assert ht.stage_of("void mxa::finish_kernel<2, 2>(mxa::Rows2Args)") == "finish"
+    assert ht.stage_of("void mxa::finish_kernel<2, 8, false, false>(mxa::Rows2Args)") == "finish"
     assert ht.stage_of("void mxa::dense_rows_kernel<4>(mxa::Rows2Args)") == "finish"
     assert ht.stage_of("mxa::attn_prep_kernel(mxa::RowsPrepArgs, mxa::RowsPrepArgs, mxa::ColsPrepArgs, unsigned int, "
                        "unsigned int)") == "prep"
@@ -147,7 +147,7 @@ def test_hbm_traffic_never_averages_two_instantiations_of_a_stage():
     ht = _load_hbm_traffic()
     deit, dit = ("void mxa::select_kernel<256, 3, 2, unsigned int, 1, 64>(mxa::Rows2Args)",
                  "void mxa::select_kernel<256, 3, 4, unsigned int, 0, 0>(mxa::Rows2Args)")
-    fin = "void mxa::finish_kernel<2, 12, true>(mxa::Rows2Args)"
+    fin = "void mxa::finish_kernel<2, 8, false, false>(mxa::Rows2Args)"
     rows = []
     for name, kib_f, kib_w, n in ((deit, 10.0, 143250.0, 7), (dit, 20.0, 473145.0, 3), (fin, 100.0, 200.0, 7)):
         for _ in range(n):
