@@ -25,7 +25,7 @@ UNITS += [("mxa_proj.hip", "", ()), ("mxa_gemm.hip", "", ())]
 # the MFMA finishing kernel's float32 and float16 / bfloat16 instantiations (MXA_FQ_XDT)
 UNITS += [("mxa_fin_qk.hip", f"_x{i}", (f"MXA_FQ_XDT={i}",)) for i in range(2)]
 SOURCES = sorted({u[0] for u in UNITS})
-HEADERS = ["mxa_common.hpp", "mxa_kernels.hpp", "mxa_prep.hpp", "mxa_proj.hpp", "mxa_proj_args.hpp", "mxa_finish.hpp",
+HEADERS = ["mxa_common.hpp", "mxa_kernels.hpp", "mxa_prep.hpp", "mxa_proj.hpp", "mxa_proj_args.hpp", "mxa_gemm_parts.hpp", "mxa_finish.hpp",
            "mxa_order.hpp", "mxa_topk_grp.hpp", "mxa_topk_wave.hpp", "mxa_finish16.hpp", "mxa_finish_qk.hpp", "mxa_tail.hpp", "mxa_gemm.hpp", "mxa_dot.hpp", "mxa_select.hpp", "mxa_rows2.hpp", "mxa_modes.hpp", "mxa_launch.hpp",
            "../../include/mxa.h"]
 ARCH = os.environ.get("MXA_OFFLOAD_ARCH", "gfx950")
@@ -63,8 +63,8 @@ def _obj_stale(obj, dep, cmd_file, cmd):
 
 
 def build(force=False, verbose=True, defines=(), tag="", only=()):
-    """defines / tag: a tools-only variant (e.g. defines=("MXA_SEL_SKIP=1",), tag="skip1"
-    -> libmxa_skip1.so, loaded by tools through MXA_LIB); never the product.  only: the
+    """defines / tag: a tools-only variant (e.g. defines=("MXA_FQ_KMIN=97",), tag="kmin97"
+    -> libmxa_kmin97.so, loaded by tools through MXA_LIB); never the product.  only: the
     source files the variant recompiles (the other units link the product's objects, which
     must be built).  Units whose object is up to date (by hipcc's dependency list) are not
     recompiled unless force."""

@@ -188,13 +188,9 @@ static int launch_qkv_proj(const mxa_attn_params& pp, const mxa_qkv_params& xq, 
                            hipStream_t stream) {
   const int nbk = (xq.C + 31) / 32, Cpad = 32 * nbk;
   const int64_t tokens = (int64_t)pp.B * pp.N;
-  RowsPrepArgs rx{};
-  rx.x = xq.x; rx.s0 = 0; rx.s1 = 0; rx.s2 = xq.x_row_stride;
-  rx.H = 1; rx.R = tokens; rx.rows = tokens; rx.D = xq.C; rx.nb = nbk; rx.dpad = Cpad;
-  rx.vec4 = aligned16(xq.x) && xq.x_row_stride % 4 == 0;
-  rx.op_kind = MXA_OP_MXINT8; rx.flush = pp.flush_subnormals; rx.bfloat = pp.bfloat; rx.dt = MXA_DT_F32;
-  rx.codes = reinterpret_cast<int8_t*>(ws + L.xc);
-  rx.sT = reinterpret_cast<int16_t*>(ws + L.xs);
+  const RowsPrepArgs rx = flat_rows_prep(xq.x, tokens, xq.C, xq.x_row_stride, aligned16(xq.x) && xq.x_row_stride % 4 == 0,
+                                         pp.flush_subnormals, pp.bfloat, reinterpret_cast<int8_t*>(ws + L.xc),
+                                         reinterpret_cast<int16_t*>(ws + L.xs), 0);
   int rc = launch_rows_prep(rx, stream);
   if (rc) return rc;
   const LinearLayout W = linear_layout(3 * pp.H * pp.D, xq.C, pp.D);
@@ -216,9 +212,7 @@ static int launch_qkv_proj(const mxa_attn_params& pp, const mxa_qkv_params& xq, 
   pa.bias = xq.bias; pa.qkv_out = xq.qkv_out;
   pa.autocast = xq.autocast_dtype;
   pa.B = pp.B; pa.N = pp.N; pa.H = pp.H; pa.D = pp.D; pa.nbk = nbk; pa.Cpad = Cpad; pa.bfloat = pp.bfloat;
-  // shifted int32 block sums stay exact while nbk * 32 * 127^2 * 2^smax < 2^31
-  pa.smax = -1;
-  while ((int64_t)nbk * 516128 * ((int64_t)1 << (pa.smax + 1)) < ((int64_t)1 << 31)) ++pa.smax;
+  pa.smax = gemm_smax(nbk);
   pa.rq = rq; pa.rk = rk; pa.cv = cv;
   return launch_proj(pa, stream);
 }
@@ -256,7 +250,7 @@ static int attention_impl(const mxa_attn_params* p, hipStream_t stream, hipEvent
   if ((p->dtype != MXA_DT_F32 || p->score_dtype > MXA_DT_F32) && p->approx &&
       (p->pred_mode == MXA_PRED_EXION || p->pred_mode == MXA_PRED_TRUE_EX || p->pred_mode == MXA_PRED_ELSA))
     return MXA_ERR_UNSUPPORTED;
-  if (p->bfloat != 0 && p->bfloat != 32 && (p->bfloat < 10 || p->bfloat > 31)) return MXA_ERR_ARG;
+  if (!valid_bfloat(p->bfloat)) return MXA_ERR_ARG;
   if (p->T > 512 || p->D > 32 * kMaxNB) return MXA_ERR_UNSUPPORTED;
   // the prepared weight must have been prepared for this geometry and these settings
   if (xq && !linear_weight_verify(xq->wq, linear_weight_header(3 * p->H * p->D, xq->C, p->D, p->flush_subnormals,
@@ -422,18 +416,12 @@ static int attention_impl(const mxa_attn_params* p, hipStream_t stream, hipEvent
   }
   if (ev) (void)hipEventRecord(ev[5], stream);
   if (pj) {
-    const int C = pp.H * pp.D, nbk = (C + 31) / 32;
+    const int C = pp.H * pp.D;
     const int64_t tokens = (int64_t)pp.B * pp.N;
     int8_t* yc = reinterpret_cast<int8_t*>(ws + L.yc);
     int16_t* ys = reinterpret_cast<int16_t*>(ws + L.ys);
-    if (!direct) {
-      RowsPrepArgs ry{};
-      ry.x = ws + L.yf; ry.s0 = 0; ry.s1 = 0; ry.s2 = C;
-      ry.H = 1; ry.R = tokens; ry.rows = tokens; ry.D = C; ry.nb = nbk; ry.dpad = 32 * nbk;
-      ry.vec4 = C % 4 == 0;
-      ry.op_kind = MXA_OP_MXINT8; ry.flush = pp.flush_subnormals; ry.bfloat = pp.bfloat; ry.dt = MXA_DT_F32;
-      ry.codes = yc; ry.sT = ys; ry.mfma_rows = 1;
-      rc = launch_rows_prep(ry, stream);
+    if (!direct) {  // (the workspace's yf is 16-B aligned)
+      rc = launch_rows_prep(flat_rows_prep(ws + L.yf, tokens, C, C, C % 4 == 0, pp.flush_subnormals, pp.bfloat, yc, ys, 1), stream);
       if (rc) return rc;
     }
     rc = launch_linear_codes(yc, ys, tokens, C, pj->wq, pj->out_features, pj->bias, pj->y, pj->y_row_stride,
@@ -552,7 +540,7 @@ static int matmul_impl(const void* a, const void* b, bool bt_rows, void* c, int6
     if (dt < MXA_DT_F32 || dt > MXA_DT_BF16) return MXA_ERR_ARG;
   if ((elem_mbits_a != 8 && elem_mbits_a != 4) || (elem_mbits_b != 8 && elem_mbits_b != 4))
     return MXA_ERR_UNSUPPORTED;
-  if (bfloat != 0 && bfloat != 32 && (bfloat < 10 || bfloat > 31)) return MXA_ERR_ARG;
+  if (!valid_bfloat(bfloat)) return MXA_ERR_ARG;
   const int64_t need = mxa_matmul_workspace_bytes(batch, M, K, Nc);
   if (!workspace || workspace_bytes < need) return MXA_ERR_WORKSPACE;
   const int nbk = (K + 31) / 32, kpad = nbk * 32;

@@ -289,6 +289,9 @@ __device__ __forceinline__ uint32_t half_reduce(uint32_t v, Op op) {
 __device__ __forceinline__ uint32_t wave_max_u32(uint32_t v) {
   return wave_reduce(v, [](uint32_t x, uint32_t y) { return x > y ? x : y; });
 }
+__device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
+  return wave_reduce(v, [](uint32_t x, uint32_t y) { return x < y ? x : y; });
+}
 
 __device__ __forceinline__ float wave_max_f32(float v) {
   return __uint_as_float(wave_reduce(__float_as_uint(v), [](uint32_t x, uint32_t y) {

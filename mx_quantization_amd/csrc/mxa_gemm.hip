@@ -7,26 +7,20 @@
 
 namespace mxa {
 
-// shifted int32 block sums stay exact while nbk * 32 * 127^2 * 2^smax < 2^31
 int gemm_smax(int nbk) {
   int s = -1;
   while ((int64_t)nbk * 516128 * ((int64_t)1 << (s + 1)) < ((int64_t)1 << 31)) ++s;
   return s;
 }
 
-template <bool PLAIN>
-static int launch_gemm_p(const GemmArgs& ga0, int64_t batch, hipStream_t stream) {
-  GemmArgs ga = ga0;
-  ga.smax = gemm_smax(ga.nbk);
-  // the tile shape (mxa_gemm.hpp GemmShape): products of <= 64 columns on 128 x 64 tiles;
-  // float32 products of 65..256 contiguous columns on 32-row strips of whole rows; else 64 x 128
-  const int sh = ga.Nc <= GemmShape<kGemmTall>::CW                           ? kGemmTall
-                 : PLAIN && ga.Nc <= GemmShape<kGemmWide>::CW && ga.ldc == ga.Nc ? kGemmWide
-                                                                              : kGemmSquare;
-  const int RW = sh == kGemmTall ? GemmShape<kGemmTall>::RW : sh == kGemmWide ? GemmShape<kGemmWide>::RW : GemmShape<kGemmSquare>::RW;
-  const int CW = sh == kGemmTall ? GemmShape<kGemmTall>::CW : sh == kGemmWide ? GemmShape<kGemmWide>::CW : GemmShape<kGemmSquare>::CW;
-  const size_t lds = gemm_lds(ga.nbk, sh).total;
-  const int64_t gx = (ga.Nc + CW - 1) / CW, gy = (ga.M + RW - 1) / RW;
+// The launch on one tile shape (mxa_gemm.hpp GemmShape<SH>); ga.smax is set.  A prepared
+// weight's digit kernel launches from here too, behind the shape's refusal tests: a Linear
+// the tile kernel would refuse is refused whichever kernel would run it.
+template <bool PLAIN, int SH>
+static int launch_gemm_shape(const GemmArgs& ga, int64_t batch, hipStream_t stream) {
+  using S = GemmShape<SH>;
+  const size_t lds = gemm_lds(ga.nbk, SH).total;
+  const int64_t gx = (ga.Nc + S::CW - 1) / S::CW, gy = (ga.M + S::RW - 1) / S::RW;
   if (lds > 160 * 1024 || gy > 65535) return MXA_ERR_UNSUPPORTED;
   if (ga.bpd && batch == 1 && ga.nbk <= kGemmDigNbkMax) {
     // a prepared weight: the exponent-folded digits, every row block in the one launch (a
@@ -37,11 +31,7 @@ static int launch_gemm_p(const GemmArgs& ga0, int64_t batch, hipStream_t stream)
     hipLaunchKernelGGL(mx_gemm_dig_kernel<PLAIN>, dim3((unsigned)((ga.M + 31) / 32)), dim3(256), dl, stream, ga);
     return hipGetLastError() == hipSuccess ? MXA_OK : MXA_ERR_LAUNCH;
   }
-  // (the wide strip stages float32 rows: only the PLAIN instantiation has it)
-  constexpr int kWide = PLAIN ? kGemmWide : kGemmSquare;
-  const void* gk = sh == kGemmTall   ? reinterpret_cast<const void*>(&mx_gemm_kernel<PLAIN, kGemmTall>)
-                   : sh == kGemmWide ? reinterpret_cast<const void*>(&mx_gemm_kernel<PLAIN, kWide>)
-                                     : reinterpret_cast<const void*>(&mx_gemm_kernel<PLAIN, kGemmSquare>);
+  const void* gk = reinterpret_cast<const void*>(&mx_gemm_kernel<PLAIN, SH>);
   if (hipFuncSetAttribute(gk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return MXA_ERR_LAUNCH;
   // grid.z <= 65535: larger batches in slices; a wave whose spreads the int32 sums cannot
   // take sums its blocks in fp64 itself (gemm_tile's run_f64): one launch per slice
@@ -51,13 +41,23 @@ static int launch_gemm_p(const GemmArgs& ga0, int64_t batch, hipStream_t stream)
     gs.a += b0 * ga.a_bat; gs.ae += b0 * ga.ae_bat; gs.b += b0 * ga.b_bat; gs.be += b0 * ga.be_bat;
     gs.c = static_cast<unsigned char*>(ga.c) + b0 * ga.c_bat * esz;
     const int64_t nb = std::min<int64_t>(65535, batch - b0);
-    const dim3 grid((unsigned)gx, (unsigned)gy, (unsigned)nb);
-    if (sh == kGemmTall) hipLaunchKernelGGL((mx_gemm_kernel<PLAIN, kGemmTall>), grid, dim3(256), lds, stream, gs);
-    else if (sh == kGemmWide) hipLaunchKernelGGL((mx_gemm_kernel<PLAIN, kWide>), grid, dim3(256), lds, stream, gs);
-    else hipLaunchKernelGGL((mx_gemm_kernel<PLAIN, kGemmSquare>), grid, dim3(256), lds, stream, gs);
+    hipLaunchKernelGGL((mx_gemm_kernel<PLAIN, SH>), dim3((unsigned)gx, (unsigned)gy, (unsigned)nb), dim3(256), lds, stream, gs);
     if (hipGetLastError() != hipSuccess) return MXA_ERR_LAUNCH;
   }
   return MXA_OK;
+}
+
+// the tile shape: products of <= 64 columns on 128 x 64 tiles; float32 products of 65..256
+// contiguous columns on 32-row strips of whole rows (the strip stages float32 rows: only the
+// PLAIN instantiation has it); else 64 x 128
+template <bool PLAIN>
+static int launch_gemm_p(const GemmArgs& ga0, int64_t batch, hipStream_t stream) {
+  GemmArgs ga = ga0;
+  ga.smax = gemm_smax(ga.nbk);
+  if (ga.Nc <= GemmShape<kGemmTall>::CW) return launch_gemm_shape<PLAIN, kGemmTall>(ga, batch, stream);
+  if constexpr (PLAIN)
+    if (ga.Nc <= GemmShape<kGemmWide>::CW && ga.ldc == ga.Nc) return launch_gemm_shape<true, kGemmWide>(ga, batch, stream);
+  return launch_gemm_shape<PLAIN, kGemmSquare>(ga, batch, stream);
 }
 
 int launch_gemm(const GemmArgs& ga, int64_t batch, hipStream_t stream) {
@@ -115,7 +115,7 @@ extern "C" int mxa_linear(const float* x, int64_t rows, int32_t in_features, int
   if (!x || !wq || !out || rows <= 0 || in_features <= 0 || out_features <= 0 || x_row_stride < in_features ||
       out_row_stride < out_features)
     return MXA_ERR_ARG;
-  if (bfloat != 0 && bfloat != 32 && (bfloat < 10 || bfloat > 31)) return MXA_ERR_ARG;
+  if (!valid_bfloat(bfloat)) return MXA_ERR_ARG;
   if (autocast_dtype != 0 && autocast_dtype != MXA_DT_F16 && autocast_dtype != MXA_DT_BF16) return MXA_ERR_ARG;
   if (!linear_weight_verify_any_group(wq, out_features, in_features, flush_subnormals, bfloat, stream))
     return MXA_ERR_ARG;
@@ -123,15 +123,10 @@ extern "C" int mxa_linear(const float* x, int64_t rows, int32_t in_features, int
   if (!workspace || workspace_bytes < need || !aligned16(workspace)) return MXA_ERR_WORKSPACE;
   const int nbk = (in_features + 31) / 32, Cpad = 32 * nbk;
   unsigned char* ws = static_cast<unsigned char*>(workspace);
-  RowsPrepArgs rx{};
-  rx.x = x; rx.s0 = 0; rx.s1 = 0; rx.s2 = x_row_stride;
-  rx.H = 1; rx.R = rows; rx.rows = rows; rx.D = in_features; rx.nb = nbk; rx.dpad = Cpad;
-  rx.vec4 = aligned16(x) && x_row_stride % 4 == 0;
-  rx.op_kind = MXA_OP_MXINT8; rx.flush = flush_subnormals; rx.bfloat = bfloat; rx.dt = MXA_DT_F32;
   const int64_t rows32 = (rows + 31) / 32 * 32;
-  rx.codes = reinterpret_cast<int8_t*>(ws);
-  rx.mfma_rows = 1;
-  rx.sT = reinterpret_cast<int16_t*>(ws + (rows32 * Cpad + 255) / 256 * 256);
+  const RowsPrepArgs rx = flat_rows_prep(x, rows, in_features, x_row_stride, aligned16(x) && x_row_stride % 4 == 0,
+                                         flush_subnormals, bfloat, reinterpret_cast<int8_t*>(ws),
+                                         reinterpret_cast<int16_t*>(ws + (rows32 * Cpad + 255) / 256 * 256), 1);
   int rc = launch_rows_prep(rx, stream);
   if (rc) return rc;
   return launch_linear_codes(rx.codes, rx.sT, rows, in_features, wq, out_features, bias, out, out_row_stride, bfloat,

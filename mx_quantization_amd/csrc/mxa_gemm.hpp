@@ -24,7 +24,7 @@
 // beyond; the reference's own fp32 GEMM order is unpinned).  The MFMA of
 // block j + 1 is issued before the epilogue of block j.
 #pragma once
-#include "mxa_proj_args.hpp"
+#include "mxa_gemm_parts.hpp"
 
 namespace mxa {
 
@@ -86,8 +86,6 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& a, int64_t bat, int tm
   using S = GemmShape<SH>;
   constexpr bool kStage = SH == kGemmWide;  // (PLAIN, one column tile, ldc == Nc: the launcher)
   constexpr int RW = S::RW, CW = S::CW, RPT = S::RPT, CPT = S::CPT;
-  typedef int v16i_g __attribute__((ext_vector_type(16)));
-  typedef int v4i_g __attribute__((ext_vector_type(4)));
   const int nbk = a.nbk;
   const GemmLds L = gemm_lds(nbk, SH);
   int16_t* xe = reinterpret_cast<int16_t*>(smem + L.xe);
@@ -115,8 +113,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& a, int64_t bat, int tm
                       : a.a_mfma ? abase + (((int64_t)(m >> 5) * nbk + kb) * 64 + (m & 31)) * 16
                                  : abase + (int64_t)m * a.lda + 32 * kb;
     const int hoff = (isrow && a.a_mfma) ? 512 : 16;  // the block's second 16 elements
-    const uint4 u = *reinterpret_cast<const uint4*>(p), v = *reinterpret_cast<const uint4*>(p + hoff);
-    return ((u.x | u.y | u.z | u.w) | (v.x | v.y | v.z | v.w)) == 0u;
+    return codes32_zero(*reinterpret_cast<const uint4*>(p), *reinterpret_cast<const uint4*>(p + hoff));
   };
   // Per row RPT threads and per column CPT threads reduce strided K-block subsets (consecutive
   // threads on consecutive exponents: coalesced, independent loads), partials through LDS.
@@ -215,18 +212,12 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& a, int64_t bat, int tm
   const int ln = lane & 31, kh = 16 * (lane >> 5), m0 = 4 * (lane >> 5);
   // the wave's fast-path test: its rows' largest spread + its columns' largest spread,
   // and the smallest output scale (a subnormal result would round twice)
-  auto wmax = [](int v) {
-    return (int)wave_reduce((uint32_t)(v + (1 << 20)), [](uint32_t x, uint32_t y) { return x > y ? x : y; }) - (1 << 20);
-  };
-  auto wmin = [](int v) {
-    return (int)wave_reduce((uint32_t)(v + (1 << 20)), [](uint32_t x, uint32_t y) { return x < y ? x : y; }) - (1 << 20);
-  };
   const int rr = wr0 + ln, cc = wc0 + lane;
   const bool rv = m0g + rr < a.M, cv = n0g + cc < a.Nc;
   // spreads (row rr: lanes 0..31 and 32..63 alike)
   const int rsp = rhi_[rr] - rlo[rr], csp = chi[cc] - clo[cc];
-  const int srow = wmax(rv ? rsp : 0), scol = wmax(cv ? csp : 0);
-  const int lrow = wmin(rv ? rlo[rr] : (1 << 19)), lcol = wmin(cv ? clo[cc] : (1 << 19));
+  const int srow = wave_max_e(rv ? rsp : 0), scol = wave_max_e(cv ? csp : 0);
+  const int lrow = wave_min_e(rv ? rlo[rr] : (1 << 19)), lcol = wave_min_e(cv ? clo[cc] : (1 << 19));
   const bool fast = srow + scol <= a.smax && lrow + lcol >= -126;
 
   const int arow = min(m0g + wr0 + ln, a.M - 1);
@@ -252,9 +243,9 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& a, int64_t bat, int tm
     bp1 = a.b + bat * a.b_bat + (int64_t)bc1 * a.ldb + kh;
     bstep = 32;
   }
-  auto ld = [astep](const int8_t* p, int kb) { return *reinterpret_cast<const v4i_g*>(p + (int64_t)astep * kb); };
-  auto ldb = [bstep](const int8_t* p, int kb) { return *reinterpret_cast<const v4i_g*>(p + (int64_t)bstep * kb); };
-  const v16i_g zero = {};
+  auto ld = [astep](const int8_t* p, int kb) { return *reinterpret_cast<const v4i_*>(p + (int64_t)astep * kb); };
+  auto ldb = [bstep](const int8_t* p, int kb) { return *reinterpret_cast<const v4i_*>(p + (int64_t)bstep * kb); };
+  const v16i zero = {};
   const int last = nbk - 1;
   const int16_t* xrow = xe + wr0 + m0;
   const int16_t* xcol = ce + wc0 + ln;
@@ -272,8 +263,9 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& a, int64_t bat, int tm
     } else if constexpr (PLAIN) {
       static_cast<float*>(a.c)[off] = a.bias ? o + a.bias[n] : o;
     } else if (a.linear) {
-      // autocast: F.linear returns the dtype, then the output rounding (linear.py:88-92),
-      // then + fp32 bias promotes back (the same order as the mx.matmul branch below)
+      // linear_out's two lines, written out: here the bias is loaded and rounded per element,
+      // behind the first rounding and only when there is one; through the helper (the bias
+      // rounded ahead of the call) the kernel's SGPR spills went from 23 to 25
       o = round_bfloat(round_dt(o, a.autocast), a.bfloat, kRoundNearest, 1, a.autocast);
       if (a.bias) o = round_bfloat(o + round_bfloat(a.bias[n], a.bfloat, kRoundNearest, 1), a.bfloat, kRoundNearest, 1);
       static_cast<float*>(a.c)[off] = o;
@@ -292,7 +284,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& a, int64_t bat, int tm
 #pragma unroll
       for (int i = 0; i < 16; ++i) acc[i] = 0.0;
       for (int kb = 0; kb < nbk; ++kb) {
-        const v16i_g c = __builtin_amdgcn_mfma_i32_32x32x32_i8(ld(ap, kb), ldb(bp, kb), zero, 0, 0, 0);
+        const v16i c = __builtin_amdgcn_mfma_i32_32x32x32_i8(ld(ap, kb), ldb(bp, kb), zero, 0, 0, 0);
         const int dc = xcol[kb * CW + 32 * j] + lc;
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
@@ -311,7 +303,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& a, int64_t bat, int tm
 #pragma unroll
     for (int i = 0; i < 16; ++i) acc0[i] = acc1[i] = 0;
     // block kb's shifted sums: row offset (4 rows per uint2 read) + column offset
-    auto epi = [&](const v16i_g& c0, const v16i_g& c1, int kb) {
+    auto epi = [&](const v16i& c0, const v16i& c1, int kb) {
       const int d0 = xcol[kb * CW], d1 = xcol[kb * CW + 32];
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
@@ -330,13 +322,13 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& a, int64_t bat, int tm
     // line of each row, so it is fetched once), then the two epilogues run while those
     // loads are in flight.  Operands of a pair: E (even block) and O (odd block) slots.
     const int last2 = last;
-    v4i_g aE = ld(ap, 0), bE0 = ldb(bp0, 0), bE1 = ldb(bp1, 0);
-    v4i_g aO = ld(ap, min(1, last2)), bO0 = ldb(bp0, min(1, last2)), bO1 = ldb(bp1, min(1, last2));
+    v4i_ aE = ld(ap, 0), bE0 = ldb(bp0, 0), bE1 = ldb(bp1, 0);
+    v4i_ aO = ld(ap, min(1, last2)), bO0 = ldb(bp0, min(1, last2)), bO1 = ldb(bp1, min(1, last2));
     for (int kb = 0; kb < nbk; kb += 2) {
       const bool h1 = kb + 1 < nbk;
-      const v16i_g cA0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(aE, bE0, zero, 0, 0, 0);
-      const v16i_g cA1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(aE, bE1, zero, 0, 0, 0);
-      v16i_g cB0 = zero, cB1 = zero;
+      const v16i cA0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(aE, bE0, zero, 0, 0, 0);
+      const v16i cA1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(aE, bE1, zero, 0, 0, 0);
+      v16i cB0 = zero, cB1 = zero;
       if (h1) {
         cB0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(aO, bO0, zero, 0, 0, 0);
         cB1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(aO, bO1, zero, 0, 0, 0);
@@ -411,8 +403,6 @@ constexpr int kGemmDigNbkMax = 72;  // 2 KB of LDS per K-block: <= 144 KB
 
 template <bool PLAIN>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) void mx_gemm_dig_kernel(GemmArgs a) {
-  typedef int v16i_g __attribute__((ext_vector_type(16)));
-  typedef int v4i_g __attribute__((ext_vector_type(4)));
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int nbk = a.nbk;
   const GemmDigLds L = gemm_dig_lds(nbk);
@@ -445,11 +435,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
       rn[m] = 1;
       continue;
     }
-    if (e <= -128) {
-      const uint4 u = *reinterpret_cast<const uint4*>(code_at(m, kb, 0));
-      const uint4 v = *reinterpret_cast<const uint4*>(code_at(m, kb, 1));
-      if (((u.x | u.y | u.z | u.w) | (v.x | v.y | v.z | v.w)) == 0u) continue;
-    }
+    if (e <= -128 && codes32_zero(*reinterpret_cast<const uint4*>(code_at(m, kb, 0)),
+                                  *reinterpret_cast<const uint4*>(code_at(m, kb, 1))))
+      continue;
     atomicMin(&rlo[m], e);
     atomicMax(&rhi[m], e);
   }
@@ -457,26 +445,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
   if (wave == 0) {  // the block's gate: row spreads, the weight's column spreads, subnormal results
     const int m = lane & 31;
     const bool em = rlo[m] > rhi[m];
-    const uint32_t smx = wave_reduce(lane < 32 && !em ? (uint32_t)(rhi[m] - rlo[m]) : 0u,
-                                     [](uint32_t u, uint32_t w) { return u > w ? u : w; });
-    const uint32_t lmn = wave_reduce(lane < 32 && !em ? (uint32_t)(rlo[m] + (1 << 20)) : 0xFFFFFFFFu,
-                                     [](uint32_t u, uint32_t w) { return u < w ? u : w; });
+    const uint32_t smx = wave_max_u32(lane < 32 && !em ? (uint32_t)(rhi[m] - rlo[m]) : 0u);
+    const uint32_t lmn = wave_min_u32(lane < 32 && !em ? (uint32_t)(rlo[m] + (1 << 20)) : 0xFFFFFFFFu);
     uint32_t gsp = 0, glo = 0xFFFFFFFFu;
     for (int g = lane; g < a.bG; g += 64) {
       gsp = max(gsp, (uint32_t)a.bgs[2 * g + 1]);
       glo = min(glo, (uint32_t)(a.bgs[2 * g] + (1 << 20)));
     }
-    gsp = wave_reduce(gsp, [](uint32_t u, uint32_t w) { return u > w ? u : w; });
-    glo = wave_reduce(glo, [](uint32_t u, uint32_t w) { return u < w ? u : w; });
+    gsp = wave_max_u32(gsp);
+    glo = wave_min_u32(glo);
     const bool ok = smx <= (uint32_t)kDigitSpread && gsp <= (uint32_t)kDigitSpread &&
                     (lmn == 0xFFFFFFFFu || (int)lmn + (int)glo - (2 << 20) >= -126);
     if (lane == 0) st[0] = ok;
   }
   __syncthreads();
-  const int ncb = (a.Nc + 31) / 32, last = nbk - 1;
+  const int ncb = (a.Nc + 31) / 32;
   const int ln = lane & 31, m0 = 4 * (lane >> 5);
-  // out = bf(fl32(sum)); out = bf(out + bf(bias))  (linear.py:88-101) for element i of the
-  // lane's 32 x 32 tile of column block cb; value(i, m) the fp32 sum of row m
+  // the Linear output (linear_out) of element i of the lane's 32 x 32 tile of column block
+  // cb; value(i, m) the fp32 sum of row m
   auto store_out = [&](int cb, auto&& value) {
     const int n = 32 * cb + ln;
     if (n >= a.Nc) return;
@@ -487,18 +473,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
       const int m = 8 * (i >> 2) + m0 + (i & 3);
       if (m >= rows) continue;
       float o = (cnan || rn[m]) ? __uint_as_float(0x7FC00000u) : value(i, m);
-      if constexpr (PLAIN) {
-        o = a.bias ? o + bb : o;
-      } else {
-        // autocast: F.linear returns the dtype, then the output rounding, then + fp32 bias
-        o = round_bfloat(round_dt(o, a.autocast), a.bfloat, kRoundNearest, 1, a.autocast);
-        if (a.bias) o = round_bfloat(o + bb, a.bfloat, kRoundNearest, 1);
-      }
+      if constexpr (PLAIN) o = a.bias ? o + bb : o;
+      else o = linear_out(o, bb, a.bias != nullptr, a.bfloat, a.autocast);
       static_cast<float*>(a.c)[(int64_t)(m0g + m) * a.ldc + n] = o;
     }
   };
   if (!st[0]) {  // (uniform over the workgroup) the fp64 block sums
-    const v16i_g zero = {};
+    const v16i zero = {};
     for (int cb = wave; cb < ncb; cb += 4) {
       const int8_t* bp = a.bpk + ((int64_t)min(cb, a.b_nb32 - 1) * nbk * 64 + lane) * 16;
       const int n = min(32 * cb + ln, a.Nc - 1);
@@ -506,9 +487,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
 #pragma unroll
       for (int i = 0; i < 16; ++i) acc[i] = 0.0;
       for (int kb = 0; kb < nbk; ++kb) {
-        const v4i_g av = *reinterpret_cast<const v4i_g*>(code_at(min(ln, rows - 1), kb, lane >> 5));
-        const v4i_g bv = *reinterpret_cast<const v4i_g*>(bp + (int64_t)kb * 1024);
-        const v16i_g c = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, bv, zero, 0, 0, 0);
+        const v4i_ av = *reinterpret_cast<const v4i_*>(code_at(min(ln, rows - 1), kb, lane >> 5));
+        const v4i_ bv = *reinterpret_cast<const v4i_*>(bp + (int64_t)kb * 1024);
+        const v16i c = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, bv, zero, 0, 0, 0);
         const int eb = exp_from16(a.be[(int64_t)n * a.be_n + (int64_t)kb * a.be_k]);
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
@@ -542,39 +523,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
 
   // ---- per wave: 32-column blocks wave, wave + 4, ... --------------------------------
   const int8_t* adl = ad + lane * 16;
-  auto cl = [&](int kb) { return min(kb, last); };
   for (int cb = wave; cb < ncb; cb += 4) {
     const int8_t* bp = a.bpd + (int64_t)cb * nbk * 2048 + lane * 16;
-    auto ldd = [&](int kb, int p) { return *reinterpret_cast<const v4i_g*>(bp + (int64_t)kb * 2048 + p * 1024); };
-    v16i_g c0 = {}, c1 = {}, c2 = {};
-    v4i_g L0 = ldd(0, 0), H0 = ldd(0, 1), L1 = ldd(cl(1), 0), H1 = ldd(cl(1), 1);
-    v4i_g L2 = ldd(cl(2), 0), H2 = ldd(cl(2), 1), L3 = ldd(cl(3), 0), H3 = ldd(cl(3), 1);
-    auto step = [&](int kb, v4i_g& Ls, v4i_g& Hs) {
-      const v4i_g al = *reinterpret_cast<const v4i_g*>(adl + kb * 2048);
-      const v4i_g ah = *reinterpret_cast<const v4i_g*>(adl + kb * 2048 + 1024);
-      c0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(al, Ls, c0, 0, 0, 0);
-      c1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(al, Hs, c1, 0, 0, 0);
-      c2 = __builtin_amdgcn_mfma_i32_32x32x32_i8(ah, Hs, c2, 0, 0, 0);
-      c1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(ah, Ls, c1, 0, 0, 0);
-      Ls = ldd(cl(kb + 4), 0);
-      Hs = ldd(cl(kb + 4), 1);
-      __builtin_amdgcn_sched_barrier(0);  // reload each slot right after its use
-    };
-    int kb = 0;
-    for (; kb + 4 <= nbk; kb += 4) {
-      step(kb, L0, H0);
-      step(kb + 1, L1, H1);
-      step(kb + 2, L2, H2);
-      step(kb + 3, L3, H3);
-    }
-    if (kb < nbk) step(kb, L0, H0);
-    if (kb + 1 < nbk) step(kb + 1, L1, H1);
-    if (kb + 2 < nbk) step(kb + 2, L2, H2);
+    const DigitSums d = digit_k_loop(
+        [&](int kb, int p) { return *reinterpret_cast<const v4i_*>(bp + (int64_t)kb * 2048 + p * 1024); }, adl, adl + 1024,
+        2048, nbk);
     const int clo = a.bps[2 * min(32 * cb + ln, a.Nc - 1)];
     store_out(cb, [&](int i, int m) {
-      const int lo = rlo[m] > rhi[m] ? 0 : rlo[m];
-      const double v = (double)c0[i] + 256.0 * (double)c1[i] + 65536.0 * (double)c2[i];
-      return (float)ldexp(v, lo + clo);
+      return digits_to_f32(d.c0[i], d.c1[i], d.c2[i], (rlo[m] > rhi[m] ? 0 : rlo[m]) + clo);
     });
   }
 }

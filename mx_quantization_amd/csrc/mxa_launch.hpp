@@ -10,6 +10,22 @@
 namespace mxa {
 
 inline bool aligned16(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15u) == 0; }
+// the bfloat settings of include/mxa.h: 0 / 32 (no rounding) or bfloat10 .. bfloat31
+inline bool valid_bfloat(int bfloat) { return bfloat == 0 || bfloat == 32 || (bfloat >= 10 && bfloat <= 31); }
+// RowsPrepArgs of a float32 row-major matrix (rows x cols, row_stride elements from row to
+// row) -> MXINT8 rows along its last axis: codes [rows][32 nb] (mfma_rows: in the MX GEMM's
+// MFMA-ready row blocks) and block exponents [rows][nb].  vec4: the caller's own test that x
+// may be read in 16-B loads
+inline RowsPrepArgs flat_rows_prep(const void* x, int64_t rows, int cols, int64_t row_stride, bool vec4, int flush,
+                                   int bfloat, int8_t* codes, int16_t* exps, int mfma_rows) {
+  RowsPrepArgs r{};
+  r.x = x; r.s0 = 0; r.s1 = 0; r.s2 = row_stride;
+  r.H = 1; r.R = rows; r.rows = rows; r.D = cols; r.nb = (cols + 31) / 32; r.dpad = 32 * r.nb;
+  r.vec4 = vec4;
+  r.op_kind = MXA_OP_MXINT8; r.flush = flush; r.bfloat = bfloat; r.dt = MXA_DT_F32;
+  r.codes = codes; r.sT = exps; r.mfma_rows = mfma_rows;
+  return r;
+}
 
 // selection kernel (mxa_sel.hip); plan: only check the LDS budget, launch nothing
 int launch_select(const Rows2Args& ra, int mode, int BH, hipStream_t stream, bool plan);
@@ -162,6 +178,9 @@ bool linear_weight_verify(const void* wq, const LinearWeightHeader& want, hipStr
 bool linear_weight_verify_any_group(const void* wq, int out_f, int in_f, int flush, int bfloat, hipStream_t stream);
 // the header of a prepared weight this process has seen (verified or prepared)
 bool linear_weight_known_header(const void* wq, LinearWeightHeader* h);
+// the largest row + column exponent spread whose shifted int32 block sums stay exact over
+// nbk K-blocks: nbk * 32 * 127^2 * 2^smax < 2^31 (mxa_gemm.hip)
+int gemm_smax(int nbk);
 // block-scaled MX GEMM (mxa_gemm.hip); mx.Linear on MX rows with a prepared weight
 // (slow: gemm_slow_bytes of device scratch for the list of waves the fp64 kernel takes)
 int launch_gemm(const GemmArgs& ga, int64_t batch, hipStream_t stream);

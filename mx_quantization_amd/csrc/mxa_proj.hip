@@ -191,23 +191,6 @@ static void linear_weight_note(const void* wq, const LinearWeightHeader& h) {
   g_weights[wq] = h;
 }
 
-bool linear_weight_verify(const void* wq, const LinearWeightHeader& want, hipStream_t stream) {
-  {
-    std::lock_guard<std::mutex> g(g_wmu);
-    auto it = g_weights.find(wq);
-    if (it != g_weights.end()) return it->second == want;
-  }
-  // a buffer prepared elsewhere (another process, or copied): read its header once
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return false;
-  LinearWeightHeader h{};
-  if (hipMemcpyAsync(&h, wq, sizeof(h), hipMemcpyDeviceToHost, stream) != hipSuccess) return false;
-  if (hipStreamSynchronize(stream) != hipSuccess) return false;
-  if (!(h == want)) return false;
-  linear_weight_note(wq, h);
-  return true;
-}
-
 bool linear_weight_known_header(const void* wq, LinearWeightHeader* h) {
   std::lock_guard<std::mutex> g(g_wmu);
   auto it = g_weights.find(wq);
@@ -216,24 +199,31 @@ bool linear_weight_known_header(const void* wq, LinearWeightHeader* h) {
   return true;
 }
 
+// a buffer prepared elsewhere (another process, or copied): its header read from the device
+// (a synchronisation: not under stream capture); the caller notes it once it has checked it
+static bool linear_weight_fetch_header(const void* wq, hipStream_t stream, LinearWeightHeader* h) {
+  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+  if (hipStreamIsCapturing(stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return false;
+  if (hipMemcpyAsync(h, wq, sizeof(*h), hipMemcpyDeviceToHost, stream) != hipSuccess) return false;
+  return hipStreamSynchronize(stream) == hipSuccess;
+}
+
+bool linear_weight_verify(const void* wq, const LinearWeightHeader& want, hipStream_t stream) {
+  LinearWeightHeader h{};
+  if (linear_weight_known_header(wq, &h)) return h == want;
+  if (!linear_weight_fetch_header(wq, stream, &h) || !(h == want)) return false;
+  linear_weight_note(wq, h);
+  return true;
+}
+
 bool linear_weight_verify_any_group(const void* wq, int out_f, int in_f, int flush, int bfloat, hipStream_t stream) {
   LinearWeightHeader h{};
-  bool known = false;
-  {
-    std::lock_guard<std::mutex> g(g_wmu);
-    auto it = g_weights.find(wq);
-    if (it != g_weights.end()) h = it->second, known = true;
-  }
-  if (!known) {
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return false;
-    if (hipMemcpyAsync(&h, wq, sizeof(h), hipMemcpyDeviceToHost, stream) != hipSuccess) return false;
-    if (hipStreamSynchronize(stream) != hipSuccess) return false;
+  if (!linear_weight_known_header(wq, &h)) {
+    if (!linear_weight_fetch_header(wq, stream, &h)) return false;
     if (h.magic != kLinearWeightMagic || h.gw <= 0 || h.out_f % h.gw) return false;
     linear_weight_note(wq, h);
   }
-  LinearWeightHeader want = linear_weight_header(out_f, in_f, h.gw, flush, bfloat);
-  return h == want;
+  return h == linear_weight_header(out_f, in_f, h.gw, flush, bfloat);
 }
 
 LinearWeightHeader linear_weight_header(int out_f, int in_f, int gw, int flush, int bfloat) {
@@ -256,17 +246,13 @@ extern "C" int mxa_linear_weight_prep(const float* w, int32_t out_features, int3
                                       int32_t flush_subnormals, int32_t bfloat, void* wq, hipStream_t stream) {
   if (!w || !wq || out_features <= 0 || in_features <= 0 || group_width <= 0 || out_features % group_width)
     return MXA_ERR_ARG;
-  if (bfloat != 0 && bfloat != 32 && (bfloat < 10 || bfloat > 31)) return MXA_ERR_ARG;
+  if (!valid_bfloat(bfloat)) return MXA_ERR_ARG;
   if (!aligned16(wq)) return MXA_ERR_ARG;
   const LinearLayout W = linear_layout(out_features, in_features, group_width);
   unsigned char* wb = static_cast<unsigned char*>(wq);
-  RowsPrepArgs rw{};
-  rw.x = w; rw.s0 = 0; rw.s1 = 0; rw.s2 = in_features;
-  rw.H = 1; rw.R = out_features; rw.rows = out_features; rw.D = in_features; rw.nb = W.nbk; rw.dpad = W.Cpad;
-  rw.vec4 = aligned16(w) && in_features % 4 == 0;
-  rw.op_kind = MXA_OP_MXINT8; rw.flush = flush_subnormals; rw.bfloat = bfloat;
-  rw.codes = reinterpret_cast<int8_t*>(wb + W.rawc);
-  rw.sT = reinterpret_cast<int16_t*>(wb + W.rawe);
+  const RowsPrepArgs rw = flat_rows_prep(w, out_features, in_features, in_features, aligned16(w) && in_features % 4 == 0,
+                                         flush_subnormals, bfloat, reinterpret_cast<int8_t*>(wb + W.rawc),
+                                         reinterpret_cast<int16_t*>(wb + W.rawe), 0);
   int rc = launch_rows_prep(rw, stream);
   if (rc) return rc;
   const int64_t pcols = (int64_t)W.G * W.NB32 * 32;

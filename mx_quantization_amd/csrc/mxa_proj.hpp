@@ -18,11 +18,9 @@
 // from q, k, v: q and k rows (codes, block exponents, approximator operands) and V's
 // codes along the 32 tokens (transposed) -- the fp32 q / k / v never reach HBM.
 #pragma once
-#include <type_traits>
-
 #include "mxa_finish.hpp"
+#include "mxa_gemm_parts.hpp"
 #include "mxa_prep.hpp"
-#include "mxa_proj_args.hpp"
 
 namespace mxa {
 
@@ -65,10 +63,6 @@ __host__ __device__ inline ProjLds proj_lds(int Cpad, int nbk, int D) {
 
 // One workgroup per (32-token block, image, head group), looping over the group's heads; 3 * NBD waves,
 // wave (s, cb) = sub-matrix s (q, k, v) and its 32-column block cb of the head.
-#ifndef MXA_PROJ_SKIP
-#define MXA_PROJ_SKIP 0  // tools-only timing variants (never the product): 1 no K loop, 2 no operand epilogue,
-                         // 4 the digit loop re-reads its first block (L1-resident weights)
-#endif
 // PLAIN (proj_plain): no bfloat rounding, no flush, no autocast, q / k operands of
 // rows_prep_block_plain and V's MXINT8 -- the bench path, compiled without the general
 // rounding code (a third of the code and registers of the general instantiation).
@@ -156,9 +150,8 @@ __device__ __forceinline__ void proj_block(const ProjArgs& a, int tb, int b, int
     const int m = lane & 31;
     const bool em = rlo[m] > rhi[m];
     const int lo = em ? 0 : rlo[m], sp = em ? 0 : rhi[m] - lo;
-    const uint32_t smx = wave_reduce(lane < 32 ? (uint32_t)sp : 0u, [](uint32_t u, uint32_t w) { return u > w ? u : w; });
-    const uint32_t bmn = wave_reduce(lane < 32 ? (uint32_t)(lo + (1 << 20)) : 0xFFFFFFFFu,
-                                     [](uint32_t u, uint32_t w) { return u < w ? u : w; });
+    const uint32_t smx = wave_max_u32(lane < 32 ? (uint32_t)sp : 0u);
+    const uint32_t bmn = wave_min_u32(lane < 32 ? (uint32_t)(lo + (1 << 20)) : 0xFFFFFFFFu);
     // the digit path: every row's spread and every column spread of the workgroup's
     // heads within kDigitSpread (the weight's folded digits exist for those columns)
     uint32_t gmx = 0;
@@ -166,7 +159,7 @@ __device__ __forceinline__ void proj_block(const ProjArgs& a, int tb, int b, int
       const int hh = h_begin + i / 3, s3 = i - 3 * (i / 3);
       gmx = max(gmx, (uint32_t)a.gs[2 * (s3 * a.H + hh) + 1]);
     }
-    gmx = wave_reduce(gmx, [](uint32_t u, uint32_t w) { return u > w ? u : w; });
+    gmx = wave_max_u32(gmx);
     if (lane == 0) {
       st[0] = (int)smx;
       st[1] = (int)bmn - (1 << 20);
@@ -244,9 +237,9 @@ __device__ __forceinline__ void proj_block(const ProjArgs& a, int tb, int b, int
     }
     const int64_t jcol = (int64_t)s * HD + (int64_t)h * D + dcol;
     const float bb = (a.bias && colv) ? (PLAIN ? a.bias[jcol] : round_bfloat(a.bias[jcol], a.bfloat, kRoundNearest, 1)) : 0.0f;
-    // ---- out = bf(fl32(sum)); out = bf(out + bf(bias))  (linear.py:88-101) -------
-    // value(i, row_lo): element i's fp32 sum; branch-free: NaN by select; bb = 0 without
-    // a bias and o + 0 = o here (o is never -0: an integer sum converts to +0)
+    // ---- the Linear output (linear_out) into the fp32 tile -------------------------
+    // value(i, row_lo): element i's fp32 sum; branch-free: NaN by select; PLAIN: bb = 0
+    // without a bias and o + 0 = o here (o is never -0: an integer sum converts to +0)
     auto store_tile = [&](auto&& value, bool cn) {
       float* orow = ot + m0 * kOst + s * 32 * NBD + dcol;
 #pragma unroll
@@ -258,22 +251,14 @@ __device__ __forceinline__ void proj_block(const ProjArgs& a, int tb, int b, int
         for (int r = 0; r < 4; ++r) {
           float o = value(4 * q + r, lo[r]);
           o = (cn || nf[r]) ? __uint_as_float(0x7FC00000u) : o;
-          if constexpr (PLAIN) {
-            o += bb;
-          } else {
-            // autocast: F.linear returns the autocast dtype, quantize_elemwise_op rounds that
-            // (as mx_gemm's epilogue); + fp32 bias promotes back
-            o = round_bfloat(round_dt(o, a.autocast), a.bfloat, kRoundNearest, 1, a.autocast);
-            if (a.bias) o = round_bfloat(o + bb, a.bfloat, kRoundNearest, 1);
-          }
+          if constexpr (PLAIN) o += bb;
+          else o = linear_out(o, bb, a.bias != nullptr, a.bfloat, a.autocast);
           orow[(8 * q + r) * kOst] = o;
         }
       }
     };
-    // the K loop and the epilogue of the shifted int32 sums (FAST; the fp64 form: run_f64)
-    auto run = [&](auto fast_c) {
-      constexpr bool FAST = decltype(fast_c)::value;
-      static_assert(FAST, "the fp64 sums: run_f64");
+    // the K loop and the epilogue of the shifted int32 sums (the fp64 form: run_f64)
+    auto run = [&]() {
       int acc[16];
 #pragma unroll
       for (int i = 0; i < 16; ++i) acc[i] = 0;
@@ -304,15 +289,8 @@ __device__ __forceinline__ void proj_block(const ProjArgs& a, int tb, int b, int
         for (int q = 0; q < 4; ++q) {
           const uint2 e4 = xcur[q];
           const int dx[4] = {(int)(e4.x & 0xFFFFu), (int)(e4.x >> 16), (int)(e4.y & 0xFFFFu), (int)(e4.y >> 16)};
-          if constexpr (FAST) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) acc[4 * q + r] += (int)((uint32_t)c[4 * q + r] << (dx[r] + ewd));
-          } else {
-            const int4 lo4 = *reinterpret_cast<const int4*>(rlo + 8 * q + m0);
-            const int lo[4] = {lo4.x, lo4.y, lo4.z, lo4.w};
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[4 * q + r] += ldexp((double)c[4 * q + r], dx[r] + lo[r] + ew);
-          }
+          for (int r = 0; r < 4; ++r) acc[4 * q + r] += (int)((uint32_t)c[4 * q + r] << (dx[r] + ewd));
         }
       };
       const v16i zero = {};
@@ -329,24 +307,24 @@ __device__ __forceinline__ void proj_block(const ProjArgs& a, int tb, int b, int
       lde(0, xA);
       // step: issue block j + 1 into cN (operand slot W, refilled with block j + 5), then
       // the epilogue of block j from cP (exponent slot E, refilled with block j + 4)
-#define MXA_PROJ_STEP(cN, xN, W, cP, xP, E, j)              \
-  cN = mfma((j) + 1, W);                                   \
-  W = ldw(cl((j) + 5));                                    \
-  lde((j) + 1, xN);                                        \
-  __builtin_amdgcn_sched_barrier(0);                       \
-  epi(cP, E, xP);                                          \
-  E = lew(cl((j) + 4));                                    \
-  __builtin_amdgcn_sched_barrier(0);
+      auto step = [&](v16i& cN, uint2 (&xN)[4], v4i_& W, const v16i& cP, const uint2 (&xP)[4], int16_t& E, int j) {
+        cN = mfma(j + 1, W);
+        W = ldw(cl(j + 5));
+        lde(j + 1, xN);
+        __builtin_amdgcn_sched_barrier(0);
+        epi(cP, E, xP);
+        E = lew(cl(j + 4));
+        __builtin_amdgcn_sched_barrier(0);
+      };
       // whole quads (blocks kb .. kb + 4 all real), one exit at the bottom
       const int nquad = last >> 2;
       int kb = 0;
       for (int p = 0; p < nquad; ++p, kb += 4) {
-        MXA_PROJ_STEP(cB, xB, W1, cA, xA, E0, kb)
-        MXA_PROJ_STEP(cA, xA, W2, cB, xB, E1, kb + 1)
-        MXA_PROJ_STEP(cB, xB, W3, cA, xA, E2, kb + 2)
-        MXA_PROJ_STEP(cA, xA, W0, cB, xB, E3, kb + 3)
+        step(cB, xB, W1, cA, xA, E0, kb);
+        step(cA, xA, W2, cB, xB, E1, kb + 1);
+        step(cB, xB, W3, cA, xA, E2, kb + 2);
+        step(cA, xA, W0, cB, xB, E3, kb + 3);
       }
-#undef MXA_PROJ_STEP
       // the last 1 .. 4 blocks kb .. last (cA = block kb in flight)
       const int r = nbk - kb;
       if (r > 1) {
@@ -369,59 +347,19 @@ __device__ __forceinline__ void proj_block(const ProjArgs& a, int tb, int b, int
         epi(cA, E2, xA);
       }
       if (r > 3) epi(cB, E3, xB);
-      store_tile(
-          [&](int i, int lo) {
-            if constexpr (FAST) return ldexpf((float)acc[i], lo + wlo);
-            else return (float)acc[i];
-          },
-          cnan);
+      store_tile([&](int i, int lo) { return ldexpf((float)acc[i], lo + wlo); }, cnan);
     };
-    // Exponent-folded operands (dig): the tile's codes times 2^(block exponent - row's
-    // smallest) and the weight's times 2^(block exponent - column's smallest), each as two
-    // signed base-256 digits, so every block's scale is already in the operands: the four
-    // digit products accumulate in the MFMA's own int32 accumulators over all K-blocks
-    // (lo x lo; lo x hi + hi x lo; hi x hi: |sum| <= 2 nbk 32 128^2 < 2^31) with no VALU
-    // per block, and sum = c0 + 2^8 c1 + 2^16 c2 (exact in fp64) rounds once.
+    // Exponent-folded operands (dig): digit_k_loop on the tile's digits (xt, xh) and the
+    // weight's (pd), sum = c0 + 2^8 c1 + 2^16 c2 rounded once (digits_to_f32)
     auto run_dig = [&]() {
       const auto drs = __builtin_amdgcn_make_buffer_rsrc(const_cast<int8_t*>(a.pd), 0, a.pd_bytes, 0x00020000);
       const int dsoff = __builtin_amdgcn_readfirstlane((int)(blkc * nbk) * 2048);
-      auto ldd = [&](int kb, int p) {
-        return __builtin_bit_cast(v4i_, __builtin_amdgcn_raw_buffer_load_b128(drs, woff, dsoff + ((MXA_PROJ_SKIP & 4) ? 0 : kb * 2048) + p * 1024, 0));
-      };
-      const int8_t* xha = xh + ln * L.xst + kh;
-      const int last = nbk - 1;
-      auto cl = [&](int kb) { return min(kb, last); };
-      v16i c0 = {}, c1 = {}, c2 = {};
-      // weight digits four blocks ahead (slot = block mod 4), the tile's from LDS
-      v4i_ L0 = ldd(0, 0), H0 = ldd(0, 1), L1 = ldd(cl(1), 0), H1 = ldd(cl(1), 1);
-      v4i_ L2 = ldd(cl(2), 0), H2 = ldd(cl(2), 1), L3 = ldd(cl(3), 0), H3 = ldd(cl(3), 1);
-      auto step = [&](int kb, v4i_& Ls, v4i_& Hs) {
-        const v4i_ al = *reinterpret_cast<const v4i_*>(xa + 32 * kb);
-        const v4i_ ah = *reinterpret_cast<const v4i_*>(xha + 32 * kb);
-        c0 = __builtin_amdgcn_mfma_i32_32x32x32_i8(al, Ls, c0, 0, 0, 0);
-        c1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(al, Hs, c1, 0, 0, 0);
-        c2 = __builtin_amdgcn_mfma_i32_32x32x32_i8(ah, Hs, c2, 0, 0, 0);
-        c1 = __builtin_amdgcn_mfma_i32_32x32x32_i8(ah, Ls, c1, 0, 0, 0);
-        Ls = ldd(cl(kb + 4), 0);
-        Hs = ldd(cl(kb + 4), 1);
-        __builtin_amdgcn_sched_barrier(0);  // reload each slot right after its use
-      };
-      int kb = 0;
-      for (; kb + 4 <= nbk; kb += 4) {
-        step(kb, L0, H0);
-        step(kb + 1, L1, H1);
-        step(kb + 2, L2, H2);
-        step(kb + 3, L3, H3);
-      }
-      if (kb < nbk) step(kb, L0, H0);
-      if (kb + 1 < nbk) step(kb + 1, L1, H1);
-      if (kb + 2 < nbk) step(kb + 2, L2, H2);
-      store_tile(
-          [&](int i, int lo) {
-            const double v = (double)c0[i] + 256.0 * (double)c1[i] + 65536.0 * (double)c2[i];
-            return (float)ldexp(v, lo + wlo);
+      const DigitSums d = digit_k_loop(
+          [&](int kb, int p) {
+            return __builtin_bit_cast(v4i_, __builtin_amdgcn_raw_buffer_load_b128(drs, woff, dsoff + kb * 2048 + p * 1024, 0));
           },
-          a.pn[pc] != 0);
+          xa, xh + ln * L.xst + kh, 32, nbk);
+      store_tile([&](int i, int lo) { return digits_to_f32(d.c0[i], d.c1[i], d.c2[i], lo + wlo); }, a.pn[pc] != 0);
     };
     // the fp64 block sums for a head whose spreads allow neither the digits nor the shifted
     // int32 sums (rare): one K-block at a time, ascending (exact while the scaled blocks span
@@ -454,9 +392,8 @@ __device__ __forceinline__ void proj_block(const ProjArgs& a, int tb, int b, int
       }
       store_tile([&](int i, int) { return (float)acc[i]; }, cnan);
     };
-    if (MXA_PROJ_SKIP & 1) store_tile([](int, int) { return 0.0f; }, false);
-    else if (fast_ok && dig) run_dig();
-    else if (fast_ok) run(std::true_type{});
+    if (fast_ok && dig) run_dig();
+    else if (fast_ok) run();
     else run_f64();  // wide spreads or a subnormal result: fp64, in this workgroup
 
     __syncthreads();
@@ -475,8 +412,7 @@ __device__ __forceinline__ void proj_block(const ProjArgs& a, int tb, int b, int
     const int64_t hrow0 = (hrow_b + h) * a.N + n0;  // row of (b, h, n0) in the q / k tables
     constexpr int kPer = 32 * NBD * 2;              // lanes per sub-matrix: a multiple of 64
     static_assert(kThreads - 2 * kPer == 64 * NBD, "V lanes");
-    if (MXA_PROJ_SKIP & 2) {
-    } else if ((int)threadIdx.x < 2 * kPer) {
+    if ((int)threadIdx.x < 2 * kPer) {
       // rows_prep's per-block body on the tile (2 lanes per 32-element block)
       const int t = (int)threadIdx.x;
       const int sk = __builtin_amdgcn_readfirstlane(t / kPer);  // uniform per wave: q or k

@@ -18,8 +18,9 @@ namespace mxa {
 //   gs  per group (of gw real columns): the smallest ps exponent, the largest spread
 //   pn  per padded column: 1 when a block exponent is NaN (int16)
 //   pd  exponent-folded codes [group][cb][kb][digit 0, 1][lane][16 B]: the code times
-//       2^(block exponent - column's smallest) as two signed base-256 digits (column
-//       spread <= kDigitSpread; else zeros, and the column's group never takes them)
+//       2^(block exponent - column's smallest) as two signed base-256 digits
+//       (mxa_gemm_parts.hpp fold_digits16; column spread <= kDigitSpread; else zeros, and
+//       the column's group never takes them)
 struct LinearLayout {
   int G, NB32, nbk, Cpad;
   int64_t hdr, rawc, rawe, pk, pe, ps, gs, pn, pd, total;
@@ -63,29 +64,6 @@ __host__ __device__ inline LinearLayout linear_layout(int out_f, int in_f, int g
   o += al(2 * pcols * L.Cpad);
   L.total = o;
   return L;
-}
-
-// 16 codes times 2^s (0 <= s <= kDigitSpread) as two signed base-256 digits:
-// c * 2^s = d0 + 256 d1, d0 in [-128, 127], |d1| <= 127
-__device__ __forceinline__ void fold_digits16(const uint4& v, int s, uint4& d0, uint4& d1) {
-  const uint32_t in[4] = {v.x, v.y, v.z, v.w};
-  uint32_t o0[4], o1[4];
-#pragma unroll
-  for (int w = 0; w < 4; ++w) {
-    uint32_t p0 = 0, p1 = 0;
-#pragma unroll
-    for (int b = 0; b < 4; ++b) {
-      const int c = (int)(int8_t)(in[w] >> (8 * b));
-      const int f = c << s;
-      const int lo = (int)(int8_t)f;
-      p0 |= ((uint32_t)lo & 0xFFu) << (8 * b);
-      p1 |= ((uint32_t)((f - lo) >> 8) & 0xFFu) << (8 * b);
-    }
-    o0[w] = p0;
-    o1[w] = p1;
-  }
-  d0 = make_uint4(o0[0], o0[1], o0[2], o0[3]);
-  d1 = make_uint4(o1[0], o1[1], o1[2], o1[3]);
 }
 
 struct ProjArgs {

@@ -470,12 +470,7 @@ __device__ __forceinline__ bool sel_rows4(const Rows2Args& a, const SelTabs& t, 
   const int64_t grow = (int64_t)bh * a.N + (valid ? r : rq);
   if (!kPacked && a.fb_only && valid) valid = kept_get(a, grow * k) < 0;
   uint32_t bad = 0u, badf = 0u;
-#ifdef MXA_SEL_SKIP
-  if (valid && !((MXA_SEL_SKIP) & 2))
-#else
-  if (valid)
-#endif
-  {
+  if (valid) {
     if constexpr (kPacked)
       sel_scores<MODE>(a, t, bh, r, gl, 16, [&](int j, float v, uint32_t key, auto fast_c) {
         if constexpr (decltype(fast_c)::value) badf |= __float_as_uint(v);  // finite: the low byte
@@ -486,14 +481,6 @@ __device__ __forceinline__ bool sel_rows4(const Rows2Args& a, const SelTabs& t, 
       sel_scores<MODE>(a, t, bh, r, gl, 16, [&](int j, float, uint32_t key, auto) { g.A[j] = pack_ki(key, (uint32_t)j); });
   }
   bad |= badf & 0xFFu;
-#ifdef MXA_SEL_SKIP  // tools-only phase timing (build_native defines): 2 = scores replaced by hashed keys
-  if ((MXA_SEL_SKIP) & 2)
-    for (int j = gl; j < T; j += 16) {
-      const uint32_t key = 0x80000000u | ((uint32_t)(j * 2654435761u + r * 40503u) >> 26 << 8);
-      if constexpr (kPacked) g.A[j] = qelem(key, (uint32_t)j);
-      else g.A[j] = pack_ki(key, (uint32_t)j);
-    }
-#endif
   if (k <= 0) return false;  // scores only
   bool left = false;
   if constexpr (kPacked) {  // this row's 16 lanes: any score that does not pack
@@ -506,10 +493,7 @@ __device__ __forceinline__ bool sel_rows4(const Rows2Args& a, const SelTabs& t, 
   }
   wave_lds_sync();
   GrpHand hand{0u, false};
-#ifdef MXA_SEL_SKIP  // 1 = no top-k
-  if (!((MXA_SEL_SKIP) & 1))
-#endif
-    grp_topk<NP, El, QM, TW>(g, T, k, valid, gl, &hand);
+  grp_topk<NP, El, QM, TW>(g, T, k, valid, gl, &hand);
   if (TW > 0 && hand.on) {  // the row's state and prefix to the tail kernel
     uint32_t* rec = a.tail_rec + grow * tail_rec_words(TW);
     if (gl == 0) {

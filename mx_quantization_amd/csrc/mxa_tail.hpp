@@ -335,15 +335,6 @@ __global__ __launch_bounds__(64 * kTailWaves) void topk_tail_kernel(TailArgs a) 
     }
   }
   const bool pend = (st & kTailPending) != 0;
-#ifdef MXA_TAIL_SKIP  // tools-only phase timing (build_native defines): 4 = the record loads alone
-  if ((MXA_TAIL_SKIP) & 4) {
-    if (pend && row < a.rows) {
-      if (a.idx_out) a.idx_out[row * k] = (int64_t)((uint32_t)A[0] & 0xFFu);
-      else a.idx16[row * k] = (uint16_t)((uint32_t)A[0] & 0xFFu);
-    }
-    return;
-  }
-#endif
   int f = (int)(st & 0xFFu), l = (int)((st >> 8) & 0xFFu), d = (int)((st >> 16) & 0xFFu);
   int ph = pend ? (int)((st >> 24) & 0x3u) : 2;  // 0 introselect, 1 introsort loop, 2 done
   int sp = 0;
@@ -355,12 +346,6 @@ __global__ __launch_bounds__(64 * kTailWaves) void topk_tail_kernel(TailArgs a) 
   }
   while (true) {
     if (ph == 0 && (l - f <= 3 || d == 0)) {  // the selection ends
-#ifdef MXA_TAIL_SKIP  // 2 = no sort of [0, k-1) (and no rank)
-      if ((MXA_TAIL_SKIP) & 2) {
-        ph = 2;
-        continue;
-      }
-#endif
       if (l - f > 3) {  // depth limit: __heap_select(f, nth + 1, l); iter_swap(f, nth)
         tn_heap_select(A, f, nth + 1, l);
         const uint32_t tt = A[f];
@@ -407,9 +392,6 @@ __global__ __launch_bounds__(64 * kTailWaves) void topk_tail_kernel(TailArgs a) 
     }
   }
   // std::sort's final insertion sort = a stable rank of [0, m) (segments mutually ordered)
-#ifdef MXA_TAIL_SKIP  // 1 = no final rank
-  if ((MXA_TAIL_SKIP) & 1) ph = 2;
-#endif
   if (__builtin_amdgcn_ballot_w64(ph == 3 && m >= 2) != 0) {  // (m <= 32: sel_tail_width)
     if (m <= 16) {
       if (ph == 3) t_rank<16>(A, m);
