@@ -305,6 +305,39 @@ int mxa_linear(const float* x, int64_t rows, int32_t in_features, int64_t x_row_
                int64_t workspace_bytes, hipStream_t stream);
 
 /*
+ * The MLP half of a block in one call: fc1 -> GELU -> fc2 with fc1 and fc2 mx.Linear
+ * (microxscaling/mx/linear.py:20-103) and nn.GELU between them -- workloads/DiT/models.py:
+ * 257-271 with act_layer = nn.GELU(approximate="tanh") at :286-287, timm's Mlp with nn.GELU
+ * (workloads/deit/models_v2.py:55), PixArt's GELU(approximate="tanh") feed-forward
+ * (MX_transformer_block.py:70-106); drop1, norm and drop2 are identities at inference:
+ *   pre = mx.Linear(x; W1, b1)      exactly what mxa_linear computes
+ *   act = gelu(pre)                 float32; MXA_ACT_GELU 0.5 h (1 + erf(h / sqrt 2)),
+ *                                   MXA_ACT_GELU_TANH torch's tanh form
+ *   y   = mx.Linear(act; W2, b2)    its input rule included: bf(act), MXINT8 blocks of 32
+ * Float32, no autocast.  fc1's epilogue applies the GELU and writes fc2's MX input codes
+ * itself, so the fp32 hidden matrix never reaches HBM; an fc1 that does not run on that
+ * kernel (w1 prepared in groups that are neither hidden_features nor a multiple of 32
+ * columns, or in_features beyond 72 blocks of 32) goes through an fp32 workspace and the row
+ * quantizer with the same GELU: the same bits.  A NaN in x gives NaN rows in pre, act and
+ * y.  pre = +-inf is not pinned (torch's own CPU kernel returns NaN for gelu(+inf) in the erf
+ * form).  w1 / w2: mxa_linear_weight_prep of W1 (hidden_features, in_features) / W2
+ * (out_features, hidden_features), any group_width, with these flush_subnormals / bfloat --
+ * MXA_ERR_ARG if a header differs.  pre_out / act_out: optional (rows, hidden_features)
+ * contiguous fp32 copies of pre and act (tests).  mxa_mlp_workspace_bytes sizes for the path
+ * the call takes, from w1's header when this process has seen it (prepared or verified
+ * here; else, and for w1 == NULL, the larger fallback size, which serves both paths).
+ */
+#define MXA_ACT_GELU 0
+#define MXA_ACT_GELU_TANH 1
+int64_t mxa_mlp_workspace_bytes(int64_t rows, int32_t in_features, const void* w1, int32_t hidden_features,
+                                int32_t out_features);
+int mxa_mlp(const float* x, int64_t rows, int32_t in_features, int64_t x_row_stride, const void* w1,
+            int32_t hidden_features, const float* b1, int32_t act, const void* w2, int32_t out_features,
+            const float* b2, float* y, int64_t y_row_stride, float* pre_out, float* act_out,
+            int32_t flush_subnormals, int32_t bfloat, void* workspace, int64_t workspace_bytes,
+            hipStream_t stream);
+
+/*
  * The attention core with the proj Linear fused behind it: the patched modules'
  *   x = attn_out.transpose(1, 2).reshape(B, N, C);  x = self.proj(x)
  * (workloads/deit/scripts/main.py:152-154, workloads/DiT/models.py:225-227; proj an

@@ -35,6 +35,7 @@ FIN_KERNELS = {1: ("finish16_kernel", "v_dot4 (kept keys)", "v_mfma_i32_16x16x32
 PRED_MODES = {"ex_pred": 0, "partial_Q": 1, "partial_K": 2, "MXINT4": 3, "two_step_leading_ones": 4,
               "true_ex": 5, "ELSA": 6}
 ROUND_MODES = {"nearest": 0, "floor": 1, "even": 2}
+ACTS = {"gelu": 0, "gelu_tanh": 1}  # MXA_ACT_*
 
 
 class AttnParams(ctypes.Structure):
@@ -93,6 +94,9 @@ _SIGS = {
     "mxa_linear_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32]),
     "mxa_linear": (c_i32, [c_vp, c_i64, c_i32, c_i64, c_vp, c_i32, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_vp, c_i64,
                            c_vp]),
+    "mxa_mlp_workspace_bytes": (c_i64, [c_i64, c_i32, c_vp, c_i32, c_i32]),
+    "mxa_mlp": (c_i32, [c_vp, c_i64, c_i32, c_i64, c_vp, c_i32, c_vp, c_i32, c_vp, c_i32, c_vp, c_vp, c_i64, c_vp, c_vp,
+                        c_i32, c_i32, c_vp, c_i64, c_vp]),
     "mxa_attention_proj_workspace_bytes": (c_i64, [ctypes.POINTER(AttnParams), ctypes.POINTER(QkvParams),
                                                    ctypes.POINTER(ProjParams)]),
     "mxa_attention_proj": (c_i32, [ctypes.POINTER(AttnParams), ctypes.POINTER(QkvParams), ctypes.POINTER(ProjParams),

@@ -66,11 +66,11 @@ int launch_gemm(const GemmArgs& ga, int64_t batch, hipStream_t stream) {
   return plain ? launch_gemm_p<true>(ga, batch, stream) : launch_gemm_p<false>(ga, batch, stream);
 }
 
-// GEMM of MX rows (rows_prep layout: codes [rows][Cpad], exponents [rows][nbk]) with a
-// prepared Linear weight (its row-major codes / exponents): out = mx.Linear epilogue
-int launch_linear_codes(const int8_t* xc, const int16_t* xs, int64_t rows, int in_f, const void* wq, int out_f,
-                        const float* bias, float* out, int64_t out_row_stride, int bfloat, int autocast,
-                        hipStream_t stream, bool x_mfma) {
+// The GemmArgs of an mx.Linear on MX rows (rows_prep layout: codes [rows][Cpad] or MFMA-ready,
+// exponents [rows][nbk]) with a prepared weight (its row-major codes / exponents; its
+// MFMA-ready codes and digits where its column blocks are the output columns)
+GemmArgs linear_gemm_args(const int8_t* xc, const int16_t* xs, int64_t rows, int in_f, const void* wq, int out_f,
+                          const float* bias, float* out, int64_t out_row_stride, int bfloat, int autocast, bool x_mfma) {
   const LinearLayout W = linear_layout(out_f, in_f, out_f);  // raw regions do not depend on gw
   const unsigned char* wb = static_cast<const unsigned char*>(wq);
   GemmArgs g{};
@@ -93,8 +93,16 @@ int launch_linear_codes(const int8_t* xc, const int16_t* xs, int64_t rows, int i
   }
   g.linear = 1; g.dt = kF32; g.bfloat = bfloat; g.autocast = autocast; g.bias = bias;
   g.c = out; g.ldc = out_row_stride;
+  return g;
+}
+
+// GEMM of MX rows with a prepared Linear weight: out = mx.Linear epilogue
+int launch_linear_codes(const int8_t* xc, const int16_t* xs, int64_t rows, int in_f, const void* wq, int out_f,
+                        const float* bias, float* out, int64_t out_row_stride, int bfloat, int autocast,
+                        hipStream_t stream, bool x_mfma) {
   if (rows > ((int64_t)1 << 31) - 1) return MXA_ERR_UNSUPPORTED;
-  return launch_gemm(g, 1, stream);
+  return launch_gemm(linear_gemm_args(xc, xs, rows, in_f, wq, out_f, bias, out, out_row_stride, bfloat, autocast, x_mfma),
+                     1, stream);
 }
 
 }  // namespace mxa

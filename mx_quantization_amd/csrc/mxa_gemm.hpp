@@ -24,6 +24,8 @@
 // beyond; the reference's own fp32 GEMM order is unpinned).  The MFMA of
 // block j + 1 is issued before the epilogue of block j.
 #pragma once
+#include <type_traits>
+
 #include "mxa_gemm_parts.hpp"
 
 namespace mxa {
@@ -401,9 +403,16 @@ __host__ __device__ inline GemmDigLds gemm_dig_lds(int nbk) {
 }
 constexpr int kGemmDigNbkMax = 72;  // 2 KB of LDS per K-block: <= 144 KB
 
-template <bool PLAIN>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) void mx_gemm_dig_kernel(GemmArgs a) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+// The kernel's body, with the epilogue of a wave's 32 x 32 tile as a parameter.  DigStoreF32:
+// the Linear's fp32 store (mx_gemm_dig_kernel).  Any other Epi is called by all 64 lanes as
+//   epi(a, cb, m0g, rows, rn, ext, value)
+// for column block cb of the row block at m0g (rows of its 32 rows exist; rn[m]: row m has a
+// NaN block; value(i, m): the fp32 sum of the lane's element i, row m = 8 (i / 4) + 4 (lane /
+// 32) + i % 4, column 32 cb + lane % 32); ext: the LDS behind gemm_dig_lds(nbk).total (the
+// launch sized it).  mxa_mlp.hpp: fc1 of the fused MLP.
+struct DigStoreF32 {};
+template <bool PLAIN, class Epi>
+__device__ __forceinline__ void gemm_dig_block(const GemmArgs a, const Epi epi, unsigned char* smem) {
   const int nbk = a.nbk;
   const GemmDigLds L = gemm_dig_lds(nbk);
   int8_t* ad = reinterpret_cast<int8_t*>(smem + L.ad);
@@ -464,18 +473,22 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
   // the Linear output (linear_out) of element i of the lane's 32 x 32 tile of column block
   // cb; value(i, m) the fp32 sum of row m
   auto store_out = [&](int cb, auto&& value) {
-    const int n = 32 * cb + ln;
-    if (n >= a.Nc) return;
-    const bool cnan = a.bpn[n] != 0;
-    const float bb = a.bias ? (PLAIN ? a.bias[n] : round_bfloat(a.bias[n], a.bfloat, kRoundNearest, 1)) : 0.0f;
+    if constexpr (!std::is_same_v<Epi, DigStoreF32>) {
+      epi(a, cb, m0g, rows, rn, smem + L.total, value);
+    } else {
+      const int n = 32 * cb + ln;
+      if (n >= a.Nc) return;
+      const bool cnan = a.bpn[n] != 0;
+      const float bb = a.bias ? (PLAIN ? a.bias[n] : round_bfloat(a.bias[n], a.bfloat, kRoundNearest, 1)) : 0.0f;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int m = 8 * (i >> 2) + m0 + (i & 3);
-      if (m >= rows) continue;
-      float o = (cnan || rn[m]) ? __uint_as_float(0x7FC00000u) : value(i, m);
-      if constexpr (PLAIN) o = a.bias ? o + bb : o;
-      else o = linear_out(o, bb, a.bias != nullptr, a.bfloat, a.autocast);
-      static_cast<float*>(a.c)[(int64_t)(m0g + m) * a.ldc + n] = o;
+      for (int i = 0; i < 16; ++i) {
+        const int m = 8 * (i >> 2) + m0 + (i & 3);
+        if (m >= rows) continue;
+        float o = (cnan || rn[m]) ? __uint_as_float(0x7FC00000u) : value(i, m);
+        if constexpr (PLAIN) o = a.bias ? o + bb : o;
+        else o = linear_out(o, bb, a.bias != nullptr, a.bfloat, a.autocast);
+        static_cast<float*>(a.c)[(int64_t)(m0g + m) * a.ldc + n] = o;
+      }
     }
   };
   if (!st[0]) {  // (uniform over the workgroup) the fp64 block sums
@@ -533,6 +546,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
       return digits_to_f32(d.c0[i], d.c1[i], d.c2[i], (rlo[m] > rhi[m] ? 0 : rlo[m]) + clo);
     });
   }
+}
+
+template <bool PLAIN>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) void mx_gemm_dig_kernel(GemmArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  gemm_dig_block<PLAIN>(a, DigStoreF32{}, smem);
 }
 
 }  // namespace mxa

@@ -49,6 +49,8 @@ struct RowsPrepArgs {
   int mfma_rows;    // codes layout: 0 row-major [rows][dpad]; 1 MFMA-ready for the MX GEMM's A operand,
                     // [rows / 32][nb][lane][16 B] with lane = row % 32 + 32 * (16-element half)
                     // (one coalesced 1-KB load per wave and K-block; rows padded to 32)
+  int act;          // 0: none; 1 + MXA_ACT_*: the MLP's activation (mxa_act.hpp) applied to the float32
+                    // values as they are loaded (launch_rows_prep only: rows_prep_act_kernel)
 };
 
 // ELSA sign hashes (and key norms) of rows already quantized by rows_prep:

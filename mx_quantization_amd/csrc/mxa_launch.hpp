@@ -184,6 +184,9 @@ int gemm_smax(int nbk);
 // block-scaled MX GEMM (mxa_gemm.hip); mx.Linear on MX rows with a prepared weight
 // (slow: gemm_slow_bytes of device scratch for the list of waves the fp64 kernel takes)
 int launch_gemm(const GemmArgs& ga, int64_t batch, hipStream_t stream);
+// the GemmArgs launch_linear_codes launches (bpd set: the weight's digits cover the output columns)
+GemmArgs linear_gemm_args(const int8_t* xc, const int16_t* xs, int64_t rows, int in_f, const void* wq, int out_f,
+                          const float* bias, float* out, int64_t out_row_stride, int bfloat, int autocast, bool x_mfma);
 int launch_linear_codes(const int8_t* xc, const int16_t* xs, int64_t rows, int in_f, const void* wq, int out_f,
                         const float* bias, float* out, int64_t out_row_stride, int bfloat, int autocast,
                         hipStream_t stream, bool x_mfma);

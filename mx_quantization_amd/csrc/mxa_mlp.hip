@@ -1,0 +1,111 @@
+// The MLP entry point of include/mxa.h (mxa_mlp): fc1 -> GELU -> fc2, the hidden matrix kept
+// as fc2's MX input codes.  fc1 on the digit kernel's body with the quantizing epilogue
+// (mxa_mlp.hpp); an fc1 the digit kernel does not take runs as mxa_linear into an fp32
+// workspace and is quantized by rows_prep with the activation applied on load
+// (RowsPrepArgs::act) -- the same GELU, the same block quantizer, the same bits.
+#include "mxa_launch.hpp"
+#include "mxa_mlp.hpp"
+
+namespace mxa {
+
+static int64_t al256(int64_t x) { return (x + 255) / 256 * 256; }
+// the MX rows of a (rows, cols) matrix as mxa_linear_workspace_bytes lays them out: MFMA-ready
+// codes (whole 32-row blocks), then the block exponents
+static int64_t mx_rows_codes_bytes(int64_t rows, int cols) { return al256((rows + 31) / 32 * 32 * ((cols + 31) / 32) * 32); }
+static int64_t mx_rows_exps_bytes(int64_t rows, int cols) { return al256(rows * ((cols + 31) / 32) * 2); }
+
+// does fc1 run on the digit kernel's body?  The weight's digits cover the output columns
+// (one group, or groups of a multiple of 32 columns: linear_gemm_args) and the K-blocks fit
+// the LDS next to the staging tiles.  A weight whose header this process has not seen yet
+// counts as not: the fallback's workspace covers both paths.
+static bool mlp_fc1_fused(const void* w1, int in_f, int hidden) {
+  LinearWeightHeader h{};
+  if (!w1 || !linear_weight_known_header(w1, &h) || h.out_f != hidden || h.in_f != in_f) return false;
+  return (h.gw == hidden || h.gw % 32 == 0) && (in_f + 31) / 32 <= kMlpNbkMax;
+}
+
+template <bool PLAIN>
+static int launch_mlp_fc1(const GemmArgs& ga, const MlpEpi<PLAIN>& e, hipStream_t stream) {
+  const size_t lds = gemm_dig_lds(ga.nbk).total + kMlpStageBytes;
+  const void* k = reinterpret_cast<const void*>(&mx_mlp_fc1_kernel<PLAIN>);
+  if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return MXA_ERR_LAUNCH;
+  hipLaunchKernelGGL(mx_mlp_fc1_kernel<PLAIN>, dim3((unsigned)((ga.M + 31) / 32)), dim3(256), lds, stream, ga, e);
+  return hipGetLastError() == hipSuccess ? MXA_OK : MXA_ERR_LAUNCH;
+}
+
+}  // namespace mxa
+
+using namespace mxa;
+
+extern "C" int64_t mxa_mlp_workspace_bytes(int64_t rows, int32_t in_features, const void* w1, int32_t hidden_features,
+                                           int32_t out_features) {
+  if (rows <= 0 || in_features <= 0 || hidden_features <= 0 || out_features <= 0 || rows > INT32_MAX) return -1;
+  int64_t n = mx_rows_codes_bytes(rows, in_features) + mx_rows_exps_bytes(rows, in_features) +
+              mx_rows_codes_bytes(rows, hidden_features) + mx_rows_exps_bytes(rows, hidden_features);
+  if (!mlp_fc1_fused(w1, in_features, hidden_features)) n += al256(rows * hidden_features * 4);
+  return n;
+}
+
+extern "C" int mxa_mlp(const float* x, int64_t rows, int32_t in_features, int64_t x_row_stride, const void* w1,
+                       int32_t hidden_features, const float* b1, int32_t act, const void* w2, int32_t out_features,
+                       const float* b2, float* y, int64_t y_row_stride, float* pre_out, float* act_out,
+                       int32_t flush_subnormals, int32_t bfloat, void* workspace, int64_t workspace_bytes,
+                       hipStream_t stream) {
+  if (!x || !w1 || !w2 || !y || rows <= 0 || rows > INT32_MAX || in_features <= 0 || hidden_features <= 0 ||
+      out_features <= 0 || x_row_stride < in_features || y_row_stride < out_features)
+    return MXA_ERR_ARG;
+  if (act != MXA_ACT_GELU && act != MXA_ACT_GELU_TANH) return MXA_ERR_ARG;
+  if (!valid_bfloat(bfloat)) return MXA_ERR_ARG;
+  if (!linear_weight_verify_any_group(w1, hidden_features, in_features, flush_subnormals, bfloat, stream) ||
+      !linear_weight_verify_any_group(w2, out_features, hidden_features, flush_subnormals, bfloat, stream))
+    return MXA_ERR_ARG;
+  const bool fused = mlp_fc1_fused(w1, in_features, hidden_features);
+  const int64_t need = mxa_mlp_workspace_bytes(rows, in_features, w1, hidden_features, out_features);
+  if (!workspace || workspace_bytes < need || !aligned16(workspace)) return MXA_ERR_WORKSPACE;
+  // (a Linear the tile kernel would refuse is refused whichever kernel would run it: launch_gemm_shape)
+  if ((rows + 63) / 64 > 65535) return MXA_ERR_UNSUPPORTED;
+
+  unsigned char* ws = static_cast<unsigned char*>(workspace);
+  int8_t* xc = reinterpret_cast<int8_t*>(ws);
+  int16_t* xe = reinterpret_cast<int16_t*>(ws + mx_rows_codes_bytes(rows, in_features));
+  unsigned char* hb = ws + mx_rows_codes_bytes(rows, in_features) + mx_rows_exps_bytes(rows, in_features);
+  int8_t* hc = reinterpret_cast<int8_t*>(hb);
+  int16_t* he = reinterpret_cast<int16_t*>(hb + mx_rows_codes_bytes(rows, hidden_features));
+  float* hf = reinterpret_cast<float*>(hb + mx_rows_codes_bytes(rows, hidden_features) +
+                                       mx_rows_exps_bytes(rows, hidden_features));  // the fallback's fp32 hidden matrix
+
+  const RowsPrepArgs rx = flat_rows_prep(x, rows, in_features, x_row_stride, aligned16(x) && x_row_stride % 4 == 0,
+                                         flush_subnormals, bfloat, xc, xe, 1);
+  int rc = launch_rows_prep(rx, stream);
+  if (rc) return rc;
+  if (fused) {
+    const GemmArgs ga = linear_gemm_args(xc, xe, rows, in_features, w1, hidden_features, b1, nullptr, hidden_features,
+                                         bfloat, 0, true);
+    if (!ga.bpd) return MXA_ERR_ARG;  // (mlp_fc1_fused read the same header)
+    const int nbh = (hidden_features + 31) / 32;
+    if (bfloat == 0 || bfloat == 32)
+      rc = launch_mlp_fc1<true>(ga, MlpEpi<true>{hc, he, pre_out, act_out, nbh, act, flush_subnormals}, stream);
+    else
+      rc = launch_mlp_fc1<false>(ga, MlpEpi<false>{hc, he, pre_out, act_out, nbh, act, flush_subnormals}, stream);
+    if (rc) return rc;
+  } else {
+    rc = launch_linear_codes(xc, xe, rows, in_features, w1, hidden_features, b1, hf, hidden_features, bfloat, 0, stream,
+                             true);
+    if (rc) return rc;
+    const int64_t n = rows * hidden_features;
+    if (pre_out && hipMemcpyAsync(pre_out, hf, (size_t)n * 4, hipMemcpyDeviceToDevice, stream) != hipSuccess)
+      return MXA_ERR_LAUNCH;
+    if (act_out) {
+      hipLaunchKernelGGL(mlp_act_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 65536)), dim3(256), 0, stream,
+                         hf, act_out, n, act);
+      if (hipGetLastError() != hipSuccess) return MXA_ERR_LAUNCH;
+    }
+    RowsPrepArgs rh = flat_rows_prep(hf, rows, hidden_features, hidden_features, hidden_features % 4 == 0,
+                                     flush_subnormals, bfloat, hc, he, 1);
+    rh.act = 1 + act;
+    rc = launch_rows_prep(rh, stream);
+    if (rc) return rc;
+  }
+  return launch_linear_codes(hc, he, rows, hidden_features, w2, out_features, b2, y, y_row_stride, bfloat, 0, stream,
+                             true);
+}

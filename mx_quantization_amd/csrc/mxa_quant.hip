@@ -11,6 +11,7 @@
 // reduced with lane shuffles, int8 codes + int16 block exponents written out.
 #include "mxa_kernels.hpp"
 #include "mxa_prep.hpp"
+#include "mxa_act.hpp"
 
 #include <algorithm>
 
@@ -157,7 +158,7 @@ __device__ __forceinline__ void load_row16(const void* xr, int c0, int D, bool v
   }
 }
 
-template <int DT>
+template <int DT, bool ACT = false>
 __device__ __forceinline__ void rows_prep_body(const RowsPrepArgs& a, uint32_t bid) {
   // two lanes per 32-element block, 16 elements per lane; 32-bit index math
   // (the launcher checks rows * nb < 2^31): a 64-bit division is a ~50-instruction
@@ -181,11 +182,20 @@ __device__ __forceinline__ void rows_prep_body(const RowsPrepArgs& a, uint32_t b
   const int c0 = blk * 32 + sub * 16;
   float xv[16];
   load_row16<DT>(xr, c0, a.D, a.vec4, valid, xv);
+  if constexpr (ACT) {  // (elements beyond D stay 0: no part in the block maximum, code 0)
+#pragma unroll
+    for (int j = 0; j < 16; ++j)
+      if (valid && c0 + j < a.D) xv[j] = mlp_act(xv[j], a.act - 1);
+  }
   if (rows_prep_plain(a)) rows_prep_block_plain<16>(a, row, blk, sub, c0, xv, valid);
   else rows_prep_block<16>(a, row, blk, sub, c0, xv, valid);
 }
 template <int DT>
 __global__ __launch_bounds__(256) void rows_prep_kernel(RowsPrepArgs a) { rows_prep_body<DT>(a, blockIdx.x); }
+// RowsPrepArgs::act: the MLP's activation on the float32 values as they are loaded (the
+// fallback of mxa_mlp: fc1's fp32 output -> fc2's MX input codes); a kernel of its own, so
+// that rows_prep_kernel stays what it is
+__global__ __launch_bounds__(256) void rows_prep_act_kernel(RowsPrepArgs a) { rows_prep_body<kF32, true>(a, blockIdx.x); }
 
 // ---------------------------------------------------------------------------
 // operand builder for matrices quantized along the row axis (V, and in2 of
@@ -546,7 +556,10 @@ int launch_rows_prep(const RowsPrepArgs& a, hipStream_t stream) {
   if (threads == 0) return MXA_OK;
   if (a.rows * a.nb >= ((int64_t)1 << 30)) return MXA_ERR_UNSUPPORTED;  // 32-bit thread indices (x2 lanes)
   const dim3 grid((unsigned)((threads + 255) / 256));
-  if (a.dt == kF16) hipLaunchKernelGGL(rows_prep_kernel<kF16>, grid, dim3(256), 0, stream, a);
+  if (a.act != kActNone) {
+    if (a.dt != kF32 || (a.act != 1 + MXA_ACT_GELU && a.act != 1 + MXA_ACT_GELU_TANH)) return MXA_ERR_ARG;
+    hipLaunchKernelGGL(rows_prep_act_kernel, grid, dim3(256), 0, stream, a);
+  } else if (a.dt == kF16) hipLaunchKernelGGL(rows_prep_kernel<kF16>, grid, dim3(256), 0, stream, a);
   else if (a.dt == kBF16) hipLaunchKernelGGL(rows_prep_kernel<kBF16>, grid, dim3(256), 0, stream, a);
   else hipLaunchKernelGGL(rows_prep_kernel<kF32>, grid, dim3(256), 0, stream, a);
   return hipGetLastError() == hipSuccess ? MXA_OK : MXA_ERR_LAUNCH;

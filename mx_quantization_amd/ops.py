@@ -440,6 +440,54 @@ def mx_linear(x: torch.Tensor, weight, bias: Optional[torch.Tensor] = None, flus
     return out
 
 
+def mx_mlp(x: torch.Tensor, w1, b1: Optional[torch.Tensor], w2, b2: Optional[torch.Tensor], act: str = "gelu",
+           flush_subnormals: bool = False, bfloat: int = 0, return_hidden: bool = False):
+    """The MLP of a DeiT / DiT / PixArt block in one call (include/mxa.h mxa_mlp; replaces
+    Mlp.forward at inference): y = mx.Linear(gelu(mx.Linear(x; w1, b1)); w2, b2), float32, no
+    autocast.  x (..., in); w1 (hidden, in) and w2 (out, hidden) tensors (prepared as one group
+    each, as mx_linear does) or LinearWeightMX; act "gelu" (erf) or "gelu_tanh".  fc1 writes
+    fc2's MX input codes itself: the fp32 hidden matrix is not materialised.
+    return_hidden: (y, pre, act) with pre = fc1's output and act = gelu(pre), (..., hidden)."""
+    dev = require_device(x, b1, b2)
+    x = _f32(x, "x")
+    if act not in N.ACTS:
+        raise ValueError(f"act must be one of {sorted(N.ACTS)} (got {act!r})")
+    wq1 = _prepared(w1, w1.shape[0] if not isinstance(w1, LinearWeightMX) else 1, flush_subnormals, bfloat)
+    wq2 = _prepared(w2, w2.shape[0] if not isinstance(w2, LinearWeightMX) else 1, flush_subnormals, bfloat)
+    if x.shape[-1] != wq1.in_features:
+        raise ValueError(f"x has {x.shape[-1]} features, fc1 takes {wq1.in_features}")
+    if wq2.in_features != wq1.out_features:
+        raise ValueError(f"fc2 takes {wq2.in_features} features, fc1 gives {wq1.out_features}")
+    hidden, outf = wq1.out_features, wq2.out_features
+    x2 = x.reshape(-1, x.shape[-1])
+    if x2.stride(-1) != 1:
+        x2 = x2.contiguous()
+    rows = x2.shape[0]
+    y = torch.empty((rows, outf), dtype=torch.float32, device=dev)
+    pre = torch.empty((rows, hidden), dtype=torch.float32, device=dev) if return_hidden else None
+    actv = torch.empty((rows, hidden), dtype=torch.float32, device=dev) if return_hidden else None
+    if rows:
+        bp = [None, None]
+        for i, b in enumerate((b1, b2)):
+            if b is not None:
+                b = _f32(b, f"b{i + 1}").contiguous()
+                bp[i] = b
+        nbytes = lib().mxa_mlp_workspace_bytes(rows, wq1.in_features, wq1.buf.data_ptr(), hidden, outf)
+        if nbytes < 0:
+            raise ValueError("mxa_mlp_workspace_bytes: bad shape")
+        ws = _workspace(dev, nbytes)
+        check(lib().mxa_mlp(x2.data_ptr(), rows, wq1.in_features, x2.stride(0), wq1.buf.data_ptr(), hidden,
+                            bp[0].data_ptr() if bp[0] is not None else None, N.ACTS[act], wq2.buf.data_ptr(), outf,
+                            bp[1].data_ptr() if bp[1] is not None else None, y.data_ptr(), y.stride(0),
+                            pre.data_ptr() if return_hidden else None, actv.data_ptr() if return_hidden else None,
+                            int(bool(flush_subnormals)), int(bfloat), ws.data_ptr(), ws.numel(), stream_ptr(dev)),
+              "mxa_mlp")
+    y = y.reshape(x.shape[:-1] + (outf,))
+    if return_hidden:
+        return y, pre.reshape(x.shape[:-1] + (hidden,)), actv.reshape(x.shape[:-1] + (hidden,))
+    return y
+
+
 def _proj_params(proj_weight, proj_bias, C: int, rows: int, flush_subnormals: bool, bfloat: int, dev):
     """(ProjParams, y (rows, out_features), keep) for the proj Linear behind the attention."""
     wp = _prepared(proj_weight, proj_weight.shape[0] if not isinstance(proj_weight, LinearWeightMX) else 1,
