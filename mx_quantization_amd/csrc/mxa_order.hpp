@@ -6,7 +6,8 @@
 // The serial helpers below follow stl_heap.h / stl_algo.h of GCC 11 literally (the
 // code behind torch's build); the group top-k (mxa_topk_grp.hpp) runs
 // them on one lane of a row for the rare paths: depth-limit heap fallbacks,
-// partial_sort (k*64 <= n) and __insertion_sort of <= 3 elements.
+// partial_sort (k*64 <= n) and __insertion_sort of <= 3 elements; the wave top-k
+// (mxa_topk_wave.hpp) and the one-lane tail (mxa_tail.hpp, on its strided row) run the same.
 #pragma once
 #include "mxa_common.hpp"
 
@@ -20,6 +21,12 @@ __device__ __forceinline__ uint32_t order_key(float f) {
   if (a > 0x7F800000u) return 0xFFFFFFFFu;
   if (a == 0u) b = 0u;
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+// order_key of a value known to be finite and not -0 (the fast ex_pred key loops, mxa_select.hpp
+// sel_scores): three instructions
+__device__ __forceinline__ uint32_t order_key_fast(float f) {
+  const uint32_t u = __float_as_uint(f);
+  return u ^ ((uint32_t)((int)u >> 31) | 0x80000000u);
 }
 
 __device__ __forceinline__ uint64_t pack_ki(uint32_t key, uint32_t idx) { return ((uint64_t)key << 32) | idx; }
@@ -54,9 +61,10 @@ typedef __attribute__((address_space(3))) int li32;
 __device__ __forceinline__ bool lgt(uint64_t x, uint64_t y) { return (uint32_t)(x >> 32) > (uint32_t)(y >> 32); }
 __device__ __forceinline__ bool lgt(uint32_t x, uint32_t y) { return x > (y | 0xFFu); }
 
-// ---- stl_heap.h on one lane's row (LP: an LDS element type) ---------------------
-template <typename LP, typename V>
-__device__ __forceinline__ void ln_push_heap(LP* f, int hole, int top, V v) {
+// ---- stl_heap.h on one lane's row (It: a pointer to LDS elements, or the one-lane
+// tail's strided TPtr, mxa_tail.hpp: operator[], + int, * and assignment from a value) ----
+template <typename It, typename V>
+__device__ __forceinline__ void ln_push_heap(It f, int hole, int top, V v) {
   int parent = (hole - 1) / 2;
   while (hole > top && lgt((V)f[parent], v)) {
     f[hole] = f[parent];
@@ -65,8 +73,8 @@ __device__ __forceinline__ void ln_push_heap(LP* f, int hole, int top, V v) {
   }
   f[hole] = v;
 }
-template <typename LP, typename V>
-__device__ __forceinline__ void ln_adjust_heap(LP* f, int hole, int len, V v) {
+template <typename It, typename V>
+__device__ __forceinline__ void ln_adjust_heap(It f, int hole, int len, V v) {
   const int top = hole;
   int second = hole;
   while (second < (len - 1) / 2) {
@@ -82,16 +90,16 @@ __device__ __forceinline__ void ln_adjust_heap(LP* f, int hole, int len, V v) {
   }
   ln_push_heap(f, hole, top, v);
 }
-template <typename LP>
-__device__ __forceinline__ void ln_pop_heap(LP* first, int len, LP* result) {
+template <typename It>
+__device__ __forceinline__ void ln_pop_heap(It first, int len, It result) {
   const auto v = +*result;
   *result = *first;
   ln_adjust_heap(first, 0, len, v);
 }
 // __heap_select(first, middle, last) on a[first..last)
-template <typename LP>
-__device__ inline void ln_heap_select(LP* a, int first, int middle, int last) {
-  LP* f = a + first;
+template <typename It>
+__device__ inline void ln_heap_select(It a, int first, int middle, int last) {
+  It f = a + first;
   const int len = middle - first;
   if (len >= 2) {  // __make_heap
     int parent = (len - 2) / 2;
@@ -104,8 +112,8 @@ __device__ inline void ln_heap_select(LP* a, int first, int middle, int last) {
   for (int i = middle; i < last; ++i)
     if (lgt(+a[i], +f[0])) ln_pop_heap(f, len, a + i);
 }
-template <typename LP>
-__device__ inline void ln_sort_heap(LP* a, int first, int last) {
+template <typename It>
+__device__ inline void ln_sort_heap(It a, int first, int last) {
   while (last - first > 1) {
     --last;
     ln_pop_heap(a + first, last - first, a + last);
@@ -115,8 +123,8 @@ __device__ inline void ln_sort_heap(LP* a, int first, int last) {
 // ---- stl_algo.h --------------------------------------------------------------
 // __insertion_sort(first, last) (guarded form; the unguarded inner loop of
 // __final_insertion_sort stops at the same element)
-template <typename LP>
-__device__ __forceinline__ void ln_insertion_sort(LP* a, int f, int l) {
+template <typename It>
+__device__ __forceinline__ void ln_insertion_sort(It a, int f, int l) {
   for (int i = f + 1; i < l; ++i) {
     const auto v = +a[i];
     int j = i;
@@ -128,37 +136,6 @@ __device__ __forceinline__ void ln_insertion_sort(LP* a, int f, int l) {
       prev = +a[j - 1];
     }
     a[j] = v;
-  }
-}
-
-// __unguarded_partition_pivot(first, last): median of (first+1, mid, last-1) to
-// first, then Hoare partition of [first+1, last) around it
-__device__ __forceinline__ int ln_partition_pivot(lu64* a, int f, int l) {
-  const int mid = f + (l - f) / 2;
-  const uint64_t xa = a[f + 1], xb = a[mid], xc = a[l - 1];
-  int m;
-  uint64_t xm;
-  if (lgt(xa, xb)) {
-    if (lgt(xb, xc)) m = mid, xm = xb;
-    else if (lgt(xa, xc)) m = l - 1, xm = xc;
-    else m = f + 1, xm = xa;
-  } else if (lgt(xa, xc)) m = f + 1, xm = xa;
-  else if (lgt(xb, xc)) m = l - 1, xm = xc;
-  else m = mid, xm = xb;
-  const uint64_t xf = a[f];
-  a[m] = xf;  // iter_swap(first, median)
-  a[f] = xm;
-  const uint32_t p = (uint32_t)(xm >> 32);
-  int i = f + 1, j = l;
-  while (true) {
-    uint64_t xi = a[i];
-    while ((uint32_t)(xi >> 32) > p) xi = a[++i];
-    uint64_t xj = a[--j];
-    while (p > (uint32_t)(xj >> 32)) xj = a[--j];
-    if (!(i < j)) return i;
-    a[i] = xj;
-    a[j] = xi;
-    ++i;
   }
 }
 

@@ -37,11 +37,9 @@ static int launch_select_w(const Rows2Args& ra0, int BH, hipStream_t stream, boo
   return hipGetLastError() == hipSuccess ? MXA_OK : MXA_ERR_LAUNCH;
 }
 // the one-lane tail (mxa_tail.hpp) over every row of the call: the rows the packed pass
-// handed over
+// handed over (the fused selection's, and the standalone mxa_topk_ws')
 template <int TW>
-static int launch_tail(const Rows2Args& ra, int BH, hipStream_t stream, bool plan) {
-  if (plan) return MXA_OK;
-  TailArgs ta{ra.tail_rec, (int64_t)BH * ra.N, ra.k_top, (ra.T + 31) / 32, ra.idx_out, ra.idx16, ra.mask_out};
+static int launch_tail(const TailArgs& ta, hipStream_t stream) {
   const size_t lds = tail_lds(TW);
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(&topk_tail_kernel<TW>), hipFuncAttributeMaxDynamicSharedMemorySize,
                           (int)lds) != hipSuccess)
@@ -53,33 +51,36 @@ static int launch_tail(const Rows2Args& ra, int BH, hipStream_t stream, bool pla
 template <int NP, int MODE, int W>
 static int launch_select_packed(const Rows2Args& ra, int BH, hipStream_t stream, bool plan) {
   const int tw = sel_tail_width(MODE, ra.T, ra.k_top, ra.bias != nullptr);
-  int rc;
-  if (tw == kTailPref) {
-    rc = launch_select_w<NP, MODE, W, uint32_t, 1, kTailPref>(ra, BH, stream, plan);
-    if (rc == MXA_OK) rc = launch_tail<kTailPref>(ra, BH, stream, plan);
-  } else {
-    rc = launch_select_w<NP, MODE, W, uint32_t, 0, 0>(ra, BH, stream, plan);
-  }
-  return rc;
+  if (tw != kTailPref) return launch_select_w<NP, MODE, W, uint32_t, 0, 0>(ra, BH, stream, plan);
+  const int rc = launch_select_w<NP, MODE, W, uint32_t, 1, kTailPref>(ra, BH, stream, plan);
+  if (rc != MXA_OK || plan) return rc;
+  return launch_tail<kTailPref>(
+      TailArgs{ra.tail_rec, (int64_t)BH * ra.N, ra.k_top, (ra.T + 31) / 32, ra.idx_out, ra.idx16, ra.mask_out}, stream);
+}
+// f(integral_constant<int, W>) for the workgroup's wave count W = sel_waves_for(...)
+template <typename F>
+static int with_sel_waves(int wsel, F&& f) {
+  return wsel == 2 ? f(std::integral_constant<int, 2>{}) : f(std::integral_constant<int, 4>{});
 }
 template <int NP, int MODE>
 static int launch_select_np(const Rows2Args& ra, int BH, hipStream_t stream, bool plan) {
-  const int wsel = sel_waves_for(ra.T, BH, ra.N);
-  // packed elements (rows of <= 256 keys) for the approximators whose scores are sums of
-  // small integers times powers of two (the one-lane tail behind it for small k); then the
-  // 64-bit kernel on the rows whose scores do not pack (fb_only: its workgroups without
-  // such rows return at once).  The true scores, ELSA and longer rows: the 64-bit kernel.
-  if constexpr (NP <= 256) {
-    if (sel_packs(MODE, ra.T, ra.bias != nullptr) && ra.k_top > 0 && ra.fb_flags) {
-      const int rc = wsel == 2 ? launch_select_packed<NP, MODE, 2>(ra, BH, stream, plan)
-                               : launch_select_packed<NP, MODE, 4>(ra, BH, stream, plan);
-      if (rc != MXA_OK) return rc;
-      Rows2Args fb = ra;
-      fb.fb_only = 1;
-      return wsel == 2 ? launch_select_w<NP, MODE, 2>(fb, BH, stream, plan) : launch_select_w<NP, MODE, 4>(fb, BH, stream, plan);
+  return with_sel_waves(sel_waves_for(ra.T, BH, ra.N), [&](auto w_c) {
+    constexpr int W = decltype(w_c)::value;
+    // packed elements (rows of <= 256 keys) for the approximators whose scores are sums of
+    // small integers times powers of two (the one-lane tail behind it for small k); then the
+    // 64-bit kernel on the rows whose scores do not pack (fb_only: its workgroups without
+    // such rows return at once).  The true scores, ELSA and longer rows: the 64-bit kernel.
+    if constexpr (NP <= 256) {
+      if (sel_packs(MODE, ra.T, ra.bias != nullptr) && ra.k_top > 0 && ra.fb_flags) {
+        const int rc = launch_select_packed<NP, MODE, W>(ra, BH, stream, plan);
+        if (rc != MXA_OK) return rc;
+        Rows2Args fb = ra;
+        fb.fb_only = 1;
+        return launch_select_w<NP, MODE, W>(fb, BH, stream, plan);
+      }
     }
-  }
-  return wsel == 2 ? launch_select_w<NP, MODE, 2>(ra, BH, stream, plan) : launch_select_w<NP, MODE, 4>(ra, BH, stream, plan);
+    return launch_select_w<NP, MODE, W>(ra, BH, stream, plan);
+  });
 }
 template <int MODE>
 static int launch_select_m(const Rows2Args& ra, int BH, hipStream_t stream, bool plan) {
@@ -133,11 +134,10 @@ static int launch_topk_grp(const GrpTopkArgs& ga, const TopkWs& w, unsigned grid
 // the workspace path of the standalone top-k: the packed pass for rows of <= 256 values
 // (mxa_select.hpp topk_rows16), the one-lane tail for k <= 33 (mxa_tail.hpp), the 64-bit
 // pass over the rows it leaves
-static int topk_ws_tw(int n, int k) { return tail_width_for(n, k); }
 static bool topk_ws_packs(int n, int k) { return n <= 256 && k > 0; }
 static int64_t topk_ws_bytes(int64_t rows, int n, int k) {
   if (!topk_ws_packs(n, k)) return 0;
-  const int tw = topk_ws_tw(n, k);
+  const int tw = tail_width_for(n, k);
   const int64_t nwg = (rows + 15) / 16;
   return ((nwg * 4 + 255) / 256) * 256 + (tw ? rows * (int64_t)tail_rec_words(tw) * 4 : 0);
 }
@@ -149,15 +149,10 @@ static int launch_topk_packed(const GrpTopkArgs& ga, const TopkWs& w, unsigned g
   else rc = launch_topk_grp<NP, uint32_t, 2, 0>(ga, w, grid, stream);
   if (rc) return rc;
   if constexpr (TW > 0) {
-    TailArgs ta{w.tail_rec, ga.rows, ga.k, (ga.n + 31) / 32, ga.out_idx, nullptr, ga.out_mask, ga.vals, ga.ld, ga.dt,
-                ga.out_vals};
-    const size_t lds = tail_lds(TW);
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&topk_tail_kernel<TW>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-      return MXA_ERR_LAUNCH;
-    hipLaunchKernelGGL(topk_tail_kernel<TW>, dim3((unsigned)((ga.rows + 64 * kTailWaves - 1) / (64 * kTailWaves))),
-                       dim3(64 * kTailWaves), lds, stream, ta);
-    if (hipGetLastError() != hipSuccess) return MXA_ERR_LAUNCH;
+    rc = launch_tail<TW>(TailArgs{w.tail_rec, ga.rows, ga.k, (ga.n + 31) / 32, ga.out_idx, nullptr, ga.out_mask, ga.vals,
+                                  ga.ld, ga.dt, ga.out_vals},
+                         stream);
+    if (rc) return rc;
   }
   TopkWs f = w;
   f.fb_only = 1;
@@ -212,7 +207,7 @@ extern "C" int mxa_topk_ws(const void* vals, int64_t rows, int32_t n, int64_t ld
   w.fb_flags = static_cast<uint32_t*>(workspace);
   w.tail_rec = reinterpret_cast<uint32_t*>(static_cast<unsigned char*>(workspace) + ((w.n_wg * 4 + 255) / 256) * 256);
   const unsigned grid = (unsigned)w.n_wg;
-  const int tw = topk_ws_tw(n, k);
+  const int tw = tail_width_for(n, k);
   if (n <= 128) {
     if (tw == kTailPref) return launch_topk_packed<128, kTailPref>(ga, w, grid, stream);
     return launch_topk_packed<128, 0>(ga, w, grid, stream);

@@ -317,8 +317,7 @@ __device__ __forceinline__ void sel_scores(const Rows2Args& a, const SelTabs& t,
 #pragma unroll
             for (int b = 0; b < NBD; ++b) sum += m[b] << (e[b] - emin);
             v = ldexpf((float)sum, emin);
-            const uint32_t u = __float_as_uint(v);
-            key = u ^ ((uint32_t)((int)u >> 31) | 0x80000000u);
+            key = order_key_fast(v);
           } else {
             v = expred_score<NBD>(sq, eq, kex, ksg, D);
             key = order_key(v);
@@ -354,8 +353,7 @@ __device__ __forceinline__ void sel_scores(const Rows2Args& a, const SelTabs& t,
         const uint32_t* ksg = t.tsg + j * NBD;
         float v = ldexpf((float)(nbk[0] - 2 * (int)__popc(sq[0] ^ ksg[0])), eq[0] + kex[0]);
         if constexpr (NBD == 2) v += ldexpf((float)(nbk[1] - 2 * (int)__popc(sq[1] ^ ksg[1])), eq[1] + kex[1]);
-        const uint32_t u = __float_as_uint(v);
-        const uint32_t key = u ^ ((uint32_t)((int)u >> 31) | 0x80000000u);
+        const uint32_t key = order_key_fast(v);
         if (!LAST || j < T) {
           if (prow) prow[j] = v;
           sink(j, v, key, std::true_type{});
@@ -430,11 +428,12 @@ __device__ __forceinline__ void sel_scores(const Rows2Args& a, const SelTabs& t,
 }
 
 // prune mask words of one row from its kept indices (zeros.scatter_(-1, idx, 1) as bits):
-// idx_at(p) for p = p0, p0 + ps, ... < k; mw is a per-row LDS scratch of ntw words
+// idx_at(p) for p = p0, p0 + ps, ... < k; mw is a per-row LDS scratch of ntw words; out[row * ntw +
+// w] the row's words (the array's base and the row's number, the index formed at the store: with
+// the row's pointer formed by the caller the packed select_kernel measured 0.3-0.5 % slower)
 template <typename IdxAt>
-__device__ __forceinline__ void sel_mask_words(const Rows2Args& a, __attribute__((address_space(3))) uint32_t* mw,
-                                               int64_t grow, bool valid, int p0, int ps, int k, IdxAt&& idx_at) {
-  const int ntw = (a.T + 31) / 32;
+__device__ __forceinline__ void sel_mask_words(uint32_t* out, int64_t row, int ntw, lu32* mw, bool valid, int p0, int ps, int k,
+                                               IdxAt&& idx_at) {
   for (int w = p0; w < ntw; w += ps) mw[w] = 0u;
   wave_lds_sync();
   if (valid)
@@ -444,18 +443,74 @@ __device__ __forceinline__ void sel_mask_words(const Rows2Args& a, __attribute__
     }
   wave_lds_sync();
   if (valid)
-    for (int w = p0; w < ntw; w += ps) a.mask_out[grow * ntw + w] = mw[w];
+    for (int w = p0; w < ntw; w += ps) out[row * ntw + w] = mw[w];
 }
 
-// ---- four query rows per wave (mxa_topk_grp.hpp) ---------------------------------
+// ---- four rows per wave (mxa_topk_grp.hpp): the row-group body behind the staged scores ----
+// Lane gl of row gi has filled its share of g.A; bad != 0 on a lane that met a score which does
+// not pack.  Shared by the fused selection (sel_rows4) and the standalone top-k (topk_rows16),
+// which differ in where the elements come from and in Out: put_first(v) writes the row's first
+// kept index (-1: left for the 64-bit pass; 0: handed to the tail, so that pass leaves the row
+// alone), put(p, ix) the p-th kept index (and whatever goes with it).
+//   El = uint32_t (packed): a row whose scores do not all leave the key's low byte free is left
+//   for the 64-bit pass.
+//   TW > 0 (packed): a row whose remaining work fits a TW-position prefix goes to the one-lane
+//   tail (mxa_tail.hpp): its state and prefix are written to its record, tail_rec[row] (the
+//   tail reads [0, tail_rec_len)); a row that `exists` and is finished here or left gets its
+//   record cleared.
+//   mask_out (nullable): the prune-mask words, ceil(n / 32) per row.
+// tail_rec and mask_out come as the arrays' bases with the row's number: the row's own pointers,
+// formed ahead of grp_topk, stayed live across it (topk_grp_kernel: up to 16 VGPRs more).
+// Returns (per lane) whether this lane's row was left for the 64-bit pass.
+template <int NP, typename El, int QM, int TW, typename Out>
+__device__ __forceinline__ bool grp_rows4_finish(const GrpRow<El>& g, int n, int k, bool valid, bool exists, uint32_t bad,
+                                                 int gi, int gl, uint32_t* tail_rec, uint32_t* mask_out, int64_t row,
+                                                 Out out) {
+  bool left = false;
+  if constexpr (sizeof(El) == 4) {  // this row's 16 lanes: any score that does not pack
+    const uint64_t bw = __builtin_amdgcn_ballot_w64(bad != 0u);
+    if (valid && ((bw >> (16 * gi)) & 0xFFFFull) != 0) {
+      if (gl == 0) out.put_first(-1);
+      valid = false;
+      left = true;
+    }
+  }
+  wave_lds_sync();
+  GrpHand hand{0u, false};
+  grp_topk<NP, El, QM, TW>(g, n, k, valid, gl, &hand);
+  if (TW > 0 && hand.on) {  // the row's state and prefix to the tail kernel
+    uint32_t* rec = tail_rec + row * tail_rec_words(TW);
+    if (gl == 0) {
+      rec[0] = hand.state | kTailPending;
+      out.put_first(0);
+    }
+    for (int p = gl; p < TW; p += 16) rec[4 + p] = (uint32_t)g.A[p];
+    valid = false;
+  } else if (TW > 0 && exists) {  // finished here, or left for the 64-bit pass: not the tail's
+    if (gl == 0) tail_rec[row * tail_rec_words(TW)] = 0u;
+  }
+  if (valid)
+    for (int p = gl; p < k; p += 16) out.put(p, GEl<El>::idx(g.A[p]));
+  if (mask_out) {
+    const int ntw = (n + 31) / 32;
+    sel_mask_words(mask_out, row, ntw, g.stk, valid, gl, 16, k, [&](int p) { return GEl<El>::idx(g.A[p]); });
+  }
+  wave_lds_sync();
+  return left;
+}
+
+// the fused selection's kept indices of row grow: kept_put
+struct SelKeptOut {
+  const Rows2Args& a;
+  int64_t grow;
+  int k;
+  __device__ void put_first(int v) const { kept_put(a, grow * k, v); }
+  __device__ void put(int p, uint32_t ix) const { kept_put(a, grow * k + p, (int)ix); }
+};
+
 // rows rq + (lane >> 4) of head bh; g0 = the wave's per-row areas (grp_row_bytes each).
 // El = uint64_t: any row (a.fb_only: only the rows the packed pass left, kept_get(row * k) < 0).
-// El = uint32_t (packed): a row whose scores do not all leave the key's low byte free is
-// left for the 64-bit pass: its first kept index is -1 (kept_put).
-// TW > 0 (packed): rows whose remaining work fits a TW-position prefix go to the one-lane
-// tail kernel (mxa_tail.hpp): their state and prefix are written to a.tail_rec (and the
-// first kept index set to 0, so the 64-bit pass leaves them alone); it writes their
-// indices and mask words.
+// El = uint32_t, TW: grp_rows4_finish (the records a.tail_rec, the indices through kept_put).
 // Returns (per lane) whether this lane's row was left for the 64-bit pass.
 template <int NP, int MODE, typename El, int QM, int TW = 0>
 __device__ __forceinline__ bool sel_rows4(const Rows2Args& a, const SelTabs& t, unsigned char* g0, int bh, int rq,
@@ -482,38 +537,8 @@ __device__ __forceinline__ bool sel_rows4(const Rows2Args& a, const SelTabs& t, 
   }
   bad |= badf & 0xFFu;
   if (k <= 0) return false;  // scores only
-  bool left = false;
-  if constexpr (kPacked) {  // this row's 16 lanes: any score that does not pack
-    const uint64_t bw = __builtin_amdgcn_ballot_w64(bad != 0u);
-    if (valid && ((bw >> (16 * gi)) & 0xFFFFull) != 0) {
-      if (gl == 0) kept_put(a, grow * k, -1);
-      valid = false;
-      left = true;
-    }
-  }
-  wave_lds_sync();
-  GrpHand hand{0u, false};
-  grp_topk<NP, El, QM, TW>(g, T, k, valid, gl, &hand);
-  if (TW > 0 && hand.on) {  // the row's state and prefix to the tail kernel
-    uint32_t* rec = a.tail_rec + grow * tail_rec_words(TW);
-    if (gl == 0) {
-      rec[0] = hand.state | kTailPending;
-      kept_put(a, grow * k, 0);
-    }
-    for (int p = gl; p < TW; p += 16) rec[4 + p] = (uint32_t)g.A[p];  // (the tail reads [0, tail_rec_len))
-    valid = false;
-  } else if (TW > 0 && r < r_end) {  // finished here, or left for the 64-bit pass: not the tail's
-    if (gl == 0) a.tail_rec[grow * tail_rec_words(TW)] = 0u;
-  }
-  // kept indices: four consecutive rows per wave
-  if (valid) {
-    for (int p = gl; p < k; p += 16) {
-      kept_put(a, grow * k + p, (int)GEl<El>::idx(g.A[p]));
-    }
-  }
-  if (a.mask_out) sel_mask_words(a, g.stk, grow, valid, gl, 16, k, [&](int p) { return GEl<El>::idx(g.A[p]); });
-  wave_lds_sync();
-  return left;
+  return grp_rows4_finish<NP, El, QM, TW>(g, T, k, valid, r < r_end, bad, gi, gl, a.tail_rec, a.mask_out, grow,
+                                          SelKeptOut{a, grow, k});
 }
 
 // One workgroup's work item: head bh, query-row chunk y (rows y * rows_per_wg ...).
@@ -539,33 +564,42 @@ __device__ __forceinline__ bool select_item(const Rows2Args& a, unsigned char* s
   return __syncthreads_or(left ? 1 : 0) != 0;
 }
 
+// The 64-bit pass's walk over the packed pass's workgroup flags (fb_only): workgroup wg takes
+// flags [kFbItems wg, kFbItems (wg + 1)) of the n_items and calls item(i) on every thread for
+// each flagged i, in order.  (Whether a barrier follows an item is the caller's business.)
+template <typename Item>
+__device__ __forceinline__ void fb_items(const uint32_t* flags, int64_t n_items, unsigned wg, Item&& item) {
+  __shared__ uint64_t sbits;
+  const int64_t i0 = (int64_t)wg * kFbItems;
+  if (threadIdx.x < kFbItems) {
+    const bool f = i0 + threadIdx.x < n_items && flags[i0 + threadIdx.x] != 0u;
+    const uint64_t bits = __builtin_amdgcn_ballot_w64(f);
+    if (threadIdx.x == 0) sbits = bits;
+  }
+  __syncthreads();
+  uint64_t bits = sbits;
+  while (bits) {
+    const int i = __ffsll((long long)bits) - 1;
+    bits &= bits - 1;
+    item(i0 + i);
+  }
+}
+
 // Selection kernel, four query rows per wave.  El = uint64_t: rows of up to 512 keys,
 // every approximator.  El = uint32_t: the packed pass (rows of <= 256 keys; half the LDS
 // per row, so more resident waves); each workgroup flags (a.fb_flags[bh * gy + y]) whether
 // it left rows for the 64-bit pass, which then runs with fb_only: one workgroup per kFbItems
-// flags, taking the flagged items one after another (a call without such rows costs a
-// small grid that exits at once).
+// flags, taking the flagged items one after another (fb_items; a call without such rows costs
+// a small grid that exits at once).
 template <int NP, int MODE, int kSelWaves, typename El = uint64_t, int QM = 0, int TW = 0>
 __global__ __launch_bounds__(64 * kSelWaves) __attribute__((amdgpu_waves_per_eu(sizeof(El) == 4 ? (TW > 0 ? kSelPOcc : kSelPOccNT) : NP <= 256 ? kSelOcc : 2, 8))) void select_kernel(Rows2Args a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   if (sizeof(El) == 8 && a.fb_only) {
-    __shared__ uint64_t sbits;
     const int gy = a.fb_gy;
-    const int64_t items = (int64_t)a.B * a.H * gy, i0 = (int64_t)blockIdx.x * kFbItems;
-    if (threadIdx.x < kFbItems) {
-      const bool f = i0 + threadIdx.x < items && a.fb_flags[i0 + threadIdx.x] != 0u;
-      const uint64_t bits = __builtin_amdgcn_ballot_w64(f);
-      if (threadIdx.x == 0) sbits = bits;
-    }
-    __syncthreads();
-    uint64_t bits = sbits;
-    while (bits) {
-      const int i = __ffsll((long long)bits) - 1;
-      bits &= bits - 1;
-      const int64_t item = i0 + i;
+    fb_items(a.fb_flags, (int64_t)a.B * a.H * gy, blockIdx.x, [&](int64_t item) {
       select_item<NP, MODE, kSelWaves, El, QM, TW>(a, smem, (int)(item / gy), (int)(item % gy));
       __syncthreads();  // the next item re-stages the tables
-    }
+    });
     return;
   }
   const bool left = select_item<NP, MODE, kSelWaves, El, QM, TW>(a, smem, blockIdx.x, blockIdx.y);
@@ -592,11 +626,21 @@ struct TopkWs {
   int fb_only;         // 64-bit pass over the flagged workgroups' rows with out_idx[row * k] < 0
 };
 
+// the standalone top-k's outputs of one row: its indices, and the values gathered at them
+struct TopkRowOut {
+  const GrpTopkArgs& a;
+  int64_t row, src;  // src: the row's first value in a.vals
+  __device__ void put_first(int v) const { a.out_idx[row * a.k] = v; }
+  __device__ void put(int p, uint32_t ix) const {
+    a.out_idx[row * a.k + p] = (int64_t)ix;
+    if (a.out_vals) store_dt(a.out_vals, row * a.k + p, load_dt(a.vals, src + ix, a.dt), a.dt);
+  }
+};
+
 // sixteen rows (four per wave) from row0: El = uint64_t any row (fb: only rows whose first
-// index is -1); El = uint32_t the packed pass (a row whose values do not leave the key's low
-// byte free gets first index -1 and is left for the 64-bit pass; TW > 0: rows whose remaining
-// work fits the tail's prefix are handed to topk_tail_kernel).  Returns (on every thread)
-// whether a row was left.
+// index is -1); El = uint32_t, TW: grp_rows4_finish (the records w.tail_rec; the tail rebuilds
+// the values from the elements, so a NaN or a -0 also leaves a row to the 64-bit pass).
+// Returns (on every thread) whether a row was left.
 template <int NP, typename El, int QM, int TW>
 __device__ __forceinline__ bool topk_rows16(const GrpTopkArgs& a, const TopkWs& w, unsigned char* smem, int64_t row0,
                                             bool fb) {
@@ -634,51 +678,8 @@ __device__ __forceinline__ bool topk_rows16(const GrpTopkArgs& a, const TopkWs& 
       }
     }
   }
-  bool left = false;
-  if constexpr (kPacked) {
-    const uint64_t bw = __builtin_amdgcn_ballot_w64(bad != 0u);
-    if (valid && ((bw >> (16 * gi)) & 0xFFFFull) != 0) {
-      if (gl == 0) a.out_idx[row * a.k] = -1;
-      valid = false;
-      left = true;
-    }
-  }
-  wave_lds_sync();
-  GrpHand hand{0u, false};
-  grp_topk<NP, El, QM, TW>(g, a.n, a.k, valid, gl, &hand);
-  if (TW > 0 && hand.on) {  // the row's state and prefix to the tail kernel
-    uint32_t* rec = w.tail_rec + row * tail_rec_words(TW);
-    if (gl == 0) {
-      rec[0] = hand.state | kTailPending;
-      a.out_idx[row * a.k] = 0;
-    }
-    for (int p = gl; p < TW; p += 16) rec[4 + p] = (uint32_t)g.A[p];
-    valid = false;
-  } else if (TW > 0 && row < a.rows && !fb) {  // not the tail's
-    if (gl == 0) w.tail_rec[row * tail_rec_words(TW)] = 0u;
-  }
-  if (valid) {
-    for (int p = gl; p < a.k; p += 16) {
-      const uint32_t ix = GEl<El>::idx(g.A[p]);
-      a.out_idx[row * a.k + p] = (int64_t)ix;
-      if (a.out_vals) store_dt(a.out_vals, row * a.k + p, load_dt(a.vals, src + ix, a.dt), a.dt);
-    }
-  }
-  if (a.out_mask) {
-    const int ntw = (a.n + 31) / 32;
-    lu32* mw = g.stk;
-    for (int i = gl; i < ntw; i += 16) mw[i] = 0u;
-    wave_lds_sync();
-    if (valid)
-      for (int p = gl; p < a.k; p += 16) {
-        const uint32_t ix = GEl<El>::idx(g.A[p]);
-        atomicOr((uint32_t*)(mw + (ix >> 5)), 1u << (ix & 31));
-      }
-    wave_lds_sync();
-    if (valid)
-      for (int i = gl; i < ntw; i += 16) a.out_mask[row * ntw + i] = mw[i];
-  }
-  wave_lds_sync();
+  const bool left = grp_rows4_finish<NP, El, QM, TW>(g, a.n, a.k, valid, row < a.rows, bad, gi, gl, w.tail_rec, a.out_mask,
+                                                     row, TopkRowOut{a, row, src});
   return __syncthreads_or(left ? 1 : 0) != 0;
 }
 
@@ -687,21 +688,8 @@ __device__ __forceinline__ bool topk_rows16(const GrpTopkArgs& a, const TopkWs& 
 template <int NP, typename El = uint64_t, int QM = 0, int TW = 0>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(sizeof(El) == 4 ? 5 : NP <= 256 ? 4 : 2, 8))) void topk_grp_kernel(GrpTopkArgs a, TopkWs w) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  if (sizeof(El) == 8 && w.fb_only) {
-    __shared__ uint64_t sbits;
-    const int64_t i0 = (int64_t)blockIdx.x * kFbItems;
-    if (threadIdx.x < kFbItems) {
-      const bool f = i0 + threadIdx.x < w.n_wg && w.fb_flags[i0 + threadIdx.x] != 0u;
-      const uint64_t bits = __builtin_amdgcn_ballot_w64(f);
-      if (threadIdx.x == 0) sbits = bits;
-    }
-    __syncthreads();
-    uint64_t bits = sbits;
-    while (bits) {
-      const int i = __ffsll((long long)bits) - 1;
-      bits &= bits - 1;
-      topk_rows16<NP, El, QM, TW>(a, w, smem, (i0 + i) * 16, true);
-    }
+  if (sizeof(El) == 8 && w.fb_only) {  // (no barrier of its own: topk_rows16 ends in one)
+    fb_items(w.fb_flags, w.n_wg, blockIdx.x, [&](int64_t item) { topk_rows16<NP, El, QM, TW>(a, w, smem, item * 16, true); });
     return;
   }
   const bool left = topk_rows16<NP, El, QM, TW>(a, w, smem, (int64_t)blockIdx.x * 16, false);
@@ -729,15 +717,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(NP <= 256 ?
   }
   if (a.out_mask) {
     const int ntw = (a.n + 31) / 32;
-    wl32* mw = (wl32*)g.SL;
-    if ((int)lane < ntw) mw[lane] = 0u;
-    wave_lds_sync();
-    for (int p = (int)lane; p < a.k; p += 64) {
-      const uint32_t ix = (uint32_t)g.A[p];
-      atomicOr((uint32_t*)(mw + (ix >> 5)), 1u << (ix & 31));
-    }
-    wave_lds_sync();
-    if ((int)lane < ntw) a.out_mask[row * ntw + lane] = mw[lane];
+    sel_mask_words(a.out_mask, row, ntw, (lu32*)g.SL, true, (int)lane, 64, a.k, [&](int p) { return (uint32_t)g.A[p]; });
   }
 }
 

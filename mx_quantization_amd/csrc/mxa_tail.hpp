@@ -50,72 +50,7 @@ struct TPtr {
   __device__ TPtr operator+(int i) const { return TPtr{p + 64 * i}; }
   __device__ TRef operator*() const { return TRef{p}; }
 };
-// stl_heap.h / stl_algo.h on a lane's strided row (mxa_order.hpp's ln_* take pointer-like
-// types; these are the same algorithms for TPtr)
-__device__ __forceinline__ void tn_push_heap(TPtr f, int hole, int top, uint32_t v) {
-  int parent = (hole - 1) / 2;
-  while (hole > top && lgt((uint32_t)f[parent], v)) {
-    f[hole] = (uint32_t)f[parent];
-    hole = parent;
-    parent = (hole - 1) / 2;
-  }
-  f[hole] = v;
-}
-__device__ __forceinline__ void tn_adjust_heap(TPtr f, int hole, int len, uint32_t v) {
-  const int top = hole;
-  int second = hole;
-  while (second < (len - 1) / 2) {
-    second = 2 * (second + 1);
-    if (lgt((uint32_t)f[second], (uint32_t)f[second - 1])) second--;
-    f[hole] = (uint32_t)f[second];
-    hole = second;
-  }
-  if ((len & 1) == 0 && second == (len - 2) / 2) {
-    second = 2 * (second + 1);
-    f[hole] = (uint32_t)f[second - 1];
-    hole = second - 1;
-  }
-  tn_push_heap(f, hole, top, v);
-}
-__device__ __forceinline__ void tn_pop_heap(TPtr first, int len, TPtr result) {
-  const uint32_t v = *result;
-  *result = (uint32_t)*first;
-  tn_adjust_heap(first, 0, len, v);
-}
-__device__ inline void tn_heap_select(TPtr a, int first, int middle, int last) {
-  TPtr f = a + first;
-  const int len = middle - first;
-  if (len >= 2) {
-    int parent = (len - 2) / 2;
-    while (true) {
-      tn_adjust_heap(f, parent, len, (uint32_t)f[parent]);
-      if (parent == 0) break;
-      parent--;
-    }
-  }
-  for (int i = middle; i < last; ++i)
-    if (lgt((uint32_t)a[i], (uint32_t)f[0])) tn_pop_heap(f, len, a + i);
-}
-__device__ inline void tn_sort_heap(TPtr a, int first, int last) {
-  while (last - first > 1) {
-    --last;
-    tn_pop_heap(a + first, last - first, a + last);
-  }
-}
-__device__ __forceinline__ void tn_insertion_sort(TPtr a, int f, int l) {
-  for (int i = f + 1; i < l; ++i) {
-    const uint32_t v = a[i];
-    int j = i;
-    uint32_t prev = a[j - 1];
-    while (lgt(v, prev)) {
-      a[j] = prev;
-      --j;
-      if (j == f) break;
-      prev = a[j - 1];
-    }
-    a[j] = v;
-  }
-}
+// (the serial stl_heap.h / stl_algo.h helpers: mxa_order.hpp's ln_* on a TPtr)
 
 template <int W>
 using TMask = std::conditional_t<(W > 32), uint64_t, uint32_t>;
@@ -347,12 +282,12 @@ __global__ __launch_bounds__(64 * kTailWaves) void topk_tail_kernel(TailArgs a) 
   while (true) {
     if (ph == 0 && (l - f <= 3 || d == 0)) {  // the selection ends
       if (l - f > 3) {  // depth limit: __heap_select(f, nth + 1, l); iter_swap(f, nth)
-        tn_heap_select(A, f, nth + 1, l);
+        ln_heap_select(A, f, nth + 1, l);
         const uint32_t tt = A[f];
         A[f] = (uint32_t)A[nth];
         A[nth] = tt;
       } else if (l - f > 1) {
-        tn_insertion_sort(A, f, l);
+        ln_insertion_sort(A, f, l);
       }
       ph = 1;
       f = 0;
@@ -362,8 +297,8 @@ __global__ __launch_bounds__(64 * kTailWaves) void topk_tail_kernel(TailArgs a) 
     if (ph == 1) {  // settle: finished segments (<= 16, or heapsorted at the depth limit)
       while (l - f <= 16 || d == 0) {
         if (l - f > 16) {
-          tn_heap_select(A, f, l, l);
-          tn_sort_heap(A, f, l);
+          ln_heap_select(A, f, l, l);
+          ln_sort_heap(A, f, l);
         }
         if (sp == 0) {
           ph = 3;  // the final stable rank is left
@@ -404,7 +339,7 @@ __global__ __launch_bounds__(64 * kTailWaves) void topk_tail_kernel(TailArgs a) 
     }
   }
   if (!pend) return;
-  // the kept elements (k <= kTailMaxK: sel_tail_width / topk_ws_tw) into registers, then the
+  // the kept elements (k <= kTailMaxK: tail_width_for) into registers, then the
   // prune-mask words (zeros.scatter_(-1, idx, 1) as bits) set by LDS ORs in the prefix's free
   // positions [k, k + ntw) (k + ntw <= TW: sel_tail_width); the standalone top-k's values at the
   // kept indices come back from the packed elements themselves (q_value: no gather from the

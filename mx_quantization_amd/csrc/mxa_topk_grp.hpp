@@ -119,15 +119,8 @@ __device__ __forceinline__ uint32_t p_get(const GrpRow<El>& g, uint32_t i) {
   else return ((lu16*)g.P)[i];
 }
 
-__device__ __forceinline__ uint32_t hi32(uint64_t x) { return (uint32_t)(x >> 32); }
 __device__ __forceinline__ uint32_t lowbits(int n) { return n >= 32 ? ~0u : ((1u << n) - 1u); }
 
-// acc * 2 + (a <= b): one compare and one add-with-carry (the compiler would emit a
-// compare, a select and an or)
-__device__ __forceinline__ uint32_t g_shl_le(uint32_t acc, uint32_t a, uint32_t b) {
-  asm("v_cmp_le_u32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(acc) : "v"(a), "v"(b) : "vcc");
-  return acc;
-}
 // the stop masks of two positions at once: L = 4 L + 2 (k0 <= pl) + (k1 <= pl),
 // R = 4 R + 2 (pr <= k0) + (pr <= k1) (pl = pr = p on 64-bit elements; the packed ones
 // compare against p | 0xFF and p & ~0xFF).  The four compares go to four SGPR pairs

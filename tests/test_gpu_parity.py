@@ -254,6 +254,23 @@ def test_topk_depth_limit_handover_16bit_values(M, dtype):
     _check_topk_both_passes(M, t, rows, n, k, f"n{n} k{k} {dtype}")
 
 
+@pytest.mark.parametrize("n,k", [(197, 20), (256, 100)])
+def test_topk_fallback_items_scattered(M, n, k):
+    """The 64-bit pass's walk over the packed workgroups' flags (kFbItems = 4 flags per workgroup)
+    on the standalone op: 101 rows are 7 packed workgroups of 16, so two 64-bit-pass workgroups, the
+    second with 3 items.  A -0 (which a packed element does not give back, so the row is left) in
+    rows 20, 60 and 100 flags items 1 and 3 of the first and item 2 of the second; row 100 lies
+    in the last group's 5 rows.  (197, 20) goes through the one-lane tail, (256, 100) is packed
+    with no tail and the queued final sort."""
+    rng = np.random.default_rng(1000 * n + k)
+    rows = rng.integers(0, 3, (101, n)).astype(np.float32)
+    rows[40:] = rng.integers(-6, 7, (61, n)).astype(np.float32) * np.float32(0.25)
+    for r in (20, 60, 100):
+        rows[r, (7 * r) % n] = -0.0
+    assert TC.tail_width_for(n, k) == (TC.TAIL_PREF if k == 20 else 0)
+    _check_topk_both_passes(M, dev(rows), rows, n, k, f"n{n} k{k} scattered fallback items")
+
+
 @pytest.mark.parametrize("T,k,mode,branch", TC.FUSED, ids=TC.case_id)
 def test_fused_depth_limit_handover(M, T, k, mode, branch):
     """The depth-limit row as approximate scores of the fused op: two MX blocks of sign counts
