@@ -368,6 +368,43 @@ int mxa_attention_proj_timed(const mxa_attn_params* p, const mxa_qkv_params* xq,
                              hipStream_t stream, int32_t iters, float* stage_ms);
 
 /*
+ * Cross-attention with its q and kv Linears fused in front: PixArt's MXCrossAttention.forward
+ * (workloads/PixArt/models/MX_transformer_block.py:765-860),
+ *   q = to_q(x);  k = to_k(cond);  v = to_v(cond)          all mx.Linear (linear.py:20-103)
+ * from two token sources -- x (B*N, C) image tokens, cond (B*T, C_kv) text tokens -- feeding
+ * the attention's MX operands directly: the fp32 q, k, v never reach HBM.  p->q, p->k, p->v
+ * are ignored; p->N and p->T are independent; p->bias is the additive mask (PixArt's
+ * (B,1,1,T) attention_mask bias through zero strides), as in mxa_attention.  Float32, no
+ * autocast: a nonzero p->score_dtype returns MXA_ERR_UNSUPPORTED.  wq_q / wq_kv are checked
+ * against their headers, (H*D, C, D) and (2*H*D, C_kv, D) with p->flush_subnormals and
+ * p->bfloat: MXA_ERR_ARG on a mismatch.  Every other mxa_attention rule applies (T <= 512,
+ * D <= 128, ELSA needs N == T).
+ * pj == NULL: p->out is written; top_k == 0 (the dense branch) is allowed.  pj != NULL: the
+ * to_out[0] mx.Linear runs behind the attention exactly as in mxa_attention_proj (top-k only;
+ * p->out is not written).  The workspace is the attention's plus the MX codes of x and cond,
+ * plus mxa_attention_proj's regions with pj.
+ */
+typedef struct mxa_cross_params {
+  const float* x;          /* (B*N, C) query tokens, row stride x_row_stride (elements)        */
+  int64_t x_row_stride;
+  int32_t C;
+  const float* cond;       /* (B*T, C_kv) key / value tokens, row stride cond_row_stride       */
+  int64_t cond_row_stride;
+  int32_t C_kv;
+  const void* wq_q;        /* mxa_linear_weight_prep of W_q (H*D, C), group_width D             */
+  const void* wq_kv;       /* ... of cat(W_k, W_v) along out_features (2*H*D, C_kv), group_width D */
+  const float* bias_q;     /* (H*D) or null                                                    */
+  const float* bias_kv;    /* (2*H*D) or null                                                  */
+  float* q_out;            /* optional (B*N, H*D) fp32 projection (tests)                      */
+  float* kv_out;           /* optional (B*T, 2*H*D) fp32 projection (tests)                    */
+} mxa_cross_params;
+
+int64_t mxa_cross_attention_workspace_bytes(const mxa_attn_params* p, const mxa_cross_params* xc,
+                                            const mxa_proj_params* pj);
+int mxa_cross_attention(const mxa_attn_params* p, const mxa_cross_params* xc, const mxa_proj_params* pj,
+                        hipStream_t stream);
+
+/*
  * mx.matmul forward (microxscaling/mx/matmul.py:31-100, :211-222): in1 (batch, M, K)
  * quantized along K, in2 (batch, K, Nc) quantized along K, fp32 result (batch, M, Nc)
  * contiguous.  Integer formats, block size 32.  a_dtype / b_dtype (MXA_DT_*): each operand's

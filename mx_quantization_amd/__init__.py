@@ -7,6 +7,8 @@ PyTorch-ROCm, exposed through
   * `mx_topk_attention` -- the fused path (MXINT8 QK^T, approximate scores,
     exact-order top-k, softmax, MXINT8 P.V),
   * `mx_qkv_attention` -- the qkv mx.Linear fused in front of it (x -> MX operands),
+  * `mx_cross_attention` -- cross-attention with its q and kv mx.Linears fused in front
+    (two token sources: PixArt's MXCrossAttention),
   * `mx_mlp` -- the block's MLP, fc1 -> GELU -> fc2 with the hidden kept as MX codes,
   * `mx_approx_scores` -- the approximator's scores alone (pred = aQ @ aK^T, ELSA),
   * `topk` -- torch.topk with torch's CPU index order (and the prune mask), on the device,
@@ -21,6 +23,7 @@ from .ops import (  # noqa: F401
     approx_values,
     elsa_cos_table,
     mx_approx_scores,
+    mx_cross_attention,
     LinearWeightMX,
     mx_linear,
     mx_matmul,
@@ -37,7 +40,7 @@ from .ops import (  # noqa: F401
 
 from .exact_topk import TORCH as exact_topk_torch, bind_exact_topk, unbind_exact_topk  # noqa: F401,E402
 
-__all__ = ["bind_exact_topk", "unbind_exact_topk", "exact_topk_torch", "mx_topk_attention", "mx_qkv_attention", "mx_topk_attention_proj", "mx_linear", "mx_mlp", "LinearWeightMX", "mx_approx_scores", "topk", "unpack_mask", "quantize_mx", "mx_matmul", "install_dropin", "NativeError"]
+__all__ = ["bind_exact_topk", "unbind_exact_topk", "exact_topk_torch", "mx_topk_attention", "mx_qkv_attention", "mx_cross_attention", "mx_topk_attention_proj", "mx_linear", "mx_mlp", "LinearWeightMX", "mx_approx_scores", "topk", "unpack_mask", "quantize_mx", "mx_matmul", "install_dropin", "NativeError"]
 
 
 def install_dropin():

@@ -66,6 +66,14 @@ class ProjParams(ctypes.Structure):
     _fields_ = [("wq", c_vp), ("out_features", c_i32), ("bias", c_vp), ("y", c_vp), ("y_row_stride", c_i64)]
 
 
+class CrossParams(ctypes.Structure):
+    """mirror of struct mxa_cross_params (include/mxa.h)"""
+    _fields_ = [("x", c_vp), ("x_row_stride", c_i64), ("C", c_i32),
+                ("cond", c_vp), ("cond_row_stride", c_i64), ("C_kv", c_i32),
+                ("wq_q", c_vp), ("wq_kv", c_vp), ("bias_q", c_vp), ("bias_kv", c_vp),
+                ("q_out", c_vp), ("kv_out", c_vp)]
+
+
 PROJ_STAGES = 6  # MXA_PROJ_STAGES
 
 _SIGS = {
@@ -103,6 +111,9 @@ _SIGS = {
                                    c_vp]),
     "mxa_attention_proj_timed": (c_i32, [ctypes.POINTER(AttnParams), ctypes.POINTER(QkvParams),
                                          ctypes.POINTER(ProjParams), c_vp, c_i32, ctypes.POINTER(c_f32)]),
+    # AttnParams, CrossParams, ProjParams (or None) by reference[, stream]
+    "mxa_cross_attention_workspace_bytes": (c_i64, [c_vp, c_vp, c_vp]),
+    "mxa_cross_attention": (c_i32, [c_vp, c_vp, c_vp, c_vp]),
     "mxa_matmul": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32,
                            c_i32, c_i32, c_i32, c_vp, c_i64, c_vp]),
     "mxa_matmul_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i32]),

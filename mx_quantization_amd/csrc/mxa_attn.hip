@@ -75,6 +75,7 @@ struct AttnLayout {
   int nbd, dpad, ntb, tpad;
   int64_t qc, qop, qz, qsT, qsA, qsg, kc, kop, kz, ksT, ksA, ksg, knorm, vt, vs, idx16, tail, fbf, mask;
   int64_t xc, xs;  // fused qkv projection: x codes / exponents
+  int64_t cc, cs;  // cross-attention: the key / value tokens' codes / exponents (xc, xs: the query tokens')
   int64_t yc, ys, yf;  // fused proj Linear: its input codes / exponents, the fp32 output
                               // copy (D % 32 != 0 only), the GEMM's fp64 wave list
   int64_t total;
@@ -98,7 +99,7 @@ bool proj_codes_direct(const mxa_attn_params* p) {
 }
 
 AttnLayout attn_layout(const mxa_attn_params* p, int mode, const mxa_qkv_params* xq = nullptr,
-                       const mxa_proj_params* pj = nullptr) {
+                       const mxa_proj_params* pj = nullptr, const mxa_cross_params* xc = nullptr) {
   AttnLayout L{};
   const int64_t BH = (int64_t)p->B * p->H;
   L.nbd = (p->D + 31) / 32;
@@ -149,6 +150,14 @@ AttnLayout attn_layout(const mxa_attn_params* p, int mode, const mxa_qkv_params*
     L.xc = take(tokens * nbk * 32);
     L.xs = take(tokens * nbk * 2);
   }
+  if (xc) {
+    const int64_t nbq = (xc->C + 31) / 32, nbc = (xc->C_kv + 31) / 32;
+    const int64_t qtok = (int64_t)p->B * p->N, ktok = (int64_t)p->B * p->T;
+    L.xc = take(qtok * nbq * 32);
+    L.xs = take(qtok * nbq * 2);
+    L.cc = take(ktok * nbc * 32);
+    L.cs = take(ktok * nbc * 2);
+  }
   if (pj) {
     const int64_t C = (int64_t)p->H * p->D, nbk = (C + 31) / 32, tokens = (int64_t)p->B * p->N;
     L.yc = take((tokens + 31) / 32 * 32 * nbk * 32);  // MFMA-ready codes: whole 32-row blocks
@@ -181,20 +190,24 @@ extern "C" int64_t mxa_attention_workspace_bytes(const mxa_attn_params* p) {
   return attn_layout(p, score_mode(p, p->top_k || p->pred_out)).total;
 }
 
-// x -> MX codes along C (rows_prep), then the projection kernel writing the q / k
-// operands (rq, rk) and V's transposed codes (cv)
-static int launch_qkv_proj(const mxa_attn_params& pp, const mxa_qkv_params& xq, const AttnLayout& L,
-                           const RowsPrepArgs& rq, const RowsPrepArgs& rk, const ColsPrepArgs& cv, unsigned char* ws,
-                           hipStream_t stream) {
-  const int nbk = (xq.C + 31) / 32, Cpad = 32 * nbk;
-  const int64_t tokens = (int64_t)pp.B * pp.N;
-  const RowsPrepArgs rx = flat_rows_prep(xq.x, tokens, xq.C, xq.x_row_stride, aligned16(xq.x) && xq.x_row_stride % 4 == 0,
-                                         pp.flush_subnormals, pp.bfloat, reinterpret_cast<int8_t*>(ws + L.xc),
-                                         reinterpret_cast<int16_t*>(ws + L.xs), 0);
+// One projection pass (part: ProjPart): x (ntok tokens per image, C features) -> MX codes along
+// C (rows_prep) into the workspace at xc_off / xs_off, then the projection kernel on the
+// prepared weight wq of parts * H * D rows, writing the part's q / k operands (rq, rk) and V's
+// transposed codes (cv)
+static int launch_proj_pass(const mxa_attn_params& pp, int part, const float* x, int64_t x_row_stride, int C, int ntok,
+                            const void* wq, const float* bias, float* proj_out, int autocast, int64_t xc_off,
+                            int64_t xs_off, const RowsPrepArgs& rq, const RowsPrepArgs& rk, const ColsPrepArgs& cv,
+                            unsigned char* ws, hipStream_t stream) {
+  const int parts = part == kPartQKV ? 3 : part == kPartKV ? 2 : 1;
+  const int nbk = (C + 31) / 32, Cpad = 32 * nbk;
+  const int64_t tokens = (int64_t)pp.B * ntok;
+  const RowsPrepArgs rx = flat_rows_prep(x, tokens, C, x_row_stride, aligned16(x) && x_row_stride % 4 == 0,
+                                         pp.flush_subnormals, pp.bfloat, reinterpret_cast<int8_t*>(ws + xc_off),
+                                         reinterpret_cast<int16_t*>(ws + xs_off), 0);
   int rc = launch_rows_prep(rx, stream);
   if (rc) return rc;
-  const LinearLayout W = linear_layout(3 * pp.H * pp.D, xq.C, pp.D);
-  const unsigned char* wb = static_cast<const unsigned char*>(xq.wq);
+  const LinearLayout W = linear_layout(parts * pp.H * pp.D, C, pp.D);
+  const unsigned char* wb = static_cast<const unsigned char*>(wq);
   ProjArgs pa{};
   pa.xc = rx.codes; pa.xs = rx.sT;
   pa.pk = reinterpret_cast<const int8_t*>(wb + W.pk);
@@ -208,13 +221,32 @@ static int launch_qkv_proj(const mxa_attn_params& pp, const mxa_qkv_params& xq, 
   pa.pk_bytes = (int)(W.pe - W.pk);
   pa.pe_bytes = (int)(W.ps - W.pe);
   pa.pd_bytes = (int)(W.total - W.pd);
-  pa.ntb = (pp.N + 31) / 32;
-  pa.bias = xq.bias; pa.qkv_out = xq.qkv_out;
-  pa.autocast = xq.autocast_dtype;
-  pa.B = pp.B; pa.N = pp.N; pa.H = pp.H; pa.D = pp.D; pa.nbk = nbk; pa.Cpad = Cpad; pa.bfloat = pp.bfloat;
+  pa.ntb = (ntok + 31) / 32;
+  pa.bias = bias; pa.qkv_out = proj_out;
+  pa.autocast = autocast;
+  pa.B = pp.B; pa.N = ntok; pa.H = pp.H; pa.D = pp.D; pa.nbk = nbk; pa.Cpad = Cpad; pa.bfloat = pp.bfloat;
   pa.smax = gemm_smax(nbk);
   pa.rq = rq; pa.rk = rk; pa.cv = cv;
-  return launch_proj(pa, stream);
+  return launch_proj(pa, stream, part);
+}
+
+static int launch_qkv_proj(const mxa_attn_params& pp, const mxa_qkv_params& xq, const AttnLayout& L,
+                           const RowsPrepArgs& rq, const RowsPrepArgs& rk, const ColsPrepArgs& cv, unsigned char* ws,
+                           hipStream_t stream) {
+  return launch_proj_pass(pp, kPartQKV, xq.x, xq.x_row_stride, xq.C, pp.N, xq.wq, xq.bias, xq.qkv_out,
+                          xq.autocast_dtype, L.xc, L.xs, rq, rk, cv, ws, stream);
+}
+
+// cross-attention: the query tokens -> the q operands, then the key / value tokens -> the k
+// operands and V's transposed codes (two launches of the projection kernel by parts)
+static int launch_cross_proj(const mxa_attn_params& pp, const mxa_cross_params& xc, const AttnLayout& L,
+                             const RowsPrepArgs& rq, const RowsPrepArgs& rk, const ColsPrepArgs& cv, unsigned char* ws,
+                             hipStream_t stream) {
+  const int rc = launch_proj_pass(pp, kPartQ, xc.x, xc.x_row_stride, xc.C, pp.N, xc.wq_q, xc.bias_q, xc.q_out, 0,
+                                  L.xc, L.xs, rq, rk, cv, ws, stream);
+  if (rc) return rc;
+  return launch_proj_pass(pp, kPartKV, xc.cond, xc.cond_row_stride, xc.C_kv, pp.T, xc.wq_kv, xc.bias_kv, xc.kv_out, 0,
+                          L.cc, L.cs, rq, rk, cv, ws, stream);
 }
 
 // plan != nullptr: only report the kernel path (MXA_PATH_*), launch nothing;
@@ -222,9 +254,11 @@ static int launch_qkv_proj(const mxa_attn_params& pp, const mxa_qkv_params& xq, 
 // xq: the fused qkv projection (q, k, v produced from x and the prepared weight)
 // pj: the proj Linear behind the attention (y = mx.Linear(out.transpose(1,2).reshape(B,N,C)))
 // fin (with plan): the finishing kernel (MXA_FIN_*, 0 for the scores alone)
+// xc: cross-attention's projections (q from x, k and v from cond; N and T independent)
 static int attention_impl(const mxa_attn_params* p, hipStream_t stream, hipEvent_t* ev, int* plan = nullptr,
                           bool scores_only = false, const mxa_qkv_params* xq = nullptr,
-                          const mxa_proj_params* pj = nullptr, int* fin = nullptr) {
+                          const mxa_proj_params* pj = nullptr, int* fin = nullptr,
+                          const mxa_cross_params* xc = nullptr) {
   if (!p) return MXA_ERR_ARG;
   if (pj) {
     if (scores_only || !p->top_k || !pj->wq || !pj->y || pj->out_features <= 0 || pj->y_row_stride < pj->out_features)
@@ -233,10 +267,14 @@ static int attention_impl(const mxa_attn_params* p, hipStream_t stream, hipEvent
   }
   if (xq) {
     if (!xq->x || !xq->wq || xq->C <= 0 || xq->x_row_stride < xq->C || p->N != p->T || scores_only) return MXA_ERR_ARG;
+  } else if (xc) {
+    if (!xc->x || !xc->cond || !xc->wq_q || !xc->wq_kv || xc->C <= 0 || xc->C_kv <= 0 || xc->x_row_stride < xc->C ||
+        xc->cond_row_stride < xc->C_kv || scores_only)
+      return MXA_ERR_ARG;
   } else if (!p->q || !p->k) {
     return MXA_ERR_ARG;
   }
-  if (!scores_only && ((!p->v && !xq) || (!p->out && !pj))) return MXA_ERR_ARG;
+  if (!scores_only && ((!p->v && !xq && !xc) || (!p->out && !pj))) return MXA_ERR_ARG;
   if (scores_only && !(p->approx ? p->pred_out : p->true_out)) return MXA_ERR_ARG;
   if (p->B <= 0 || p->H <= 0 || p->N <= 0 || p->T <= 0 || p->D <= 0) return MXA_ERR_ARG;
   if (!scores_only && p->top_k && (p->k_top <= 0 || p->k_top > p->T)) return MXA_ERR_ARG;
@@ -245,6 +283,8 @@ static int attention_impl(const mxa_attn_params* p, hipStream_t stream, hipEvent
     return MXA_ERR_ARG;
   if (xq && (p->dtype != MXA_DT_F32 || (xq->autocast_dtype != 0 && xq->autocast_dtype != p->score_dtype)))
     return MXA_ERR_ARG;  // the fused projection reads fp32 x; under autocast its scores follow autocast
+  if (xc && p->dtype != MXA_DT_F32) return MXA_ERR_ARG;
+  if (xc && p->score_dtype != 0) return MXA_ERR_UNSUPPORTED;  // the cross projections: float32, no autocast
   // approximators whose operands are not exact in float16 / bfloat16 (EXION's e*(2^l1+2^l2),
   // true_ex's per-element exponents, ELSA's fp32 projections): float32 only
   if ((p->dtype != MXA_DT_F32 || p->score_dtype > MXA_DT_F32) && p->approx &&
@@ -256,6 +296,11 @@ static int attention_impl(const mxa_attn_params* p, hipStream_t stream, hipEvent
   if (xq && !linear_weight_verify(xq->wq, linear_weight_header(3 * p->H * p->D, xq->C, p->D, p->flush_subnormals,
                                                                 p->bfloat),
                                   stream))
+    return MXA_ERR_ARG;
+  if (xc && !(linear_weight_verify(xc->wq_q, linear_weight_header(p->H * p->D, xc->C, p->D, p->flush_subnormals,
+                                                                   p->bfloat), stream) &&
+              linear_weight_verify(xc->wq_kv, linear_weight_header(2 * p->H * p->D, xc->C_kv, p->D,
+                                                                    p->flush_subnormals, p->bfloat), stream)))
     return MXA_ERR_ARG;
   if (pj && !linear_weight_verify_any_group(pj->wq, pj->out_features, p->H * p->D, p->flush_subnormals, p->bfloat,
                                             stream))
@@ -271,7 +316,7 @@ static int attention_impl(const mxa_attn_params* p, hipStream_t stream, hipEvent
   const bool ranked = topk || scores_only;  // the selection kernel runs
   const int mode = score_mode(&pp, ranked);
   if (mode == kModeElsa && (!pp.elsa_proj || pp.N != pp.T)) return MXA_ERR_ARG;  // elsa_approximation.py:126, :142
-  const AttnLayout L = attn_layout(&pp, mode, xq, pj);
+  const AttnLayout L = attn_layout(&pp, mode, xq, pj, xc);
   const int64_t BH = (int64_t)pp.B * pp.H;
 
   int opq = MXA_OP_SIGN, opk = MXA_OP_SIGN;
@@ -311,7 +356,7 @@ static int attention_impl(const mxa_attn_params* p, hipStream_t stream, hipEvent
   rq.H = pp.H; rq.R = pp.N; rq.rows = BH * pp.N; rq.D = pp.D; rq.nb = L.nbd; rq.dpad = L.dpad;
   const int64_t vpe = pp.dtype == MXA_DT_F32 ? 4 : 8;  // elements per 16 B
   rq.vec4 = aligned16(pp.q) && (pp.q_strides[0] % vpe == 0) && (pp.q_strides[1] % vpe == 0) && (pp.q_strides[2] % vpe == 0);
-  rq.op_kind = opq; rq.flush = pp.flush_subnormals; rq.bfloat = pp.bfloat; rq.dt = xq ? MXA_DT_F32 : pp.dtype;
+  rq.op_kind = opq; rq.flush = pp.flush_subnormals; rq.bfloat = pp.bfloat; rq.dt = (xq || xc) ? MXA_DT_F32 : pp.dtype;
   rq.codes = reinterpret_cast<int8_t*>(ws + L.qc);
   rq.sT = reinterpret_cast<int16_t*>(ws + L.qsT);
   rq.op = need_op ? reinterpret_cast<int8_t*>(ws + L.qop) : nullptr;
@@ -340,6 +385,8 @@ static int attention_impl(const mxa_attn_params* p, hipStream_t stream, hipEvent
   cv.scale = reinterpret_cast<int16_t*>(ws + L.vs);
   if (xq) {
     rc = launch_qkv_proj(pp, *xq, L, rq, rk, cv, ws, stream);
+  } else if (xc) {
+    rc = launch_cross_proj(pp, *xc, L, rq, rk, cv, ws, stream);
   } else if (scores_only) {
     rc = launch_rows_prep(rq, stream);
     if (!rc) rc = launch_rows_prep(rk, stream);
@@ -456,6 +503,20 @@ extern "C" int mxa_attention_proj(const mxa_attn_params* p, const mxa_qkv_params
                                   hipStream_t stream) {
   if (!pj) return MXA_ERR_ARG;
   return attention_impl(p, stream, nullptr, nullptr, false, xq, pj);
+}
+
+extern "C" int64_t mxa_cross_attention_workspace_bytes(const mxa_attn_params* p, const mxa_cross_params* xc,
+                                                       const mxa_proj_params* pj) {
+  if (!p || !xc || p->B <= 0 || p->H <= 0 || p->N <= 0 || p->T <= 0 || p->D <= 0 || xc->C <= 0 || xc->C_kv <= 0)
+    return -1;
+  if (pj && pj->out_features <= 0) return -1;
+  return attn_layout(p, score_mode(p, pj || p->top_k || p->pred_out), nullptr, pj, xc).total;
+}
+
+extern "C" int mxa_cross_attention(const mxa_attn_params* p, const mxa_cross_params* xc, const mxa_proj_params* pj,
+                                   hipStream_t stream) {
+  if (!xc) return MXA_ERR_ARG;
+  return attention_impl(p, stream, nullptr, nullptr, false, nullptr, pj, nullptr, xc);
 }
 
 extern "C" int mxa_attention_proj_timed(const mxa_attn_params* p, const mxa_qkv_params* xq, const mxa_proj_params* pj,

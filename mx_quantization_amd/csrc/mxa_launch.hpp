@@ -167,8 +167,9 @@ int launch_finish32_p3(const Rows2Args& ra, int BH, hipStream_t stream, bool pla
 int launch_finish32_p4(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 // the row kernel of the path: finishing kernel (top-k) or dense row kernel (mxa_fin.hip)
 int launch_rows(const Rows2Args& ra, bool topk, bool true_mode, int S, int BH, hipStream_t stream, bool plan);
-// fused qkv projection kernel (mxa_proj.hip)
-int launch_proj(const ProjArgs& pa, hipStream_t stream);
+// fused projection kernel (mxa_proj.hip): part 0 the self-attention q, k, v of one token
+// matrix, 1 / 2 cross-attention's q and k, v passes (mxa_proj.hpp ProjPart)
+int launch_proj(const ProjArgs& pa, hipStream_t stream, int part = 0);
 // does the prepared weight at wq carry this header?  Buffers prepared in this process
 // are looked up host-side; others have their header read once (not under stream capture)
 LinearWeightHeader linear_weight_header(int out_f, int in_f, int gw, int flush, int bfloat);

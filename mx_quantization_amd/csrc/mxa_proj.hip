@@ -111,11 +111,13 @@ static bool proj_plain(const ProjArgs& pa) {
          !pa.cv.flush && plain_bf(pa.cv.bfloat) && pa.cv.dt == kF32;
 }
 
-template <int NBD, bool PLAIN>
-static int launch_proj_nbd(const ProjArgs& pa, hipStream_t stream) {
-  const size_t lds = proj_lds(pa.Cpad, pa.nbk, pa.D).total;
+// Kernel: qkv_proj_kernel<NBD, PLAIN> (PART kPartQKV) or cross_proj_kernel<NBD, PLAIN, PART>
+template <auto Kernel, int PART, int NBD>
+static int launch_proj_kernel(const ProjArgs& pa, hipStream_t stream) {
+  constexpr int kParts = ProjParts<PART>::kParts, kThreads = 64 * kParts * NBD;
+  const size_t lds = proj_lds(pa.Cpad, pa.nbk, pa.D, kParts).total;
   if (lds > 160 * 1024) return MXA_ERR_UNSUPPORTED;
-  const void* kern = reinterpret_cast<const void*>(&qkv_proj_kernel<NBD, PLAIN>);
+  const void* kern = reinterpret_cast<const void*>(Kernel);
   if (hipFuncSetAttribute(kern,
                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return MXA_ERR_LAUNCH;
@@ -134,7 +136,7 @@ static int launch_proj_nbd(const ProjArgs& pa, hipStream_t stream) {
     auto it = cache.find({dev, lds});
     if (it == cache.end()) {
       int n = 0, c = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, 64 * 3 * NBD, lds) != hipSuccess || n < 1) n = 1;
+      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, kThreads, lds) != hipSuccess || n < 1) n = 1;
       if (hipDeviceGetAttribute(&c, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || c < 1) c = 256;
       it = cache.emplace(std::make_pair(dev, lds), std::make_pair(n, c)).first;
     }
@@ -156,24 +158,32 @@ static int launch_proj_nbd(const ProjArgs& pa, hipStream_t stream) {
   }
   p.hpg = (pa.H + best_g - 1) / best_g;
   const int ng = (pa.H + p.hpg - 1) / p.hpg;
-  hipLaunchKernelGGL((qkv_proj_kernel<NBD, PLAIN>), dim3((unsigned)((pa.N + 31) / 32), (unsigned)pa.B, (unsigned)ng),
-                     dim3(64 * 3 * NBD), lds, stream, p);
+  hipLaunchKernelGGL(Kernel, dim3((unsigned)((pa.N + 31) / 32), (unsigned)pa.B, (unsigned)ng), dim3(kThreads), lds,
+                     stream, p);
   return hipGetLastError() == hipSuccess ? MXA_OK : MXA_ERR_LAUNCH;
 }
 
-
-template <bool PLAIN>
-static int launch_proj_p(const ProjArgs& pa, hipStream_t stream) {
-  switch ((pa.D + 31) / 32) {
-    case 1: return launch_proj_nbd<1, PLAIN>(pa, stream);
-    case 2: return launch_proj_nbd<2, PLAIN>(pa, stream);
-    case 3: return launch_proj_nbd<3, PLAIN>(pa, stream);
-    default: return launch_proj_nbd<4, PLAIN>(pa, stream);
+template <int NBD, bool PLAIN>
+static int launch_proj_nbd(const ProjArgs& pa, int part, hipStream_t stream) {
+  switch (part) {
+    case kPartQ: return launch_proj_kernel<cross_proj_kernel<NBD, PLAIN, kPartQ>, kPartQ, NBD>(pa, stream);
+    case kPartKV: return launch_proj_kernel<cross_proj_kernel<NBD, PLAIN, kPartKV>, kPartKV, NBD>(pa, stream);
+    default: return launch_proj_kernel<qkv_proj_kernel<NBD, PLAIN>, kPartQKV, NBD>(pa, stream);
   }
 }
 
-int launch_proj(const ProjArgs& pa, hipStream_t stream) {
-  return proj_plain(pa) ? launch_proj_p<true>(pa, stream) : launch_proj_p<false>(pa, stream);
+template <bool PLAIN>
+static int launch_proj_p(const ProjArgs& pa, int part, hipStream_t stream) {
+  switch ((pa.D + 31) / 32) {
+    case 1: return launch_proj_nbd<1, PLAIN>(pa, part, stream);
+    case 2: return launch_proj_nbd<2, PLAIN>(pa, part, stream);
+    case 3: return launch_proj_nbd<3, PLAIN>(pa, part, stream);
+    default: return launch_proj_nbd<4, PLAIN>(pa, part, stream);
+  }
+}
+
+int launch_proj(const ProjArgs& pa, hipStream_t stream, int part) {
+  return proj_plain(pa) ? launch_proj_p<true>(pa, part, stream) : launch_proj_p<false>(pa, part, stream);
 }
 
 __global__ void linear_header_kernel(LinearWeightHeader* h, LinearWeightHeader v) {

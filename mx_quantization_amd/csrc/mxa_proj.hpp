@@ -17,6 +17,9 @@
 // and is quantized in place into exactly what rows_prep / cols_prep would produce
 // from q, k, v: q and k rows (codes, block exponents, approximator operands) and V's
 // codes along the 32 tokens (transposed) -- the fp32 q / k / v never reach HBM.
+// Cross-attention (PixArt's MXCrossAttention: q = to_q(x), k, v = to_k / to_v(cond),
+// workloads/PixArt/models/MX_transformer_block.py:765-860) runs the same workgroup body in two
+// passes over its two token sources: q alone, then k and v (ProjParts, cross_proj_kernel).
 #pragma once
 #include "mxa_finish.hpp"
 #include "mxa_gemm_parts.hpp"
@@ -31,11 +34,11 @@ struct ProjLds {
 // x code tile [32][Cpad + 16] (or its exponent-folded low digits; the high digits in a
 // second tile), x exponents relative to the row's smallest [nbk][32]
 // (int16, NaN -> 0), per-row smallest / largest exponent and NaN flag, tile stats, the
-// fp32 output tile of one head [32][96 NBD + 1]: q, k, v at columns 0, 32 NBD, 64 NBD
-// (padding columns beyond D take the padded MFMA columns, so every lane stores
-// unpredicated; the odd stride keeps V's column reads conflict-free; compile-time, so
-// the epilogue's 16 stores take immediate offsets)
-__host__ __device__ inline ProjLds proj_lds(int Cpad, int nbk, int D) {
+// fp32 output tile of one head [32][32 parts NBD + 1]: the pass's sub-matrices (q, k, v:
+// parts = 3) at columns 0, 32 NBD, 64 NBD (padding columns beyond D take the padded MFMA
+// columns, so every lane stores unpredicated; the odd stride keeps V's column reads
+// conflict-free; compile-time, so the epilogue's 16 stores take immediate offsets)
+__host__ __device__ inline ProjLds proj_lds(int Cpad, int nbk, int D, int parts = 3) {
   ProjLds L;
   auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
   size_t o = 0;
@@ -54,28 +57,41 @@ __host__ __device__ inline ProjLds proj_lds(int Cpad, int nbk, int D) {
   o += 32 * 4;
   L.st = o;
   o += 16;  // max row spread, smallest row exponent, the digit-path flag
-  L.ost = 96 * ((D + 31) / 32) + 1;
+  L.ost = 32 * parts * ((D + 31) / 32) + 1;
   L.ot = o;
   o += al((size_t)32 * L.ost * 4);
   L.total = o;
   return L;
 }
 
-// One workgroup per (32-token block, image, head group), looping over the group's heads; 3 * NBD waves,
+// The sub-matrices a pass computes per head (proj_block's PART): self-attention's q, k, v from
+// one token matrix and a (3 H D, C) weight, or cross-attention's two passes -- q from the query
+// tokens and an (H D, C) weight, then k, v from the key / value tokens and a (2 H D, C_kv)
+// weight (ProjArgs::N the pass's tokens per image; ProjPart, mxa_proj_args.hpp).  The weight's
+// groups are s * H + h.
+template <int PART>
+struct ProjParts {
+  static constexpr int kParts = PART == kPartQKV ? 3 : PART == kPartKV ? 2 : 1;  // sub-matrices
+  static constexpr int kRowParts = PART == kPartQKV ? 2 : 1;                     // row-quantized: q and / or k
+  static constexpr bool kHasV = PART != kPartQ;                                  // the last one is V
+};
+
+// One workgroup per (32-token block, image, head group), looping over the group's heads; parts * NBD waves,
 // wave (s, cb) = sub-matrix s (q, k, v) and its 32-column block cb of the head.
 // PLAIN (proj_plain): no bfloat rounding, no flush, no autocast, q / k operands of
 // rows_prep_block_plain and V's MXINT8 -- the bench path, compiled without the general
 // rounding code (a third of the code and registers of the general instantiation).
 // Per head: the exponent-folded digits, the shifted int32 block sums, or (wide spreads, a
 // subnormal result) fp64 block sums, all in this workgroup.
-template <int NBD, bool PLAIN>
+template <int NBD, bool PLAIN, int PART = kPartQKV>
 __device__ __forceinline__ void proj_block(const ProjArgs& a, int tb, int b, int h_begin, int h_end,
                                            unsigned char* smem) {
-  constexpr int kThreads = 64 * 3 * NBD;
-  constexpr int kOst = 96 * NBD + 1;  // == proj_lds(...).ost
+  constexpr int kParts = ProjParts<PART>::kParts;
+  constexpr int kThreads = 64 * kParts * NBD;
+  constexpr int kOst = 32 * kParts * NBD + 1;  // == proj_lds(...).ost
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int D = a.D, HD = a.H * D, nbk = a.nbk;
-  const ProjLds L = proj_lds(a.Cpad, nbk, D);
+  const ProjLds L = proj_lds(a.Cpad, nbk, D, kParts);
   int8_t* xt = reinterpret_cast<int8_t*>(smem + L.xt);
   int16_t* xe = reinterpret_cast<int16_t*>(smem + L.xe);
   int* rlo = reinterpret_cast<int*>(smem + L.rlo);
@@ -155,8 +171,8 @@ __device__ __forceinline__ void proj_block(const ProjArgs& a, int tb, int b, int
     // the digit path: every row's spread and every column spread of the workgroup's
     // heads within kDigitSpread (the weight's folded digits exist for those columns)
     uint32_t gmx = 0;
-    for (int i = lane; i < 3 * (h_end - h_begin); i += 64) {
-      const int hh = h_begin + i / 3, s3 = i - 3 * (i / 3);
+    for (int i = lane; i < kParts * (h_end - h_begin); i += 64) {
+      const int hh = h_begin + i / kParts, s3 = i - kParts * (i / kParts);
       gmx = max(gmx, (uint32_t)a.gs[2 * (s3 * a.H + hh) + 1]);
     }
     gmx = wave_max_u32(gmx);
@@ -220,14 +236,14 @@ __device__ __forceinline__ void proj_block(const ProjArgs& a, int tb, int b, int
     // the correctly rounded result (2 VALU per element and block).  Otherwise (or when
     // the result could be subnormal) the blocks are summed in fp64 (run_f64, below):
     // exact while their scaled exponents span <= 34 bits, within fp32 rounding beyond.
-    // The decision is per head (the largest column spread of its q, k, v weight groups,
+    // The decision is per head (the largest column spread of its weight groups -- q, k, v --
     // uniform over the workgroup).  A workgroup whose row spreads and heads' column spreads
     // are all <= kDigitSpread takes the exponent-folded operands instead (run_dig below).
     bool fast_ok;
     {
       int gsp = 0, glo = 1 << 20;
 #pragma unroll
-      for (int s3 = 0; s3 < 3; ++s3) {
+      for (int s3 = 0; s3 < kParts; ++s3) {
         const int g = s3 * a.H + h;
         glo = min(glo, (int)a.gs[2 * g]);
         gsp = max(gsp, (int)a.gs[2 * g + 1]);
@@ -398,21 +414,23 @@ __device__ __forceinline__ void proj_block(const ProjArgs& a, int tb, int b, int
 
     __syncthreads();
     if (a.qkv_out) {  // the fp32 projection (tests): whole rows of the tile, coalesced
-      for (int i = threadIdx.x; i < 32 * 3 * D; i += kThreads) {
-        const int m = i / (3 * D), col = i - m * (3 * D), sc = col / D;
+      for (int i = threadIdx.x; i < 32 * kParts * D; i += kThreads) {
+        const int m = i / (kParts * D), col = i - m * (kParts * D), sc = col / D;
         if (m < rows)
-          a.qkv_out[(row0 + m) * (3 * HD) + (int64_t)sc * HD + (int64_t)h * D + (col - sc * D)] =
+          a.qkv_out[(row0 + m) * (kParts * HD) + (int64_t)sc * HD + (int64_t)h * D + (col - sc * D)] =
               ot[m * kOst + sc * 32 * NBD + col - sc * D];
       }
     }
 
-    // ---- q and k rows (waves 0 .. 2 NBD - 1) beside V's columns (the other NBD waves:
-    // 64 NBD >= D lanes, one column each).  Before, the wave that took the first q rows
-    // then took V as well while the rest waited at the barrier.
+    // ---- q and k rows (waves 0 .. 2 NBD - 1; a pass with one of them: NBD waves) beside V's
+    // columns (the other NBD waves: 64 NBD >= D lanes, one column each; none in the Q pass).
+    // Before, the wave that took the first q rows then took V as well while the rest waited
+    // at the barrier.
     const int64_t hrow0 = (hrow_b + h) * a.N + n0;  // row of (b, h, n0) in the q / k tables
     constexpr int kPer = 32 * NBD * 2;              // lanes per sub-matrix: a multiple of 64
-    static_assert(kThreads - 2 * kPer == 64 * NBD, "V lanes");
-    if ((int)threadIdx.x < 2 * kPer) {
+    constexpr int kRowLanes = ProjParts<PART>::kRowParts * kPer;
+    static_assert(kThreads - kRowLanes == (ProjParts<PART>::kHasV ? 64 * NBD : 0), "V lanes");
+    if ((int)threadIdx.x < kRowLanes) {
       // rows_prep's per-block body on the tile (2 lanes per 32-element block)
       const int t = (int)threadIdx.x;
       const int sk = __builtin_amdgcn_readfirstlane(t / kPer);  // uniform per wave: q or k
@@ -423,21 +441,22 @@ __device__ __forceinline__ void proj_block(const ProjArgs& a, int tb, int b, int
       float xv[16];
 #pragma unroll
       for (int j = 0; j < 16; ++j) xv[j] = c0 + j < D ? ot[m * kOst + sk * 32 * NBD + c0 + j] : 0.0f;
-      const RowsPrepArgs& ra = sk ? a.rk : a.rq;
+      const RowsPrepArgs& ra = (PART == kPartKV || sk) ? a.rk : a.rq;
       if constexpr (PLAIN) {
         rows_prep_block_plain<16, kF32>(ra, hrow0 + m, blk, sub, c0, xv, m < rows);
       } else {
         if (rows_prep_plain(ra)) rows_prep_block_plain<16>(ra, hrow0 + m, blk, sub, c0, xv, m < rows);
         else rows_prep_block<16>(ra, hrow0 + m, blk, sub, c0, xv, m < rows);
       }
-    } else if (const int c = (int)threadIdx.x - 2 * kPer; c < D) {
+    } else if (const int c = (int)threadIdx.x - kRowLanes; ProjParts<PART>::kHasV && c < D) {
       // V: cols_prep's per-column body over the 32 tokens
+      constexpr int kVcol = 32 * (kParts - 1) * NBD;  // V is the pass's last sub-matrix
       float xv[32];
       uint32_t mx = 0;
 #pragma unroll
       for (int j = 0; j < 32; ++j) {
-        const float v = j >= rows ? 0.0f : PLAIN ? ot[j * kOst + 64 * NBD + c]
-                                                 : round_bfloat(ot[j * kOst + 64 * NBD + c], a.cv.bfloat, kRoundNearest, 1);
+        const float v = j >= rows ? 0.0f : PLAIN ? ot[j * kOst + kVcol + c]
+                                                 : round_bfloat(ot[j * kOst + kVcol + c], a.cv.bfloat, kRoundNearest, 1);
         xv[j] = v;
         const uint32_t ub = __float_as_uint(v) & 0x7FFFFFFFu;
         mx = ub > mx ? ub : mx;
@@ -453,6 +472,16 @@ __global__ __launch_bounds__(64 * 3 * NBD) __attribute__((amdgpu_waves_per_eu(4,
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   proj_block<NBD, PLAIN>(a, blockIdx.x, blockIdx.y, (int)blockIdx.z * a.hpg,
                                 min(a.H, ((int)blockIdx.z + 1) * a.hpg), smem);
+}
+
+// cross-attention's passes (PART kPartQ over the query tokens, kPartKV over the key / value
+// tokens, a.N the pass's tokens per image): 64 * parts * NBD threads
+template <int NBD, bool PLAIN, int PART>
+__global__ __launch_bounds__(64 * ProjParts<PART>::kParts * NBD) __attribute__((amdgpu_waves_per_eu(4, 8))) void
+cross_proj_kernel(ProjArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  proj_block<NBD, PLAIN, PART>(a, blockIdx.x, blockIdx.y, (int)blockIdx.z * a.hpg,
+                               min(a.H, ((int)blockIdx.z + 1) * a.hpg), smem);
 }
 
 }  // namespace mxa

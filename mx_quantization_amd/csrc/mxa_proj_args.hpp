@@ -66,6 +66,9 @@ __host__ __device__ inline LinearLayout linear_layout(int out_f, int in_f, int g
   return L;
 }
 
+// what a launch of the projection kernel computes per head (launch_proj's part)
+enum ProjPart { kPartQKV = 0, kPartQ = 1, kPartKV = 2 };
+
 struct ProjArgs {
   const int8_t* xc;   // x codes [B*N][Cpad]
   const int16_t* xs;  // x code-unit exponents [B*N][nbk]
@@ -75,15 +78,15 @@ struct ProjArgs {
   const int16_t* gs;  // per weight group: smallest exponent, largest spread (the head's fast-path test)
   const int16_t* pn;  // per padded column: NaN block flag
   const int8_t* pd;   // exponent-folded digit codes
-  const float* bias;  // [3*H*D] or null
-  float* qkv_out;     // optional [B*N][3*H*D] projection (tests)
-  int B, N, H, D, nbk, Cpad, bfloat, ntb;
+  const float* bias;  // [parts*H*D] or null (parts: 3 for q, k, v; cross-attention's passes 1 and 2)
+  float* qkv_out;     // optional [B*N][parts*H*D] projection (tests)
+  int B, N, H, D, nbk, Cpad, bfloat, ntb;  // N: the pass's tokens per image (the kv pass: T)
   int pk_bytes, pe_bytes, pd_bytes;  // buffer-descriptor extents of pk / pe / pd (< 2 GiB: launch_proj checks)
   int smax;  // largest exponent spread whose shifted int32 block sums cannot overflow
   int hpg;   // heads per workgroup (grid z = head groups: fills the last round of workgroups)
   int autocast;  // 0, or the dtype torch.autocast rounds the product to before the fp32 bias add
-  RowsPrepArgs rq, rk;  // q / k row outputs (rows_prep layout)
-  ColsPrepArgs cv;      // V outputs (cols_prep layout)
+  RowsPrepArgs rq, rk;  // q / k row outputs (rows_prep layout; the q pass writes rq only)
+  ColsPrepArgs cv;      // V outputs (cols_prep layout; the kv pass writes rk and cv)
 };
 
 // block-scaled MX GEMM (mxa_gemm.hpp): mx.matmul and mx.Linear

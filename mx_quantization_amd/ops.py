@@ -603,6 +603,93 @@ def mx_qkv_attention(x: torch.Tensor, weight, bias: Optional[torch.Tensor], num_
     return (out, idx, qkv) if return_qkv else (out, idx)
 
 
+def _token_rows(t: torch.Tensor, name: str):
+    """(B, rows, C) float32 tokens with contiguous C and evenly strided rows -> the row stride"""
+    t = _f32(t, name)
+    if t.dim() != 3 or t.stride(2) != 1:
+        raise ValueError(f"{name} must be (B, rows, C) with contiguous C")
+    if t.shape[0] > 1 and t.stride(0) != t.shape[1] * t.stride(1):
+        raise ValueError(f"{name} rows must be evenly strided over (B, rows)")
+    return t.stride(1)
+
+
+def mx_cross_attention(x: torch.Tensor, cond: torch.Tensor, q_weight, q_bias: Optional[torch.Tensor], kv_weight,
+                       kv_bias: Optional[torch.Tensor], num_heads: int, scale: float, k_top: int = 20,
+                       pred_mode: str = "ex_pred", top_k: bool = True, approx: bool = True,
+                       bias: Optional[torch.Tensor] = None, flush_subnormals: bool = False, bfloat: int = 0,
+                       return_proj: bool = False, proj_weight=None, proj_bias: Optional[torch.Tensor] = None):
+    """Cross-attention with its q and kv mx.Linears fused in front (include/mxa.h
+    mxa_cross_attention; PixArt's MXCrossAttention.forward): x (B, N, C) float32 query tokens,
+    cond (B, T, C_kv) float32 key / value tokens; q_weight (H*D, C) and kv_weight
+    = cat([W_k, W_v]) (2*H*D, C_kv), tensors or LinearWeightMX of group width D; bias the
+    additive mask, broadcast to (B, H, N, T).  Returns (out (B,H,N,D), idx (B,H,N,k) or None);
+    with proj_weight the proj mx.Linear runs behind the attention and y (B, N, out_features)
+    takes out's place (top-k only); return_proj appends the fp32 projections q (B, N, H*D) and
+    kv (B, T, 2*H*D).  Float32, no autocast."""
+    dev = require_device(x, cond, q_bias, kv_bias, bias)
+    xs, cs = _token_rows(x, "x"), _token_rows(cond, "cond")
+    B, Ntok, C = x.shape
+    Bc, T, Ckv = cond.shape
+    if Bc != B:
+        raise ValueError(f"x has {B} images, cond {Bc}")
+    HD = q_weight.out_features if isinstance(q_weight, LinearWeightMX) else q_weight.shape[0]
+    if HD % num_heads:
+        raise ValueError(f"q weight rows {HD} are not heads * head_dim")
+    D = HD // num_heads
+    wq = _prepared(q_weight, D, flush_subnormals, bfloat)
+    wkv = _prepared(kv_weight, D, flush_subnormals, bfloat)
+    if wq.in_features != C or wq.group_width != D:
+        raise ValueError(f"q weight ({wq.out_features}, {wq.in_features}) / group {wq.group_width} does not fit "
+                         f"x C={C}, heads={num_heads}")
+    if wkv.out_features != 2 * HD or wkv.in_features != Ckv or wkv.group_width != D:
+        raise ValueError(f"kv weight ({wkv.out_features}, {wkv.in_features}) / group {wkv.group_width} does not fit "
+                         f"cond C_kv={Ckv}, 2 * heads * head_dim = {2 * HD}")
+    if approx and top_k and pred_mode not in N.PRED_MODES:
+        raise ValueError(f"pred_mode {pred_mode!r} not supported")
+    # q / k / v are produced inside the call: stand-in views carry the shapes only
+    stand = torch.empty((D,), device=dev)
+    shape_q = stand.as_strided((B, num_heads, Ntok, D), (0, 0, 0, 1))
+    shape_k = stand.as_strided((B, num_heads, T, D), (0, 0, 0, 1))
+    p, _, _, keep = _attn_params(shape_q, shape_k, shape_k, scale, k_top, pred_mode, top_k, approx and top_k, bias,
+                                 flush_subnormals, bfloat, None)
+    p.q = p.k = p.v = None
+    idx = torch.empty((B, num_heads, Ntok, k_top), dtype=torch.int64, device=dev) if top_k else None
+    p.idx_out = idx.data_ptr() if idx is not None else None
+    xc = N.CrossParams()
+    xc.x, xc.x_row_stride, xc.C = x.data_ptr(), xs, C
+    xc.cond, xc.cond_row_stride, xc.C_kv = cond.data_ptr(), cs, Ckv
+    xc.wq_q, xc.wq_kv = wq.buf.data_ptr(), wkv.buf.data_ptr()
+    if q_bias is not None:
+        q_bias = _f32(q_bias, "q_bias").contiguous()
+        xc.bias_q = q_bias.data_ptr()
+    if kv_bias is not None:
+        kv_bias = _f32(kv_bias, "kv_bias").contiguous()
+        xc.bias_kv = kv_bias.data_ptr()
+    qo = kvo = None
+    if return_proj:
+        qo = torch.empty((B, Ntok, HD), dtype=torch.float32, device=dev)
+        kvo = torch.empty((B, T, 2 * HD), dtype=torch.float32, device=dev)
+        xc.q_out, xc.kv_out = qo.data_ptr(), kvo.data_ptr()
+    pj = None
+    if proj_weight is not None:
+        if not top_k:
+            raise ValueError("the fused proj runs on the top-k path")
+        pj, y, keep2 = _proj_params(proj_weight, proj_bias, HD, B * Ntok, flush_subnormals, bfloat, dev)
+        res = y.reshape(B, Ntok, -1)
+    else:
+        res = torch.empty((B, num_heads, Ntok, D), dtype=torch.float32, device=dev)
+        p.out = res.data_ptr()
+        p.out_strides[:] = (res.stride(0), res.stride(1), res.stride(2))
+    pjp = ctypes.byref(pj) if pj is not None else None
+    nbytes = lib().mxa_cross_attention_workspace_bytes(ctypes.byref(p), ctypes.byref(xc), pjp)
+    if nbytes < 0:
+        raise ValueError("bad shape")
+    ws = _workspace(dev, nbytes)
+    p.workspace, p.workspace_bytes = ws.data_ptr(), ws.numel()
+    check(lib().mxa_cross_attention(ctypes.byref(p), ctypes.byref(xc), pjp, stream_ptr(dev)), "mxa_cross_attention")
+    return (res, idx, qo, kvo) if return_proj else (res, idx)
+
+
 def selftest_mfma(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     dev = require_device(a, b)
     c = torch.empty((16, 16), dtype=torch.int32, device=dev)

@@ -1,0 +1,92 @@
+"""M.mx_cross_attention (with the proj Linear behind it) against the unfused chain of public
+ops -- M.mx_linear (q), M.mx_linear (kv), M.mx_topk_attention, M.mx_linear (to_out[0]) -- at the
+PixArt-alpha cross-attention block: B = 8, N = 256 image tokens, T = 120 text tokens,
+C = C_kv = 1152, H = 16 (D = 72), k = 20, MXINT4 and ex_pred, flush_subnormals and the mask bias,
+weights prepared once.
+
+    python tools/bench_cross.py [--steps 20] [--warmup 3] [--reps 3]
+
+Both chains and both modes are warmed up first; then per mode `reps` repetitions alternate the
+two chains, each timed with device events around `steps` calls.  Prints per mode the median
+and the spread (max - min over the repetitions) of both chains in ms per call, whether idx
+agrees and the normwise relative difference of the two y.  One JSON line per mode."""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import mx_quantization_amd as M  # noqa: E402
+
+B, N, T, C, CKV, H, K_TOP = 8, 256, 120, 1152, 1152, 16, 20
+MODES = ("MXINT4", "ex_pred")
+
+
+def timed(fn, steps):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(steps):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) / steps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--reps", type=int, default=3)
+    args = ap.parse_args()
+    if args.steps < 20:
+        ap.error("--steps must be at least 20")
+    dev = torch.device("cuda", 0)
+    g = torch.Generator(device="cpu").manual_seed(0)
+    D = C // H
+    scale = D ** -0.5
+    x, cond = torch.randn(B, N, C, generator=g).to(dev), torch.randn(B, T, CKV, generator=g).to(dev)
+    lin = lambda o, i: ((torch.randn(o, i, generator=g) * i ** -0.5).to(dev), (torch.randn(o, generator=g) * 0.1).to(dev))  # noqa: E731
+    (Wq, bq), (Wkv, bkv), (Wo, bo) = lin(C, C), lin(2 * C, CKV), lin(C, C)
+    bias = torch.where(torch.arange(T) < T // 2, 0.0, -10000.0).reshape(1, 1, 1, T).repeat(B, 1, 1, 1).to(dev)
+    kw = dict(flush_subnormals=True)
+    # the fused call takes the weights in head groups; mx_linear takes any grouping: one group each
+    wq_f, wkv_f = M.LinearWeightMX(Wq, D, **kw), M.LinearWeightMX(Wkv, D, **kw)
+    wq_u, wkv_u, wo = M.LinearWeightMX(Wq, C, **kw), M.LinearWeightMX(Wkv, 2 * C, **kw), M.LinearWeightMX(Wo, C, **kw)
+
+    def fused(mode):
+        return M.mx_cross_attention(x, cond, wq_f, bq, wkv_f, bkv, H, scale, k_top=K_TOP, pred_mode=mode, bias=bias,
+                                    proj_weight=wo, proj_bias=bo, **kw)
+
+    def unfused(mode):
+        q = M.mx_linear(x, wq_u, bq, **kw).view(B, N, H, D).transpose(1, 2)
+        kv = M.mx_linear(cond, wkv_u, bkv, **kw).view(B, T, 2, H, D)
+        k, v = kv[:, :, 0].transpose(1, 2), kv[:, :, 1].transpose(1, 2)
+        out, idx = M.mx_topk_attention(q, k, v, scale, k_top=K_TOP, pred_mode=mode, bias=bias, **kw)
+        return M.mx_linear(out.transpose(1, 2).reshape(B, N, C), wo, bo, **kw), idx
+
+    for mode in MODES:  # warm-up of both chains before any timing
+        for _ in range(args.warmup):
+            fused(mode)
+            unfused(mode)
+    torch.cuda.synchronize()
+    for mode in MODES:
+        tf, tu = [], []
+        for _ in range(args.reps):  # alternating
+            tf.append(timed(lambda: fused(mode), args.steps))
+            tu.append(timed(lambda: unfused(mode), args.steps))
+        (yf, idf), (yu, idu) = fused(mode), unfused(mode)
+        diff = (torch.linalg.norm((yf - yu).double()) / torch.linalg.norm(yu.double())).item()
+        print(json.dumps({
+            "shape": "pixart_cross", "B_N_T_C_H_k": (B, N, T, C, H, K_TOP), "pred_mode": mode, "steps": args.steps,
+            "reps": args.reps,
+            "fused_ms_median": round(statistics.median(tf), 4), "fused_ms_spread": round(max(tf) - min(tf), 4),
+            "unfused_ms_median": round(statistics.median(tu), 4), "unfused_ms_spread": round(max(tu) - min(tu), 4),
+            "fused_ms": [round(t, 4) for t in tf], "unfused_ms": [round(t, 4) for t in tu],
+            "idx_equal": bool(torch.equal(idf, idu)), "y_normwise_rel_diff": diff}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
