@@ -52,7 +52,7 @@ constexpr int kGStk = 24;  // pending introsort segments (>= depth limit 2*lg(51
 constexpr int kGSeg = 16;  // final sort segments queued for one ranking pass
 
 // Row capacity: NP (128, 256 or 512, a template parameter: the exchange slots'
-// width and the swap-rank split HP = NP/2) and the mirror's allocated positions NPA
+// width and count) and the mirror's allocated positions NPA
 // (runtime: T rounded up to a window width, so that the LDS per row -- and with it
 // the resident waves -- follows the row length)
 // per-row LDS: mirror A[NPA] (El), exchange slots P[NP] + 16 trash slots (u8 for
@@ -186,12 +186,11 @@ constexpr int pow2_floor() { return E >= 32 ? 32 : E >= 16 ? 16 : E >= 8 ? 8 : E
 // (f+1, mid, l-1) moved to f, then __unguarded_partition of (f, l)) on every row of
 // the wave with act set (l - f >= 4), all rows in lockstep.  Window: lane gl holds
 // positions lb + e, lb = b + E*gl, e < E (b even, b <= f, l <= b + 16E <= NPA).
-// HP = NP / 2 (>= any swap count).  Returns the cut.
+// The exchange slots [0, NP) hold any step's 2 nsw <= l - f - 1 swaps.  Returns the cut.
 template <int E, int NP, typename El>
 __device__ __forceinline__ int grp_partition(const GrpRow<El>& g, int f, int l, int b, bool act, int gl) {
   using T = GEl<El>;
   static_assert(E % 2 == 0, "window widths are even");
-  constexpr int HP = NP / 2;
   const int fa = act ? f : 0, la = act ? l : 4;  // idle rows read harmless positions
   const int mid = fa + (int)((uint32_t)(la - fa) >> 1);
   const int lb = b + E * gl;
@@ -262,30 +261,58 @@ __device__ __forceinline__ int grp_partition(const GrpRow<El>& g, int f, int l, 
   const uint32_t sums = g_sum(cj);
   const int cut = b + (int)(sums & 0xFFFFu);
   const uint32_t nsw = sums >> 16;
-  // the exchange: every swapping left stop publishes its position at HP + its rank,
-  // every swapping right stop (the nsw highest right stops) at its rank from the top,
-  // the rest at the lane's trash slot; then the t-th pairs trade elements, 16 pairs a
-  // row at a time (only the swaps move: ~range/4 of the positions)
-  // (u8 slots: the slot values are LDS byte addresses, the base folded into the
-  // popcount accumulations)
+  // the swapping right stops are the nsw highest right stops: in this lane its cS
+  // highest-position ones, cS = nsw - (right stops above the lane) clamped to the lane's
+  // count, which are the cS lowest set bits of Rm: Rm below bit w, w the largest with
+  // popc(Rm below bit w) <= cS (binary search on 32 - w; w <= 31 is enough, but for the
+  // whole mask at E = 32).  E = 2 needs no search: all of Rm, or bit 0 of Rm = 3, or none
+  // (= cS); there the search would cost more than the one-mask loop saves
+  const int cntR = (int)(cnt >> 16), here_up = (int)(totR - PR);
+  const int cS = min(max((int)nsw - (here_up - cntR), 0), cntR);
+  uint32_t SRm;
+  if constexpr (E == 2) {
+    SRm = cS == cntR ? Rm : (uint32_t)cS;
+  } else {
+    int wn = 32;
+#pragma unroll
+    for (int st = E >= 32 ? 16 : pow2_floor<E>(); st >= 1; st >>= 1) {
+      const int c = wn - st;
+      wn = __popc(Rm << c) <= cS ? c : wn;
+    }
+    SRm = __builtin_amdgcn_ubfe(Rm, 0u, (uint32_t)(32 - wn));
+    if constexpr (E >= 32) SRm = cS == cntR ? Rm : SRm;
+  }
+  // the exchange.  Every swapping left stop lies below the cut and every swapping right
+  // stop at or above it, so one slot index space serves both: along the row's positions
+  // the swapping left stops take the slots [0, nsw) and the swapping right stops
+  // [nsw, 2 nsw), and the t-th pair is slot t <-> slot 2 nsw - 1 - t.  A lane's slots are
+  // consecutive from its base: the left stops before it (PL) where it has positions below
+  // the cut (in the one lane the cut falls inside, PL + popc(SLm) = nsw, so its right
+  // stops continue there), else nsw + the swapping right stops of the lower lanes.  Each
+  // position publishes itself at its slot -- one combined mask, one running count -- or
+  // at the lane's trash slot; then the pairs trade elements, 16 pairs a row at a time
+  // (only the swaps move: ~range/4 of the positions)
+  // (u8 slots: the slot values are LDS byte addresses, the base folded into the count)
   const uint32_t ob = NP <= 256 ? (uint32_t)(size_t)g.P : 0u;
-  const uint32_t trash = ob + 2 * HP + gl, lbase = ob + HP + PL, rbase = ob + totR - PR, rlim = ob + nsw;
+  const uint32_t trash = ob + NP + gl;
+  const uint32_t Xm = SLm | SRm;
+  uint32_t run = ob + (j > 0 ? PL : 2 * nsw - (uint32_t)min((int)nsw, here_up));
 #pragma unroll
   for (int e = 0; e < E; ++e) {
-    const int sh = E - 1 - e;
-    const uint32_t tl = lbase + (uint32_t)__popc((Lm >> sh) >> 1);
-    const uint32_t tr = rbase - (uint32_t)__popc(Rm >> sh);
-    // branch-free: slot = swapping left stop ? tl : (swapping right stop ? tr : trash)
-    const uint32_t rsw = ((Rm >> sh) & 1u) & (uint32_t)(tr < rlim);
-    uint32_t slot = rsw ? tr : trash;
-    slot = ((SLm >> sh) & 1u) ? tl : slot;
+    // branch-free: on = -(bit e of X); slot = on ? run : trash; run += bit.  The select
+    // is a bit-field insert (left to itself the compiler forms a compare and a
+    // conditional move with a wait state between them)
+    const uint32_t on = (uint32_t)__builtin_amdgcn_sbfe((int)Xm, E - 1 - e, 1);
+    uint32_t slot;
+    asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(slot) : "v"(on), "v"(run), "v"(trash));
+    run -= on;
     if constexpr (NP <= 256) *(lu8*)(size_t)slot = (uint8_t)(lb + e);
     else p_put<NP>(g, slot, (uint32_t)(lb + e));
   }
   wave_lds_sync();
   for (uint32_t t = gl; __builtin_amdgcn_ballot_w64(t < nsw) != 0; t += 16) {
     if (t < nsw) {
-      const uint32_t y = p_get<NP>(g, t), x = p_get<NP>(g, HP + t);
+      const uint32_t x = p_get<NP>(g, t), y = p_get<NP>(g, 2 * nsw - 1 - t);
       const El ax = g.A[x], ay = g.A[y];
       g.A[x] = ay;
       g.A[y] = ax;

@@ -23,7 +23,12 @@ of each segment.  The depth-limit fallbacks (heap_select / heapsort) and the
 partial_sort branch are serial in the kernel too; here they are restated from
 stl_heap.h.
 
-Used by tests/test_topk_model.py to check the model against oracle/topk_ref.cpp.
+`partition_lanes` is the same step in the form the row-group kernel computes it
+(mxa_topk_grp.hpp grp_partition: 16 lanes of E positions, one slot index space for
+both kinds of swapping stop); `Row(keys, lanes=True)` runs the whole top-k on it.
+
+Used by tests/test_topk_model.py to check the model against oracle/topk_ref.cpp and
+by tests/test_exchange_model_cpu.py to check the lane form against the reference form.
 """
 from __future__ import annotations
 
@@ -45,11 +50,114 @@ def lg(n: int) -> int:
     return n.bit_length() - 1
 
 
+LANES = 16  # one DPP row per top-k row (mxa_topk_grp.hpp)
+WIDTHS = (2, 4, 6, 8, 10, 12, 14, 16, 24, 32)  # grp_partition_any's window widths E
+
+
+def popc(x: int) -> int:
+    return bin(x).count("1")
+
+
+def lowbits(n: int) -> int:
+    return (1 << n) - 1
+
+
+def grp_alloc(n: int) -> int:
+    """mxa_topk_grp.hpp grp_alloc: the mirror's allocated positions."""
+    return (n + 31) & ~31 if n <= 256 else (384 if n <= 384 else 512)
+
+
+def window_for(n: int, f: int, l: int):
+    """(E, b) of grp_partition_any for the range [f, l) of an n-key row (n <= 512): the
+    narrowest 16 E positions from an even base at or below f that hold the range."""
+    assert n <= 512
+    npa = grp_alloc(n)
+    need = l - (f & ~1)
+    for E in WIDTHS:
+        if LANES * E <= npa and need <= LANES * E:
+            return E, min(f & ~1, npa - LANES * E)
+    raise ValueError((n, f, l))
+
+
+def partition_lanes(keys, f, l, E, b, idx=None):
+    """One partition step as grp_partition (mxa_topk_grp.hpp) computes it: 16 lanes of E
+    positions from base b (b <= f, l <= b + 16 E); lane g holds positions b + E g + e, bit
+    E-1-e of its masks.  The median step first (as __unguarded_partition_pivot), then per
+    lane: stop masks Lm / Rm, prefix counts PL / PR over the lower lanes, the prefix length
+    j of its positions below the cut, its swapping left stops SLm (the left stops of those
+    j positions) and its swapping right stops SRm (its cS highest-position right stops,
+    the cS lowest set bits of Rm), X = SLm | SRm.  Along the row every swapping left stop
+    precedes every swapping right stop, so ONE slot index space serves both: the slot of a
+    set bit of X is base + the set bits of X before it in the lane, base = PL where the lane
+    has positions below the cut, else nsw + the swapping right stops of the lower lanes.
+    Left stops fill [0, nsw), right stops [nsw, 2 nsw), both in position order; the t-th
+    pair is slot[t] <-> slot[2 nsw - 1 - t].
+    Returns (keys, idx, cut, info): the arrays after the step and info = {nsw, slots (the
+    slot table as a dict), X (the lanes' combined masks), j (the lanes' prefix lengths)}."""
+    k = np.array(keys, dtype=np.uint64)
+    i = np.arange(len(k), dtype=np.int64) if idx is None else np.array(idx, dtype=np.int64)
+    assert b <= f and l <= b + LANES * E and l - f >= 3
+    r = Row(k)
+    r.i = i
+    r.median_to_first(f, l)
+    k, i = r.k, r.i
+    p = int(k[f])
+    Lm, Rm = [0] * LANES, [0] * LANES
+    for g in range(LANES):
+        for e in range(E):
+            z = b + E * g + e
+            if f + 1 <= z < l:  # the pivot position never counts, nor the window's padding
+                Lm[g] |= (int(k[z]) <= p) << (E - 1 - e)
+                Rm[g] |= (int(k[z]) >= p) << (E - 1 - e)
+    cntL, cntR = [popc(x) for x in Lm], [popc(x) for x in Rm]
+    PL = [sum(cntL[:g]) for g in range(LANES)]
+    PR = [sum(cntR[:g]) for g in range(LANES)]
+    totR = sum(cntR)
+    # the cut: per lane the longest prefix of its positions with T(z) <= totR
+    j = []
+    for g in range(LANES):
+        c = 0
+        while c < E and PL[g] + PR[g] + popc(Lm[g] >> (E - c - 1)) + popc(Rm[g] >> (E - c - 1)) <= totR:
+            c += 1
+        j.append(c)
+    SLm = [Lm[g] & ~lowbits(E - j[g]) for g in range(LANES)]
+    cut = b + sum(j)
+    nsw = sum(popc(x) for x in SLm)
+    X, base = [], []
+    for g in range(LANES):
+        here_up = totR - PR[g]  # right stops in this lane and above
+        cS = min(max(nsw - (here_up - cntR[g]), 0), cntR[g])
+        w = 0  # largest prefix (from the low bits: the highest positions) with <= cS right stops
+        while w < E and popc(Rm[g] & lowbits(w + 1)) <= cS:
+            w += 1
+        SRm = Rm[g] & lowbits(w)
+        assert popc(SRm) == cS and SLm[g] & SRm == 0
+        X.append(SLm[g] | SRm)
+        base.append(PL[g] if j[g] > 0 else 2 * nsw - min(nsw, here_up))
+    slots = {}
+    for g in range(LANES):
+        for e in range(E):
+            sh = E - 1 - e
+            if (X[g] >> sh) & 1:
+                s = base[g] + popc((X[g] >> sh) >> 1)
+                assert s not in slots
+                slots[s] = b + E * g + e
+    kk, ii = k.copy(), i.copy()
+    for t in range(nsw):
+        x, y = slots[t], slots[2 * nsw - 1 - t]
+        k[x], k[y] = kk[y], kk[x]
+        i[x], i[y] = ii[y], ii[x]
+    return k, i, cut, {"nsw": nsw, "slots": slots, "X": X, "j": j}
+
+
 class Row:
-    def __init__(self, keys):
+    def __init__(self, keys, lanes=False):
+        """lanes: every partition step runs in the lane form (partition_lanes, in the
+        window grp_partition_any picks) instead of the reference form partition_pivot."""
         self.k = np.array(keys, dtype=np.uint64)
         self.i = np.arange(len(keys), dtype=np.int64)
         self.fallbacks = 0
+        self.lanes = lanes
 
     def gt(self, a, b):  # comp(a, b) on positions
         return self.k[a] > self.k[b]
@@ -58,8 +166,8 @@ class Row:
         self.k[[a, b]] = self.k[[b, a]]
         self.i[[a, b]] = self.i[[b, a]]
 
-    # -- parallel-rule partition -------------------------------------------------
-    def partition_pivot(self, first, last):
+    def median_to_first(self, first, last):
+        """__move_median_to_first(first, first + 1, mid, last - 1)"""
         mid = first + (last - first) // 2
         a, b, c = first + 1, mid, last - 1
         if self.gt(a, b):
@@ -75,6 +183,18 @@ class Row:
             self.swap(first, c)
         else:
             self.swap(first, b)
+
+    # -- parallel-rule partition -------------------------------------------------
+    def partition(self, first, last):
+        """One __unguarded_partition_pivot step in the form the row was built for."""
+        if not self.lanes:
+            return self.partition_pivot(first, last)
+        E, b = window_for(len(self.k), first, last)
+        self.k, self.i, cut, _ = partition_lanes(self.k, first, last, E, b, self.i)
+        return cut
+
+    def partition_pivot(self, first, last):
+        self.median_to_first(first, last)
         p = self.k[first]
         pos = np.arange(first, last)
         seg = self.k[first:last]
@@ -167,7 +287,7 @@ class Row:
                 self.swap(first, nth)
                 return
             depth -= 1
-            cut = self.partition_pivot(first, last)
+            cut = self.partition(first, last)
             if cut <= nth:
                 first = cut
             else:
@@ -188,7 +308,7 @@ class Row:
                     l = f  # segment finished (heapsort is a full sort)
                     break
                 depth -= 1
-                cut = self.partition_pivot(f, l)
+                cut = self.partition(f, l)
                 stack.append((cut, l, depth))
                 l = cut
             if l > f:
@@ -199,9 +319,10 @@ class Row:
         self.sort_heap(0, middle)
 
 
-def topk_model(vals: np.ndarray, k: int):
-    """Index order of torch.topk(vals, k, largest=True, sorted=True) on CPU."""
-    r = Row(keys_from_f32(vals))
+def topk_model(vals: np.ndarray, k: int, lanes: bool = False):
+    """Index order of torch.topk(vals, k, largest=True, sorted=True) on CPU; lanes: every
+    partition step in the lane form of the row-group kernel (rows of <= 512 keys)."""
+    r = Row(keys_from_f32(vals), lanes=lanes)
     n = len(vals)
     if k * 64 <= n:
         r.partial_sort(k)
