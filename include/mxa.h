@@ -35,8 +35,12 @@ extern "C" {
 /* storage dtypes of tensor arguments.  The reference's ops follow their input's dtype
  * (microxscaling/mx/mx_ops.py:85, :283; elemwise_ops.py:146): on float16 / bfloat16
  * tensors the shared exponent is floor(log2) computed in that dtype, a float16 all-zero
- * block quantizes to NaN (2^-126 underflows: log2(0) = -inf, scale 2^-127 = 0, 0/0),
- * and every op's result is a tensor of that dtype. */
+ * block quantizes to NaN (2^-126 underflows: log2(0) = -inf, scale 2^-127 = 0, 0/0; with
+ * scale_bits <= 5 the clamped scale 2^-15 is a float16 and the block stays 0), so does a
+ * float16 block whose maximum is one of the top five codes 0x7bfb .. 0x7bff (floor(log2)
+ * computed in float16 is 16 there and the scale 2^16 is inf), x / 2^e that falls below the
+ * dtype's normals is rounded to the dtype (a negative x that underflows gives +0.0), and
+ * every op's result is a tensor of that dtype. */
 #define MXA_DT_F32 0
 #define MXA_DT_F16 1
 #define MXA_DT_BF16 2
@@ -99,7 +103,12 @@ int mxa_shared_exponents(const void* x, void* out, int64_t outer, int64_t axis_l
 /*
  * Elementwise bfloatX quantization.  Replaces quantize_elemwise_op / _quantize_bfloat
  * (microxscaling/mx/elemwise_ops.py:201-277) and quantize_elemwise_func_cuda
- * (microxscaling/mx/cpp/elemwise.cu:12-95).
+ * (microxscaling/mx/cpp/elemwise.cu:12-95).  bfloat 10..31 (0 / 32: identity), any
+ * MXA_ROUND_*, allow_denorm 0 / 1.  As in the reference's Python path the result is NaN where
+ * floor(log2|x|), computed in the tensor's dtype, is above the dtype's largest exponent --
+ * the top codes of the top binade, both signs: float32 0x7f7fffd4 .. 0x7f7fffff (FLT_MAX
+ * among them), bfloat16 0x7f58 .. 0x7f7f, float16 0x7bfb .. 0x7bff (2^pe is inf, x / inf = 0,
+ * 0 * inf = NaN).  The same holds wherever a `bfloat` argument rounds operands or results.
  */
 int mxa_quantize_bfloat(const void* x, void* y, int64_t n, int32_t bfloat, int32_t round_mode,
                         int32_t allow_denorm, int32_t dtype, hipStream_t stream);

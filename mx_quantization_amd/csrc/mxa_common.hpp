@@ -76,8 +76,9 @@ __device__ __forceinline__ int scale_exponent(uint32_t maxbits, int scale_emax, 
 // dtype.  Element values convert exactly to float; what differs is (i) the shared
 // exponent, floor(log2(max)) with log2 rounded to the dtype, (ii) for float16 the
 // zero block: 2^-126 underflows to 0, log2(0) = -inf, the scale 2^-127 is 0 in
-// float16 and 0/0 makes the whole block NaN, and (iii) the rounding's |y| + 0.5 is
-// rounded to the dtype (round_code).  Probes in DESIGN.md §2.
+// float16 and 0/0 makes the whole block NaN, as 2^16 = inf does for the block of a top
+// code (scale_exponent_dt), and (iii) the rounding's x / 2^e and |y| + 0.5 are rounded
+// to the dtype (round_code).  Probes in DESIGN.md §2.
 enum DType : int { kF32 = 0, kF16 = 1, kBF16 = 2 };
 
 __device__ __forceinline__ float bf16_bits_to_f(uint16_t h) { return __uint_as_float((uint32_t)h << 16); }
@@ -147,12 +148,22 @@ __device__ __forceinline__ int floor_log2_dt(uint32_t ub, int dt) {
   return e + (M >= thr ? 1 : 0);
 }
 
-// scale_exponent for a block of a dtype tensor: the float16 zero block is NaN
+// largest exponent e with 2^e finite in the dtype (mx_ops.py:293 and elemwise_ops.py:146
+// form 2^e in the tensor's dtype)
+__device__ __forceinline__ int dt_emax(int dt) { return dt == kF16 ? 15 : 127; }
+
+// scale_exponent for a block of a dtype tensor.  float16 has two NaN blocks of its own,
+// both from the scale 2^e formed in float16 (mx_ops.py:293-300): the zero block when the
+// clamp -scale_emax is below -24 (scale_bits >= 6: 2^-scale_emax is 0 and 0 / 0 is NaN; a
+// narrower scale keeps the block 0), and the block whose maximum is one of the top five
+// codes, 0x7bfb .. 0x7bff: floor(log2) is 16 there, 2^16 is inf, x / inf = 0 and 0 * inf
+// is NaN.
 __device__ __forceinline__ int scale_exponent_dt(uint32_t maxbits, int scale_emax, int dt, int* e_raw) {
   if (dt == kF32) return scale_exponent(maxbits, scale_emax, e_raw);
   const int e = floor_log2_dt(maxbits, dt);
   *e_raw = e == kExpZeroF16 ? -1000 : e;
-  if (e == kExpNaN || e == kExpZeroF16 || e > scale_emax) return kExpNaN;
+  if (e == kExpZeroF16) return scale_emax > 24 ? kExpNaN : -scale_emax;
+  if (e == kExpNaN || e > scale_emax || e > dt_emax(dt)) return kExpNaN;
   return e < -scale_emax ? -scale_emax : e;
 }
 
@@ -160,11 +171,20 @@ __device__ __forceinline__ int scale_exponent_dt(uint32_t maxbits, int scale_ema
 // returns the integer code as float, clamped to +-(2^(mbits-1)-1).
 // es is finite and in [-127, 127], so 2^-es is an exact float and x * 2^-es is
 // the correctly rounded x / 2^es.  Compiled with -ffp-contract=off.
-// On a float16 / bfloat16 tensor (dt) the reference adds the 0.5 in that dtype: |y| + 0.5
-// rounds to it (bfloat16 0.498046875 + 0.5 -> 1.0), so the sum is rounded to dt before the
-// floor (y itself is exact in dt: a power-of-two scaling of a dt value).
+// On a float16 / bfloat16 tensor (dt) the reference divides and adds the 0.5 in that dtype.
+// x / 2^es rounded to dt is exact unless it falls below the dtype's normals (float16 2^-14,
+// bfloat16 2^-126).  There it is below any code's half step, so every rounding mode gives
+// code 0 with or without the lost bits; what the rounding decides is the zero's sign: at or
+// below half the smallest subnormal (float16 2^-25, bfloat16 2^-134; ties go to even)
+// x / 2^es is +-0, sign(+-0) is 0 and the result is +0.0 whatever the sign of x (in float32
+// the product itself does this).  So the sign is taken from y against that limit (dt_zero).
+// Then |y| + 0.5 rounds to dt (bfloat16 0.498046875 + 0.5 -> 1.0) before the floor.
+__device__ __forceinline__ float dt_zero(int dt) {
+  return __uint_as_float(dt == kF16 ? 0x33000000u : (dt == kBF16 ? 0x00008000u : 0u));
+}
 __device__ __forceinline__ float round_code(float x, int es, int mbits, int rnd, int dt = 0) {
   float y = x * pow2f(-es);
+  const bool neg = y < -dt_zero(dt);  // x / 2^es, rounded to dt, is negative
   y = y * (float)(1 << (mbits - 2));
   const float a = fabsf(y);
   float r;
@@ -179,7 +199,7 @@ __device__ __forceinline__ float round_code(float x, int es, int mbits, int rnd,
   }
   const float lim = (float)((1 << (mbits - 1)) - 1);
   r = r > lim ? lim : r;
-  return y < 0.0f ? -r : r;
+  return neg ? -r : r;
 }
 
 // The MXINT8 nearest-rounding case of round_code as an int: x * 2^(6-es) is exact and
@@ -199,6 +219,9 @@ __device__ __forceinline__ int q8_code(float x, float s, int dt = 0) {
 // -> _quantize_elemwise_core :92-180 with saturate_normals=False).  bfloat in {0,32} = identity.
 // On a float16 / bfloat16 tensor (dt) the private exponent is floor(log2) computed in the
 // dtype (floor_log2_dt) and the result is a value of the dtype.
+// The private exponent is one above the dtype's largest for the top codes of the top binade,
+// where log2 rounds up to it (float32 0x7f7fffd4 .. 0x7f7fffff, bfloat16 0x7f58 .. 0x7f7f,
+// float16 0x7bfb .. 0x7bff): 2^pe is inf, A / inf = 0 and 0 * inf makes the result NaN.
 __device__ __forceinline__ float round_bfloat(float x, int bfloat, int rnd, int allow_denorm, int dt = 0) {
   if (bfloat == 0 || bfloat == 32) return x;
   const uint32_t ub = __float_as_uint(x) & 0x7FFFFFFFu;
@@ -207,6 +230,7 @@ __device__ __forceinline__ float round_bfloat(float x, int bfloat, int rnd, int 
   float xin = x;
   if (!allow_denorm && ub < 0x00800000u) xin = 0.0f * x;  // |A| < min_norm -> 0 (sign kept)
   int pe = ub == 0u ? 0 : floor_log2_dt(ub, dt);  // log2(|A| + (A==0))
+  if (pe > dt_emax(dt)) return __uint_as_float(0x7FC00000u);
   pe = pe < -126 ? -126 : pe;
   float y = xin * pow2f(-pe);
   y = y * (float)(1 << (bits - 2));
@@ -222,7 +246,7 @@ __device__ __forceinline__ float round_bfloat(float x, int bfloat, int rnd, int 
     }
   }
   float o = (y < 0.0f ? -r : r) * (1.0f / (float)(1 << (bits - 2)));
-  o = o * pow2f(pe > 127 ? 127 : pe);
+  o = o * pow2f(pe);
   const float max_norm = 1.7014118346046923e38f * ((float)((1 << (bits - 1)) - 1) / (float)(1 << (bits - 2)));
   if (fabsf(o) > max_norm) o = o < 0.0f ? -INFINITY : INFINITY;
   return round_dt(o, dt);

@@ -324,7 +324,9 @@ __global__ __launch_bounds__(256) void approx_values_kernel(ApproxArgs a) {
   const bool flush = a.flush && !(e_raw != kExpNaN && e_raw > -127);
   const float qnan = __uint_as_float(0x7FC00000u);
   const float xv = flush ? xin * 0.0f : xin;
-  const int cd = nanblk ? 0 : (int)round_code(xv, es, 8, kRoundNearest, dt);
+  // the code as the float the reference holds (a negative x that rounds to code 0 is -0.0) and as an int
+  const float cf = nanblk ? 0.0f : round_code(xv, es, 8, kRoundNearest, dt);
+  const int cd = (int)cf;
   const int maxc = (int)lanes32_max((uint32_t)(cd < 0 ? -cd : cd));
   // exponent of the MX block (in the dtype: the MX max is a value of the dtype)
   const int eA = nanblk ? kExpNaN
@@ -336,7 +338,7 @@ __global__ __launch_bounds__(256) void approx_values_kernel(ApproxArgs a) {
   } else if (a.op_kind == MXA_OP_MXINT4) {
     out = (round_code(xv, es, 4, kRoundNearest, dt) * 0.25f) * pow2f(es);
   } else {
-    const float mxv = round_dt(((float)cd * pow2f(-6)) * pow2f(es), dt);  // MX int8 value
+    const float mxv = round_dt((cf * pow2f(-6)) * pow2f(es), dt);  // MX int8 value
     switch (a.op_kind) {
       case MXA_OP_SIGN:  // (mx < 0 ? -1 : +1) * 2^eA
         out = (mxv < 0.0f ? -1.0f : 1.0f) * pow2f(eA);
@@ -389,12 +391,14 @@ __global__ __launch_bounds__(256) void approx_values_v4_kernel(ApproxArgs a) {
   const int es = scale_exponent(mb, 127, &e_raw);
   const bool nanblk = es == kExpNaN;
   const bool flush = a.flush && !(e_raw != kExpNaN && e_raw > -127);
+  float cf[4];  // the codes as floats: -0.0 where a negative x rounds to code 0
   int cd[4];
   uint32_t mc = 0u;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     const float xv = flush ? xin[i] * 0.0f : xin[i];
-    cd[i] = nanblk ? 0 : (int)round_code(xv, es, 8, kRoundNearest);
+    cf[i] = nanblk ? 0.0f : round_code(xv, es, 8, kRoundNearest);
+    cd[i] = (int)cf[i];
     mc = umax(mc, (uint32_t)(cd[i] < 0 ? -cd[i] : cd[i]));
   }
   const int maxc = (int)oct_reduce(mc, umax);
@@ -409,7 +413,7 @@ __global__ __launch_bounds__(256) void approx_values_v4_kernel(ApproxArgs a) {
       const float xv = flush ? xin[i] * 0.0f : xin[i];
       out[i] = (round_code(xv, es, 4, kRoundNearest) * 0.25f) * pow2f(es);
     } else {
-      const float mxv = ((float)cd[i] * pow2f(-6)) * pow2f(es);
+      const float mxv = (cf[i] * pow2f(-6)) * pow2f(es);
       if (OPK == MXA_OP_SIGN) {
         out[i] = (mxv < 0.0f ? -1.0f : 1.0f) * pow2f(eA);
       } else if (OPK == MXA_OP_EXION) {

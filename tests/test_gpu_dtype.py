@@ -57,6 +57,17 @@ def same(a, b, what=""):
                              f"{a[tuple(bad[0])]} vs {b[tuple(bad[0])]}")
 
 
+def same_bits(a, b, what=""):
+    """float32 arrays equal as bit patterns (-0.0 is not +0.0); NaN equals NaN"""
+    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
+    assert a.shape == b.shape, (what, a.shape, b.shape)
+    ok = (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))
+    if not ok.all():
+        bad = np.argwhere(~ok)
+        raise AssertionError(f"{what}: {bad.shape[0]}/{ok.size} mismatches, first {bad[:4].tolist()}: "
+                             f"{a[tuple(bad[0])]!r} vs {b[tuple(bad[0])]!r}")
+
+
 def out_close(got, ref, tol, what):
     """the NaN pattern bit-exact, the finite elements within tol normwise"""
     same(np.isnan(got), np.isnan(ref), what + " NaN pattern")
@@ -79,7 +90,8 @@ def test_shared_exponents_every_value(M, D, dt):
 @pytest.mark.parametrize("dt", ["f16", "bf16"])
 def test_quantize_mx_kats(M, D, dt):
     """quantize_mx_op on dtype tensors: random blocks, the float16 zero-block NaN, tiny
-    and large blocks, inf / NaN, both axes, int4, subnormal flush."""
+    and large blocks, inf / NaN, both axes, int4, subnormal flush.  Bit patterns: the
+    sign of a zero counts."""
     from mx_quantization_amd.mx import mx_ops
     from mx_quantization_amd.mx.specs import apply_mx_specs
     base = dict(block_size=32, scale_bits=8, shared_exp_method="max", custom_cuda=False,
@@ -91,7 +103,7 @@ def test_quantize_mx_kats(M, D, dt):
                                ("q_int8_flush", "int8", -1, apply_mx_specs(dict(base, mx_flush_fp32_subnorms=True)))):
         got = mx_ops.quantize_mx_op(x, spec, elem_format=fmt, axes=[ax])
         assert got.dtype == TDT[dt]
-        same(host(got), D[f"{dt}/{key}"], f"{dt} {key}")
+        same_bits(host(got), D[f"{dt}/{key}"], f"{dt} {key}")
     if dt == "f16":  # the all-zero block of row 1 is NaN in float16 (0 / 2^-127 underflowed)
         assert np.isnan(D["f16/q_int8_ax1"][1, 32:64]).all()
 
