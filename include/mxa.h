@@ -289,6 +289,20 @@ typedef struct mxa_qkv_params {
 int64_t mxa_linear_weight_bytes(int32_t out_features, int32_t in_features, int32_t group_width);
 int mxa_linear_weight_prep(const float* w, int32_t out_features, int32_t in_features, int32_t group_width,
                            int32_t flush_subnormals, int32_t bfloat, void* wq, hipStream_t stream);
+/*
+ * The same with the element width as an argument: elem_bits 8 is mxa_linear_weight_bytes /
+ * mxa_linear_weight_prep exactly (the same bytes, the same size); elem_bits 4 prepares MXINT4
+ * (the reference's w_elem_format "int4": codes in [-7, 7], one exponent-folded digit plane --
+ * a smaller buffer, its header marked 4 bits); any other width: -1 / MXA_ERR_ARG before any
+ * HIP call.  mxa_linear and mxa_mlp take the width from the weight's header and quantize their
+ * activations at the same width (W4A4); the attention entry points (mxa_qkv_attention,
+ * mxa_attention_proj, mxa_cross_attention) return MXA_ERR_ARG for a 4-bit weight.
+ */
+int64_t mxa_linear_weight_bytes_bits(int32_t out_features, int32_t in_features, int32_t group_width,
+                                     int32_t elem_bits);
+int mxa_linear_weight_prep_bits(const float* w, int32_t out_features, int32_t in_features, int32_t group_width,
+                                int32_t flush_subnormals, int32_t bfloat, int32_t elem_bits, void* wq,
+                                hipStream_t stream);
 int64_t mxa_qkv_attention_workspace_bytes(const mxa_attn_params* p, const mxa_qkv_params* x);
 int mxa_qkv_attention(const mxa_attn_params* p, const mxa_qkv_params* x, hipStream_t stream);
 /* mxa_attention_timed for the fused projection path (stage 0 = x quantize + projection) */
@@ -301,7 +315,8 @@ int mxa_qkv_attention_timed(const mxa_attn_params* p, const mxa_qkv_params* x, h
  *   out = bf(out + bf(bias))          (bf = quantize_elemwise_op: bfloat rounding or none)
  * x (rows, in_features) fp32 at x_row_stride; wq from mxa_linear_weight_prep(W, out_features,
  * in_features, any group_width, flush_subnormals, bfloat) -- MXA_ERR_ARG if its header
- * differs; out (rows, out_features) fp32 at out_row_stride.  Every product is the exact sum
+ * differs -- or from mxa_linear_weight_prep_bits: MX is MXINT8, or MXINT4 for both operands
+ * with a 4-bit weight (its header's width); out (rows, out_features) fp32 at out_row_stride.  Every product is the exact sum
  * rounded once (the reference's MKL sgemm order is unpinned: equal within fp32 rounding).
  * autocast_dtype: 0, or MXA_DT_F16 / BF16 (torch.autocast: the product rounded to that
  * dtype before the fp32 bias add).  The patched modules' proj Linear (deit main.py:154, DiT
@@ -323,10 +338,12 @@ int mxa_linear(const float* x, int64_t rows, int32_t in_features, int64_t x_row_
  *   act = gelu(pre)                 float32; MXA_ACT_GELU 0.5 h (1 + erf(h / sqrt 2)),
  *                                   MXA_ACT_GELU_TANH torch's tanh form
  *   y   = mx.Linear(act; W2, b2)    its input rule included: bf(act), MXINT8 blocks of 32
+ *                                   (MXINT4 throughout when w1 and w2 are 4-bit weights;
+ *                                   weights of different widths: MXA_ERR_ARG)
  * Float32, no autocast.  fc1's epilogue applies the GELU and writes fc2's MX input codes
  * itself, so the fp32 hidden matrix never reaches HBM; an fc1 that does not run on that
  * kernel (w1 prepared in groups that are neither hidden_features nor a multiple of 32
- * columns, or in_features beyond 72 blocks of 32) goes through an fp32 workspace and the row
+ * columns, or in_features beyond 72 blocks of 32 -- 144 for 4-bit weights) goes through an fp32 workspace and the row
  * quantizer with the same GELU: the same bits.  A NaN in x gives NaN rows in pre, act and
  * y.  pre = +-inf is not pinned (torch's own CPU kernel returns NaN for gelu(+inf) in the erf
  * form).  w1 / w2: mxa_linear_weight_prep of W1 (hidden_features, in_features) / W2

@@ -17,18 +17,22 @@ int gemm_smax(int nbk) {
 // weight's digit kernel launches from here too, behind the shape's refusal tests: a Linear
 // the tile kernel would refuse is refused whichever kernel would run it.
 template <bool PLAIN, int SH>
-static int launch_gemm_shape(const GemmArgs& ga, int64_t batch, hipStream_t stream) {
+static int launch_gemm_shape(const GemmArgs& ga, int64_t batch, hipStream_t stream, bool bits4) {
   using S = GemmShape<SH>;
   const size_t lds = gemm_lds(ga.nbk, SH).total;
   const int64_t gx = (ga.Nc + S::CW - 1) / S::CW, gy = (ga.M + S::RW - 1) / S::RW;
   if (lds > 160 * 1024 || gy > 65535) return MXA_ERR_UNSUPPORTED;
-  if (ga.bpd && batch == 1 && ga.nbk <= kGemmDigNbkMax) {
+  if (ga.bpd && batch == 1 && ga.nbk <= (bits4 ? kGemmDig4NbkMax : kGemmDigNbkMax)) {
     // a prepared weight: the exponent-folded digits, every row block in the one launch (a
-    // block the digits cannot take sums its K-blocks in fp64 in the same workgroup)
-    const size_t dl = gemm_dig_lds(ga.nbk).total;
-    const void* dk = reinterpret_cast<const void*>(&mx_gemm_dig_kernel<PLAIN>);
+    // block the digits cannot take sums its K-blocks in fp64 in the same workgroup); an
+    // MXINT4 weight (its header's width) on the one-digit kernel
+    const size_t dl = gemm_dig_lds(ga.nbk, bits4 ? 1 : 2).total;
+    const void* dk = bits4 ? reinterpret_cast<const void*>(&mx_gemm_dig4_kernel<PLAIN>)
+                              : reinterpret_cast<const void*>(&mx_gemm_dig_kernel<PLAIN>);
     if (hipFuncSetAttribute(dk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)dl) != hipSuccess) return MXA_ERR_LAUNCH;
-    hipLaunchKernelGGL(mx_gemm_dig_kernel<PLAIN>, dim3((unsigned)((ga.M + 31) / 32)), dim3(256), dl, stream, ga);
+    const dim3 grid((unsigned)((ga.M + 31) / 32));
+    if (bits4) hipLaunchKernelGGL(mx_gemm_dig4_kernel<PLAIN>, grid, dim3(256), dl, stream, ga);
+    else hipLaunchKernelGGL(mx_gemm_dig_kernel<PLAIN>, grid, dim3(256), dl, stream, ga);
     return hipGetLastError() == hipSuccess ? MXA_OK : MXA_ERR_LAUNCH;
   }
   const void* gk = reinterpret_cast<const void*>(&mx_gemm_kernel<PLAIN, SH>);
@@ -51,26 +55,27 @@ static int launch_gemm_shape(const GemmArgs& ga, int64_t batch, hipStream_t stre
 // contiguous columns on 32-row strips of whole rows (the strip stages float32 rows: only the
 // PLAIN instantiation has it); else 64 x 128
 template <bool PLAIN>
-static int launch_gemm_p(const GemmArgs& ga0, int64_t batch, hipStream_t stream) {
+static int launch_gemm_p(const GemmArgs& ga0, int64_t batch, hipStream_t stream, bool bits4) {
   GemmArgs ga = ga0;
   ga.smax = gemm_smax(ga.nbk);
-  if (ga.Nc <= GemmShape<kGemmTall>::CW) return launch_gemm_shape<PLAIN, kGemmTall>(ga, batch, stream);
+  if (ga.Nc <= GemmShape<kGemmTall>::CW) return launch_gemm_shape<PLAIN, kGemmTall>(ga, batch, stream, bits4);
   if constexpr (PLAIN)
-    if (ga.Nc <= GemmShape<kGemmWide>::CW && ga.ldc == ga.Nc) return launch_gemm_shape<true, kGemmWide>(ga, batch, stream);
-  return launch_gemm_shape<PLAIN, kGemmSquare>(ga, batch, stream);
+    if (ga.Nc <= GemmShape<kGemmWide>::CW && ga.ldc == ga.Nc) return launch_gemm_shape<true, kGemmWide>(ga, batch, stream, bits4);
+  return launch_gemm_shape<PLAIN, kGemmSquare>(ga, batch, stream, bits4);
 }
 
-int launch_gemm(const GemmArgs& ga, int64_t batch, hipStream_t stream) {
+int launch_gemm(const GemmArgs& ga, int64_t batch, hipStream_t stream, bool bits4) {
   if (ga.M <= 0 || ga.Nc <= 0 || ga.nbk <= 0 || batch <= 0) return MXA_ERR_ARG;
   const bool plain = (ga.bfloat == 0 || ga.bfloat == 32) && (ga.linear ? ga.autocast == 0 : ga.dt == kF32);
-  return plain ? launch_gemm_p<true>(ga, batch, stream) : launch_gemm_p<false>(ga, batch, stream);
+  return plain ? launch_gemm_p<true>(ga, batch, stream, bits4) : launch_gemm_p<false>(ga, batch, stream, bits4);
 }
 
 // The GemmArgs of an mx.Linear on MX rows (rows_prep layout: codes [rows][Cpad] or MFMA-ready,
 // exponents [rows][nbk]) with a prepared weight (its row-major codes / exponents; its
 // MFMA-ready codes and digits where its column blocks are the output columns)
 GemmArgs linear_gemm_args(const int8_t* xc, const int16_t* xs, int64_t rows, int in_f, const void* wq, int out_f,
-                          const float* bias, float* out, int64_t out_row_stride, int bfloat, int autocast, bool x_mfma) {
+                          const float* bias, float* out, int64_t out_row_stride, int bfloat, int autocast, bool x_mfma,
+                          bool* bits4) {
   const LinearLayout W = linear_layout(out_f, in_f, out_f);  // raw regions do not depend on gw
   const unsigned char* wb = static_cast<const unsigned char*>(wq);
   GemmArgs g{};
@@ -81,8 +86,10 @@ GemmArgs linear_gemm_args(const int8_t* xc, const int16_t* xs, int64_t rows, int
   // the MFMA-ready codes when the buffer's column blocks are the output columns (one group,
   // or groups of a multiple of 32 columns): its header's group width decides
   LinearWeightHeader h{};
-  if (linear_weight_known_header(wq, &h) && (h.gw == out_f || h.gw % 32 == 0)) {
-    const LinearLayout P = linear_layout(out_f, in_f, h.gw);
+  const bool known = linear_weight_known_header(wq, &h);
+  if (bits4) *bits4 = known && h.elem_bits == 4;
+  if (known && (h.gw == out_f || h.gw % 32 == 0)) {
+    const LinearLayout P = linear_layout(out_f, in_f, h.gw, h.elem_bits);
     g.bpk = reinterpret_cast<const int8_t*>(wb + P.pk);
     g.b_nb32 = P.G * P.NB32;
     g.bpd = reinterpret_cast<const int8_t*>(wb + P.pd);
@@ -101,8 +108,10 @@ int launch_linear_codes(const int8_t* xc, const int16_t* xs, int64_t rows, int i
                         const float* bias, float* out, int64_t out_row_stride, int bfloat, int autocast,
                         hipStream_t stream, bool x_mfma) {
   if (rows > ((int64_t)1 << 31) - 1) return MXA_ERR_UNSUPPORTED;
-  return launch_gemm(linear_gemm_args(xc, xs, rows, in_f, wq, out_f, bias, out, out_row_stride, bfloat, autocast, x_mfma),
-                     1, stream);
+  bool bits4 = false;
+  const GemmArgs ga =
+      linear_gemm_args(xc, xs, rows, in_f, wq, out_f, bias, out, out_row_stride, bfloat, autocast, x_mfma, &bits4);
+  return launch_gemm(ga, 1, stream, bits4);
 }
 
 }  // namespace mxa
@@ -125,18 +134,20 @@ extern "C" int mxa_linear(const float* x, int64_t rows, int32_t in_features, int
     return MXA_ERR_ARG;
   if (!valid_bfloat(bfloat)) return MXA_ERR_ARG;
   if (autocast_dtype != 0 && autocast_dtype != MXA_DT_F16 && autocast_dtype != MXA_DT_BF16) return MXA_ERR_ARG;
-  if (!linear_weight_verify_any_group(wq, out_features, in_features, flush_subnormals, bfloat, stream))
+  int bits = 0;  // the weight's element width (its header's): x is quantized at the same
+  if (!linear_weight_verify_any_group(wq, out_features, in_features, flush_subnormals, bfloat, stream, &bits))
     return MXA_ERR_ARG;
   const int64_t need = mxa_linear_workspace_bytes(rows, in_features, out_features);
   if (!workspace || workspace_bytes < need || !aligned16(workspace)) return MXA_ERR_WORKSPACE;
   const int nbk = (in_features + 31) / 32, Cpad = 32 * nbk;
   unsigned char* ws = static_cast<unsigned char*>(workspace);
   const int64_t rows32 = (rows + 31) / 32 * 32;
+  int8_t* xc = reinterpret_cast<int8_t*>(ws);
+  int16_t* xe = reinterpret_cast<int16_t*>(ws + (rows32 * Cpad + 255) / 256 * 256);
   const RowsPrepArgs rx = flat_rows_prep(x, rows, in_features, x_row_stride, aligned16(x) && x_row_stride % 4 == 0,
-                                         flush_subnormals, bfloat, reinterpret_cast<int8_t*>(ws),
-                                         reinterpret_cast<int16_t*>(ws + (rows32 * Cpad + 255) / 256 * 256), 1);
+                                         flush_subnormals, bfloat, xc, xe, 1, bits);
   int rc = launch_rows_prep(rx, stream);
   if (rc) return rc;
-  return launch_linear_codes(rx.codes, rx.sT, rows, in_features, wq, out_features, bias, out, out_row_stride, bfloat,
+  return launch_linear_codes(xc, xe, rows, in_features, wq, out_features, bias, out, out_row_stride, bfloat,
                              autocast_dtype, stream, true);
 }

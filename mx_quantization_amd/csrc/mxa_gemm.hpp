@@ -388,13 +388,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) voi
 // K-blocks: the sums of gemm_tile's run_f64, exact while the scaled blocks span <= 34 bits
 // -- so also wherever the shifted int32 sums are exact), so one launch covers every row
 // block: no flag, no follow-up kernels.
+//
+// DIG = 1, MXINT4 rows and weight (launch_gemm's bits4; codes in [-7, 7], exponents of a code unit
+// es - 2): the same body with one digit.  code * 2^s fits one signed int8 for s <= kDigit4Spread
+// (7 * 16 = 112), so the rows fold into one plane (1 KB of LDS per K-block), the weight's pd is
+// one plane, the K loop issues one MFMA per K-block into one accumulator (|sum| <= nbk 32 112^2
+// < 2^31 for every nbk the LDS holds) and the result is ldexp((double)c, rlo + clo), rounded
+// once.  The gate: spreads <= kDigit4Spread and the same subnormal bound (the exponents are the
+// code units', so min ex + min ew >= -126 is the same expression).
 struct GemmDigLds {
   size_t ad, rlo, rhi, rn, st, total;
 };
-__host__ __device__ inline GemmDigLds gemm_dig_lds(int nbk) {
+__host__ __device__ inline GemmDigLds gemm_dig_lds(int nbk, int dig = 2) {
   GemmDigLds L;
   L.ad = 0;
-  L.rlo = (size_t)nbk * 2048;
+  L.rlo = (size_t)nbk * 1024 * dig;
   L.rhi = L.rlo + 128;
   L.rn = L.rhi + 128;
   L.st = L.rn + 128;
@@ -402,6 +410,7 @@ __host__ __device__ inline GemmDigLds gemm_dig_lds(int nbk) {
   return L;
 }
 constexpr int kGemmDigNbkMax = 72;  // 2 KB of LDS per K-block: <= 144 KB
+constexpr int kGemmDig4NbkMax = 144;  // one digit, 1 KB per K-block: the same 144 KB (K <= 4,608)
 
 // The kernel's body, with the epilogue of a wave's 32 x 32 tile as a parameter.  DigStoreF32:
 // the Linear's fp32 store (mx_gemm_dig_kernel).  Any other Epi is called by all 64 lanes as
@@ -411,10 +420,12 @@ constexpr int kGemmDigNbkMax = 72;  // 2 KB of LDS per K-block: <= 144 KB
 // 32) + i % 4, column 32 cb + lane % 32); ext: the LDS behind gemm_dig_lds(nbk).total (the
 // launch sized it).  mxa_mlp.hpp: fc1 of the fused MLP.
 struct DigStoreF32 {};
-template <bool PLAIN, class Epi>
+template <bool PLAIN, class Epi, int DIG = 2>
 __device__ __forceinline__ void gemm_dig_block(const GemmArgs a, const Epi epi, unsigned char* smem) {
+  static_assert(DIG == 1 || DIG == 2, "digits per code");
+  constexpr int kSpread = DIG == 1 ? kDigit4Spread : kDigitSpread;
   const int nbk = a.nbk;
-  const GemmDigLds L = gemm_dig_lds(nbk);
+  const GemmDigLds L = gemm_dig_lds(nbk, DIG);
   int8_t* ad = reinterpret_cast<int8_t*>(smem + L.ad);
   int* rlo = reinterpret_cast<int*>(smem + L.rlo);
   int* rhi = reinterpret_cast<int*>(smem + L.rhi);
@@ -463,7 +474,7 @@ __device__ __forceinline__ void gemm_dig_block(const GemmArgs a, const Epi epi, 
     }
     gsp = wave_max_u32(gsp);
     glo = wave_min_u32(glo);
-    const bool ok = smx <= (uint32_t)kDigitSpread && gsp <= (uint32_t)kDigitSpread &&
+    const bool ok = smx <= (uint32_t)kSpread && gsp <= (uint32_t)kSpread &&
                     (lmn == 0xFFFFFFFFu || (int)lmn + (int)glo - (2 << 20) >= -126);
     if (lane == 0) st[0] = ok;
   }
@@ -525,26 +536,38 @@ __device__ __forceinline__ void gemm_dig_block(const GemmArgs a, const Epi epi, 
     if (m < rows) {
       v = *reinterpret_cast<const uint4*>(code_at(m, kb, ln >> 5));
       const int e = exp_at(m, kb), lo = rlo[m] > rhi[m] ? 0 : rlo[m];
-      sh = e == kExpNaN ? 0 : min(max(e - lo, 0), kDigitSpread);  // (a left-out zero block: any shift)
+      sh = e == kExpNaN ? 0 : min(max(e - lo, 0), kSpread);  // (a left-out zero block: any shift)
     }
-    uint4 d0, d1;
-    fold_digits16(v, sh, d0, d1);
-    *reinterpret_cast<uint4*>(ad + kb * 2048 + ln * 16) = d0;
-    *reinterpret_cast<uint4*>(ad + kb * 2048 + 1024 + ln * 16) = d1;
+    if constexpr (DIG == 1) {
+      *reinterpret_cast<uint4*>(ad + kb * 1024 + ln * 16) = fold_digit16(v, sh);
+    } else {
+      uint4 d0, d1;
+      fold_digits16(v, sh, d0, d1);
+      *reinterpret_cast<uint4*>(ad + kb * 2048 + ln * 16) = d0;
+      *reinterpret_cast<uint4*>(ad + kb * 2048 + 1024 + ln * 16) = d1;
+    }
   }
   __syncthreads();
 
   // ---- per wave: 32-column blocks wave, wave + 4, ... --------------------------------
   const int8_t* adl = ad + lane * 16;
   for (int cb = wave; cb < ncb; cb += 4) {
-    const int8_t* bp = a.bpd + (int64_t)cb * nbk * 2048 + lane * 16;
-    const DigitSums d = digit_k_loop(
-        [&](int kb, int p) { return *reinterpret_cast<const v4i_*>(bp + (int64_t)kb * 2048 + p * 1024); }, adl, adl + 1024,
-        2048, nbk);
-    const int clo = a.bps[2 * min(32 * cb + ln, a.Nc - 1)];
-    store_out(cb, [&](int i, int m) {
-      return digits_to_f32(d.c0[i], d.c1[i], d.c2[i], (rlo[m] > rhi[m] ? 0 : rlo[m]) + clo);
-    });
+    if constexpr (DIG == 1) {
+      const int8_t* bp = a.bpd + (int64_t)cb * nbk * 1024 + lane * 16;
+      const v16i c = digit4_k_loop([&](int kb) { return *reinterpret_cast<const v4i_*>(bp + (int64_t)kb * 1024); }, adl,
+                                   1024, nbk);
+      const int clo = a.bps[2 * min(32 * cb + ln, a.Nc - 1)];
+      store_out(cb, [&](int i, int m) { return (float)ldexp((double)c[i], (rlo[m] > rhi[m] ? 0 : rlo[m]) + clo); });
+    } else {
+      const int8_t* bp = a.bpd + (int64_t)cb * nbk * 2048 + lane * 16;
+      const DigitSums d = digit_k_loop(
+          [&](int kb, int p) { return *reinterpret_cast<const v4i_*>(bp + (int64_t)kb * 2048 + p * 1024); }, adl,
+          adl + 1024, 2048, nbk);
+      const int clo = a.bps[2 * min(32 * cb + ln, a.Nc - 1)];
+      store_out(cb, [&](int i, int m) {
+        return digits_to_f32(d.c0[i], d.c1[i], d.c2[i], (rlo[m] > rhi[m] ? 0 : rlo[m]) + clo);
+      });
+    }
   }
 }
 
@@ -552,6 +575,12 @@ template <bool PLAIN>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) void mx_gemm_dig_kernel(GemmArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   gemm_dig_block<PLAIN>(a, DigStoreF32{}, smem);
+}
+// MXINT4 rows and weight: the one-digit body
+template <bool PLAIN>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) void mx_gemm_dig4_kernel(GemmArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  gemm_dig_block<PLAIN, DigStoreF32, 1>(a, DigStoreF32{}, smem);
 }
 
 }  // namespace mxa

@@ -99,4 +99,49 @@ __device__ __forceinline__ float digits_to_f32(int c0, int c1, int c2, int e) {
   return (float)ldexp((double)c0 + 256.0 * (double)c1 + 65536.0 * (double)c2, e);
 }
 
+// ---- MXINT4: one digit ---------------------------------------------------------------
+// 16 int4 codes (|c| <= 7) times 2^s (0 <= s <= kDigit4Spread): |c * 2^s| <= 112, one signed
+// int8 each
+__device__ __forceinline__ uint4 fold_digit16(const uint4& v, int s) {
+  const uint32_t in[4] = {v.x, v.y, v.z, v.w};
+  uint32_t o[4];
+#pragma unroll
+  for (int w = 0; w < 4; ++w) {
+    uint32_t p = 0;
+#pragma unroll
+    for (int b = 0; b < 4; ++b) p |= ((uint32_t)((int)(int8_t)(in[w] >> (8 * b)) << s) & 0xFFu) << (8 * b);
+    o[w] = p;
+  }
+  return make_uint4(o[0], o[1], o[2], o[3]);
+}
+
+// digit_k_loop for one-digit operands: one MFMA per K-block into one accumulator (|sum| <=
+// nbk 32 112^2 < 2^31 for nbk <= 5,349).  wdig(kb): the lane's 16 B of the weight's digit
+// chunk of K-block kb, loaded four blocks ahead as above; a_d: the lane's 16 B of the rows'
+// digits of block 0 in LDS, astep bytes from block to block.
+template <class WDig>
+__device__ __forceinline__ v16i digit4_k_loop(WDig&& wdig, const int8_t* a_d, int astep, int nbk) {
+  v16i c = {};
+  const int last = nbk - 1;
+  auto cl = [&](int kb) { return min(kb, last); };
+  v4i_ W0 = wdig(0), W1 = wdig(cl(1)), W2 = wdig(cl(2)), W3 = wdig(cl(3));
+  auto step = [&](int kb, v4i_& Ws) {
+    const v4i_ ad = *reinterpret_cast<const v4i_*>(a_d + astep * kb);
+    c = __builtin_amdgcn_mfma_i32_32x32x32_i8(ad, Ws, c, 0, 0, 0);
+    Ws = wdig(cl(kb + 4));
+    __builtin_amdgcn_sched_barrier(0);  // reload each slot right after its use
+  };
+  int kb = 0;
+  for (; kb + 4 <= nbk; kb += 4) {
+    step(kb, W0);
+    step(kb + 1, W1);
+    step(kb + 2, W2);
+    step(kb + 3, W3);
+  }
+  if (kb < nbk) step(kb, W0);
+  if (kb + 1 < nbk) step(kb + 1, W1);
+  if (kb + 2 < nbk) step(kb + 2, W2);
+  return c;
+}
+
 }  // namespace mxa

@@ -15,15 +15,21 @@ inline bool valid_bfloat(int bfloat) { return bfloat == 0 || bfloat == 32 || (bf
 // RowsPrepArgs of a float32 row-major matrix (rows x cols, row_stride elements from row to
 // row) -> MXINT8 rows along its last axis: codes [rows][32 nb] (mfma_rows: in the MX GEMM's
 // MFMA-ready row blocks) and block exponents [rows][nb].  vec4: the caller's own test that x
-// may be read in 16-B loads
+// may be read in 16-B loads.  elem_bits 4 (a prepared weight's header width; 0 / 8: MXINT8):
+// MXINT4 codes in [-7, 7] and the code unit's exponents es - 2 into the same two arrays (the
+// block body's op / sA outputs)
 inline RowsPrepArgs flat_rows_prep(const void* x, int64_t rows, int cols, int64_t row_stride, bool vec4, int flush,
-                                   int bfloat, int8_t* codes, int16_t* exps, int mfma_rows) {
+                                   int bfloat, int8_t* codes, int16_t* exps, int mfma_rows, int elem_bits = 0) {
   RowsPrepArgs r{};
   r.x = x; r.s0 = 0; r.s1 = 0; r.s2 = row_stride;
   r.H = 1; r.R = rows; r.rows = rows; r.D = cols; r.nb = (cols + 31) / 32; r.dpad = 32 * r.nb;
   r.vec4 = vec4;
   r.op_kind = MXA_OP_MXINT8; r.flush = flush; r.bfloat = bfloat; r.dt = MXA_DT_F32;
   r.codes = codes; r.sT = exps; r.mfma_rows = mfma_rows;
+  if (elem_bits == 4) {
+    r.op_kind = MXA_OP_MXINT4;
+    r.codes = nullptr; r.sT = nullptr; r.op = codes; r.sA = exps;
+  }
   return r;
 }
 
@@ -172,11 +178,16 @@ int launch_rows(const Rows2Args& ra, bool topk, bool true_mode, int S, int BH, h
 int launch_proj(const ProjArgs& pa, hipStream_t stream, int part = 0);
 // does the prepared weight at wq carry this header?  Buffers prepared in this process
 // are looked up host-side; others have their header read once (not under stream capture)
-LinearWeightHeader linear_weight_header(int out_f, int in_f, int gw, int flush, int bfloat);
+// (elem_bits: the header's field -- 0 an MXINT8 weight, 4 an MXINT4 one; the attention entry
+// points ask for 0, so they refuse a 4-bit weight)
+LinearWeightHeader linear_weight_header(int out_f, int in_f, int gw, int flush, int bfloat, int elem_bits = 0);
 bool linear_weight_verify(const void* wq, const LinearWeightHeader& want, hipStream_t stream);
 
 // does the prepared weight carry (out_f, in_f, flush, bfloat), whatever its group width?
-bool linear_weight_verify_any_group(const void* wq, int out_f, int in_f, int flush, int bfloat, hipStream_t stream);
+// elem_bits null: an MXINT8 weight only; else the weight's own width (0 or 4) is accepted and
+// returned
+bool linear_weight_verify_any_group(const void* wq, int out_f, int in_f, int flush, int bfloat, hipStream_t stream,
+                                    int* elem_bits = nullptr);
 // the header of a prepared weight this process has seen (verified or prepared)
 bool linear_weight_known_header(const void* wq, LinearWeightHeader* h);
 // the largest row + column exponent spread whose shifted int32 block sums stay exact over
@@ -184,10 +195,14 @@ bool linear_weight_known_header(const void* wq, LinearWeightHeader* h);
 int gemm_smax(int nbk);
 // block-scaled MX GEMM (mxa_gemm.hip); mx.Linear on MX rows with a prepared weight
 // (slow: gemm_slow_bytes of device scratch for the list of waves the fp64 kernel takes)
-int launch_gemm(const GemmArgs& ga, int64_t batch, hipStream_t stream);
-// the GemmArgs launch_linear_codes launches (bpd set: the weight's digits cover the output columns)
+// bits4: the operands are MXINT4 and ga.bpd, where set, is a 4-bit weight's one digit plane
+// (mx_gemm_dig4_kernel; the tile kernel takes the codes as they are)
+int launch_gemm(const GemmArgs& ga, int64_t batch, hipStream_t stream, bool bits4 = false);
+// the GemmArgs launch_linear_codes launches (bpd set: the weight's digits cover the output
+// columns); *bits4: the weight's header says MXINT4 (the rows must be MXINT4 too)
 GemmArgs linear_gemm_args(const int8_t* xc, const int16_t* xs, int64_t rows, int in_f, const void* wq, int out_f,
-                          const float* bias, float* out, int64_t out_row_stride, int bfloat, int autocast, bool x_mfma);
+                          const float* bias, float* out, int64_t out_row_stride, int bfloat, int autocast, bool x_mfma,
+                          bool* bits4 = nullptr);
 int launch_linear_codes(const int8_t* xc, const int16_t* xs, int64_t rows, int in_f, const void* wq, int out_f,
                         const float* bias, float* out, int64_t out_row_stride, int bfloat, int autocast,
                         hipStream_t stream, bool x_mfma);

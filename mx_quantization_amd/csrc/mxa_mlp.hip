@@ -21,15 +21,19 @@ static int64_t mx_rows_exps_bytes(int64_t rows, int cols) { return al256(rows * 
 static bool mlp_fc1_fused(const void* w1, int in_f, int hidden) {
   LinearWeightHeader h{};
   if (!w1 || !linear_weight_known_header(w1, &h) || h.out_f != hidden || h.in_f != in_f) return false;
-  return (h.gw == hidden || h.gw % 32 == 0) && (in_f + 31) / 32 <= kMlpNbkMax;
+  return (h.gw == hidden || h.gw % 32 == 0) && (in_f + 31) / 32 <= (h.elem_bits == 4 ? kMlp4NbkMax : kMlpNbkMax);
 }
 
 template <bool PLAIN>
-static int launch_mlp_fc1(const GemmArgs& ga, const MlpEpi<PLAIN>& e, hipStream_t stream) {
-  const size_t lds = gemm_dig_lds(ga.nbk).total + kMlpStageBytes;
-  const void* k = reinterpret_cast<const void*>(&mx_mlp_fc1_kernel<PLAIN>);
+static int launch_mlp_fc1(const GemmArgs& ga, const MlpEpi<PLAIN>& e, bool bits4, hipStream_t stream) {
+  const MlpEpi<PLAIN, true> e4{e.codes, e.exps, e.pre_out, e.act_out, e.nbh, e.act, e.flush};
+  const size_t lds = gemm_dig_lds(ga.nbk, bits4 ? 1 : 2).total + kMlpStageBytes;
+  const void* k = bits4 ? reinterpret_cast<const void*>(&mx_mlp_fc1_4_kernel<PLAIN>)
+                           : reinterpret_cast<const void*>(&mx_mlp_fc1_kernel<PLAIN>);
   if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return MXA_ERR_LAUNCH;
-  hipLaunchKernelGGL(mx_mlp_fc1_kernel<PLAIN>, dim3((unsigned)((ga.M + 31) / 32)), dim3(256), lds, stream, ga, e);
+  const dim3 grid((unsigned)((ga.M + 31) / 32));
+  if (bits4) hipLaunchKernelGGL(mx_mlp_fc1_4_kernel<PLAIN>, grid, dim3(256), lds, stream, ga, e4);
+  else hipLaunchKernelGGL(mx_mlp_fc1_kernel<PLAIN>, grid, dim3(256), lds, stream, ga, e);
   return hipGetLastError() == hipSuccess ? MXA_OK : MXA_ERR_LAUNCH;
 }
 
@@ -56,8 +60,10 @@ extern "C" int mxa_mlp(const float* x, int64_t rows, int32_t in_features, int64_
     return MXA_ERR_ARG;
   if (act != MXA_ACT_GELU && act != MXA_ACT_GELU_TANH) return MXA_ERR_ARG;
   if (!valid_bfloat(bfloat)) return MXA_ERR_ARG;
-  if (!linear_weight_verify_any_group(w1, hidden_features, in_features, flush_subnormals, bfloat, stream) ||
-      !linear_weight_verify_any_group(w2, out_features, hidden_features, flush_subnormals, bfloat, stream))
+  int bits = 0, bits2 = 0;  // the weights' element width (their headers'): one for the whole chain
+  if (!linear_weight_verify_any_group(w1, hidden_features, in_features, flush_subnormals, bfloat, stream, &bits) ||
+      !linear_weight_verify_any_group(w2, out_features, hidden_features, flush_subnormals, bfloat, stream, &bits2) ||
+      bits != bits2)
     return MXA_ERR_ARG;
   const bool fused = mlp_fc1_fused(w1, in_features, hidden_features);
   const int64_t need = mxa_mlp_workspace_bytes(rows, in_features, w1, hidden_features, out_features);
@@ -75,7 +81,7 @@ extern "C" int mxa_mlp(const float* x, int64_t rows, int32_t in_features, int64_
                                        mx_rows_exps_bytes(rows, hidden_features));  // the fallback's fp32 hidden matrix
 
   const RowsPrepArgs rx = flat_rows_prep(x, rows, in_features, x_row_stride, aligned16(x) && x_row_stride % 4 == 0,
-                                         flush_subnormals, bfloat, xc, xe, 1);
+                                         flush_subnormals, bfloat, xc, xe, 1, bits);
   int rc = launch_rows_prep(rx, stream);
   if (rc) return rc;
   if (fused) {
@@ -84,9 +90,9 @@ extern "C" int mxa_mlp(const float* x, int64_t rows, int32_t in_features, int64_
     if (!ga.bpd) return MXA_ERR_ARG;  // (mlp_fc1_fused read the same header)
     const int nbh = (hidden_features + 31) / 32;
     if (bfloat == 0 || bfloat == 32)
-      rc = launch_mlp_fc1<true>(ga, MlpEpi<true>{hc, he, pre_out, act_out, nbh, act, flush_subnormals}, stream);
+      rc = launch_mlp_fc1<true>(ga, MlpEpi<true>{hc, he, pre_out, act_out, nbh, act, flush_subnormals}, bits == 4, stream);
     else
-      rc = launch_mlp_fc1<false>(ga, MlpEpi<false>{hc, he, pre_out, act_out, nbh, act, flush_subnormals}, stream);
+      rc = launch_mlp_fc1<false>(ga, MlpEpi<false>{hc, he, pre_out, act_out, nbh, act, flush_subnormals}, bits == 4, stream);
     if (rc) return rc;
   } else {
     rc = launch_linear_codes(xc, xe, rows, in_features, w1, hidden_features, b1, hf, hidden_features, bfloat, 0, stream,
@@ -101,7 +107,7 @@ extern "C" int mxa_mlp(const float* x, int64_t rows, int32_t in_features, int64_
       if (hipGetLastError() != hipSuccess) return MXA_ERR_LAUNCH;
     }
     RowsPrepArgs rh = flat_rows_prep(hf, rows, hidden_features, hidden_features, hidden_features % 4 == 0,
-                                     flush_subnormals, bfloat, hc, he, 1);
+                                     flush_subnormals, bfloat, hc, he, 1, bits);
     rh.act = 1 + act;
     rc = launch_rows_prep(rh, stream);
     if (rc) return rc;

@@ -25,8 +25,12 @@ constexpr size_t kMlpStageBytes = 4 * 8 * 33 * 4;  // four waves' staging tiles
 // workloads' 24 and 36 K-blocks three and two workgroups per CU, as mx_gemm_dig_kernel has
 constexpr int kMlpNbkMax = kGemmDigNbkMax;
 static_assert((size_t)kMlpNbkMax * 2048 + 400 + kMlpStageBytes <= 160 * 1024, "LDS");
+// MXINT4 weights (the one-digit body, 1 KB per K-block): the same bytes at twice the K
+constexpr int kMlp4NbkMax = kGemmDig4NbkMax;
+static_assert((size_t)kMlp4NbkMax * 1024 + 400 + kMlpStageBytes <= 160 * 1024, "LDS");
 
-template <bool PLAIN>
+// B4: fc2's input codes are MXINT4 (the block body's op / sA outputs: codes in [-7, 7], es - 2)
+template <bool PLAIN, bool B4 = false>
 struct MlpEpi {
   int8_t* codes;   // fc2's A operand, MFMA-ready: [ceil(rows / 32)][nbh][64 lanes][16 B]
   int16_t* exps;   // [rows][nbh] exponent of a code unit
@@ -74,7 +78,11 @@ struct MlpEpi {
       }
       wave_lds_sync();
     }
-    const RowsPrepArgs ro = xo_rows_args(codes, exps, a.Nc, nbh, flush, a.bfloat);
+    RowsPrepArgs ro = xo_rows_args(codes, exps, a.Nc, nbh, flush, a.bfloat);
+    if constexpr (B4) {
+      ro.op_kind = MXA_OP_MXINT4;
+      ro.codes = nullptr; ro.sT = nullptr; ro.op = codes; ro.sA = exps;
+    }
     xo_block(ro, m0g + (row < rows ? row : 0), cb, sub, 32 * cb + 16 * sub, xv, row < rows);
   }
 };
@@ -83,6 +91,12 @@ template <bool PLAIN>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) void mx_mlp_fc1_kernel(GemmArgs a, MlpEpi<PLAIN> e) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   gemm_dig_block<PLAIN>(a, e, smem);
+}
+// MXINT4 weights and rows: the one-digit body, fc2's codes written as MXINT4
+template <bool PLAIN>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 8))) void mx_mlp_fc1_4_kernel(GemmArgs a, MlpEpi<PLAIN, true> e) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  gemm_dig_block<PLAIN, MlpEpi<PLAIN, true>, 1>(a, e, smem);
 }
 
 // the activation alone, elementwise (the fallback's act_out: the tests' copy)

@@ -85,6 +85,26 @@ __global__ __launch_bounds__(256) void linear_digits_kernel(const int8_t* pk, co
   }
 }
 
+// the same for an MXINT4 weight: one plane, [blkc][kb][lane][16 B] (mxa_gemm_parts.hpp fold_digit16)
+__global__ __launch_bounds__(256) void linear_digit4_kernel(const int8_t* pk, const int16_t* pe, const int16_t* ps,
+                                                            int nbk, int64_t pcols, int8_t* pd) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= pcols * nbk) return;
+  const int64_t pc = t / nbk;
+  const int kb = (int)(t - pc * nbk);
+  const int64_t blkc = pc / 32;
+  const int n = (int)(pc - blkc * 32);
+  const int e = exp_from16(pe[pc * nbk + kb]);
+  const int s = e == kExpNaN ? 0 : e - ps[2 * pc];
+  const bool ok = ps[2 * pc + 1] <= kDigit4Spread;
+  const int64_t chunk = ((blkc * nbk + kb) * 64) * 16;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const uint4 v = *reinterpret_cast<const uint4*>(pk + chunk + (n + 32 * h) * 16);
+    *reinterpret_cast<uint4*>(pd + chunk + (n + 32 * h) * 16) = ok ? fold_digit16(v, s) : make_uint4(0, 0, 0, 0);
+  }
+}
+
 // per group of gw real columns: smallest column exponent, largest column spread
 __global__ __launch_bounds__(64) void linear_group_stats_kernel(const int16_t* ps, int G, int NB32, int gw, int16_t* gs) {
   const int g = blockIdx.x * blockDim.x + threadIdx.x;
@@ -190,8 +210,6 @@ __global__ void linear_header_kernel(LinearWeightHeader* h, LinearWeightHeader v
   if (threadIdx.x == 0) *h = v;
 }
 
-LinearWeightHeader linear_weight_header(int out_f, int in_f, int gw, int flush, int bfloat);
-
 // prepared buffers whose header is known to the host (pointer -> header)
 static std::mutex g_wmu;
 static std::unordered_map<const void*, LinearWeightHeader> g_weights;
@@ -226,20 +244,25 @@ bool linear_weight_verify(const void* wq, const LinearWeightHeader& want, hipStr
   return true;
 }
 
-bool linear_weight_verify_any_group(const void* wq, int out_f, int in_f, int flush, int bfloat, hipStream_t stream) {
+bool linear_weight_verify_any_group(const void* wq, int out_f, int in_f, int flush, int bfloat, hipStream_t stream,
+                                    int* elem_bits) {
   LinearWeightHeader h{};
   if (!linear_weight_known_header(wq, &h)) {
     if (!linear_weight_fetch_header(wq, stream, &h)) return false;
-    if (h.magic != kLinearWeightMagic || h.gw <= 0 || h.out_f % h.gw) return false;
+    if (h.magic != kLinearWeightMagic || h.gw <= 0 || h.out_f % h.gw || (h.elem_bits != 0 && h.elem_bits != 4))
+      return false;
     linear_weight_note(wq, h);
   }
-  return h == linear_weight_header(out_f, in_f, h.gw, flush, bfloat);
+  const int bits = elem_bits ? h.elem_bits : 0;
+  if (!(h == linear_weight_header(out_f, in_f, h.gw, flush, bfloat, bits))) return false;
+  if (elem_bits) *elem_bits = bits;
+  return true;
 }
 
-LinearWeightHeader linear_weight_header(int out_f, int in_f, int gw, int flush, int bfloat) {
+LinearWeightHeader linear_weight_header(int out_f, int in_f, int gw, int flush, int bfloat, int elem_bits) {
   LinearWeightHeader h{};
   h.magic = kLinearWeightMagic; h.version = 3;
-  h.out_f = out_f; h.in_f = in_f; h.gw = gw; h.flush = flush ? 1 : 0; h.bfloat = bfloat;
+  h.out_f = out_f; h.in_f = in_f; h.gw = gw; h.flush = flush ? 1 : 0; h.bfloat = bfloat; h.elem_bits = elem_bits;
   return h;
 }
 
@@ -247,39 +270,59 @@ LinearWeightHeader linear_weight_header(int out_f, int in_f, int gw, int flush, 
 
 using namespace mxa;
 
-extern "C" int64_t mxa_linear_weight_bytes(int32_t out_features, int32_t in_features, int32_t group_width) {
-  if (out_features <= 0 || in_features <= 0 || group_width <= 0 || out_features % group_width) return -1;
-  return linear_layout(out_features, in_features, group_width).total;
+static bool weight_shape_ok(int out_f, int in_f, int gw, int elem_bits) {
+  return out_f > 0 && in_f > 0 && gw > 0 && out_f % gw == 0 && (elem_bits == 8 || elem_bits == 4);
 }
 
-extern "C" int mxa_linear_weight_prep(const float* w, int32_t out_features, int32_t in_features, int32_t group_width,
-                                      int32_t flush_subnormals, int32_t bfloat, void* wq, hipStream_t stream) {
-  if (!w || !wq || out_features <= 0 || in_features <= 0 || group_width <= 0 || out_features % group_width)
-    return MXA_ERR_ARG;
+extern "C" int64_t mxa_linear_weight_bytes_bits(int32_t out_features, int32_t in_features, int32_t group_width,
+                                                int32_t elem_bits) {
+  if (!weight_shape_ok(out_features, in_features, group_width, elem_bits)) return -1;
+  return linear_layout(out_features, in_features, group_width, elem_bits == 4 ? 4 : 0).total;
+}
+
+extern "C" int64_t mxa_linear_weight_bytes(int32_t out_features, int32_t in_features, int32_t group_width) {
+  return mxa_linear_weight_bytes_bits(out_features, in_features, group_width, 8);
+}
+
+extern "C" int mxa_linear_weight_prep_bits(const float* w, int32_t out_features, int32_t in_features,
+                                           int32_t group_width, int32_t flush_subnormals, int32_t bfloat,
+                                           int32_t elem_bits, void* wq, hipStream_t stream) {
+  if (!w || !wq || !weight_shape_ok(out_features, in_features, group_width, elem_bits)) return MXA_ERR_ARG;
   if (!valid_bfloat(bfloat)) return MXA_ERR_ARG;
   if (!aligned16(wq)) return MXA_ERR_ARG;
-  const LinearLayout W = linear_layout(out_features, in_features, group_width);
+  const int hbits = elem_bits == 4 ? 4 : 0;  // the header's field: an MXINT8 buffer keeps 0
+  const LinearLayout W = linear_layout(out_features, in_features, group_width, hbits);
   unsigned char* wb = static_cast<unsigned char*>(wq);
+  // (4 bits: rows_prep's MXINT4 operand -- codes in [-7, 7], exponents es - 2 -- into the raw regions)
   const RowsPrepArgs rw = flat_rows_prep(w, out_features, in_features, in_features, aligned16(w) && in_features % 4 == 0,
                                          flush_subnormals, bfloat, reinterpret_cast<int8_t*>(wb + W.rawc),
-                                         reinterpret_cast<int16_t*>(wb + W.rawe), 0);
+                                         reinterpret_cast<int16_t*>(wb + W.rawe), 0, hbits);
   int rc = launch_rows_prep(rw, stream);
   if (rc) return rc;
+  const int8_t* rawc = reinterpret_cast<const int8_t*>(wb + W.rawc);
+  const int16_t* rawe = reinterpret_cast<const int16_t*>(wb + W.rawe);
   const int64_t pcols = (int64_t)W.G * W.NB32 * 32;
   hipLaunchKernelGGL(linear_pack_kernel, dim3((unsigned)((pcols * W.nbk + 255) / 256)), dim3(256), 0, stream,
-                     rw.codes, rw.sT, out_features, group_width, W.NB32, W.nbk, W.Cpad, pcols,
+                     rawc, rawe, out_features, group_width, W.NB32, W.nbk, W.Cpad, pcols,
                      reinterpret_cast<int8_t*>(wb + W.pk), reinterpret_cast<int16_t*>(wb + W.pe));
   if (hipGetLastError() != hipSuccess) return MXA_ERR_LAUNCH;
   hipLaunchKernelGGL(linear_stats_kernel, dim3((unsigned)((pcols + 255) / 256)), dim3(256), 0, stream,
                      reinterpret_cast<const int16_t*>(wb + W.pe), pcols, W.nbk, reinterpret_cast<int16_t*>(wb + W.ps),
                      reinterpret_cast<int16_t*>(wb + W.pn));
-  hipLaunchKernelGGL(linear_digits_kernel, dim3((unsigned)((pcols * W.nbk + 255) / 256)), dim3(256), 0, stream,
-                     reinterpret_cast<const int8_t*>(wb + W.pk), reinterpret_cast<const int16_t*>(wb + W.pe),
-                     reinterpret_cast<const int16_t*>(wb + W.ps), W.nbk, pcols, reinterpret_cast<int8_t*>(wb + W.pd));
+  const dim3 dgrid((unsigned)((pcols * W.nbk + 255) / 256));
+  if (hbits == 4)
+    hipLaunchKernelGGL(linear_digit4_kernel, dgrid, dim3(256), 0, stream, reinterpret_cast<const int8_t*>(wb + W.pk),
+                       reinterpret_cast<const int16_t*>(wb + W.pe), reinterpret_cast<const int16_t*>(wb + W.ps), W.nbk,
+                       pcols, reinterpret_cast<int8_t*>(wb + W.pd));
+  else
+    hipLaunchKernelGGL(linear_digits_kernel, dgrid, dim3(256), 0, stream, reinterpret_cast<const int8_t*>(wb + W.pk),
+                       reinterpret_cast<const int16_t*>(wb + W.pe), reinterpret_cast<const int16_t*>(wb + W.ps), W.nbk,
+                       pcols, reinterpret_cast<int8_t*>(wb + W.pd));
   hipLaunchKernelGGL(linear_group_stats_kernel, dim3((unsigned)((W.G + 63) / 64)), dim3(64), 0, stream,
                      reinterpret_cast<const int16_t*>(wb + W.ps), W.G, W.NB32, group_width,
                      reinterpret_cast<int16_t*>(wb + W.gs));
-  const LinearWeightHeader h = linear_weight_header(out_features, in_features, group_width, flush_subnormals, bfloat);
+  const LinearWeightHeader h =
+      linear_weight_header(out_features, in_features, group_width, flush_subnormals, bfloat, hbits);
   hipLaunchKernelGGL(linear_header_kernel, dim3(1), dim3(64), 0, stream, reinterpret_cast<LinearWeightHeader*>(wb + W.hdr),
                      h);
   if (hipGetLastError() != hipSuccess) return MXA_ERR_LAUNCH;
@@ -287,3 +330,7 @@ extern "C" int mxa_linear_weight_prep(const float* w, int32_t out_features, int3
   return MXA_OK;
 }
 
+extern "C" int mxa_linear_weight_prep(const float* w, int32_t out_features, int32_t in_features, int32_t group_width,
+                                      int32_t flush_subnormals, int32_t bfloat, void* wq, hipStream_t stream) {
+  return mxa_linear_weight_prep_bits(w, out_features, in_features, group_width, flush_subnormals, bfloat, 8, wq, stream);
+}

@@ -21,21 +21,28 @@ namespace mxa {
 //       2^(block exponent - column's smallest) as two signed base-256 digits
 //       (mxa_gemm_parts.hpp fold_digits16; column spread <= kDigitSpread; else zeros, and
 //       the column's group never takes them)
+// A 4-bit weight (LinearWeightHeader::elem_bits 4: MXINT4 codes in [-7, 7], exponents of a
+// code unit es - 2) has the same regions with one digit plane,
+//   pd  [group][cb][kb][lane][16 B]: the code times 2^(block exponent - column's smallest),
+//       one signed int8 (7 * 2^4 = 112; column spread <= kDigit4Spread; else zeros)
 struct LinearLayout {
   int G, NB32, nbk, Cpad;
   int64_t hdr, rawc, rawe, pk, pe, ps, gs, pn, pd, total;
 };
 constexpr int kDigitSpread = 8;  // 127 * 2^8 < 2^15: two signed int8 digits
+constexpr int kDigit4Spread = 4;  // 7 * 2^4 = 112 <= 127: one signed int8 digit
 constexpr uint32_t kLinearWeightMagic = 0x5741584du;  // "MXAW"
 struct LinearWeightHeader {
   uint32_t magic;
-  int32_t version, out_f, in_f, gw, flush, bfloat, reserved;
+  int32_t version, out_f, in_f, gw, flush, bfloat;
+  int32_t elem_bits;  // 0: MXINT8 (the header every 8-bit buffer has always had); 4: MXINT4
   bool operator==(const LinearWeightHeader& o) const {
     return magic == o.magic && version == o.version && out_f == o.out_f && in_f == o.in_f && gw == o.gw &&
-           flush == o.flush && bfloat == o.bfloat;
+           flush == o.flush && bfloat == o.bfloat && elem_bits == o.elem_bits;
   }
 };
-__host__ __device__ inline LinearLayout linear_layout(int out_f, int in_f, int gw) {
+// elem_bits: the header's (0 / 8 two digit planes, 4 one)
+__host__ __device__ inline LinearLayout linear_layout(int out_f, int in_f, int gw, int elem_bits = 0) {
   LinearLayout L;
   auto al = [](int64_t x) { return (x + 255) / 256 * 256; };
   L.G = out_f / gw;
@@ -61,7 +68,7 @@ __host__ __device__ inline LinearLayout linear_layout(int out_f, int in_f, int g
   L.pn = o;
   o += al(pcols * 2);
   L.pd = o;
-  o += al(2 * pcols * L.Cpad);
+  o += al((elem_bits == 4 ? 1 : 2) * pcols * L.Cpad);
   L.total = o;
   return L;
 }

@@ -1,8 +1,9 @@
 """MX Linear -- drop-in for microxscaling/mx/linear.py (forward / inference).
 
 out = MX(x, along in_features) @ MX(W, along in_features)^T (+ bias), on the
-device: float32 inputs through mxa_linear (the block-scaled int8-MFMA GEMM with the
-weight prepared once per weight version), other dtypes through mxa_matmul.  This is the
+device: float32 inputs with both element formats int8 or both int4 through mxa_linear (the
+block-scaled int8-MFMA GEMM with the weight prepared once per weight version), everything
+else (other dtypes, mixed widths) through mxa_matmul.  This is the
 qkv / proj projection around the attention core (a SURVEY §8f "next" row) as the
 patched modules' `from mx import Linear` sees it.  The fused forms are
 mx_quantization_amd.mx_qkv_attention (qkv Linear -> attention operands, and with
@@ -35,15 +36,28 @@ def invalidate_prepared(weight=None):
         _PREPARED.pop(id(weight), None)
 
 
+def fused_elem_bits(s):
+    """The element width of the prepared-weight route (mxa_linear) for the applied specs s: 8
+    or 4 when the activation and weight formats are both int8 or both int4 and every rounding
+    is "nearest"; 0: the mx_matmul route.  A function of the specs alone."""
+    a, w = _mbits(s["a_elem_format"]), _mbits(s["w_elem_format"])
+    if a != w or a not in (8, 4):
+        return 0
+    if not all(s.get(r, "nearest") == "nearest" for r in ("round_output", "round_weight", "round_mx_output")):
+        return 0
+    return a
+
+
 def _prepared_weight(weight, s):
     """The weight's MX codes, prepared once per weight version (inference: constant)."""
     import weakref
     stamp = (weight.data_ptr(), tuple(weight.shape), tuple(weight.stride()), str(weight.device), weight._version,
-             bool(s["mx_flush_fp32_subnorms"]), int(s["bfloat"]))
+             bool(s["mx_flush_fp32_subnorms"]), int(s["bfloat"]), fused_elem_bits(s))
     ent = _PREPARED.get(id(weight))
     if ent is not None and ent[0]() is weight and ent[1] == stamp:
         return ent[2]
-    wq = ops.LinearWeightMX(weight.detach().contiguous(), weight.shape[0], s["mx_flush_fp32_subnorms"], s["bfloat"])
+    wq = ops.LinearWeightMX(weight.detach().contiguous(), weight.shape[0], s["mx_flush_fp32_subnorms"], s["bfloat"],
+                            fused_elem_bits(s))
     wid = id(weight)
     ref = weakref.ref(weight, lambda _r, wid=wid: _PREPARED.pop(wid, None) if _PREPARED.get(wid, (None,))[0] is _r
                       else None)
@@ -58,9 +72,7 @@ def linear(input, weight, bias=None, mx_specs=None, prequantized_weights=False, 
     s = apply_mx_specs(mx_specs)
     _check_specs(s)
     if (input.dtype == torch.float32 and weight.dtype == torch.float32 and not prequantized_weights
-            and _mbits(s["a_elem_format"]) == 8 and _mbits(s["w_elem_format"]) == 8
-            and (bias is None or bias.dtype == torch.float32)
-            and all(s.get(r, "nearest") == "nearest" for r in ("round_output", "round_weight", "round_mx_output"))):
+            and fused_elem_bits(s) and (bias is None or bias.dtype == torch.float32)):
         # mxa_linear: bf(x), MX along in_features, exact-then-rounded product, bf(out + bf(bias))
         wq = _prepared_weight(weight, s)
         return ops.mx_linear(input, wq, bias, flush_subnormals=s["mx_flush_fp32_subnorms"], bfloat=s["bfloat"],

@@ -379,40 +379,55 @@ class LinearWeightMX:
     """A Linear weight (out_features, in_features) as MXINT8 codes + block exponents
     along in_features on the device (mxa_linear_weight_prep), MFMA-ready in column
     groups of group_width (qkv: the head dim): prepared once, reused by every fused
-    call (the weights are constant at inference)."""
+    call (the weights are constant at inference).  elem_bits 8: MXINT8; 4: MXINT4 (the
+    reference's "int4"), which mx_linear / mx_mlp run with the activations at 4 bits too."""
 
-    def __init__(self, weight: torch.Tensor, group_width: int, flush_subnormals: bool = False, bfloat: int = 0):
+    def __init__(self, weight: torch.Tensor, group_width: int, flush_subnormals: bool = False, bfloat: int = 0,
+                 elem_bits: int = 8):
+        if int(elem_bits) not in (8, 4):
+            raise ValueError(f"elem_bits must be 8 or 4 (got {elem_bits!r})")
+        self.elem_bits = int(elem_bits)
         dev = require_device(weight)
         w = _f32(weight.detach(), "weight").contiguous()
         self.out_features, self.in_features = w.shape
         self.group_width = int(group_width)
-        nbytes = lib().mxa_linear_weight_bytes(self.out_features, self.in_features, self.group_width)
+        nbytes = lib().mxa_linear_weight_bytes_bits(self.out_features, self.in_features, self.group_width,
+                                                    self.elem_bits)
         if nbytes < 0:
             raise ValueError(f"group_width {group_width} does not divide out_features {self.out_features}")
         self.buf = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        check(lib().mxa_linear_weight_prep(w.data_ptr(), self.out_features, self.in_features, self.group_width,
-                                           int(bool(flush_subnormals)), int(bfloat), self.buf.data_ptr(),
-                                           stream_ptr(dev)), "mxa_linear_weight_prep")
+        check(lib().mxa_linear_weight_prep_bits(w.data_ptr(), self.out_features, self.in_features, self.group_width,
+                                                int(bool(flush_subnormals)), int(bfloat), self.elem_bits,
+                                                self.buf.data_ptr(), stream_ptr(dev)), "mxa_linear_weight_prep_bits")
         self.flush, self.bfloat = bool(flush_subnormals), int(bfloat)
 
 
-def _prepared(weight, group_width: int, flush_subnormals: bool, bfloat: int) -> "LinearWeightMX":
-    wq = weight if isinstance(weight, LinearWeightMX) else LinearWeightMX(weight, group_width, flush_subnormals, bfloat)
+def _prepared(weight, group_width: int, flush_subnormals: bool, bfloat: int, elem_bits: int = 8) -> "LinearWeightMX":
+    """elem_bits applies to a weight given as a tensor; a LinearWeightMX brings its own width
+    (an explicit non-default elem_bits must agree with it)."""
+    if isinstance(weight, LinearWeightMX):
+        wq = weight
+        if int(elem_bits) != 8 and int(elem_bits) != wq.elem_bits:
+            raise ValueError(f"the prepared weight has {wq.elem_bits}-bit elements, elem_bits={elem_bits} was asked for")
+    else:
+        wq = LinearWeightMX(weight, group_width, flush_subnormals, bfloat, elem_bits)
     if (wq.flush, wq.bfloat) != (bool(flush_subnormals), int(bfloat)):
         raise ValueError("the prepared weight was quantized with other flush / bfloat settings")
     return wq
 
 
 def mx_linear(x: torch.Tensor, weight, bias: Optional[torch.Tensor] = None, flush_subnormals: bool = False,
-              bfloat: int = 0, autocast: Optional[torch.dtype] = None) -> torch.Tensor:
+              bfloat: int = 0, autocast: Optional[torch.dtype] = None, elem_bits: int = 8) -> torch.Tensor:
     """mx.Linear forward (microxscaling/mx/linear.py:20-103; include/mxa.h mxa_linear):
     x (..., in_features) float32, weight an (out, in) tensor or a LinearWeightMX (any group
     width); out (..., out) float32 = bf(fl32(MX(x) @ MX(W)^T)) [+ bf(bias)], every product
     the exact sum rounded once.  autocast: the product rounded to float16 / bfloat16 before
-    the fp32 bias add (F.linear under torch.autocast)."""
+    the fp32 bias add (F.linear under torch.autocast).  elem_bits: the width a weight tensor is
+    prepared at (8: MXINT8, 4: MXINT4 -- x is quantized at the weight's width)."""
     dev = require_device(x, bias)
     x = _f32(x, "x")
-    wq = _prepared(weight, weight.shape[0] if not isinstance(weight, LinearWeightMX) else 1, flush_subnormals, bfloat)
+    wq = _prepared(weight, weight.shape[0] if not isinstance(weight, LinearWeightMX) else 1, flush_subnormals, bfloat,
+                   elem_bits)
     if x.shape[-1] != wq.in_features:
         raise ValueError(f"x has {x.shape[-1]} features, the weight {wq.in_features}")
     x2 = x.reshape(-1, x.shape[-1])
@@ -441,19 +456,22 @@ def mx_linear(x: torch.Tensor, weight, bias: Optional[torch.Tensor] = None, flus
 
 
 def mx_mlp(x: torch.Tensor, w1, b1: Optional[torch.Tensor], w2, b2: Optional[torch.Tensor], act: str = "gelu",
-           flush_subnormals: bool = False, bfloat: int = 0, return_hidden: bool = False):
+           flush_subnormals: bool = False, bfloat: int = 0, return_hidden: bool = False, elem_bits: int = 8):
     """The MLP of a DeiT / DiT / PixArt block in one call (include/mxa.h mxa_mlp; replaces
     Mlp.forward at inference): y = mx.Linear(gelu(mx.Linear(x; w1, b1)); w2, b2), float32, no
     autocast.  x (..., in); w1 (hidden, in) and w2 (out, hidden) tensors (prepared as one group
     each, as mx_linear does) or LinearWeightMX; act "gelu" (erf) or "gelu_tanh".  fc1 writes
     fc2's MX input codes itself: the fp32 hidden matrix is not materialised.
-    return_hidden: (y, pre, act) with pre = fc1's output and act = gelu(pre), (..., hidden)."""
+    return_hidden: (y, pre, act) with pre = fc1's output and act = gelu(pre), (..., hidden).
+    elem_bits: as mx_linear; both weights (and x and the hidden codes) have one width."""
     dev = require_device(x, b1, b2)
     x = _f32(x, "x")
     if act not in N.ACTS:
         raise ValueError(f"act must be one of {sorted(N.ACTS)} (got {act!r})")
-    wq1 = _prepared(w1, w1.shape[0] if not isinstance(w1, LinearWeightMX) else 1, flush_subnormals, bfloat)
-    wq2 = _prepared(w2, w2.shape[0] if not isinstance(w2, LinearWeightMX) else 1, flush_subnormals, bfloat)
+    wq1 = _prepared(w1, w1.shape[0] if not isinstance(w1, LinearWeightMX) else 1, flush_subnormals, bfloat, elem_bits)
+    wq2 = _prepared(w2, w2.shape[0] if not isinstance(w2, LinearWeightMX) else 1, flush_subnormals, bfloat, elem_bits)
+    if wq1.elem_bits != wq2.elem_bits:
+        raise ValueError(f"w1 has {wq1.elem_bits}-bit elements, w2 {wq2.elem_bits}-bit")
     if x.shape[-1] != wq1.in_features:
         raise ValueError(f"x has {x.shape[-1]} features, fc1 takes {wq1.in_features}")
     if wq2.in_features != wq1.out_features:

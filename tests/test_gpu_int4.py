@@ -1,0 +1,345 @@
+"""GPU parity of the MXINT4 Linear / MLP (M.LinearWeightMX(elem_bits=4), M.mx_linear / M.mx_mlp
+with elem_bits=4; the drop-in mx.Linear under the reference's PixArt int4 specs): the one-digit
+kernel (mxa_gemm.hpp mx_gemm_dig4_kernel), its fp64 block sums, the tile kernel beyond its K,
+the fused fc1 with the MXINT4 hidden codes (mxa_mlp.hpp mx_mlp_fc1_4_kernel) and its fallback.
+
+Bit-exact (compared as bits): against the reference's own mx.Linear outputs (linear_int4.npz,
+tests/golden/gen_int4_golden.py) and against O.mx_linear(..., elem="int4").  Every input comes
+from tests/int4_cases.py, and before its first device call each test repeats the CPU
+assertion of tests/test_int4_cpu.py on which side of the gate every row block sits."""
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import int4_cases as C
+from int4_cases import same_bits
+from oracle import mx_oracle as O
+
+pytestmark = pytest.mark.gpu
+G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+ACTS = ("gelu", "gelu_tanh")
+
+
+def dev(x):
+    return torch.from_numpy(np.ascontiguousarray(x)).cuda()
+
+
+def host(t):
+    return t.detach().cpu().numpy()
+
+
+@pytest.fixture(scope="module")
+def M():
+    import mx_quantization_amd as m
+    return m
+
+
+@pytest.fixture(scope="module")
+def P():
+    return np.load(os.path.join(G, "linear_int4.npz"))
+
+
+def lin4(M, x, W, b=None, **kw):
+    y = M.mx_linear(dev(x), dev(W) if isinstance(W, np.ndarray) else W, None if b is None else dev(b), elem_bits=4, **kw)
+    torch.cuda.synchronize()
+    return host(y)
+
+
+# ---- the reference fixture ------------------------------------------------------------------
+@pytest.mark.parametrize("bf", [16, 32])
+@pytest.mark.parametrize("i", [0, 1, 2])
+def test_linear_vs_reference(M, P, i, bf):
+    """(70, 96 -> 160), (33, 100 -> 136: ragged K), (45, 4608 -> 40: the one-digit kernel's last
+    K) under the reference's PixArt specs, bfloat 16 and 32"""
+    x, W, b = C.golden_linear(P, i)
+    C.assert_side(x, W, "digits", bf)
+    same_bits(lin4(M, x, W, b, bfloat=bf), P[f"lin{i}/y_bf{bf}"], f"lin{i} bfloat {bf}")
+
+
+@pytest.mark.parametrize("bf", [16, 32])
+def test_mlp_vs_reference(M, P, bf):
+    """The reference's fc1 -> GELU(tanh) -> fc2 chain at (70, 96 -> 160 -> 40): pre bit for bit.
+    y is not bit-pinned by construction (the GELU's last bits are the math library's), so its
+    bar is measured, on the CPU with the oracle's int4 chain: every GELU value perturbed by
+    +-(2 E_ref + 1) units of test_gelu_accuracy's metric (|pre| 2^-24; E_ref 1.9 tanh, 6.2 erf;
+    random signs, three draws).  Measured: normwise error of y 0.0 in all three draws at this
+    chain (bfloat 16 and 32), and 0.0 at int4_cases.mlp_case's (70, 96 -> 160 -> 40), (33, 100 ->
+    136 -> 96) and (45, 64 -> 4608 -> 40) for both activations -- not one MXINT4 hidden code
+    changed: a perturbation of 5 |pre| 2^-24 moves a value by < 2e-6 code units of its block, so
+    it crosses a rounding boundary (spaced one unit apart) with probability of about 4e-6 per
+    value, 0.05 per draw of this chain's 11,200 values.  Twice the largest error seen is 0: the
+    bar is equality, and the figure is printed before it is asserted."""
+    x, W1, b1, W2, b2 = C.golden_mlp(P)
+    C.assert_side(x, W1, "digits", bf)
+    y, pre, a = M.mx_mlp(dev(x), dev(W1), dev(b1), dev(W2), dev(b2), act="gelu_tanh", bfloat=bf, return_hidden=True,
+                         elem_bits=4)
+    torch.cuda.synchronize()
+    same_bits(host(pre), P[f"mlp/pre_bf{bf}"], "pre")
+    err = O.normwise_rel_err(host(y), P[f"mlp/y_bf{bf}"])
+    qa = O.quantize_mx(O.quantize_bfloat(host(a), bf), "int4", 32, -1)[1]
+    qr = O.quantize_mx(O.quantize_bfloat(P[f"mlp/act_bf{bf}"], bf), "int4", 32, -1)[1]
+    print(f"bfloat {bf}: y normwise rel err {err:.3e}, act max abs diff {np.abs(host(a) - P[f'mlp/act_bf{bf}']).max():.3e}, "
+          f"hidden codes that differ {int((qa != qr).sum())}")
+    assert err <= 0.0
+
+
+# ---- bit-exact against the oracle ---------------------------------------------------------------
+@pytest.mark.parametrize("bias", [True, False])
+@pytest.mark.parametrize("kw", [{}, {"bfloat": 16}, {"flush_subnormals": True}], ids=["plain", "bfloat16", "flush"])
+@pytest.mark.parametrize("rows,inf,outf", [(33, 96, 40), (70, 256, 64)])
+def test_linear_plain_vs_oracle(M, rows, inf, outf, kw, bias):
+    x, W, b = C.linear_case(rows, inf, outf, inf)
+    bf = kw.get("bfloat", 32)
+    C.assert_side(x, W, "digits", bf)
+    if not bias:
+        b = None
+    want = O.mx_linear(x, W, b, elem="int4", bfloat=bf, flush=kw.get("flush_subnormals", False))
+    same_bits(lin4(M, x, W, b, **kw), want, f"{rows, inf, outf} {kw}")
+
+
+def _quantize_bfloat_in_dtype(A, bfloat):
+    """_quantize_bfloat (elemwise_ops.py:201-216) on a float16 / bfloat16 tensor, every step in
+    the tensor's own dtype as torch computes it (test_gpu_proj.py)."""
+    if bfloat in (0, 32):
+        return A
+    bits = bfloat - 7
+    pe = torch.floor(torch.log2(torch.abs(A) + (A == 0).type(A.dtype))).clip(min=-126)
+    out = A / (2 ** pe) * (2 ** (bits - 2))
+    out = torch.sign(out) * torch.floor(torch.abs(out) + 0.5)
+    return out / (2 ** (bits - 2)) * (2 ** pe)
+
+
+@pytest.mark.parametrize("dt", [torch.float16, torch.bfloat16])
+@pytest.mark.parametrize("bfloat", [0, 16])
+def test_linear_autocast(M, dt, bfloat):
+    """_check_linear_autocast's construction (test_gpu_proj.py) at 4 bits: the exact product
+    rounded to the autocast dtype, then the output rounding in that dtype; with a float32 bias
+    the result is float32."""
+    rng = np.random.default_rng(5)
+    x = rng.standard_normal((33, 64), dtype=np.float32)
+    W = rng.standard_normal((48, 64), dtype=np.float32)
+    b = rng.standard_normal(48, dtype=np.float32)
+    C.assert_side(x, W, "digits", bfloat or 32)
+    qx = O.quantize_mx(O.quantize_bfloat(x, bfloat), "int4", 32, -1)[0]
+    qw = O.quantize_mx(O.quantize_bfloat(W, bfloat), "int4", 32, -1)[0]
+    exact = O.exact_matmul_f32(qx, np.swapaxes(qw, -1, -2))
+    want = _quantize_bfloat_in_dtype(torch.from_numpy(exact).to(dt), bfloat)
+    y = M.mx_linear(dev(x), dev(W), None, bfloat=bfloat, autocast=dt, elem_bits=4)
+    assert y.dtype == dt
+    same_bits(host(y.float()), host(want.float()), f"autocast, no bias, bfloat={bfloat}")
+    yb = M.mx_linear(dev(x), dev(W), dev(b), bfloat=bfloat, autocast=dt, elem_bits=4)
+    assert yb.dtype == torch.float32
+    bb = O.quantize_bfloat(b, bfloat)
+    same_bits(host(yb), O.quantize_bfloat((want.float().numpy() + bb).astype(np.float32), bfloat), "autocast + fp32 bias")
+
+
+def test_linear_nan_zero_row_zero_block(M):
+    """A NaN element (its row NaN, no other), a zero row, and an all-zero block beside blocks
+    2^30 larger: the zero block is left out of the spread, so the digits still take the rows."""
+    x, W, b = C.linear_case(70, 256, 64, 256)
+    x[2, 7] = np.nan
+    x[4] = 0.0
+    x[40:48, 64:96] = 0.0
+    x[40:48, :64] *= np.float32(2.0 ** 30)
+    x[40:48, 96:] *= np.float32(2.0 ** 30)
+    C.assert_side(x, W, "digits")
+    _, sp_all = C.row_stats(x, False)
+    assert (sp_all[40:48] > C.DIGIT4_SPREAD).all()  # on the digits only because the block is left out
+    y = lin4(M, x, W, b)
+    same_bits(y, O.mx_linear(x, W, b, elem="int4"), "NaN / zero row / zero block")
+    assert np.isnan(y[2]).all() and np.isnan(y).any(axis=1).sum() == 1
+    same_bits(y[4], b, "the zero row")
+
+
+@pytest.mark.parametrize("name", sorted(C.EDGES))
+def test_linear_gate_edges(M, name):
+    """Row-block spread 4 (digits) and 5 (fp64), weight column spread 4 and 5, min ex + min ew =
+    -126 (digits), -127 and -155 (fp64, subnormal results rounded once)"""
+    x, W = C.edge(name)
+    C.assert_edge(name, x, W)
+    same_bits(lin4(M, x, W), O.mx_linear(x, W, None, elem="int4"), name)
+
+
+@pytest.mark.parametrize("alternate", [False, True], ids=["same_sign", "alternating"])
+def test_linear_largest_accumulator(M, alternate):
+    """every code +-7, all blocks but one per row and column at shift 4, K = 4,608: |c| ~ 5.7e7"""
+    x, W = C.accumulator(alternate)
+    C.assert_accumulator(x, W, alternate)
+    same_bits(lin4(M, x, W), O.mx_linear(x, W, None, elem="int4"), "largest accumulator")
+
+
+@pytest.mark.parametrize("inf", C.K_EDGE_IN)
+def test_linear_k_edge(M, inf):
+    """in_features 4,608: 144 K-blocks, the one-digit kernel's last; 4,640: the tile kernel"""
+    x, W, b = C.k_edge(inf)
+    C.assert_k_edge(inf, x, W)
+    same_bits(lin4(M, x, W, b), O.mx_linear(x, W, b, elem="int4"), f"K = {inf}")
+
+
+@pytest.mark.parametrize("bf", [0, 16])
+def test_linear_grouped_weight_tile_kernel(M, bf):
+    """a weight in groups of 24 columns has no digits over the output columns: the tile kernel
+    takes the int4 codes as they are"""
+    x, W, b = C.linear_case(70, 256, 48, 24)
+    wq = M.LinearWeightMX(dev(W), 24, False, bf, elem_bits=4)
+    assert wq.elem_bits == 4
+    same_bits(lin4(M, x, wq, b, bfloat=bf), O.mx_linear(x, W, b, elem="int4", bfloat=bf or 32), "groups of 24")
+
+
+# ---- the MLP ----------------------------------------------------------------------------------------
+def _check_chain(M, x, W1, b1, W2, b2, act, bfloat=0, w1=None, what="", flush=False):
+    """test_gpu_mlp.py's equalities at elem_bits=4: pre is mx_linear's and the oracle's fc1; y is
+    mx_linear's and the oracle's fc2 of the activation the device produced."""
+    d = lambda a: None if a is None else dev(a)  # noqa: E731
+    kw = dict(flush_subnormals=flush, bfloat=bfloat, elem_bits=4)
+    ok = dict(elem="int4", flush=flush, bfloat=bfloat or 32)
+    y, pre, a = M.mx_mlp(dev(x), dev(W1) if w1 is None else w1, d(b1), dev(W2), d(b2), act=act, return_hidden=True, **kw)
+    torch.cuda.synchronize()
+    same_bits(host(pre), host(M.mx_linear(dev(x), dev(W1), d(b1), **kw)), f"{what} pre vs mx_linear")
+    same_bits(host(pre), O.mx_linear(x, W1, b1, **ok), f"{what} pre vs oracle")
+    same_bits(host(y), host(M.mx_linear(a, dev(W2), d(b2), **kw)), f"{what} y vs mx_linear(act)")
+    same_bits(host(y), O.mx_linear(host(a), W2, b2, **ok), f"{what} y vs the oracle's Linear of act")
+    y2 = M.mx_mlp(dev(x), dev(W1) if w1 is None else w1, d(b1), dev(W2), d(b2), act=act, **kw)
+    same_bits(host(y2), host(y), f"{what} y without the hidden copies")
+    return host(y), host(pre), host(a)
+
+
+@pytest.mark.parametrize("bias", [True, False])
+@pytest.mark.parametrize("act", ACTS)
+@pytest.mark.parametrize("rows,inf,hid,outf", C.MLP_SHAPES)
+def test_mlp_chain_bit_for_bit(M, rows, inf, hid, outf, act, bias):
+    """(70, 96 -> 160 -> 40): a wave's second round, a partial last row block; (33, 100 -> 136 ->
+    96): ragged K, a last hidden block of 8 columns; (45, 64 -> 4608 -> 40): fc2 runs 144
+    K-blocks on the one-digit kernel; (45, 64 -> 4640 -> 40): on the tile kernel; (5, 32 -> 32 ->
+    7): one block of everything."""
+    x, W1, b1, W2, b2 = C.mlp_case(rows, inf, hid, outf, rows * 13 + hid)
+    C.assert_side(x, W1, "digits", what="fc1")
+    if not bias:
+        b1 = b2 = None
+    _check_chain(M, x, W1, b1, W2, b2, act)
+
+
+@pytest.mark.parametrize("bf", [0, 16])
+@pytest.mark.parametrize("act", ACTS)
+def test_mlp_fallback_equals_fused(M, act, bf):
+    """W1 in groups of 20 columns: fc1 as mx_linear into the fp32 workspace, the GELU and the
+    MXINT4 quantizer in the row kernel.  Bit for bit the fused path's pre, act and y."""
+    rows, inf, hid, outf = 70, 96, 160, 40
+    x, W1, b1, W2, b2 = C.mlp_case(rows, inf, hid, outf, 20)
+    x[3, 5] = np.nan
+    one, grp = M.LinearWeightMX(dev(W1), hid, False, bf, elem_bits=4), M.LinearWeightMX(dev(W1), 20, False, bf, elem_bits=4)
+    w2 = M.LinearWeightMX(dev(W2), outf, False, bf, elem_bits=4)
+    fused = M.mx_mlp(dev(x), one, dev(b1), w2, dev(b2), act=act, bfloat=bf, return_hidden=True)
+    fallb = M.mx_mlp(dev(x), grp, dev(b1), w2, dev(b2), act=act, bfloat=bf, return_hidden=True)
+    torch.cuda.synchronize()
+    for name, f, g in zip(("y", "pre", "act"), fused, fallb):
+        same_bits(host(g), host(f), f"fallback vs fused {name}")
+    same_bits(host(fused[1]), O.mx_linear(x, W1, b1, elem="int4", bfloat=bf or 32), "pre vs oracle")
+
+
+@pytest.mark.parametrize("act", ACTS)
+def test_mlp_fp64_branch_nan_and_zero_rows(M, act):
+    """half the rows with 32-blocks 2^-10 .. 2^10 apart (every row block then sums in fp64), a
+    NaN element in two rows, a zero row"""
+    rows, inf, hid, outf = 70, 256, 160, 40
+    x, W1, b1, W2, b2 = C.mlp_case(rows, inf, hid, outf, 256)
+    rng = np.random.default_rng(9)
+    xs = np.repeat(np.exp2(rng.integers(-10, 11, size=(rows, inf // 32))).astype(np.float32), 32, axis=1)
+    x[: rows // 2] *= xs[: rows // 2]
+    x[64:] *= xs[64:]
+    x[2, 7] = np.nan
+    x[66, 3] = np.nan
+    x[4] = 0.0
+    C.assert_side(x, W1, "fp64", what="fc1")
+    y, pre, a = _check_chain(M, x, W1, b1, W2, b2, act)
+    for name, t in (("pre", pre), ("act", a), ("y", y)):
+        assert np.isnan(t[[2, 66]]).all(), name
+        assert np.isnan(t).any(axis=1).sum() == 2, name
+
+
+# ---- the drop-in ----------------------------------------------------------------------------------
+@pytest.mark.parametrize("bf", [16, 32])
+def test_dropin_linear_int4(M, bf):
+    """mx.Linear under the reference's PixArt specs takes the prepared-weight route: its output
+    is mx_linear(elem_bits=4)'s and, bit for bit, the old mx_matmul route's (quantize_elemwise_op
+    + ops.mx_matmul(..., 4, 4) + the bias lines of mx/linear.py, called directly)."""
+    from mx_quantization_amd import ops
+    import importlib
+    L = importlib.import_module("mx_quantization_amd.mx.linear")  # (the package exports the function `linear` too)
+    from mx_quantization_amd.mx.elemwise_ops import quantize_elemwise_op
+    from mx_quantization_amd.mx.specs import apply_mx_specs
+    specs = dict(C.SPECS, bfloat=bf)
+    s = apply_mx_specs(specs)
+    assert L.fused_elem_bits(s) == 4
+    x, W, b = C.linear_case(70, 96, 160, 7)
+    lin = L.Linear(96, 160, bias=True, mx_specs=specs).cuda()
+    lin.weight.data, lin.bias.data = dev(W), dev(b)
+    with torch.no_grad():
+        y = lin(dev(x))
+        assert L._PREPARED[id(lin.weight)][2].elem_bits == 4  # the route that ran
+        # the old route, called directly
+        bf_in = quantize_elemwise_op(dev(x), mx_specs=s, round=s["round_output"])
+        bf_w = quantize_elemwise_op(lin.weight, mx_specs=s, round=s["round_weight"])
+        old = ops.mx_matmul(bf_in.reshape(1, -1, 96), bf_w.t().unsqueeze(0), 4, 4, flush=s["mx_flush_fp32_subnorms"],
+                            out_dtype=None).reshape(70, 160)
+        old = quantize_elemwise_op(old, mx_specs=s, round=s["round_output"])
+        bb = quantize_elemwise_op(lin.bias, mx_specs=s, round=s["round_weight"])
+        old = quantize_elemwise_op(old + bb, mx_specs=s, round=s["round_output"])
+    torch.cuda.synchronize()
+    same_bits(host(y), lin4(M, x, W, b, bfloat=bf), "drop-in vs mx_linear(elem_bits=4)")
+    same_bits(host(y), host(old), "drop-in vs the mx_matmul route")
+    same_bits(host(y), O.mx_linear(x, W, b, elem="int4", bfloat=bf), "drop-in vs oracle")
+
+
+# ---- refusals ---------------------------------------------------------------------------------------
+def test_refusals(M):
+    rng = np.random.default_rng(1)
+    B, N, H, D = 1, 32, 2, 32
+    Cc = H * D
+    t = lambda *s: torch.from_numpy(rng.standard_normal(s, dtype=np.float32)).cuda()  # noqa: E731
+    with pytest.raises(ValueError):
+        M.LinearWeightMX(t(64, 32), 64, elem_bits=5)
+    w4 = lambda *s: M.LinearWeightMX(t(*s), D, elem_bits=4)  # noqa: E731
+    with pytest.raises(M.NativeError, match=r"status -1\)"):
+        M.mx_qkv_attention(t(B, N, Cc), w4(3 * Cc, Cc), None, H, 0.125, k_top=8)
+    with pytest.raises(M.NativeError, match=r"status -1\)"):
+        M.mx_topk_attention_proj(t(B, H, N, D), t(B, H, N, D), t(B, H, N, D), 0.125, w4(Cc, Cc), k_top=8)
+    with pytest.raises(M.NativeError, match=r"status -1\)"):
+        M.mx_cross_attention(t(B, N, Cc), t(B, N, Cc), w4(Cc, Cc), None, w4(2 * Cc, Cc), None, H, 0.125, k_top=8)
+    x, W1, W2 = t(8, 32), t(64, 32), t(16, 64)
+    with pytest.raises(ValueError):  # mixed widths
+        M.mx_mlp(x, M.LinearWeightMX(W1, 64, elem_bits=4), None, M.LinearWeightMX(W2, 16), None)
+    with pytest.raises(ValueError):  # an explicit width that disagrees with the prepared weight's
+        M.mx_linear(x, M.LinearWeightMX(W1, 64), None, elem_bits=4)
+    # ... and the C entry point itself refuses mixed widths
+    from mx_quantization_amd import _native as N
+    a, b8 = M.LinearWeightMX(W1, 64, elem_bits=4), M.LinearWeightMX(W2, 16)
+    y = torch.empty(8, 16, device="cuda")
+    ws = torch.empty(N.lib().mxa_mlp_workspace_bytes(8, 32, None, 64, 16), dtype=torch.uint8, device="cuda")
+    rc = N.lib().mxa_mlp(x.data_ptr(), 8, 32, 32, a.buf.data_ptr(), 64, None, 0, b8.buf.data_ptr(), 16, None, y.data_ptr(), 16,
+                         None, None, 0, 0, ws.data_ptr(), ws.numel(), torch.cuda.current_stream().cuda_stream)
+    assert rc == -1
+
+
+def test_eight_bit_buffer_is_byte_identical(M):
+    """an MXINT8 LinearWeightMX prepared through mxa_linear_weight_prep and through
+    mxa_linear_weight_prep_bits(.., 8): the same size, the same bytes (header included)"""
+    from mx_quantization_amd import _native as N
+    lib = N.lib()
+    W = dev(C.rnd((160, 100), 3, 0.15))
+    W[5, 7] = float("nan")
+    for gw in (160, 32, 20):
+        n = lib.mxa_linear_weight_bytes(160, 100, gw)
+        assert n == lib.mxa_linear_weight_bytes_bits(160, 100, gw, 8)
+        old = torch.full((n,), 0xA5, dtype=torch.uint8, device="cuda")
+        new = torch.full((n,), 0xA5, dtype=torch.uint8, device="cuda")
+        st = torch.cuda.current_stream().cuda_stream
+        assert lib.mxa_linear_weight_prep(W.data_ptr(), 160, 100, gw, 0, 16, old.data_ptr(), st) == 0
+        assert lib.mxa_linear_weight_prep_bits(W.data_ptr(), 160, 100, gw, 0, 16, 8, new.data_ptr(), st) == 0
+        torch.cuda.synchronize()
+        assert torch.equal(old, new), gw
+        assert host(old[28:32]).view(np.int32)[0] == 0  # the header's elem_bits of an MXINT8 buffer
+        four = M.LinearWeightMX(W, gw, False, 16, elem_bits=4)
+        assert four.buf.numel() < n and host(four.buf[28:32]).view(np.int32)[0] == 4
