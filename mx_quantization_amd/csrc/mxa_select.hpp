@@ -54,11 +54,13 @@ inline int sel_waves_for(int T, int64_t BH, int N) {
 struct SelLds {
   size_t cd, ex, sg, z, cs, kf, rows;
 };
-// ex_pred's key exponents go to LDS as int32 for nbd <= 2 (raw int16 values sign-extended:
-// no extraction in the key loop; for nbd >= 3 int16, which keeps DiT's workgroups per CU),
-// with 16 flag words kf: bit i of kf[g] = key g + 16 i has a
-// block exponent outside [kExpFastLo, kExpFastHi] (or NaN), i.e. its score may need the
-// exact slow path (sel_scores)
+// ex_pred for nbd <= 2: one record per key over the ex and sg areas (the same bytes: 8 nbd per
+// key), which the key loop reads with one LDS load -- the key's nbd sign words, then per block
+// the float bits of 2^ek, (ek + 127) << 23, or for a block exponent outside [kExpFastLo,
+// kExpFastHi] (or NaN) a NaN that carries it (expred_rec_word); with 16 flag words kf: bit i of
+// kf[g] = key g + 16 i has such a block, i.e. its score needs the exact slow path (sel_scores,
+// expred_score_rec).  For nbd >= 3 int16 exponents and sign words in two tables,
+// which keeps DiT's workgroups per CU.
 constexpr int kExpFastLo = -50, kExpFastHi = 61;
 __host__ __device__ inline SelLds sel_lds(int mode, int T, int D, int kst, int nbd) {
   SelLds L;
@@ -112,6 +114,28 @@ __device__ __forceinline__ float expred_score(const uint32_t* sq, const int* eq,
 #pragma unroll
   for (int b = 0; b < NBD; ++b) acc += (double)m[b] * pow2d(e[b]);
   return (float)acc;
+}
+// The exponent word of a key record (sel_lds: nbd <= 2) for the raw block exponent ek: the float
+// bits of 2^ek inside the fast range; outside it a NaN whose payload holds ek in bits 8..22 (15
+// bits: ex_pred's exponents are float exponents, far inside; -16384 stands for the NaN block's
+// INT16_MIN) and whose low byte is 0 -- whatever the key loop computes from it is a NaN or an
+// infinity with a zero low byte, which leaves the row's packing test alone.
+__device__ __forceinline__ uint32_t expred_rec_word(int ek) {
+  if (ek >= kExpFastLo && ek <= kExpFastHi) return (uint32_t)(ek + 127) << 23;
+  return 0x7F800000u | (((uint32_t)(ek == kExpNaN16 ? -16384 : ek) & 0x7FFFu) << 8);
+}
+__device__ __forceinline__ int16_t expred_rec_exp(uint32_t w) {
+  if (w < 0x7F800000u) return (int16_t)((int)(w >> 23) - 127);
+  const int s = (int)(w << 9) >> 17;  // bits 8..22, sign-extended
+  return s == -16384 ? kExpNaN16 : (int16_t)s;
+}
+// ... of the key whose record is rec
+template <int NBD>
+__device__ __forceinline__ float expred_score_rec(const uint32_t* sq, const int* eq, const uint32_t* rec, int D) {
+  int16_t ke[NBD];
+#pragma unroll
+  for (int b = 0; b < NBD; ++b) ke[b] = expred_rec_exp(rec[NBD + b]);
+  return expred_score<NBD>(sq, eq, ke, rec, D);
 }
 
 // MX dot product of a query row (codes in registers, two uint4 per 32-block, block
@@ -179,9 +203,9 @@ __device__ __forceinline__ float elsa_cos_entry(int D, int h) {
 // ---- the head's score tables in LDS (sel_lds) -------------------------------------
 struct SelTabs {
   int8_t* tcd;    // key codes
-  int16_t* tex;   // key exponents (ex_pred: tex32)
-  int* tex32;
-  uint32_t* kf;   // ex_pred: the keys outside the fast path's exponent range (SelLds)
+  int16_t* tex;   // key exponents
+  uint32_t* trec; // ex_pred, nbd <= 2: the key records (SelLds), in place of tex and tsg
+  uint32_t* kf;   // ... and the keys outside the fast path's exponent range
   uint32_t* tsg;  // sign / hash words
   int8_t* tz;     // true_ex zero indicators
   float* tcs;     // ELSA cosine table
@@ -195,7 +219,7 @@ __device__ __forceinline__ SelTabs sel_stage(const Rows2Args& a, unsigned char* 
   t.tsg = reinterpret_cast<uint32_t*>(smem + L.sg);
   t.tz = reinterpret_cast<int8_t*>(smem + L.z);
   t.tcs = reinterpret_cast<float*>(smem + L.cs);
-  t.tex32 = reinterpret_cast<int*>(smem + L.ex);
+  t.trec = reinterpret_cast<uint32_t*>(__builtin_assume_aligned(smem + L.ex, 16));
   t.kf = reinterpret_cast<uint32_t*>(smem + L.kf);
   const int T = a.T, D = a.D, nbd = a.nbd, kst = a.kst;
   if (MODE == kModeExSign && nbd <= 2) {  // (the range flags serve the nbd <= 2 key loop)
@@ -218,20 +242,15 @@ __device__ __forceinline__ SelTabs sel_stage(const Rows2Args& a, unsigned char* 
   {
     const int16_t* esrc = MODE == kModeTrue ? a.ksT : a.ksA;
     for (int i = threadIdx.x; i < T * nbd; i += blockDim.x) {
-      if (MODE == kModeExSign) {
+      if (MODE == kModeExSign && nbd <= 2) {
         const int ek = esrc[kb * nbd + i];  // raw (NaN: INT16_MIN, outside the range)
-        if (nbd <= 2) {
-          t.tex32[i] = ek;
-          if (ek < kExpFastLo || ek > kExpFastHi) {
-            const int j = i / nbd;
-            atomicOr(t.kf + (j & 15), 1u << (j >> 4));
-          }
-        } else {
-          t.tex[i] = (int16_t)ek;
-        }
-      } else if (MODE != kModeElsa) {
-        t.tex[i] = esrc[kb * nbd + i];
+        const int j = nbd == 2 ? i >> 1 : i, b = i - j * nbd;  // (no division: nbd is 1 or 2)
+        t.trec[2 * nbd * j + b] = a.ksg[kb * nbd + i];
+        t.trec[2 * nbd * j + nbd + b] = expred_rec_word(ek);
+        if (ek < kExpFastLo || ek > kExpFastHi) atomicOr(t.kf + (j & 15), 1u << (j >> 4));
+        continue;
       }
+      if (MODE != kModeElsa) t.tex[i] = esrc[kb * nbd + i];
       if (MODE == kModeExSign || MODE == kModeElsa) t.tsg[i] = a.ksg[kb * nbd + i];
     }
     if (MODE == kModeElsa)
@@ -276,9 +295,11 @@ __device__ __forceinline__ void sel_scores(const Rows2Args& a, const SelTabs& t,
     }
     auto keys = [&](auto nbd_c) {  // the key loop for a compile-time block count
       constexpr int NBD = decltype(nbd_c)::value;
-      if (brow >= 0 || a.s_dt != kF32 || js != 16) {
+      // (an odd D: the fast loop below halves the block lengths)
+      if (brow >= 0 || a.s_dt != kF32 || js != 16 || (NBD <= 2 && (D & 1))) {
         if constexpr (NBD <= 2)
-          for (int j = j0; j < T; j += js) emit(j, expred_score<NBD>(sq, eq, t.tex32 + j * NBD, t.tsg + j * NBD, D));
+          for (int j = j0; j < T; j += js)
+            emit(j, expred_score_rec<NBD>(sq, eq, t.trec + 2 * NBD * j, D));
         else
           for (int j = j0; j < T; j += js) emit(j, expred_score<NBD>(sq, eq, t.tex + j * NBD, t.tsg + j * NBD, D));
         return;
@@ -330,45 +351,78 @@ __device__ __forceinline__ void sel_scores(const Rows2Args& a, const SelTabs& t,
       // No bias, float32 scores: every lane runs the same ceil(T / 16) keys (the last trip
       // peeled: keys >= T are dropped), with no branch in the loop.  When every block
       // exponent of the row and of the key lies in [kExpFastLo, kExpFastHi], the block
-      // terms m_b 2^(eq_b + ek_b) are exact floats (|m_b| <= 32, 2^-100 <= 2^e <= 2^122):
-      // v = x0 + x1, one IEEE addition of two exact terms = fl32(exact sum) (NBD <= 2).
-      // Keys outside (range flags kf, a NaN block) are redone afterwards by
-      // the exact expred_score, under a wave-uniform branch.  A fast value is finite and
-      // never -0, so its order key takes two instructions and its packing test is the low
-      // byte of its bits.
-      int nbk[NBD];
+      // terms m_b 2^(eq_b + ek_b) are exact floats (|m_b| <= 32, 2^-100 <= 2^e <= 2^122), formed
+      // as products: with h_b = m_b / 2 = popc(~sq_b ^ sk_b) + n_b / 2 - 32 (one v_bcnt with its
+      // accumulate operand; the words' bits from n_b up are equal, so they count 32 - n_b) and
+      // t_b = 2^ek_b (the key's record) * 2^(eq_b + 1) (once per row), a normal power of two,
+      //   x0 = (float)h0 * t0 (exact),  v = fmaf((float)h1, t1, x0):
+      // one rounding of the exact two-term sum = fl32(exact sum), a zero sum +0 (the conversion
+      // never yields -0) (NBD <= 2).  Keys outside (range flags kf; their records hold a NaN for
+      // 2^ek) are redone afterwards by the exact expred_score, under a wave-uniform branch.  A
+      // fast value is finite and never -0, so its order key takes two instructions and its
+      // packing test is the low byte of its bits.  pred_out is null in the attention calls: the
+      // loop is compiled with and without its store, chosen once per row.
       bool row_fast = true;
+      uint32_t sqn[NBD];
+      int hc[NBD];
+      float q2[NBD];
 #pragma unroll
       for (int b = 0; b < NBD; ++b) {
-        nbk[b] = min(32, D - 32 * b);
         row_fast = row_fast && eq[b] >= kExpFastLo && eq[b] <= kExpFastHi;  // (NaN: kExpNaN)
+        sqn[b] = ~sq[b];
+        hc[b] = min(32, D - 32 * b) / 2 - 32;
       }
-      float* prow = a.pred_out ? a.pred_out + grow * T : nullptr;
+#pragma unroll
+      for (int b = 0; b < NBD; ++b) q2[b] = row_fast ? __uint_as_float((uint32_t)(eq[b] + 128) << 23) : 0.0f;
       const int nt = (T + 15) >> 4;
       uint32_t redo = row_fast ? t.kf[j0 & 15] : lowbits(nt);  // per trip i: key j0 + 16 i
-      auto one = [&](int i, auto last_c) {
-        constexpr bool LAST = decltype(last_c)::value;
-        const int j = j0 + 16 * i;
-        const int* kex = t.tex32 + j * NBD;
-        const uint32_t* ksg = t.tsg + j * NBD;
-        float v = ldexpf((float)(nbk[0] - 2 * (int)__popc(sq[0] ^ ksg[0])), eq[0] + kex[0]);
-        if constexpr (NBD == 2) v += ldexpf((float)(nbk[1] - 2 * (int)__popc(sq[1] ^ ksg[1])), eq[1] + kex[1]);
-        const uint32_t key = order_key_fast(v);
-        if (!LAST || j < T) {
-          if (prow) prow[j] = v;
-          sink(j, v, key, std::true_type{});
+      // (the lane's first key as a value of this row: the loop's addresses are formed here, not
+      // once per kernel and kept -- spilled -- across every row group: 28 B of scratch more)
+      int jl = j0;
+      asm volatile("" : "+v"(jl));
+      auto loop = [&](auto pred_c) {
+        constexpr bool PRED = decltype(pred_c)::value;
+        float* prow = PRED ? a.pred_out + grow * T : nullptr;
+        auto one = [&](int i, auto last_c) {
+          constexpr bool LAST = decltype(last_c)::value;
+          const int j = jl + 16 * i;
+          uint32_t w[2 * NBD];
+          if constexpr (NBD == 2) {
+            const uint4 x = *reinterpret_cast<const uint4*>(t.trec + 4 * j);
+            w[0] = x.x, w[1] = x.y, w[2] = x.z, w[3] = x.w;
+          } else {
+            const uint2 x = *reinterpret_cast<const uint2*>(t.trec + 2 * j);
+            w[0] = x.x, w[1] = x.y;
+          }
+          float v = (float)((int)__popc(sqn[0] ^ w[0]) + hc[0]) * (__uint_as_float(w[NBD]) * q2[0]);
+          if constexpr (NBD == 2)
+            v = __builtin_fmaf((float)((int)__popc(sqn[1] ^ w[1]) + hc[1]), __uint_as_float(w[3]) * q2[1], v);
+          const uint32_t key = order_key_fast(v);
+          if (!LAST || j < T) {
+            if constexpr (PRED) prow[j] = v;
+            sink(j, v, key, std::true_type{});
+          }
+        };
+        // (in pairs: one step of the record and mirror addresses per two keys)
+        int i = 0;
+#pragma unroll 1
+        for (; i + 2 < nt; i += 2) {
+          one(i, std::false_type{});
+          one(i + 1, std::false_type{});
         }
+        if (i + 1 < nt) one(i, std::false_type{});
+        one(nt - 1, std::true_type{});
       };
-#pragma unroll 1  // (unrolled by 2 / 4: the same within the spread, profiles/r06_ab_tail.txt)
-      for (int i = 0; i < nt - 1; ++i) one(i, std::false_type{});
-      one(nt - 1, std::true_type{});
+      if (a.pred_out) loop(std::true_type{});
+      else loop(std::false_type{});
       if (__builtin_amdgcn_ballot_w64(redo != 0u) != 0) {  // rare: the exact path for those keys
+        float* prow = a.pred_out ? a.pred_out + grow * T : nullptr;
         while (redo) {
           const int i = __ffs((int)redo) - 1;
           redo &= redo - 1u;
           const int j = j0 + 16 * i;
           if (j < T) {
-            const float v = expred_score<NBD>(sq, eq, t.tex32 + j * NBD, t.tsg + j * NBD, D);
+            const float v = expred_score_rec<NBD>(sq, eq, t.trec + 2 * NBD * j, D);
             if (prow) prow[j] = v;
             sink(j, v, order_key(v), std::false_type{});
           }
