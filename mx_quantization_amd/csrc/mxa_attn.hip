@@ -21,8 +21,6 @@
 #include <cstdlib>
 #include <vector>
 
-
-
 namespace mxa {
 
 typedef int v16i __attribute__((ext_vector_type(16)));
@@ -67,20 +65,6 @@ using namespace mxa;
 
 namespace {
 
-constexpr int64_t kAlign = 256;
-inline int64_t align_up(int64_t x) { return (x + kAlign - 1) / kAlign * kAlign; }
-
-// workspace regions, 256-B aligned
-struct AttnLayout {
-  int nbd, dpad, ntb, tpad;
-  int64_t qc, qop, qz, qsT, qsA, qsg, kc, kop, kz, ksT, ksA, ksg, knorm, vt, vs, idx16, tail, fbf, mask;
-  int64_t xc, xs;  // fused qkv projection: x codes / exponents
-  int64_t cc, cs;  // cross-attention: the key / value tokens' codes / exponents (xc, xs: the query tokens')
-  int64_t yc, ys, yf;  // fused proj Linear: its input codes / exponents, the fp32 output
-                              // copy (D % 32 != 0 only), the GEMM's fp64 wave list
-  int64_t total;
-};
-
 // the selection kernel's score mode of a call (ranked: the selection kernel runs)
 int score_mode(const mxa_attn_params* p, bool ranked) {
   if (!(p->approx && ranked)) return kModeTrue;
@@ -93,172 +77,122 @@ int score_mode(const mxa_attn_params* p, bool ranked) {
   }
 }
 
+// the operands a score mode reads next to the MX codes and exponents of Q and K: approximator
+// codes, zero indicators (true_ex), approximator scales, sign / hash words, key norms (ELSA);
+// prep_signs: rows_prep writes the sign words (ELSA's hash words are elsa_prep's)
+struct ModeNeeds { bool op, z, sa, sg, knorm, prep_signs; };
+ModeNeeds mode_needs(int mode) {
+  ModeNeeds n{};
+  n.op = mode == kModeOpExp || mode == kModeOpMul || mode == kModeTrueEx;
+  n.z = mode == kModeTrueEx;
+  n.sa = mode != kModeTrue && mode != kModeElsa;
+  n.sg = mode == kModeExSign || mode == kModeElsa;
+  n.knorm = mode == kModeElsa;
+  n.prep_signs = mode == kModeExSign;
+  return n;
+}
+
 // the proj Linear's input comes MX-quantized out of the finishing kernel
 bool proj_codes_direct(const mxa_attn_params* p) {
   return p->D % 32 == 0 && p->dtype == MXA_DT_F32 && p->score_dtype <= MXA_DT_F32;
 }
 
-AttnLayout attn_layout(const mxa_attn_params* p, int mode, const mxa_qkv_params* xq = nullptr,
-                       const mxa_proj_params* pj = nullptr, const mxa_cross_params* xc = nullptr) {
+// one side's (Q's or K's) row operands; null: the score mode does not read it
+struct AttnOperands { int8_t *codes, *op, *z; int16_t *sT, *sA; uint32_t* sg; };
+AttnOperands carve_operands(Carver& ws, int64_t rows, int nbd, const ModeNeeds& n) {
+  const int64_t dpad = 32 * (int64_t)nbd;
+  AttnOperands o{};
+  o.codes = ws.take<int8_t>(rows * dpad);
+  o.op = ws.take<int8_t>(n.op ? rows * dpad : 0);
+  o.z = ws.take<int8_t>(n.z ? rows * dpad : 0);
+  o.sT = ws.take<int16_t>(rows * nbd);
+  o.sA = ws.take<int16_t>(n.sa ? rows * nbd : 0);
+  o.sg = ws.take<uint32_t>(n.sg ? rows * nbd : 0);
+  return o;
+}
+
+// workspace regions in their order, 256-B aligned
+struct AttnLayout {
+  int nbd, dpad, ntb, tpad;
+  ModeNeeds needs;
+  AttnOperands q, k;
+  float* knorm;
+  int8_t* vt; int16_t* vs;
+  uint16_t* idx16; uint32_t *tail, *fbf, *mask;
+  MxRows x, c;  // fused qkv projection: x's codes / exponents; cross-attention: the query (x), key / value (c) tokens'
+  MxRows y;     // fused proj Linear: its input (MFMA-ready) ...
+  float* yf;    // ... and the attention's fp32 output it is quantized from (D % 32 != 0 only)
+  int64_t total;
+};
+
+// workspace: the call's, or null to size it
+AttnLayout attn_layout(const mxa_attn_params* p, int mode, const mxa_qkv_params* xq, const mxa_cross_params* xc,
+                       const mxa_proj_params* pj, void* workspace) {
   AttnLayout L{};
+  Carver ws(workspace);
   const int64_t BH = (int64_t)p->B * p->H;
-  L.nbd = (p->D + 31) / 32;
-  L.dpad = L.nbd * 32;
-  L.ntb = (p->T + 31) / 32;
-  L.tpad = L.ntb * 32;
-  const bool need_pred = mode != kModeTrue;
-  const bool op = mode == kModeOpExp || mode == kModeOpMul || mode == kModeTrueEx;  // approximator codes
-  const bool sg = mode == kModeExSign || mode == kModeElsa;                         // sign / hash words
-  const bool sa = need_pred && mode != kModeElsa;                                   // approximator scales
-  int64_t off = 0;
-  auto take = [&](int64_t bytes) {
-    const int64_t o = off;
-    off += align_up(bytes);
-    return o;
-  };
+  L.nbd = (p->D + 31) / 32; L.dpad = L.nbd * 32;
+  L.ntb = (p->T + 31) / 32; L.tpad = L.ntb * 32;
+  L.needs = mode_needs(mode);
   const int64_t qrows = BH * p->N, krows = BH * p->T;
-  L.qc = take(qrows * L.dpad);
-  L.qop = take(op ? qrows * L.dpad : 0);
-  L.qz = take(mode == kModeTrueEx ? qrows * L.dpad : 0);
-  L.qsT = take(qrows * L.nbd * 2);
-  L.qsA = take(sa ? qrows * L.nbd * 2 : 0);
-  L.qsg = take(sg ? qrows * L.nbd * 4 : 0);
-  L.kc = take(krows * L.dpad);
-  L.kop = take(op ? krows * L.dpad : 0);
-  L.kz = take(mode == kModeTrueEx ? krows * L.dpad : 0);
-  L.ksT = take(krows * L.nbd * 2);
-  L.ksA = take(sa ? krows * L.nbd * 2 : 0);
-  L.ksg = take(sg ? krows * L.nbd * 4 : 0);
-  L.knorm = take(mode == kModeElsa ? krows * 4 : 0);
-  L.vt = take(BH * p->D * (int64_t)L.tpad);
-  L.vs = take(BH * L.ntb * (int64_t)p->D * 2);
-  L.idx16 = take(p->top_k ? qrows * (int64_t)p->k_top * 2 : 0);  // used when the caller takes no idx
+  L.q = carve_operands(ws, qrows, L.nbd, L.needs);
+  L.k = carve_operands(ws, krows, L.nbd, L.needs);
+  L.knorm = ws.take<float>(L.needs.knorm ? krows : 0);
+  L.vt = ws.take<int8_t>(BH * p->D * (int64_t)L.tpad);
+  L.vs = ws.take<int16_t>(BH * L.ntb * (int64_t)p->D);
+  L.idx16 = ws.take<uint16_t>(p->top_k ? qrows * (int64_t)p->k_top : 0);  // used when the caller takes no idx
   {  // the one-lane top-k tail's staging records (mxa_tail.hpp); the packed selection
      // pass's per-workgroup flags (at most one workgroup per 16 query rows of a head)
     const bool pk = p->top_k && sel_packs(mode, p->T, p->bias != nullptr);
     const int tw = p->top_k ? sel_tail_width(mode, p->T, p->k_top, p->bias != nullptr) : 0;
-    L.tail = take(tw ? qrows * (int64_t)tail_rec_words(tw) * 4 : 0);
-    L.fbf = take(pk ? BH * (int64_t)((p->N + 15) / 16) * 4 : 0);
+    L.tail = ws.take<uint32_t>(tw ? qrows * (int64_t)tail_rec_words(tw) : 0);
+    L.fbf = ws.take<uint32_t>(pk ? BH * (int64_t)((p->N + 15) / 16) : 0);
   }
   // the prune-mask words for the MFMA finishing kernel when the caller takes none
   // (reserved whatever mask_out is: the size must not depend on it)
-  L.mask = take(p->top_k && finish_qk_wanted(p->k_top, p->T, L.nbd, pj && proj_codes_direct(p))
-                    ? qrows * (int64_t)L.ntb * 4
-                    : 0);
-  if (xq) {
-    const int64_t nbk = (xq->C + 31) / 32, tokens = (int64_t)p->B * p->N;
-    L.xc = take(tokens * nbk * 32);
-    L.xs = take(tokens * nbk * 2);
-  }
+  L.mask = ws.take<uint32_t>(p->top_k && finish_qk_wanted(p->k_top, p->T, L.nbd, pj && proj_codes_direct(p))
+                                 ? qrows * (int64_t)L.ntb
+                                 : 0);
+  const int64_t qtok = (int64_t)p->B * p->N;
+  if (xq) L.x = carve_mx_rows(ws, qtok, xq->C, false);
   if (xc) {
-    const int64_t nbq = (xc->C + 31) / 32, nbc = (xc->C_kv + 31) / 32;
-    const int64_t qtok = (int64_t)p->B * p->N, ktok = (int64_t)p->B * p->T;
-    L.xc = take(qtok * nbq * 32);
-    L.xs = take(qtok * nbq * 2);
-    L.cc = take(ktok * nbc * 32);
-    L.cs = take(ktok * nbc * 2);
+    L.x = carve_mx_rows(ws, qtok, xc->C, false);
+    L.c = carve_mx_rows(ws, (int64_t)p->B * p->T, xc->C_kv, false);
   }
   if (pj) {
-    const int64_t C = (int64_t)p->H * p->D, nbk = (C + 31) / 32, tokens = (int64_t)p->B * p->N;
-    L.yc = take((tokens + 31) / 32 * 32 * nbk * 32);  // MFMA-ready codes: whole 32-row blocks
-    L.ys = take(tokens * nbk * 2);
-    L.yf = take(proj_codes_direct(p) ? 0 : tokens * C * 4);
+    L.y = carve_mx_rows(ws, qtok, p->H * p->D, true);
+    L.yf = ws.take<float>(proj_codes_direct(p) ? 0 : qtok * p->H * p->D);
   }
-  L.total = off;
+  L.total = ws.off;
   return L;
 }
 
+bool attn_shape_ok(const mxa_attn_params* p) { return p && p->B > 0 && p->H > 0 && p->N > 0 && p->T > 0 && p->D > 0; }
 
-}  // namespace
-
-extern "C" int mxa_abi_version(void) { return MXA_ABI_VERSION; }
-
-extern "C" const char* mxa_status_string(int status) {
-  switch (status) {
-    case MXA_OK: return "ok";
-    case MXA_ERR_ARG: return "invalid argument";
-    case MXA_ERR_UNSUPPORTED: return "unsupported configuration";
-    case MXA_ERR_LAUNCH: return "HIP kernel launch failed";
-    case MXA_ERR_WORKSPACE: return "workspace too small";
-    default: return "unknown status";
-  }
+// the workspace of a call; sized for the approximator whenever it may run (the proj Linear
+// and top-k run the selection kernel, pred_out the scores alone)
+int64_t attn_workspace_total(const mxa_attn_params* p, const mxa_qkv_params* xq, const mxa_cross_params* xc,
+                             const mxa_proj_params* pj) {
+  return attn_layout(p, score_mode(p, pj || p->top_k || p->pred_out), xq, xc, pj, nullptr).total;
 }
 
-extern "C" int64_t mxa_attention_workspace_bytes(const mxa_attn_params* p) {
-  if (!p || p->B <= 0 || p->H <= 0 || p->N <= 0 || p->T <= 0 || p->D <= 0) return -1;
-  // sized for the approximator whenever it may run (top-k, or the scores alone)
-  return attn_layout(p, score_mode(p, p->top_k || p->pred_out)).total;
-}
+// One attention call
+struct AttnCall {
+  const mxa_attn_params* p;
+  hipStream_t stream;
+  const mxa_qkv_params* xq;    // the fused qkv projection (q, k, v produced from x and the prepared weight)
+  const mxa_cross_params* xc;  // cross-attention's projections (q from x, k and v from cond; N and T independent)
+  const mxa_proj_params* pj;   // the proj Linear behind it (y = mx.Linear(out.transpose(1,2).reshape(B,N,C)))
+  bool scores_only;  // the approximate (or true) scores into p->pred_out / true_out, no top-k
+  hipEvent_t* ev;    // the timed entry points' stage events
+  int *plan, *fin;   // plan: only report the kernel path (MXA_PATH_*), launch nothing; fin (with plan): the
+                     // finishing kernel (MXA_FIN_*, 0 for the scores alone)
+};
 
-// One projection pass (part: ProjPart): x (ntok tokens per image, C features) -> MX codes along
-// C (rows_prep) into the workspace at xc_off / xs_off, then the projection kernel on the
-// prepared weight wq of parts * H * D rows, writing the part's q / k operands (rq, rk) and V's
-// transposed codes (cv)
-static int launch_proj_pass(const mxa_attn_params& pp, int part, const float* x, int64_t x_row_stride, int C, int ntok,
-                            const void* wq, const float* bias, float* proj_out, int autocast, int64_t xc_off,
-                            int64_t xs_off, const RowsPrepArgs& rq, const RowsPrepArgs& rk, const ColsPrepArgs& cv,
-                            unsigned char* ws, hipStream_t stream) {
-  const int parts = part == kPartQKV ? 3 : part == kPartKV ? 2 : 1;
-  const int nbk = (C + 31) / 32, Cpad = 32 * nbk;
-  const int64_t tokens = (int64_t)pp.B * ntok;
-  const RowsPrepArgs rx = flat_rows_prep(x, tokens, C, x_row_stride, aligned16(x) && x_row_stride % 4 == 0,
-                                         pp.flush_subnormals, pp.bfloat, reinterpret_cast<int8_t*>(ws + xc_off),
-                                         reinterpret_cast<int16_t*>(ws + xs_off), 0);
-  int rc = launch_rows_prep(rx, stream);
-  if (rc) return rc;
-  const LinearLayout W = linear_layout(parts * pp.H * pp.D, C, pp.D);
-  const unsigned char* wb = static_cast<const unsigned char*>(wq);
-  ProjArgs pa{};
-  pa.xc = rx.codes; pa.xs = rx.sT;
-  pa.pk = reinterpret_cast<const int8_t*>(wb + W.pk);
-  pa.pe = reinterpret_cast<const int16_t*>(wb + W.pe);
-  pa.ps = reinterpret_cast<const int16_t*>(wb + W.ps);
-  pa.gs = reinterpret_cast<const int16_t*>(wb + W.gs);
-  pa.pn = reinterpret_cast<const int16_t*>(wb + W.pn);
-  pa.pd = reinterpret_cast<const int8_t*>(wb + W.pd);
-  if (W.ps - W.pk >= ((int64_t)1 << 31) || W.total - W.pd >= ((int64_t)1 << 31))
-    return MXA_ERR_UNSUPPORTED;  // 32-bit buffer offsets
-  pa.pk_bytes = (int)(W.pe - W.pk);
-  pa.pe_bytes = (int)(W.ps - W.pe);
-  pa.pd_bytes = (int)(W.total - W.pd);
-  pa.ntb = (ntok + 31) / 32;
-  pa.bias = bias; pa.qkv_out = proj_out;
-  pa.autocast = autocast;
-  pa.B = pp.B; pa.N = ntok; pa.H = pp.H; pa.D = pp.D; pa.nbk = nbk; pa.Cpad = Cpad; pa.bfloat = pp.bfloat;
-  pa.smax = gemm_smax(nbk);
-  pa.rq = rq; pa.rk = rk; pa.cv = cv;
-  return launch_proj(pa, stream, part);
-}
-
-static int launch_qkv_proj(const mxa_attn_params& pp, const mxa_qkv_params& xq, const AttnLayout& L,
-                           const RowsPrepArgs& rq, const RowsPrepArgs& rk, const ColsPrepArgs& cv, unsigned char* ws,
-                           hipStream_t stream) {
-  return launch_proj_pass(pp, kPartQKV, xq.x, xq.x_row_stride, xq.C, pp.N, xq.wq, xq.bias, xq.qkv_out,
-                          xq.autocast_dtype, L.xc, L.xs, rq, rk, cv, ws, stream);
-}
-
-// cross-attention: the query tokens -> the q operands, then the key / value tokens -> the k
-// operands and V's transposed codes (two launches of the projection kernel by parts)
-static int launch_cross_proj(const mxa_attn_params& pp, const mxa_cross_params& xc, const AttnLayout& L,
-                             const RowsPrepArgs& rq, const RowsPrepArgs& rk, const ColsPrepArgs& cv, unsigned char* ws,
-                             hipStream_t stream) {
-  const int rc = launch_proj_pass(pp, kPartQ, xc.x, xc.x_row_stride, xc.C, pp.N, xc.wq_q, xc.bias_q, xc.q_out, 0,
-                                  L.xc, L.xs, rq, rk, cv, ws, stream);
-  if (rc) return rc;
-  return launch_proj_pass(pp, kPartKV, xc.cond, xc.cond_row_stride, xc.C_kv, pp.T, xc.wq_kv, xc.bias_kv, xc.kv_out, 0,
-                          L.cc, L.cs, rq, rk, cv, ws, stream);
-}
-
-// plan != nullptr: only report the kernel path (MXA_PATH_*), launch nothing;
-// scores_only: the approximate (or true) scores into p->pred_out / true_out, no top-k
-// xq: the fused qkv projection (q, k, v produced from x and the prepared weight)
-// pj: the proj Linear behind the attention (y = mx.Linear(out.transpose(1,2).reshape(B,N,C)))
-// fin (with plan): the finishing kernel (MXA_FIN_*, 0 for the scores alone)
-// xc: cross-attention's projections (q from x, k and v from cond; N and T independent)
-static int attention_impl(const mxa_attn_params* p, hipStream_t stream, hipEvent_t* ev, int* plan = nullptr,
-                          bool scores_only = false, const mxa_qkv_params* xq = nullptr,
-                          const mxa_proj_params* pj = nullptr, int* fin = nullptr,
-                          const mxa_cross_params* xc = nullptr) {
+// the refusals of a call, in their order; every one before the prepared weights' header
+// checks returns without a HIP call
+int attn_validate(const AttnCall& c) {
+  const auto [p, stream, xq, xc, pj, scores_only, ev, plan, fin] = c;
   if (!p) return MXA_ERR_ARG;
   if (pj) {
     if (scores_only || !p->top_k || !pj->wq || !pj->y || pj->out_features <= 0 || pj->y_row_stride < pj->out_features)
@@ -276,7 +210,7 @@ static int attention_impl(const mxa_attn_params* p, hipStream_t stream, hipEvent
   }
   if (!scores_only && ((!p->v && !xq && !xc) || (!p->out && !pj))) return MXA_ERR_ARG;
   if (scores_only && !(p->approx ? p->pred_out : p->true_out)) return MXA_ERR_ARG;
-  if (p->B <= 0 || p->H <= 0 || p->N <= 0 || p->T <= 0 || p->D <= 0) return MXA_ERR_ARG;
+  if (!attn_shape_ok(p)) return MXA_ERR_ARG;
   if (!scores_only && p->top_k && (p->k_top <= 0 || p->k_top > p->T)) return MXA_ERR_ARG;
   if (p->pred_mode < MXA_PRED_EX_PRED || p->pred_mode > MXA_PRED_ELSA) return MXA_ERR_ARG;
   if (p->dtype < MXA_DT_F32 || p->dtype > MXA_DT_BF16 || p->score_dtype < 0 || p->score_dtype > MXA_DT_BF16)
@@ -292,32 +226,181 @@ static int attention_impl(const mxa_attn_params* p, hipStream_t stream, hipEvent
     return MXA_ERR_UNSUPPORTED;
   if (!valid_bfloat(p->bfloat)) return MXA_ERR_ARG;
   if (p->T > 512 || p->D > 32 * kMaxNB) return MXA_ERR_UNSUPPORTED;
-  // the prepared weight must have been prepared for this geometry and these settings
-  if (xq && !linear_weight_verify(xq->wq, linear_weight_header(3 * p->H * p->D, xq->C, p->D, p->flush_subnormals,
-                                                                p->bfloat),
-                                  stream))
+  // the prepared weights must have been prepared for this geometry and these settings
+  const int HD = p->H * p->D, fl = p->flush_subnormals, bf = p->bfloat;
+  if (xq && !linear_weight_verify(xq->wq, linear_weight_header(3 * HD, xq->C, p->D, fl, bf), stream)) return MXA_ERR_ARG;
+  if (xc && !(linear_weight_verify(xc->wq_q, linear_weight_header(HD, xc->C, p->D, fl, bf), stream) &&
+              linear_weight_verify(xc->wq_kv, linear_weight_header(2 * HD, xc->C_kv, p->D, fl, bf), stream)))
     return MXA_ERR_ARG;
-  if (xc && !(linear_weight_verify(xc->wq_q, linear_weight_header(p->H * p->D, xc->C, p->D, p->flush_subnormals,
-                                                                   p->bfloat), stream) &&
-              linear_weight_verify(xc->wq_kv, linear_weight_header(2 * p->H * p->D, xc->C_kv, p->D,
-                                                                    p->flush_subnormals, p->bfloat), stream)))
-    return MXA_ERR_ARG;
-  if (pj && !linear_weight_verify_any_group(pj->wq, pj->out_features, p->H * p->D, p->flush_subnormals, p->bfloat,
-                                            stream))
-    return MXA_ERR_ARG;
-  mxa_attn_params pp = *p;
-  if (scores_only) {  // the selection kernel alone, with no kept keys
-    pp.top_k = 0;
-    pp.k_top = 0;
-    pp.idx_out = nullptr;
-    pp.mask_out = nullptr;
+  if (pj && !linear_weight_verify_any_group(pj->wq, pj->out_features, HD, fl, bf, stream)) return MXA_ERR_ARG;
+  return MXA_OK;
+}
+
+// the operand builder's arguments for one side: x at strides s (B, H, row), R rows per head
+RowsPrepArgs attn_rows_prep(const mxa_attn_params& pp, const AttnLayout& L, const AttnOperands& o, const void* x,
+                            const int64_t* s, int R, int op_kind) {
+  RowsPrepArgs r{};
+  r.x = x; r.s0 = s[0]; r.s1 = s[1]; r.s2 = s[2];
+  r.H = pp.H; r.R = R; r.rows = (int64_t)pp.B * pp.H * R; r.D = pp.D; r.nb = L.nbd; r.dpad = L.dpad;
+  r.vec4 = may_load_16B(x, pp.dtype, s[0], s[1], s[2]);
+  r.op_kind = op_kind; r.flush = pp.flush_subnormals; r.bfloat = pp.bfloat;
+  r.dt = pp.dtype;  // (the fused projections, which write these operands themselves, take float32 only)
+  r.codes = o.codes; r.sT = o.sT; r.op = o.op; r.zind = o.z; r.sA = o.sA;
+  r.signs = L.needs.prep_signs ? o.sg : nullptr;
+  return r;
+}
+
+// the token matrix of one projection pass: ntok tokens per image of C features, its prepared
+// weight (parts * H * D rows) and bias, the optional fp32 output, its MX rows in the workspace
+struct ProjTokens {
+  const float* x; int64_t row_stride; int C, ntok;
+  const void* wq; const float* bias;
+  float* out; int autocast;
+  MxRows rows;
+};
+
+// One projection pass (part: ProjPart): x -> MX codes along C (rows_prep) into the workspace,
+// then the projection kernel on the prepared weight, writing the part's q / k operands (rq,
+// rk) and V's transposed codes (cv)
+int launch_proj_pass(const mxa_attn_params& pp, int part, const ProjTokens& t, const RowsPrepArgs& rq,
+                     const RowsPrepArgs& rk, const ColsPrepArgs& cv, hipStream_t stream) {
+  const int parts = part == kPartQKV ? 3 : part == kPartKV ? 2 : 1;
+  const int nbk = (t.C + 31) / 32, Cpad = 32 * nbk;
+  const int64_t tokens = (int64_t)pp.B * t.ntok;
+  const RowsPrepArgs rx = flat_rows_prep(t.x, tokens, t.C, t.row_stride, pp.flush_subnormals, pp.bfloat, t.rows.codes, t.rows.exps, 0);
+  int rc = launch_rows_prep(rx, stream);
+  if (rc) return rc;
+  const LinearLayout W = linear_layout(parts * pp.H * pp.D, t.C, pp.D);
+  const unsigned char* wb = static_cast<const unsigned char*>(t.wq);
+  ProjArgs pa{};
+  pa.xc = rx.codes; pa.xs = rx.sT;
+  pa.pk = reinterpret_cast<const int8_t*>(wb + W.pk);
+  pa.pe = reinterpret_cast<const int16_t*>(wb + W.pe);
+  pa.ps = reinterpret_cast<const int16_t*>(wb + W.ps);
+  pa.gs = reinterpret_cast<const int16_t*>(wb + W.gs);
+  pa.pn = reinterpret_cast<const int16_t*>(wb + W.pn);
+  pa.pd = reinterpret_cast<const int8_t*>(wb + W.pd);
+  if (W.ps - W.pk >= ((int64_t)1 << 31) || W.total - W.pd >= ((int64_t)1 << 31))
+    return MXA_ERR_UNSUPPORTED;  // 32-bit buffer offsets
+  pa.pk_bytes = (int)(W.pe - W.pk);
+  pa.pe_bytes = (int)(W.ps - W.pe);
+  pa.pd_bytes = (int)(W.total - W.pd);
+  pa.ntb = (t.ntok + 31) / 32;
+  pa.bias = t.bias; pa.qkv_out = t.out; pa.autocast = t.autocast;
+  pa.B = pp.B; pa.N = t.ntok; pa.H = pp.H; pa.D = pp.D; pa.nbk = nbk; pa.Cpad = Cpad; pa.bfloat = pp.bfloat;
+  pa.smax = gemm_smax(nbk);
+  pa.rq = rq; pa.rk = rk; pa.cv = cv;
+  return launch_proj(pa, stream, part);
+}
+
+// Q's and K's operands and V's transposed codes: from q, k, v in one launch (scores alone: Q
+// and K), or out of the fused projections -- qkv in one pass; cross-attention's query tokens
+// -> the q operands, then its key / value tokens -> the k operands and V (two launches of
+// the projection kernel by parts)
+int attn_build_operands(const AttnCall& c, const mxa_attn_params& pp, const AttnLayout& L, int opq, int opk) {
+  const RowsPrepArgs rq = attn_rows_prep(pp, L, L.q, pp.q, pp.q_strides, pp.N, opq);
+  const RowsPrepArgs rk = attn_rows_prep(pp, L, L.k, pp.k, pp.k_strides, pp.T, opk);
+  ColsPrepArgs cv{};
+  cv.x = pp.v; cv.s0 = pp.v_strides[0]; cv.s1 = pp.v_strides[1]; cv.s2 = pp.v_strides[2];
+  cv.H = pp.H; cv.mats = (int64_t)pp.B * pp.H; cv.R = pp.T; cv.C = pp.D; cv.nb = L.ntb; cv.rpad = L.tpad;
+  cv.mbits = 8; cv.flush = pp.flush_subnormals; cv.bfloat = pp.bfloat; cv.dt = pp.dtype;
+  cv.codes_t = L.vt; cv.tb_major = 1; cv.scale = L.vs;
+  if (c.xq) {
+    const mxa_qkv_params& xq = *c.xq;
+    return launch_proj_pass(pp, kPartQKV, {xq.x, xq.x_row_stride, xq.C, pp.N, xq.wq, xq.bias, xq.qkv_out, xq.autocast_dtype, L.x},
+                            rq, rk, cv, c.stream);
+  }
+  if (c.xc) {
+    const mxa_cross_params& xc = *c.xc;
+    const int rc = launch_proj_pass(pp, kPartQ, {xc.x, xc.x_row_stride, xc.C, pp.N, xc.wq_q, xc.bias_q, xc.q_out, 0, L.x}, rq,
+                                    rk, cv, c.stream);
+    if (rc) return rc;
+    return launch_proj_pass(pp, kPartKV, {xc.cond, xc.cond_row_stride, xc.C_kv, pp.T, xc.wq_kv, xc.bias_kv, xc.kv_out, 0, L.c},
+                            rq, rk, cv, c.stream);
+  }
+  if (c.scores_only) {
+    const int rc = launch_rows_prep(rq, c.stream);
+    return rc ? rc : launch_rows_prep(rk, c.stream);
+  }
+  return launch_attn_prep(rq, rk, cv, c.stream);  // Q, K and V in one launch
+}
+
+// ELSA: hashes of MX(Q), MX(K); norms of MX(K) rows
+int attn_elsa_prep(const mxa_attn_params& pp, const AttnLayout& L, hipStream_t stream) {
+  const int64_t BH = (int64_t)pp.B * pp.H;
+  ElsaPrepArgs eq{};
+  eq.codes = L.q.codes; eq.sT = L.q.sT; eq.proj = pp.elsa_proj; eq.rows = BH * pp.N;
+  eq.D = pp.D; eq.nb = L.nbd; eq.dpad = L.dpad; eq.hash = L.q.sg;
+  const int rc = launch_elsa_prep(eq, stream);
+  if (rc) return rc;
+  ElsaPrepArgs ek = eq;
+  ek.codes = L.k.codes; ek.sT = L.k.sT; ek.rows = BH * pp.T; ek.hash = L.k.sg; ek.norm = L.knorm;
+  return launch_elsa_prep(ek, stream);
+}
+
+// the selection and finishing kernels' arguments: the call's geometry ...
+Rows2Args rows2_shape(const mxa_attn_params& pp, const AttnLayout& L) {
+  Rows2Args r2{};
+  r2.B = pp.B; r2.H = pp.H; r2.N = pp.N; r2.T = pp.T; r2.D = pp.D;
+  r2.nbd = L.nbd; r2.dpad = L.dpad; r2.ntb = L.ntb; r2.tpad = L.tpad; r2.k_top = pp.top_k ? pp.k_top : 0;
+  r2.kst = L.dpad + 16; r2.vst = L.tpad + 16;  // conflict-free b128 reads of the LDS code tables
+  return r2;
+}
+// ... and, once the workspace is known to hold the layout, its operands and outputs (direct:
+// the finishing kernel writes the proj Linear's input codes)
+int rows2_bind(Rows2Args& r2, const mxa_attn_params& pp, const AttnLayout& L, const mxa_proj_params* pj, bool direct) {
+  r2.qc = L.q.codes; r2.qop = L.q.op; r2.qz = L.q.z; r2.qsT = L.q.sT; r2.qsA = L.q.sA; r2.qsg = L.q.sg;
+  r2.kc = L.k.codes; r2.kop = L.k.op; r2.kz = L.k.z; r2.ksT = L.k.sT; r2.ksA = L.k.sA; r2.ksg = L.k.sg;
+  r2.knorm = L.knorm; r2.elsa_cos = pp.elsa_cos; r2.vt = L.vt; r2.vs = L.vs;
+  r2.bfloat = pp.bfloat; r2.flush_p = pp.flush_subnormals; r2.scale = pp.scale;
+  r2.in_dt = pp.dtype; r2.s_dt = pp.score_dtype > MXA_DT_F32 ? pp.score_dtype : pp.dtype;
+  r2.bias = pp.bias;
+  r2.bs0 = pp.bias_strides[0]; r2.bs1 = pp.bias_strides[1]; r2.bs2 = pp.bias_strides[2]; r2.bs3 = pp.bias_strides[3];
+  r2.out = pp.out; r2.os0 = pp.out_strides[0]; r2.os1 = pp.out_strides[1]; r2.os2 = pp.out_strides[2];
+  r2.idx_out = pp.idx_out; r2.true_out = pp.true_out; r2.pred_out = pp.pred_out; r2.mask_out = pp.mask_out;
+  r2.idx16 = L.idx16; r2.tail_rec = L.tail; r2.fb_flags = L.fbf;
+  if (!r2.mask_out) r2.mask_out = L.mask;  // (the layout holds one exactly when the MFMA finishing kernel runs)
+  if (direct) {
+    r2.xo_codes = L.y.codes; r2.xo_exps = L.y.exps;
+  } else if (pj) {  // fp32 (B, N, H*D) into the workspace, then the row quantizer
+    r2.out = L.yf;
+    r2.os0 = (int64_t)pp.N * pp.H * pp.D; r2.os1 = pp.D; r2.os2 = (int64_t)pp.H * pp.D;
+    r2.s_dt = MXA_DT_F32;
+    if (pp.dtype != MXA_DT_F32 || pp.score_dtype > MXA_DT_F32) return MXA_ERR_UNSUPPORTED;
+  }
+  return MXA_OK;
+}
+
+// the proj Linear on the attention's output rows (quantized first unless the finishing
+// kernel wrote the codes)
+int attn_proj_linear(const mxa_attn_params& pp, const AttnLayout& L, const mxa_proj_params& pj, bool direct,
+                     hipStream_t stream) {
+  const int C = pp.H * pp.D;
+  const int64_t tokens = (int64_t)pp.B * pp.N;
+  if (!direct) {
+    const int rc =
+        launch_rows_prep(flat_rows_prep(L.yf, tokens, C, C, pp.flush_subnormals, pp.bfloat, L.y.codes, L.y.exps, 1), stream);
+    if (rc) return rc;
+  }
+  return launch_linear_codes(L.y.codes, L.y.exps, tokens, C, pj.wq, pj.out_features, pj.bias, pj.y, pj.y_row_stride,
+                             pp.bfloat, 0, stream, true);
+}
+
+int attention_impl(const AttnCall& c) {
+  int rc = attn_validate(c);
+  if (rc) return rc;
+  mxa_attn_params pp = *c.p;
+  if (c.scores_only) {  // the selection kernel alone, with no kept keys
+    pp.top_k = pp.k_top = 0;
+    pp.idx_out = nullptr; pp.mask_out = nullptr;
   }
   const bool topk = pp.top_k != 0;
-  const bool ranked = topk || scores_only;  // the selection kernel runs
+  const bool ranked = topk || c.scores_only;  // the selection kernel runs
   const int mode = score_mode(&pp, ranked);
   if (mode == kModeElsa && (!pp.elsa_proj || pp.N != pp.T)) return MXA_ERR_ARG;  // elsa_approximation.py:126, :142
-  const AttnLayout L = attn_layout(&pp, mode, xq, pj, xc);
-  const int64_t BH = (int64_t)pp.B * pp.H;
+  const AttnLayout L = attn_layout(&pp, mode, c.xq, c.xc, c.pj, pp.workspace);
+  const int BH = (int)((int64_t)pp.B * pp.H);
+  const bool direct = c.pj && proj_codes_direct(&pp);
 
   int opq = MXA_OP_SIGN, opk = MXA_OP_SIGN;
   switch (pp.pred_mode) {
@@ -330,223 +413,44 @@ static int attention_impl(const mxa_attn_params* p, hipStream_t stream, hipEvent
   }
   const int S0 = (pp.T + 63) / 64;
   const int S = S0 <= 1 ? 1 : (S0 <= 2 ? 2 : (S0 <= 4 ? 4 : 8));
-  Rows2Args r2{};
-  r2.B = pp.B; r2.H = pp.H; r2.N = pp.N; r2.T = pp.T; r2.D = pp.D;
-  r2.nbd = L.nbd; r2.dpad = L.dpad; r2.ntb = L.ntb; r2.tpad = L.tpad; r2.k_top = topk ? pp.k_top : 0;
-  r2.kst = L.dpad + 16;  // conflict-free b128 reads of the LDS code tables
-  r2.vst = L.tpad + 16;
-  // feasibility of the path's kernels (LDS budgets)
-  int rc = scores_only ? MXA_OK : launch_rows(r2, topk, mode == kModeTrue, S, (int)BH, stream, true);
-  if (!rc && ranked) rc = launch_select(r2, mode, (int)BH, stream, true);
+  Rows2Args r2 = rows2_shape(pp, L);
+  // feasibility of the path's kernels (LDS budgets), before any pointer is bound
+  rc = c.scores_only ? MXA_OK : launch_rows(r2, topk, mode == kModeTrue, S, BH, c.stream, true);
+  if (!rc && ranked) rc = launch_select(r2, mode, BH, c.stream, true);
   if (rc) return rc;
-  if (plan) {
-    *plan = topk ? MXA_PATH_ROWS_SPLIT : MXA_PATH_ROWS_FUSED;
-    if (fin)
-      *fin = scores_only ? 0 : rows_kernel_kind(topk, r2.k_top, r2.T, r2.nbd, pj && proj_codes_direct(&pp));
+  if (c.plan) {
+    *c.plan = topk ? MXA_PATH_ROWS_SPLIT : MXA_PATH_ROWS_FUSED;
+    if (c.fin) *c.fin = c.scores_only ? 0 : rows_kernel_kind(topk, r2.k_top, r2.T, r2.nbd, direct);
     return MXA_OK;
   }
   if (!pp.workspace || pp.workspace_bytes < L.total) return MXA_ERR_WORKSPACE;
-  unsigned char* ws = static_cast<unsigned char*>(pp.workspace);
-  if (!aligned16(ws)) return MXA_ERR_ARG;
-  const bool need_op = mode == kModeOpExp || mode == kModeOpMul || mode == kModeTrueEx;
-  const bool need_sa = mode != kModeTrue && mode != kModeElsa;
+  if (!aligned16(pp.workspace)) return MXA_ERR_ARG;
 
-  RowsPrepArgs rq{};
-  rq.x = pp.q; rq.s0 = pp.q_strides[0]; rq.s1 = pp.q_strides[1]; rq.s2 = pp.q_strides[2];
-  rq.H = pp.H; rq.R = pp.N; rq.rows = BH * pp.N; rq.D = pp.D; rq.nb = L.nbd; rq.dpad = L.dpad;
-  const int64_t vpe = pp.dtype == MXA_DT_F32 ? 4 : 8;  // elements per 16 B
-  rq.vec4 = aligned16(pp.q) && (pp.q_strides[0] % vpe == 0) && (pp.q_strides[1] % vpe == 0) && (pp.q_strides[2] % vpe == 0);
-  rq.op_kind = opq; rq.flush = pp.flush_subnormals; rq.bfloat = pp.bfloat; rq.dt = (xq || xc) ? MXA_DT_F32 : pp.dtype;
-  rq.codes = reinterpret_cast<int8_t*>(ws + L.qc);
-  rq.sT = reinterpret_cast<int16_t*>(ws + L.qsT);
-  rq.op = need_op ? reinterpret_cast<int8_t*>(ws + L.qop) : nullptr;
-  rq.zind = mode == kModeTrueEx ? reinterpret_cast<int8_t*>(ws + L.qz) : nullptr;
-  rq.signs = mode == kModeExSign ? reinterpret_cast<uint32_t*>(ws + L.qsg) : nullptr;
-  rq.sA = need_sa ? reinterpret_cast<int16_t*>(ws + L.qsA) : nullptr;
-  if (ev) (void)hipEventRecord(ev[0], stream);
-
-  RowsPrepArgs rk = rq;
-  rk.x = pp.k; rk.s0 = pp.k_strides[0]; rk.s1 = pp.k_strides[1]; rk.s2 = pp.k_strides[2];
-  rk.R = pp.T; rk.rows = BH * pp.T;
-  rk.vec4 = aligned16(pp.k) && (pp.k_strides[0] % vpe == 0) && (pp.k_strides[1] % vpe == 0) && (pp.k_strides[2] % vpe == 0);
-  rk.op_kind = opk;
-  rk.codes = reinterpret_cast<int8_t*>(ws + L.kc);
-  rk.sT = reinterpret_cast<int16_t*>(ws + L.ksT);
-  rk.op = need_op ? reinterpret_cast<int8_t*>(ws + L.kop) : nullptr;
-  rk.zind = mode == kModeTrueEx ? reinterpret_cast<int8_t*>(ws + L.kz) : nullptr;
-  rk.signs = mode == kModeExSign ? reinterpret_cast<uint32_t*>(ws + L.ksg) : nullptr;
-  rk.sA = need_sa ? reinterpret_cast<int16_t*>(ws + L.ksA) : nullptr;
-  ColsPrepArgs cv{};
-  cv.x = pp.v; cv.s0 = pp.v_strides[0]; cv.s1 = pp.v_strides[1]; cv.s2 = pp.v_strides[2];
-  cv.H = pp.H; cv.mats = BH; cv.R = pp.T; cv.C = pp.D; cv.nb = L.ntb; cv.rpad = L.tpad;
-  cv.mbits = 8; cv.flush = pp.flush_subnormals; cv.bfloat = pp.bfloat; cv.dt = rq.dt;
-  cv.codes_t = reinterpret_cast<int8_t*>(ws + L.vt);
-  cv.tb_major = 1;
-  cv.scale = reinterpret_cast<int16_t*>(ws + L.vs);
-  if (xq) {
-    rc = launch_qkv_proj(pp, *xq, L, rq, rk, cv, ws, stream);
-  } else if (xc) {
-    rc = launch_cross_proj(pp, *xc, L, rq, rk, cv, ws, stream);
-  } else if (scores_only) {
-    rc = launch_rows_prep(rq, stream);
-    if (!rc) rc = launch_rows_prep(rk, stream);
-  } else {
-    rc = launch_attn_prep(rq, rk, cv, stream);  // Q, K and V in one launch
-  }
+  auto mark = [&c](int slot) { if (c.ev) (void)hipEventRecord(c.ev[slot], c.stream); };  // a stage's start
+  mark(0);
+  rc = attn_build_operands(c, pp, L, opq, opk);
+  if (!rc && mode == kModeElsa) rc = attn_elsa_prep(pp, L, c.stream);
   if (rc) return rc;
-  if (mode == kModeElsa) {  // hashes of MX(Q), MX(K); norms of MX(K) rows
-    ElsaPrepArgs eq{};
-    eq.codes = rq.codes; eq.sT = rq.sT; eq.proj = pp.elsa_proj; eq.rows = rq.rows;
-    eq.D = pp.D; eq.nb = L.nbd; eq.dpad = L.dpad;
-    eq.hash = reinterpret_cast<uint32_t*>(ws + L.qsg);
-    rc = launch_elsa_prep(eq, stream);
-    if (rc) return rc;
-    ElsaPrepArgs ek = eq;
-    ek.codes = rk.codes; ek.sT = rk.sT; ek.rows = rk.rows;
-    ek.hash = reinterpret_cast<uint32_t*>(ws + L.ksg);
-    ek.norm = reinterpret_cast<float*>(ws + L.knorm);
-    rc = launch_elsa_prep(ek, stream);
+  mark(1), mark(2), mark(3);  // stages 1 and 2 are empty: the operand builders run as stage 0
+  rc = rows2_bind(r2, pp, L, c.pj, direct);
+  if (!rc && ranked) rc = launch_select(r2, mode, BH, c.stream, false);
+  if (rc) return rc;
+  mark(4);
+  if (!c.scores_only) {
+    rc = launch_rows(r2, topk, mode == kModeTrue, S, BH, c.stream, false);
     if (rc) return rc;
   }
-  if (ev) {  // stages 1 and 2 are empty: the operand builders run as stage 0
-    (void)hipEventRecord(ev[1], stream);
-    (void)hipEventRecord(ev[2], stream);
-    (void)hipEventRecord(ev[3], stream);
-  }
-
-  r2.qc = reinterpret_cast<const int8_t*>(ws + L.qc);
-  r2.qop = reinterpret_cast<const int8_t*>(ws + L.qop);
-  r2.qz = reinterpret_cast<const int8_t*>(ws + L.qz);
-  r2.qsT = reinterpret_cast<const int16_t*>(ws + L.qsT);
-  r2.qsA = reinterpret_cast<const int16_t*>(ws + L.qsA);
-  r2.qsg = reinterpret_cast<const uint32_t*>(ws + L.qsg);
-  r2.kc = reinterpret_cast<const int8_t*>(ws + L.kc);
-  r2.kop = reinterpret_cast<const int8_t*>(ws + L.kop);
-  r2.kz = reinterpret_cast<const int8_t*>(ws + L.kz);
-  r2.ksT = reinterpret_cast<const int16_t*>(ws + L.ksT);
-  r2.ksA = reinterpret_cast<const int16_t*>(ws + L.ksA);
-  r2.ksg = reinterpret_cast<const uint32_t*>(ws + L.ksg);
-  r2.knorm = reinterpret_cast<const float*>(ws + L.knorm);
-  r2.elsa_cos = pp.elsa_cos;
-  r2.vt = reinterpret_cast<const int8_t*>(ws + L.vt);
-  r2.vs = reinterpret_cast<const int16_t*>(ws + L.vs);
-  r2.bfloat = pp.bfloat; r2.flush_p = pp.flush_subnormals; r2.scale = pp.scale;
-  r2.in_dt = pp.dtype;
-  r2.s_dt = pp.score_dtype > MXA_DT_F32 ? pp.score_dtype : pp.dtype;
-  r2.bias = pp.bias;
-  r2.bs0 = pp.bias_strides[0]; r2.bs1 = pp.bias_strides[1]; r2.bs2 = pp.bias_strides[2]; r2.bs3 = pp.bias_strides[3];
-  r2.out = pp.out; r2.os0 = pp.out_strides[0]; r2.os1 = pp.out_strides[1]; r2.os2 = pp.out_strides[2];
-  r2.idx_out = pp.idx_out; r2.true_out = pp.true_out; r2.pred_out = pp.pred_out; r2.mask_out = pp.mask_out;
-  r2.idx16 = reinterpret_cast<uint16_t*>(ws + L.idx16);
-  r2.tail_rec = reinterpret_cast<uint32_t*>(ws + L.tail);
-  r2.fb_flags = reinterpret_cast<uint32_t*>(ws + L.fbf);
-  const bool direct = pj && proj_codes_direct(&pp);
-  if (topk && !r2.mask_out && finish_qk_wanted(r2.k_top, r2.T, r2.nbd, direct))
-    r2.mask_out = reinterpret_cast<uint32_t*>(ws + L.mask);
-  if (direct) {  // the finishing kernel writes the proj's input codes
-    r2.xo_codes = reinterpret_cast<int8_t*>(ws + L.yc);
-    r2.xo_exps = reinterpret_cast<int16_t*>(ws + L.ys);
-  } else if (pj) {  // fp32 (B, N, H*D) into the workspace, then the row quantizer
-    r2.out = ws + L.yf;
-    r2.os0 = (int64_t)pp.N * pp.H * pp.D; r2.os1 = pp.D; r2.os2 = (int64_t)pp.H * pp.D;
-    r2.s_dt = MXA_DT_F32;
-    if (pp.dtype != MXA_DT_F32 || pp.score_dtype > MXA_DT_F32) return MXA_ERR_UNSUPPORTED;
-  }
-  if (ranked) {
-    rc = launch_select(r2, mode, (int)BH, stream, false);
+  mark(5);
+  if (c.pj) {
+    rc = attn_proj_linear(pp, L, *c.pj, direct, c.stream);
     if (rc) return rc;
-  }
-  if (ev) (void)hipEventRecord(ev[4], stream);
-  if (!scores_only) {
-    rc = launch_rows(r2, topk, mode == kModeTrue, S, (int)BH, stream, false);
-    if (rc) return rc;
-  }
-  if (ev) (void)hipEventRecord(ev[5], stream);
-  if (pj) {
-    const int C = pp.H * pp.D;
-    const int64_t tokens = (int64_t)pp.B * pp.N;
-    int8_t* yc = reinterpret_cast<int8_t*>(ws + L.yc);
-    int16_t* ys = reinterpret_cast<int16_t*>(ws + L.ys);
-    if (!direct) {  // (the workspace's yf is 16-B aligned)
-      rc = launch_rows_prep(flat_rows_prep(ws + L.yf, tokens, C, C, C % 4 == 0, pp.flush_subnormals, pp.bfloat, yc, ys, 1), stream);
-      if (rc) return rc;
-    }
-    rc = launch_linear_codes(yc, ys, tokens, C, pj->wq, pj->out_features, pj->bias, pj->y, pj->y_row_stride,
-                             pp.bfloat, 0, stream, true);
-    if (rc) return rc;
-    if (ev) (void)hipEventRecord(ev[6], stream);
+    mark(6);
   }
   return MXA_OK;
 }
 
-extern "C" int64_t mxa_qkv_attention_workspace_bytes(const mxa_attn_params* p, const mxa_qkv_params* xq) {
-  if (!p || !xq || p->B <= 0 || p->H <= 0 || p->N <= 0 || p->T <= 0 || p->D <= 0 || xq->C <= 0) return -1;
-  return attn_layout(p, score_mode(p, p->top_k || p->pred_out), xq).total;
-}
-
-extern "C" int mxa_qkv_attention(const mxa_attn_params* p, const mxa_qkv_params* xq, hipStream_t stream) {
-  if (!xq) return MXA_ERR_ARG;
-  return attention_impl(p, stream, nullptr, nullptr, false, xq);
-}
-
-static int timed_impl(const mxa_attn_params* p, const mxa_qkv_params* xq, hipStream_t stream, int32_t iters,
-                      float* stage_ms, const mxa_proj_params* pj);
-
-extern "C" int64_t mxa_attention_proj_workspace_bytes(const mxa_attn_params* p, const mxa_qkv_params* xq,
-                                                      const mxa_proj_params* pj) {
-  if (!p || !pj || p->B <= 0 || p->H <= 0 || p->N <= 0 || p->T <= 0 || p->D <= 0 || pj->out_features <= 0) return -1;
-  if (xq && xq->C <= 0) return -1;
-  return attn_layout(p, score_mode(p, true), xq, pj).total;
-}
-
-extern "C" int mxa_attention_proj(const mxa_attn_params* p, const mxa_qkv_params* xq, const mxa_proj_params* pj,
-                                  hipStream_t stream) {
-  if (!pj) return MXA_ERR_ARG;
-  return attention_impl(p, stream, nullptr, nullptr, false, xq, pj);
-}
-
-extern "C" int64_t mxa_cross_attention_workspace_bytes(const mxa_attn_params* p, const mxa_cross_params* xc,
-                                                       const mxa_proj_params* pj) {
-  if (!p || !xc || p->B <= 0 || p->H <= 0 || p->N <= 0 || p->T <= 0 || p->D <= 0 || xc->C <= 0 || xc->C_kv <= 0)
-    return -1;
-  if (pj && pj->out_features <= 0) return -1;
-  return attn_layout(p, score_mode(p, pj || p->top_k || p->pred_out), nullptr, pj, xc).total;
-}
-
-extern "C" int mxa_cross_attention(const mxa_attn_params* p, const mxa_cross_params* xc, const mxa_proj_params* pj,
-                                   hipStream_t stream) {
-  if (!xc) return MXA_ERR_ARG;
-  return attention_impl(p, stream, nullptr, nullptr, false, nullptr, pj, nullptr, xc);
-}
-
-extern "C" int mxa_attention_proj_timed(const mxa_attn_params* p, const mxa_qkv_params* xq, const mxa_proj_params* pj,
-                                        hipStream_t stream, int32_t iters, float* stage_ms) {
-  if (!pj) return MXA_ERR_ARG;
-  return timed_impl(p, xq, stream, iters, stage_ms, pj);
-}
-
-extern "C" int mxa_approx_scores(const mxa_attn_params* p, hipStream_t stream) {
-  return attention_impl(p, stream, nullptr, nullptr, true);
-}
-
-extern "C" int mxa_attention(const mxa_attn_params* p, hipStream_t stream) {
-  return attention_impl(p, stream, nullptr);
-}
-
-extern "C" int mxa_attention_path(const mxa_attn_params* p) {
-  int plan = -1;
-  const int rc = attention_impl(p, nullptr, nullptr, &plan);
-  return rc ? rc : plan;
-}
-
-extern "C" int mxa_attention_finish_kernel(const mxa_attn_params* p) {
-  int plan = -1, fin = -1;
-  const int rc = attention_impl(p, nullptr, nullptr, &plan, false, nullptr, nullptr, &fin);
-  return rc ? rc : fin;
-}
-
-static int timed_impl(const mxa_attn_params* p, const mxa_qkv_params* xq, hipStream_t stream, int32_t iters,
-                      float* stage_ms, const mxa_proj_params* pj) {
+int timed_impl(const mxa_attn_params* p, const mxa_qkv_params* xq, const mxa_proj_params* pj, hipStream_t stream,
+               int32_t iters, float* stage_ms) {
   if (iters <= 0 || !stage_ms) return MXA_ERR_ARG;
   const int ns = pj ? MXA_PROJ_STAGES : MXA_ATTN_STAGES, ne = ns + 1;
   std::vector<hipEvent_t> ev((size_t)iters * ne);
@@ -554,7 +458,7 @@ static int timed_impl(const mxa_attn_params* p, const mxa_qkv_params* xq, hipStr
     if (hipEventCreate(&e) != hipSuccess) return MXA_ERR_LAUNCH;
   int rc = MXA_OK;
   for (int i = 0; i < iters && rc == MXA_OK; ++i)
-    rc = attention_impl(p, stream, &ev[(size_t)i * ne], nullptr, false, xq, pj);
+    rc = attention_impl({.p = p, .stream = stream, .xq = xq, .pj = pj, .ev = &ev[(size_t)i * ne]});
   if (rc == MXA_OK && hipStreamSynchronize(stream) != hipSuccess) rc = MXA_ERR_LAUNCH;
   if (rc == MXA_OK) {
     for (int s = 0; s < ns; ++s) {
@@ -571,21 +475,109 @@ static int timed_impl(const mxa_attn_params* p, const mxa_qkv_params* xq, hipStr
   return rc;
 }
 
+}  // namespace
+
+extern "C" int mxa_abi_version(void) { return MXA_ABI_VERSION; }
+
+extern "C" const char* mxa_status_string(int status) {
+  switch (status) {
+    case MXA_OK: return "ok";
+    case MXA_ERR_ARG: return "invalid argument";
+    case MXA_ERR_UNSUPPORTED: return "unsupported configuration";
+    case MXA_ERR_LAUNCH: return "HIP kernel launch failed";
+    case MXA_ERR_WORKSPACE: return "workspace too small";
+    default: return "unknown status";
+  }
+}
+
+extern "C" int64_t mxa_attention_workspace_bytes(const mxa_attn_params* p) {
+  return attn_shape_ok(p) ? attn_workspace_total(p, nullptr, nullptr, nullptr) : -1;
+}
+
+extern "C" int64_t mxa_qkv_attention_workspace_bytes(const mxa_attn_params* p, const mxa_qkv_params* xq) {
+  if (!attn_shape_ok(p) || !xq || xq->C <= 0) return -1;
+  return attn_workspace_total(p, xq, nullptr, nullptr);
+}
+
+extern "C" int64_t mxa_attention_proj_workspace_bytes(const mxa_attn_params* p, const mxa_qkv_params* xq,
+                                                      const mxa_proj_params* pj) {
+  if (!attn_shape_ok(p) || !pj || pj->out_features <= 0 || (xq && xq->C <= 0)) return -1;
+  return attn_workspace_total(p, xq, nullptr, pj);
+}
+
+extern "C" int64_t mxa_cross_attention_workspace_bytes(const mxa_attn_params* p, const mxa_cross_params* xc,
+                                                       const mxa_proj_params* pj) {
+  if (!attn_shape_ok(p) || !xc || xc->C <= 0 || xc->C_kv <= 0 || (pj && pj->out_features <= 0)) return -1;
+  return attn_workspace_total(p, nullptr, xc, pj);
+}
+
+extern "C" int mxa_attention(const mxa_attn_params* p, hipStream_t stream) {
+  return attention_impl({.p = p, .stream = stream});
+}
+
+extern "C" int mxa_approx_scores(const mxa_attn_params* p, hipStream_t stream) {
+  return attention_impl({.p = p, .stream = stream, .scores_only = true});
+}
+
+extern "C" int mxa_qkv_attention(const mxa_attn_params* p, const mxa_qkv_params* xq, hipStream_t stream) {
+  if (!xq) return MXA_ERR_ARG;
+  return attention_impl({.p = p, .stream = stream, .xq = xq});
+}
+
+extern "C" int mxa_attention_proj(const mxa_attn_params* p, const mxa_qkv_params* xq, const mxa_proj_params* pj,
+                                  hipStream_t stream) {
+  if (!pj) return MXA_ERR_ARG;
+  return attention_impl({.p = p, .stream = stream, .xq = xq, .pj = pj});
+}
+
+extern "C" int mxa_cross_attention(const mxa_attn_params* p, const mxa_cross_params* xc, const mxa_proj_params* pj,
+                                   hipStream_t stream) {
+  if (!xc) return MXA_ERR_ARG;
+  return attention_impl({.p = p, .stream = stream, .xc = xc, .pj = pj});
+}
+
+extern "C" int mxa_attention_path(const mxa_attn_params* p) {
+  int plan = -1;
+  const int rc = attention_impl({.p = p, .plan = &plan});
+  return rc ? rc : plan;
+}
+
+extern "C" int mxa_attention_finish_kernel(const mxa_attn_params* p) {
+  int plan = -1, fin = -1;
+  const int rc = attention_impl({.p = p, .plan = &plan, .fin = &fin});
+  return rc ? rc : fin;
+}
+
 extern "C" int mxa_attention_timed(const mxa_attn_params* p, hipStream_t stream, int32_t iters, float* stage_ms) {
-  return timed_impl(p, nullptr, stream, iters, stage_ms, nullptr);
+  return timed_impl(p, nullptr, nullptr, stream, iters, stage_ms);
 }
 
 extern "C" int mxa_qkv_attention_timed(const mxa_attn_params* p, const mxa_qkv_params* xq, hipStream_t stream,
                                        int32_t iters, float* stage_ms) {
   if (!xq) return MXA_ERR_ARG;
-  return timed_impl(p, xq, stream, iters, stage_ms, nullptr);
+  return timed_impl(p, xq, nullptr, stream, iters, stage_ms);
+}
+
+extern "C" int mxa_attention_proj_timed(const mxa_attn_params* p, const mxa_qkv_params* xq, const mxa_proj_params* pj,
+                                        hipStream_t stream, int32_t iters, float* stage_ms) {
+  if (!pj) return MXA_ERR_ARG;
+  return timed_impl(p, xq, pj, stream, iters, stage_ms);
+}
+
+// mx.matmul's workspace: the MX rows along K of a, then of b's transpose (Nc rows per matrix)
+struct MatmulLayout { MxRows a, bt; };
+static MatmulLayout matmul_layout(Carver& ws, int64_t batch, int M, int K, int Nc) {
+  MatmulLayout L{};
+  L.a = carve_mx_rows(ws, batch * M, K, false);
+  L.bt = carve_mx_rows(ws, batch * Nc, K, false);
+  return L;
 }
 
 extern "C" int64_t mxa_matmul_workspace_bytes(int64_t batch, int32_t M, int32_t K, int32_t Nc) {
   if (batch <= 0 || M <= 0 || K <= 0 || Nc <= 0) return -1;
-  const int64_t nbk = (K + 31) / 32, kpad = nbk * 32;
-  return align_up(batch * M * kpad) + align_up(batch * M * nbk * 2) + align_up(batch * Nc * kpad) +
-         align_up(batch * nbk * Nc * 2);
+  Carver ws;
+  matmul_layout(ws, batch, M, K, Nc);
+  return ws.off;
 }
 
 // in2 given as b (batch, K, Nc) row-major (cols_prep: codes transposed to [Nc][kpad],
@@ -602,22 +594,18 @@ static int matmul_impl(const void* a, const void* b, bool bt_rows, void* c, int6
   if ((elem_mbits_a != 8 && elem_mbits_a != 4) || (elem_mbits_b != 8 && elem_mbits_b != 4))
     return MXA_ERR_UNSUPPORTED;
   if (!valid_bfloat(bfloat)) return MXA_ERR_ARG;
-  const int64_t need = mxa_matmul_workspace_bytes(batch, M, K, Nc);
-  if (!workspace || workspace_bytes < need) return MXA_ERR_WORKSPACE;
+  Carver ws(workspace);
+  const MatmulLayout L = matmul_layout(ws, batch, M, K, Nc);
+  if (!workspace || workspace_bytes < ws.off) return MXA_ERR_WORKSPACE;
   const int nbk = (K + 31) / 32, kpad = nbk * 32;
-  unsigned char* ws = static_cast<unsigned char*>(workspace);
-  int8_t* ac = reinterpret_cast<int8_t*>(ws);
-  int16_t* as = reinterpret_cast<int16_t*>(ws + align_up(batch * M * kpad));
-  int8_t* bt = reinterpret_cast<int8_t*>(ws + align_up(batch * M * kpad) + align_up(batch * M * nbk * 2));
-  int16_t* bsc = reinterpret_cast<int16_t*>(ws + align_up(batch * M * kpad) + align_up(batch * M * nbk * 2) +
-                                            align_up(batch * Nc * kpad));
+  int8_t *ac = L.a.codes, *bt = L.bt.codes;
+  int16_t *as = L.a.exps, *bsc = L.bt.exps;
   // MX rows along K (rows_prep): a, and b's transpose when given so
   auto rows_mx = [&](const void* x, int64_t bstride, int R, int mbits, int dt, int8_t* codes, int16_t* exps) {
     RowsPrepArgs ra{};
     ra.x = x; ra.s0 = bstride; ra.s1 = 0; ra.s2 = K; ra.H = 1; ra.R = R; ra.rows = batch * R;
     ra.D = K; ra.nb = nbk; ra.dpad = kpad;
-    const int64_t vpe = dt == MXA_DT_F32 ? 4 : 8;
-    ra.vec4 = aligned16(x) && (bstride % vpe == 0) && (K % vpe == 0);
+    ra.vec4 = may_load_16B(x, dt, bstride, 0, K);
     ra.op_kind = mbits == 8 ? MXA_OP_MXINT8 : MXA_OP_MXINT4;
     ra.flush = flush_subnormals; ra.bfloat = bfloat; ra.dt = dt;
     ra.codes = nullptr; ra.sT = nullptr; ra.op = codes; ra.sA = exps;

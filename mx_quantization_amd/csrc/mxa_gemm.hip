@@ -120,9 +120,9 @@ using namespace mxa;
 
 extern "C" int64_t mxa_linear_workspace_bytes(int64_t rows, int32_t in_features, int32_t out_features) {
   if (rows <= 0 || in_features <= 0 || out_features <= 0 || rows > INT32_MAX) return -1;
-  const int64_t nbk = (in_features + 31) / 32;
-  const int64_t rows32 = (rows + 31) / 32 * 32;  // the MFMA-ready codes hold whole 32-row blocks
-  return (rows32 * nbk * 32 + 255) / 256 * 256 + (rows * nbk * 2 + 255) / 256 * 256;
+  Carver ws;
+  carve_mx_rows(ws, rows, in_features, true);  // x as MFMA-ready codes + exponents: the whole workspace
+  return ws.off;
 }
 
 extern "C" int mxa_linear(const float* x, int64_t rows, int32_t in_features, int64_t x_row_stride, const void* wq,
@@ -139,15 +139,11 @@ extern "C" int mxa_linear(const float* x, int64_t rows, int32_t in_features, int
     return MXA_ERR_ARG;
   const int64_t need = mxa_linear_workspace_bytes(rows, in_features, out_features);
   if (!workspace || workspace_bytes < need || !aligned16(workspace)) return MXA_ERR_WORKSPACE;
-  const int nbk = (in_features + 31) / 32, Cpad = 32 * nbk;
-  unsigned char* ws = static_cast<unsigned char*>(workspace);
-  const int64_t rows32 = (rows + 31) / 32 * 32;
-  int8_t* xc = reinterpret_cast<int8_t*>(ws);
-  int16_t* xe = reinterpret_cast<int16_t*>(ws + (rows32 * Cpad + 255) / 256 * 256);
-  const RowsPrepArgs rx = flat_rows_prep(x, rows, in_features, x_row_stride, aligned16(x) && x_row_stride % 4 == 0,
-                                         flush_subnormals, bfloat, xc, xe, 1, bits);
-  int rc = launch_rows_prep(rx, stream);
+  Carver ws(workspace);
+  const MxRows xr = carve_mx_rows(ws, rows, in_features, true);
+  int rc = launch_rows_prep(
+      flat_rows_prep(x, rows, in_features, x_row_stride, flush_subnormals, bfloat, xr.codes, xr.exps, 1, bits), stream);
   if (rc) return rc;
-  return launch_linear_codes(xc, xe, rows, in_features, wq, out_features, bias, out, out_row_stride, bfloat,
+  return launch_linear_codes(xr.codes, xr.exps, rows, in_features, wq, out_features, bias, out, out_row_stride, bfloat,
                              autocast_dtype, stream, true);
 }

@@ -12,18 +12,52 @@ namespace mxa {
 inline bool aligned16(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15u) == 0; }
 // the bfloat settings of include/mxa.h: 0 / 32 (no rounding) or bfloat10 .. bfloat31
 inline bool valid_bfloat(int bfloat) { return bfloat == 0 || bfloat == 32 || (bfloat >= 10 && bfloat <= 31); }
+// may rows at ptr + i0 * s0 + i1 * s1 + i2 * s2 (elements of dtype) be read in 16-B loads?
+inline bool may_load_16B(const void* ptr, int dtype, int64_t s0, int64_t s1, int64_t s2) {
+  const int64_t vpe = dtype == MXA_DT_F32 ? 4 : 8;  // elements per 16 B
+  return aligned16(ptr) && s0 % vpe == 0 && s1 % vpe == 0 && s2 % vpe == 0;
+}
+
+// A cursor over a caller's workspace.  take<T>(count): the typed pointer at the running
+// offset, which advances by the bytes rounded up to 256; count 0 takes nothing and gives
+// nullptr (a region the call does not need).  A null base only sizes.  A workspace layout is
+// one function of a cursor and the shapes: its *_workspace_bytes function runs it on a null
+// base (the size is the final offset), the entry point on the caller's pointer.
+struct Carver {
+  uintptr_t base;
+  int64_t off = 0;
+  explicit Carver(void* workspace = nullptr) : base(reinterpret_cast<uintptr_t>(workspace)) {}
+  template <class T>
+  T* take(int64_t count) {
+    if (count <= 0) return nullptr;
+    T* ptr = base ? reinterpret_cast<T*>(base + (uintptr_t)off) : nullptr;
+    off += (count * (int64_t)sizeof(T) + 255) / 256 * 256;
+    return ptr;
+  }
+};
+// MXINT8 rows of a (rows x cols) matrix along cols: codes [rows][32 nb], block exponents
+// [rows][nb].  mfma_rows: the codes in the MX GEMM's MFMA-ready blocks of 32 whole rows
+// (RowsPrepArgs::mfma_rows)
+struct MxRows { int8_t* codes; int16_t* exps; };
+inline MxRows carve_mx_rows(Carver& ws, int64_t rows, int cols, bool mfma_rows) {
+  const int64_t nb = (cols + 31) / 32;
+  MxRows r{};
+  r.codes = ws.take<int8_t>((mfma_rows ? (rows + 31) / 32 * 32 : rows) * nb * 32);
+  r.exps = ws.take<int16_t>(rows * nb);
+  return r;
+}
+
 // RowsPrepArgs of a float32 row-major matrix (rows x cols, row_stride elements from row to
 // row) -> MXINT8 rows along its last axis: codes [rows][32 nb] (mfma_rows: in the MX GEMM's
-// MFMA-ready row blocks) and block exponents [rows][nb].  vec4: the caller's own test that x
-// may be read in 16-B loads.  elem_bits 4 (a prepared weight's header width; 0 / 8: MXINT8):
+// MFMA-ready row blocks) and block exponents [rows][nb].  elem_bits 4 (a prepared weight's header width; 0 / 8: MXINT8):
 // MXINT4 codes in [-7, 7] and the code unit's exponents es - 2 into the same two arrays (the
 // block body's op / sA outputs)
-inline RowsPrepArgs flat_rows_prep(const void* x, int64_t rows, int cols, int64_t row_stride, bool vec4, int flush,
-                                   int bfloat, int8_t* codes, int16_t* exps, int mfma_rows, int elem_bits = 0) {
+inline RowsPrepArgs flat_rows_prep(const void* x, int64_t rows, int cols, int64_t row_stride, int flush, int bfloat,
+                                   int8_t* codes, int16_t* exps, int mfma_rows, int elem_bits = 0) {
   RowsPrepArgs r{};
   r.x = x; r.s0 = 0; r.s1 = 0; r.s2 = row_stride;
   r.H = 1; r.R = rows; r.rows = rows; r.D = cols; r.nb = (cols + 31) / 32; r.dpad = 32 * r.nb;
-  r.vec4 = vec4;
+  r.vec4 = may_load_16B(x, MXA_DT_F32, 0, 0, row_stride);
   r.op_kind = MXA_OP_MXINT8; r.flush = flush; r.bfloat = bfloat; r.dt = MXA_DT_F32;
   r.codes = codes; r.sT = exps; r.mfma_rows = mfma_rows;
   if (elem_bits == 4) {

@@ -8,12 +8,6 @@
 
 namespace mxa {
 
-static int64_t al256(int64_t x) { return (x + 255) / 256 * 256; }
-// the MX rows of a (rows, cols) matrix as mxa_linear_workspace_bytes lays them out: MFMA-ready
-// codes (whole 32-row blocks), then the block exponents
-static int64_t mx_rows_codes_bytes(int64_t rows, int cols) { return al256((rows + 31) / 32 * 32 * ((cols + 31) / 32) * 32); }
-static int64_t mx_rows_exps_bytes(int64_t rows, int cols) { return al256(rows * ((cols + 31) / 32) * 2); }
-
 // does fc1 run on the digit kernel's body?  The weight's digits cover the output columns
 // (one group, or groups of a multiple of 32 columns: linear_gemm_args) and the K-blocks fit
 // the LDS next to the staging tiles.  A weight whose header this process has not seen yet
@@ -22,6 +16,17 @@ static bool mlp_fc1_fused(const void* w1, int in_f, int hidden) {
   LinearWeightHeader h{};
   if (!w1 || !linear_weight_known_header(w1, &h) || h.out_f != hidden || h.in_f != in_f) return false;
   return (h.gw == hidden || h.gw % 32 == 0) && (in_f + 31) / 32 <= (h.elem_bits == 4 ? kMlp4NbkMax : kMlpNbkMax);
+}
+
+// the workspace: x and the hidden matrix as MX rows the way mxa_linear lays its input out
+// (MFMA-ready codes, then exponents), then the unfused fallback's fp32 hidden matrix
+struct MlpLayout { MxRows x, h; float* hf; };
+static MlpLayout mlp_layout(Carver& ws, int64_t rows, int in_f, int hidden, bool fused) {
+  MlpLayout L{};
+  L.x = carve_mx_rows(ws, rows, in_f, true);
+  L.h = carve_mx_rows(ws, rows, hidden, true);
+  L.hf = ws.take<float>(fused ? 0 : rows * hidden);
+  return L;
 }
 
 template <bool PLAIN>
@@ -44,10 +49,9 @@ using namespace mxa;
 extern "C" int64_t mxa_mlp_workspace_bytes(int64_t rows, int32_t in_features, const void* w1, int32_t hidden_features,
                                            int32_t out_features) {
   if (rows <= 0 || in_features <= 0 || hidden_features <= 0 || out_features <= 0 || rows > INT32_MAX) return -1;
-  int64_t n = mx_rows_codes_bytes(rows, in_features) + mx_rows_exps_bytes(rows, in_features) +
-              mx_rows_codes_bytes(rows, hidden_features) + mx_rows_exps_bytes(rows, hidden_features);
-  if (!mlp_fc1_fused(w1, in_features, hidden_features)) n += al256(rows * hidden_features * 4);
-  return n;
+  Carver ws;
+  mlp_layout(ws, rows, in_features, hidden_features, mlp_fc1_fused(w1, in_features, hidden_features));
+  return ws.off;
 }
 
 extern "C" int mxa_mlp(const float* x, int64_t rows, int32_t in_features, int64_t x_row_stride, const void* w1,
@@ -71,17 +75,13 @@ extern "C" int mxa_mlp(const float* x, int64_t rows, int32_t in_features, int64_
   // (a Linear the tile kernel would refuse is refused whichever kernel would run it: launch_gemm_shape)
   if ((rows + 63) / 64 > 65535) return MXA_ERR_UNSUPPORTED;
 
-  unsigned char* ws = static_cast<unsigned char*>(workspace);
-  int8_t* xc = reinterpret_cast<int8_t*>(ws);
-  int16_t* xe = reinterpret_cast<int16_t*>(ws + mx_rows_codes_bytes(rows, in_features));
-  unsigned char* hb = ws + mx_rows_codes_bytes(rows, in_features) + mx_rows_exps_bytes(rows, in_features);
-  int8_t* hc = reinterpret_cast<int8_t*>(hb);
-  int16_t* he = reinterpret_cast<int16_t*>(hb + mx_rows_codes_bytes(rows, hidden_features));
-  float* hf = reinterpret_cast<float*>(hb + mx_rows_codes_bytes(rows, hidden_features) +
-                                       mx_rows_exps_bytes(rows, hidden_features));  // the fallback's fp32 hidden matrix
+  Carver ws(workspace);
+  const MlpLayout L = mlp_layout(ws, rows, in_features, hidden_features, fused);
+  int8_t *xc = L.x.codes, *hc = L.h.codes;
+  int16_t *xe = L.x.exps, *he = L.h.exps;
+  float* hf = L.hf;  // the unfused fallback's fp32 hidden matrix
 
-  const RowsPrepArgs rx = flat_rows_prep(x, rows, in_features, x_row_stride, aligned16(x) && x_row_stride % 4 == 0,
-                                         flush_subnormals, bfloat, xc, xe, 1, bits);
+  const RowsPrepArgs rx = flat_rows_prep(x, rows, in_features, x_row_stride, flush_subnormals, bfloat, xc, xe, 1, bits);
   int rc = launch_rows_prep(rx, stream);
   if (rc) return rc;
   if (fused) {
@@ -106,8 +106,7 @@ extern "C" int mxa_mlp(const float* x, int64_t rows, int32_t in_features, int64_
                          hf, act_out, n, act);
       if (hipGetLastError() != hipSuccess) return MXA_ERR_LAUNCH;
     }
-    RowsPrepArgs rh = flat_rows_prep(hf, rows, hidden_features, hidden_features, hidden_features % 4 == 0,
-                                     flush_subnormals, bfloat, hc, he, 1, bits);
+    RowsPrepArgs rh = flat_rows_prep(hf, rows, hidden_features, hidden_features, flush_subnormals, bfloat, hc, he, 1, bits);
     rh.act = 1 + act;
     rc = launch_rows_prep(rh, stream);
     if (rc) return rc;

@@ -294,7 +294,7 @@ extern "C" int mxa_linear_weight_prep_bits(const float* w, int32_t out_features,
   const LinearLayout W = linear_layout(out_features, in_features, group_width, hbits);
   unsigned char* wb = static_cast<unsigned char*>(wq);
   // (4 bits: rows_prep's MXINT4 operand -- codes in [-7, 7], exponents es - 2 -- into the raw regions)
-  const RowsPrepArgs rw = flat_rows_prep(w, out_features, in_features, in_features, aligned16(w) && in_features % 4 == 0,
+  const RowsPrepArgs rw = flat_rows_prep(w, out_features, in_features, in_features,
                                          flush_subnormals, bfloat, reinterpret_cast<int8_t*>(wb + W.rawc),
                                          reinterpret_cast<int16_t*>(wb + W.rawe), 0, hbits);
   int rc = launch_rows_prep(rw, stream);

@@ -29,6 +29,15 @@ def _f32(t: torch.Tensor, name: str) -> torch.Tensor:
     return t
 
 
+def _f32c(t: Optional[torch.Tensor], name: str) -> Optional[torch.Tensor]:
+    """None, or t as a contiguous float32 tensor (a bias, as the kernels read it)"""
+    return None if t is None else _f32(t, name).contiguous()
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return None if t is None else t.data_ptr()
+
+
 def _dt(t: torch.Tensor, name: str) -> int:
     """MXA_DT_* of a float32 / float16 / bfloat16 tensor.  The kernels read the tensor in
     its own dtype and follow the reference's dtype rules (include/mxa.h MXA_DT_*)."""
@@ -237,15 +246,13 @@ def elsa_cos_table(d: int) -> torch.Tensor:
     return torch.cos(torch.clamp(est - 0.127, min=0))
 
 
-def _attn_params(q, k, v, scale, k_top, pred_mode, top_k, approx, bias, flush_subnormals, bfloat, elsa_proj,
-                 autocast=None):
-    """autocast: None, or the torch.autocast dtype (float16 / bfloat16) under which the
-    reference's matmuls return that dtype (include/mxa.h score_dtype)."""
-    dev = require_device(q, k, v, bias, elsa_proj)
-    dt = _dt(q, "q")
-    for t, nm in ((k, "k"),) + (((v, "v"),) if v is not None else ()):
-        if t.dtype != q.dtype:
-            raise TypeError(f"{nm} must have q's dtype {q.dtype} (got {t.dtype})")
+def _attn_shape_params(dev, dtype, B, H, Nq, T, D, scale, k_top, pred_mode, top_k, approx, bias, flush_subnormals,
+                       bfloat, elsa_proj, autocast=None):
+    """(AttnParams, keep) of a call on (B, H, Nq, D) queries and T keys of torch dtype `dtype`:
+    everything but q, k, v and the outputs (the fused projections produce q, k, v inside the
+    call).  keep: tensors whose storage the call reads.  autocast: None, or the torch.autocast
+    dtype (float16 / bfloat16) under which the reference's matmuls return that dtype
+    (include/mxa.h score_dtype)."""
     sdt = 0
     if autocast is not None and autocast != torch.float32:
         if autocast not in (torch.float16, torch.bfloat16):
@@ -255,34 +262,23 @@ def _attn_params(q, k, v, scale, k_top, pred_mode, top_k, approx, bias, flush_su
         # elsa_approximation.approximation_scores adds no bias (deit main.py:120-121, DiT
         # models.py:188-189, PixArt :676-677): ranking ELSA scores plus a bias would differ
         raise ValueError("pred_mode 'ELSA' takes no bias: the reference's ELSA scores are unbiased")
-    B, H, Nq, D = q.shape
-    Bk, Hk, T, Dk = k.shape
-    if (Bk, Hk, Dk) != (B, H, D) or (v is not None and tuple(v.shape) != (B, H, T, D)):
-        raise ValueError(f"shape mismatch q{tuple(q.shape)} k{tuple(k.shape)} "
-                         f"v{None if v is None else tuple(v.shape)}")
     if top_k and not (0 < k_top <= T):
         raise ValueError(f"k={k_top} out of range for {T} keys")
     if approx and pred_mode not in N.PRED_MODES:
         raise ValueError(f"pred_mode {pred_mode!r} not supported by the fused op "
                          f"(supported: {sorted(N.PRED_MODES)})")
-    keep = []  # tensors whose storage the call reads
+    keep = []
     p = N.AttnParams()
-    p.q, p.k = q.data_ptr(), k.data_ptr()
-    p.v = v.data_ptr() if v is not None else None
-    p.q_strides[:] = _strides3(q, "q")
-    p.k_strides[:] = _strides3(k, "k")
-    if v is not None:
-        p.v_strides[:] = _strides3(v, "v")
     p.B, p.H, p.N, p.T, p.D = B, H, Nq, T, D
     p.k_top = int(k_top) if top_k else 0
     p.scale = float(torch.tensor(scale, dtype=torch.float32).item())  # torch: python scale -> fp32 operand
     p.pred_mode = N.PRED_MODES.get(pred_mode, 0)
     p.top_k, p.approx = int(bool(top_k)), int(bool(approx))
     p.flush_subnormals, p.bfloat = int(bool(flush_subnormals)), int(bfloat)
-    p.dtype, p.score_dtype = dt, sdt
+    p.dtype, p.score_dtype = N.DTYPES[dtype], sdt
     if bias is not None:
-        if bias.dtype != q.dtype:
-            raise TypeError(f"bias must have q's dtype {q.dtype} (got {bias.dtype})")
+        if bias.dtype != dtype:
+            raise TypeError(f"bias must have q's dtype {dtype} (got {bias.dtype})")
         bias4 = bias
         while bias4.dim() < 4:
             bias4 = bias4.unsqueeze(0)
@@ -305,11 +301,59 @@ def _attn_params(q, k, v, scale, k_top, pred_mode, top_k, approx, bias, flush_su
         cos = _ELSA_COS[ck]
         keep += [proj, cos]
         p.elsa_proj, p.elsa_cos = proj.data_ptr(), cos.data_ptr()
+    return p, keep
+
+
+def _attn_params(q, k, v, scale, k_top, pred_mode, top_k, approx, bias, flush_subnormals, bfloat, elsa_proj,
+                 autocast=None):
+    """(AttnParams, device, (B, H, N, T, D), keep) for q, k, v tensors (v None: the scores alone)."""
+    dev = require_device(q, k, v, bias, elsa_proj)
+    _dt(q, "q")
+    for t, nm in ((k, "k"),) + (((v, "v"),) if v is not None else ()):
+        if t.dtype != q.dtype:
+            raise TypeError(f"{nm} must have q's dtype {q.dtype} (got {t.dtype})")
+    B, H, Nq, D = q.shape
+    Bk, Hk, T, Dk = k.shape
+    if (Bk, Hk, Dk) != (B, H, D) or (v is not None and tuple(v.shape) != (B, H, T, D)):
+        raise ValueError(f"shape mismatch q{tuple(q.shape)} k{tuple(k.shape)} "
+                         f"v{None if v is None else tuple(v.shape)}")
+    p, keep = _attn_shape_params(dev, q.dtype, B, H, Nq, T, D, scale, k_top, pred_mode, top_k, approx, bias,
+                                 flush_subnormals, bfloat, elsa_proj, autocast)
+    p.q, p.k = q.data_ptr(), k.data_ptr()
+    p.q_strides[:], p.k_strides[:] = _strides3(q, "q"), _strides3(k, "k")
+    if v is not None:
+        p.v = v.data_ptr()
+        p.v_strides[:] = _strides3(v, "v")
     return p, dev, (B, H, Nq, T, D), keep
 
 
 def _out_dtype(q, autocast):
     return autocast if autocast in (torch.float16, torch.bfloat16) else q.dtype
+
+
+def _bind_out(p, out: torch.Tensor) -> torch.Tensor:
+    p.out = out.data_ptr()
+    p.out_strides[:] = (out.stride(0), out.stride(1), out.stride(2))
+    return out
+
+
+def _new_idx(p, B, H, Nq, k_top, top_k, dev):
+    """The kept indices (B, H, N, k) int64 bound to p.idx_out; None without top-k."""
+    idx = torch.empty((B, H, Nq, k_top), dtype=torch.int64, device=dev) if top_k else None
+    p.idx_out = _ptr(idx)
+    return idx
+
+
+def _call_with_workspace(size_fn, fn, name, p, *extra, dev, bad="bad attention shape"):
+    """fn(p, *extra, stream) on the stream's workspace of size_fn(p, *extra) bytes (extra: the
+    call's further parameter structs by reference, or None).  bad: the ValueError's text for a
+    negative size; None: no error here (fn refuses the call)."""
+    nbytes = size_fn(ctypes.byref(p), *extra)
+    if nbytes < 0 and bad is not None:
+        raise ValueError(bad)
+    ws = _workspace(dev, nbytes)
+    p.workspace, p.workspace_bytes = ws.data_ptr(), ws.numel()
+    check(fn(ctypes.byref(p), *extra, stream_ptr(dev)), name)
 
 
 def mx_topk_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, k_top: int = 20,
@@ -331,12 +375,10 @@ def mx_topk_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: 
         out = torch.empty((B, H, Nq, D), dtype=odt, device=dev)
     elif out.dtype != odt:
         raise TypeError(f"out must be {odt} (got {out.dtype})")
-    p.out = out.data_ptr()
-    p.out_strides[:] = (out.stride(0), out.stride(1), out.stride(2))
+    _bind_out(p, out)
     if out.stride(3) != 1:
         raise ValueError("out must be contiguous in its last axis")
-    idx = torch.empty((B, H, Nq, k_top), dtype=torch.int64, device=dev) if top_k else None
-    p.idx_out = idx.data_ptr() if idx is not None else None
+    idx = _new_idx(p, B, H, Nq, k_top, top_k, dev)
     mask = None
     if return_mask:
         if not top_k:
@@ -348,14 +390,8 @@ def mx_topk_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: 
         true_s = torch.empty((B, H, Nq, T), dtype=torch.float32, device=dev)
         pred_s = torch.full((B, H, Nq, T), float("nan"), dtype=torch.float32, device=dev)
         p.true_out, p.pred_out = true_s.data_ptr(), pred_s.data_ptr()
-    nbytes = lib().mxa_attention_workspace_bytes(ctypes.byref(p))
-    if nbytes < 0:
-        raise ValueError("bad attention shape")
-    ws = _workspace(dev, nbytes)
-    p.workspace, p.workspace_bytes = ws.data_ptr(), ws.numel()
-    check(lib().mxa_attention(ctypes.byref(p), stream_ptr(dev)), "mxa_attention")
-    res = (out, idx) + ((true_s, pred_s) if return_scores else ()) + ((mask,) if return_mask else ())
-    return res
+    _call_with_workspace(lib().mxa_attention_workspace_bytes, lib().mxa_attention, "mxa_attention", p, dev=dev)
+    return (out, idx) + ((true_s, pred_s) if return_scores else ()) + ((mask,) if return_mask else ())
 
 
 def mx_approx_scores(q: torch.Tensor, k: torch.Tensor, pred_mode: str = "ex_pred",
@@ -367,10 +403,8 @@ def mx_approx_scores(q: torch.Tensor, k: torch.Tensor, pred_mode: str = "ex_pred
                                                   flush_subnormals, bfloat, elsa_proj, autocast)
     pred = torch.empty((B, H, Nq, T), dtype=torch.float32, device=dev)
     p.pred_out = pred.data_ptr()
-    nbytes = lib().mxa_attention_workspace_bytes(ctypes.byref(p))
-    ws = _workspace(dev, nbytes)
-    p.workspace, p.workspace_bytes = ws.data_ptr(), ws.numel()
-    check(lib().mxa_approx_scores(ctypes.byref(p), stream_ptr(dev)), "mxa_approx_scores")
+    _call_with_workspace(lib().mxa_attention_workspace_bytes, lib().mxa_approx_scores, "mxa_approx_scores", p, dev=dev,
+                         bad=None)
     odt = _out_dtype(q, autocast)
     return pred if odt == torch.float32 else pred.to(odt)  # the values are exact in odt
 
@@ -402,18 +436,27 @@ class LinearWeightMX:
         self.flush, self.bfloat = bool(flush_subnormals), int(bfloat)
 
 
-def _prepared(weight, group_width: int, flush_subnormals: bool, bfloat: int, elem_bits: int = 8) -> "LinearWeightMX":
-    """elem_bits applies to a weight given as a tensor; a LinearWeightMX brings its own width
-    (an explicit non-default elem_bits must agree with it)."""
+def _prepared(weight, group_width: Optional[int] = None, flush_subnormals: bool = False, bfloat: int = 0,
+              elem_bits: int = 8) -> "LinearWeightMX":
+    """A weight tensor is prepared in groups of group_width (None: one group, its out_features)
+    at elem_bits; a LinearWeightMX brings its own groups and width (an explicit non-default
+    elem_bits must agree with it)."""
     if isinstance(weight, LinearWeightMX):
         wq = weight
         if int(elem_bits) != 8 and int(elem_bits) != wq.elem_bits:
             raise ValueError(f"the prepared weight has {wq.elem_bits}-bit elements, elem_bits={elem_bits} was asked for")
     else:
-        wq = LinearWeightMX(weight, group_width, flush_subnormals, bfloat, elem_bits)
+        wq = LinearWeightMX(weight, weight.shape[0] if group_width is None else group_width, flush_subnormals, bfloat,
+                            elem_bits)
     if (wq.flush, wq.bfloat) != (bool(flush_subnormals), int(bfloat)):
         raise ValueError("the prepared weight was quantized with other flush / bfloat settings")
     return wq
+
+
+def _rows2d(x: torch.Tensor) -> torch.Tensor:
+    """x (..., features) as 2-D rows with unit inner stride (a copy only when it has to be)"""
+    x2 = x.reshape(-1, x.shape[-1])
+    return x2 if x2.stride(-1) == 1 else x2.contiguous()
 
 
 def mx_linear(x: torch.Tensor, weight, bias: Optional[torch.Tensor] = None, flush_subnormals: bool = False,
@@ -426,28 +469,19 @@ def mx_linear(x: torch.Tensor, weight, bias: Optional[torch.Tensor] = None, flus
     prepared at (8: MXINT8, 4: MXINT4 -- x is quantized at the weight's width)."""
     dev = require_device(x, bias)
     x = _f32(x, "x")
-    wq = _prepared(weight, weight.shape[0] if not isinstance(weight, LinearWeightMX) else 1, flush_subnormals, bfloat,
-                   elem_bits)
+    wq = _prepared(weight, None, flush_subnormals, bfloat, elem_bits)
     if x.shape[-1] != wq.in_features:
         raise ValueError(f"x has {x.shape[-1]} features, the weight {wq.in_features}")
-    x2 = x.reshape(-1, x.shape[-1])
-    if x2.stride(-1) != 1:
-        x2 = x2.contiguous()
+    x2 = _rows2d(x)
     rows = x2.shape[0]
     out = torch.empty((rows, wq.out_features), dtype=torch.float32, device=dev)
     if rows == 0:
         return out.reshape(x.shape[:-1] + (wq.out_features,))
-    ac = 0
-    if autocast is not None and autocast != torch.float32:
-        ac = N.DTYPES[autocast]
-    bptr = None
-    if bias is not None:
-        bias = _f32(bias, "bias").contiguous()
-        bptr = bias.data_ptr()
-    nbytes = lib().mxa_linear_workspace_bytes(rows, wq.in_features, wq.out_features)
-    ws = _workspace(dev, nbytes)
+    ac = N.DTYPES[autocast] if autocast is not None and autocast != torch.float32 else 0
+    bias = _f32c(bias, "bias")
+    ws = _workspace(dev, lib().mxa_linear_workspace_bytes(rows, wq.in_features, wq.out_features))
     check(lib().mxa_linear(x2.data_ptr(), rows, wq.in_features, x2.stride(0), wq.buf.data_ptr(), wq.out_features,
-                           bptr, out.data_ptr(), out.stride(0), int(bool(flush_subnormals)), int(bfloat), ac,
+                           _ptr(bias), out.data_ptr(), out.stride(0), int(bool(flush_subnormals)), int(bfloat), ac,
                            ws.data_ptr(), ws.numel(), stream_ptr(dev)), "mxa_linear")
     out = out.reshape(x.shape[:-1] + (wq.out_features,))
     if ac and bias is None:  # F.linear's autocast dtype (the values are already rounded to it)
@@ -468,8 +502,8 @@ def mx_mlp(x: torch.Tensor, w1, b1: Optional[torch.Tensor], w2, b2: Optional[tor
     x = _f32(x, "x")
     if act not in N.ACTS:
         raise ValueError(f"act must be one of {sorted(N.ACTS)} (got {act!r})")
-    wq1 = _prepared(w1, w1.shape[0] if not isinstance(w1, LinearWeightMX) else 1, flush_subnormals, bfloat, elem_bits)
-    wq2 = _prepared(w2, w2.shape[0] if not isinstance(w2, LinearWeightMX) else 1, flush_subnormals, bfloat, elem_bits)
+    wq1 = _prepared(w1, None, flush_subnormals, bfloat, elem_bits)
+    wq2 = _prepared(w2, None, flush_subnormals, bfloat, elem_bits)
     if wq1.elem_bits != wq2.elem_bits:
         raise ValueError(f"w1 has {wq1.elem_bits}-bit elements, w2 {wq2.elem_bits}-bit")
     if x.shape[-1] != wq1.in_features:
@@ -477,27 +511,20 @@ def mx_mlp(x: torch.Tensor, w1, b1: Optional[torch.Tensor], w2, b2: Optional[tor
     if wq2.in_features != wq1.out_features:
         raise ValueError(f"fc2 takes {wq2.in_features} features, fc1 gives {wq1.out_features}")
     hidden, outf = wq1.out_features, wq2.out_features
-    x2 = x.reshape(-1, x.shape[-1])
-    if x2.stride(-1) != 1:
-        x2 = x2.contiguous()
+    x2 = _rows2d(x)
     rows = x2.shape[0]
     y = torch.empty((rows, outf), dtype=torch.float32, device=dev)
     pre = torch.empty((rows, hidden), dtype=torch.float32, device=dev) if return_hidden else None
     actv = torch.empty((rows, hidden), dtype=torch.float32, device=dev) if return_hidden else None
     if rows:
-        bp = [None, None]
-        for i, b in enumerate((b1, b2)):
-            if b is not None:
-                b = _f32(b, f"b{i + 1}").contiguous()
-                bp[i] = b
+        b1, b2 = _f32c(b1, "b1"), _f32c(b2, "b2")
         nbytes = lib().mxa_mlp_workspace_bytes(rows, wq1.in_features, wq1.buf.data_ptr(), hidden, outf)
         if nbytes < 0:
             raise ValueError("mxa_mlp_workspace_bytes: bad shape")
         ws = _workspace(dev, nbytes)
         check(lib().mxa_mlp(x2.data_ptr(), rows, wq1.in_features, x2.stride(0), wq1.buf.data_ptr(), hidden,
-                            bp[0].data_ptr() if bp[0] is not None else None, N.ACTS[act], wq2.buf.data_ptr(), outf,
-                            bp[1].data_ptr() if bp[1] is not None else None, y.data_ptr(), y.stride(0),
-                            pre.data_ptr() if return_hidden else None, actv.data_ptr() if return_hidden else None,
+                            _ptr(b1), N.ACTS[act], wq2.buf.data_ptr(), outf, _ptr(b2), y.data_ptr(), y.stride(0),
+                            _ptr(pre), _ptr(actv),
                             int(bool(flush_subnormals)), int(bfloat), ws.data_ptr(), ws.numel(), stream_ptr(dev)),
               "mxa_mlp")
     y = y.reshape(x.shape[:-1] + (outf,))
@@ -508,17 +535,14 @@ def mx_mlp(x: torch.Tensor, w1, b1: Optional[torch.Tensor], w2, b2: Optional[tor
 
 def _proj_params(proj_weight, proj_bias, C: int, rows: int, flush_subnormals: bool, bfloat: int, dev):
     """(ProjParams, y (rows, out_features), keep) for the proj Linear behind the attention."""
-    wp = _prepared(proj_weight, proj_weight.shape[0] if not isinstance(proj_weight, LinearWeightMX) else 1,
-                   flush_subnormals, bfloat)
+    wp = _prepared(proj_weight, None, flush_subnormals, bfloat)
     if wp.in_features != C:
         raise ValueError(f"proj weight takes {wp.in_features} features, the attention gives H*D = {C}")
     pj = N.ProjParams()
     pj.wq, pj.out_features = wp.buf.data_ptr(), wp.out_features
-    keep = [wp]
-    if proj_bias is not None:
-        pb = _f32(proj_bias, "proj_bias").contiguous()
-        keep.append(pb)
-        pj.bias = pb.data_ptr()
+    pb = _f32c(proj_bias, "proj_bias")
+    pj.bias = _ptr(pb)
+    keep = [wp, pb]
     y = torch.empty((rows, wp.out_features), dtype=torch.float32, device=dev)
     pj.y, pj.y_row_stride = y.data_ptr(), y.stride(0)
     return pj, y, keep
@@ -535,16 +559,17 @@ def mx_topk_attention_proj(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, sc
                                                   flush_subnormals, bfloat, elsa_proj)
     if p.dtype != N.DT_F32:
         raise TypeError("the fused proj takes float32 q, k, v")
-    idx = torch.empty((B, H, Nq, k_top), dtype=torch.int64, device=dev)
-    p.idx_out = idx.data_ptr()
+    idx = _new_idx(p, B, H, Nq, k_top, True, dev)
     pj, y, keep2 = _proj_params(proj_weight, proj_bias, H * D, B * Nq, flush_subnormals, bfloat, dev)
-    nbytes = lib().mxa_attention_proj_workspace_bytes(ctypes.byref(p), None, ctypes.byref(pj))
-    if nbytes < 0:
-        raise ValueError("bad attention shape")
-    ws = _workspace(dev, nbytes)
-    p.workspace, p.workspace_bytes = ws.data_ptr(), ws.numel()
-    check(lib().mxa_attention_proj(ctypes.byref(p), None, ctypes.byref(pj), stream_ptr(dev)), "mxa_attention_proj")
+    _call_with_workspace(lib().mxa_attention_proj_workspace_bytes, lib().mxa_attention_proj, "mxa_attention_proj", p,
+                         None, ctypes.byref(pj), dev=dev)
     return y.reshape(B, Nq, -1), idx
+
+
+def _check_fits(wq: "LinearWeightMX", name: str, in_features: int, D: int, out_features: int, want: str):
+    """a fused projection's prepared weight: its features, head-dim groups and rows"""
+    if wq.in_features != in_features or wq.group_width != D or wq.out_features != out_features:
+        raise ValueError(f"{name} ({wq.out_features}, {wq.in_features}) / group {wq.group_width} does not fit {want}")
 
 
 def mx_qkv_attention(x: torch.Tensor, weight, bias: Optional[torch.Tensor], num_heads: int, scale: float,
@@ -559,75 +584,51 @@ def mx_qkv_attention(x: torch.Tensor, weight, bias: Optional[torch.Tensor], num_
     product is rounded to it before the fp32 bias add, and the attention's matmuls return
     it (the output is of that dtype)."""
     dev = require_device(x, bias, elsa_proj)
-    x = _f32(x, "x")
-    if x.dim() != 3 or x.stride(2) != 1:
-        raise ValueError("x must be (B, N, C) with contiguous C")
+    xs = _token_rows(x, "x", "N")
     B, Ntok, C = x.shape
     out_f = weight.out_features if isinstance(weight, LinearWeightMX) else weight.shape[0]
     if out_f % (3 * num_heads):
         raise ValueError(f"weight rows {out_f} are not 3 * heads * head_dim")
     D = out_f // (3 * num_heads)
-    wq = weight if isinstance(weight, LinearWeightMX) else LinearWeightMX(weight, D, flush_subnormals, bfloat)
-    if wq.in_features != C or wq.group_width != D:
-        raise ValueError(f"weight ({wq.out_features}, {wq.in_features}) / group {wq.group_width} does not fit "
-                         f"x C={C}, heads={num_heads}")
-    if (wq.flush, wq.bfloat) != (bool(flush_subnormals), int(bfloat)):
-        raise ValueError("the prepared weight was quantized with other flush / bfloat settings")
+    wq = _prepared(weight, D, flush_subnormals, bfloat)
+    _check_fits(wq, "weight", C, D, out_f, f"x C={C}, heads={num_heads}")
     if top_k and not (0 < k_top <= Ntok):
         raise ValueError(f"k={k_top} out of range for {Ntok} keys")
     if approx and top_k and pred_mode not in N.PRED_MODES:
         raise ValueError(f"pred_mode {pred_mode!r} not supported")
-    # q / k / v are produced inside the call: stand-in views carry the shapes only
-    shape_q = torch.empty((D,), device=dev).as_strided((B, num_heads, Ntok, D), (0, 0, 0, 1))
-    p, _, _, keep = _attn_params(shape_q, shape_q, shape_q, scale, k_top, pred_mode, top_k, approx and top_k, None,
-                                 flush_subnormals, bfloat, elsa_proj, autocast)
-    p.q = p.k = p.v = None
-    out = torch.empty((B, num_heads, Ntok, D), dtype=_out_dtype(x, autocast), device=dev)
-    p.out = out.data_ptr()
-    p.out_strides[:] = (out.stride(0), out.stride(1), out.stride(2))
-    idx = torch.empty((B, num_heads, Ntok, k_top), dtype=torch.int64, device=dev) if top_k else None
-    p.idx_out = idx.data_ptr() if idx is not None else None
+    # q / k / v are produced inside the call
+    p, keep = _attn_shape_params(dev, torch.float32, B, num_heads, Ntok, Ntok, D, scale, k_top, pred_mode, top_k,
+                                 approx and top_k, None, flush_subnormals, bfloat, elsa_proj, autocast)
+    out = _bind_out(p, torch.empty((B, num_heads, Ntok, D), dtype=_out_dtype(x, autocast), device=dev))
+    idx = _new_idx(p, B, num_heads, Ntok, k_top, top_k, dev)
     xp = N.QkvParams()
-    xp.x, xp.x_row_stride, xp.C, xp.wq = x.data_ptr(), x.stride(1), C, wq.buf.data_ptr()
+    xp.x, xp.x_row_stride, xp.C, xp.wq = x.data_ptr(), xs, C, wq.buf.data_ptr()
     xp.autocast_dtype = p.score_dtype
-    if B > 1 and x.stride(0) != Ntok * x.stride(1):
-        raise ValueError("x rows must be evenly strided over (B, N)")
-    if bias is not None:
-        bias = _f32(bias, "bias").contiguous()
-        xp.bias = bias.data_ptr()
+    bias = _f32c(bias, "bias")
     qkv = torch.empty((B, Ntok, wq.out_features), dtype=torch.float32, device=dev) if return_qkv else None
-    xp.qkv_out = qkv.data_ptr() if return_qkv else None
+    xp.bias, xp.qkv_out = _ptr(bias), _ptr(qkv)
     if proj_weight is not None:
         # ... then the proj mx.Linear on the attention output (mxa_attention_proj): (y, idx[, qkv])
         if not top_k or autocast not in (None, torch.float32):
             raise ValueError("the fused proj runs on the float32 top-k path")
         pj, y, keep2 = _proj_params(proj_weight, proj_bias, num_heads * D, B * Ntok, flush_subnormals, bfloat, dev)
         p.out = None
-        nbytes = lib().mxa_attention_proj_workspace_bytes(ctypes.byref(p), ctypes.byref(xp), ctypes.byref(pj))
-        if nbytes < 0:
-            raise ValueError("bad shape")
-        ws = _workspace(dev, nbytes)
-        p.workspace, p.workspace_bytes = ws.data_ptr(), ws.numel()
-        check(lib().mxa_attention_proj(ctypes.byref(p), ctypes.byref(xp), ctypes.byref(pj), stream_ptr(dev)),
-              "mxa_attention_proj")
+        _call_with_workspace(lib().mxa_attention_proj_workspace_bytes, lib().mxa_attention_proj, "mxa_attention_proj", p,
+                             ctypes.byref(xp), ctypes.byref(pj), dev=dev, bad="bad shape")
         y = y.reshape(B, Ntok, -1)
         return (y, idx, qkv) if return_qkv else (y, idx)
-    nbytes = lib().mxa_qkv_attention_workspace_bytes(ctypes.byref(p), ctypes.byref(xp))
-    if nbytes < 0:
-        raise ValueError("bad shape")
-    ws = _workspace(dev, nbytes)
-    p.workspace, p.workspace_bytes = ws.data_ptr(), ws.numel()
-    check(lib().mxa_qkv_attention(ctypes.byref(p), ctypes.byref(xp), stream_ptr(dev)), "mxa_qkv_attention")
+    _call_with_workspace(lib().mxa_qkv_attention_workspace_bytes, lib().mxa_qkv_attention, "mxa_qkv_attention", p,
+                         ctypes.byref(xp), dev=dev, bad="bad shape")
     return (out, idx, qkv) if return_qkv else (out, idx)
 
 
-def _token_rows(t: torch.Tensor, name: str):
+def _token_rows(t: torch.Tensor, name: str, rows: str = "rows"):
     """(B, rows, C) float32 tokens with contiguous C and evenly strided rows -> the row stride"""
     t = _f32(t, name)
     if t.dim() != 3 or t.stride(2) != 1:
-        raise ValueError(f"{name} must be (B, rows, C) with contiguous C")
+        raise ValueError(f"{name} must be (B, {rows}, C) with contiguous C")
     if t.shape[0] > 1 and t.stride(0) != t.shape[1] * t.stride(1):
-        raise ValueError(f"{name} rows must be evenly strided over (B, rows)")
+        raise ValueError(f"{name} rows must be evenly strided over (B, {rows})")
     return t.stride(1)
 
 
@@ -656,33 +657,20 @@ def mx_cross_attention(x: torch.Tensor, cond: torch.Tensor, q_weight, q_bias: Op
     D = HD // num_heads
     wq = _prepared(q_weight, D, flush_subnormals, bfloat)
     wkv = _prepared(kv_weight, D, flush_subnormals, bfloat)
-    if wq.in_features != C or wq.group_width != D:
-        raise ValueError(f"q weight ({wq.out_features}, {wq.in_features}) / group {wq.group_width} does not fit "
-                         f"x C={C}, heads={num_heads}")
-    if wkv.out_features != 2 * HD or wkv.in_features != Ckv or wkv.group_width != D:
-        raise ValueError(f"kv weight ({wkv.out_features}, {wkv.in_features}) / group {wkv.group_width} does not fit "
-                         f"cond C_kv={Ckv}, 2 * heads * head_dim = {2 * HD}")
+    _check_fits(wq, "q weight", C, D, HD, f"x C={C}, heads={num_heads}")
+    _check_fits(wkv, "kv weight", Ckv, D, 2 * HD, f"cond C_kv={Ckv}, 2 * heads * head_dim = {2 * HD}")
     if approx and top_k and pred_mode not in N.PRED_MODES:
         raise ValueError(f"pred_mode {pred_mode!r} not supported")
-    # q / k / v are produced inside the call: stand-in views carry the shapes only
-    stand = torch.empty((D,), device=dev)
-    shape_q = stand.as_strided((B, num_heads, Ntok, D), (0, 0, 0, 1))
-    shape_k = stand.as_strided((B, num_heads, T, D), (0, 0, 0, 1))
-    p, _, _, keep = _attn_params(shape_q, shape_k, shape_k, scale, k_top, pred_mode, top_k, approx and top_k, bias,
-                                 flush_subnormals, bfloat, None)
-    p.q = p.k = p.v = None
-    idx = torch.empty((B, num_heads, Ntok, k_top), dtype=torch.int64, device=dev) if top_k else None
-    p.idx_out = idx.data_ptr() if idx is not None else None
+    # q / k / v are produced inside the call
+    p, keep = _attn_shape_params(dev, torch.float32, B, num_heads, Ntok, T, D, scale, k_top, pred_mode, top_k,
+                                 approx and top_k, bias, flush_subnormals, bfloat, None)
+    idx = _new_idx(p, B, num_heads, Ntok, k_top, top_k, dev)
     xc = N.CrossParams()
     xc.x, xc.x_row_stride, xc.C = x.data_ptr(), xs, C
     xc.cond, xc.cond_row_stride, xc.C_kv = cond.data_ptr(), cs, Ckv
     xc.wq_q, xc.wq_kv = wq.buf.data_ptr(), wkv.buf.data_ptr()
-    if q_bias is not None:
-        q_bias = _f32(q_bias, "q_bias").contiguous()
-        xc.bias_q = q_bias.data_ptr()
-    if kv_bias is not None:
-        kv_bias = _f32(kv_bias, "kv_bias").contiguous()
-        xc.bias_kv = kv_bias.data_ptr()
+    q_bias, kv_bias = _f32c(q_bias, "q_bias"), _f32c(kv_bias, "kv_bias")
+    xc.bias_q, xc.bias_kv = _ptr(q_bias), _ptr(kv_bias)
     qo = kvo = None
     if return_proj:
         qo = torch.empty((B, Ntok, HD), dtype=torch.float32, device=dev)
@@ -695,16 +683,9 @@ def mx_cross_attention(x: torch.Tensor, cond: torch.Tensor, q_weight, q_bias: Op
         pj, y, keep2 = _proj_params(proj_weight, proj_bias, HD, B * Ntok, flush_subnormals, bfloat, dev)
         res = y.reshape(B, Ntok, -1)
     else:
-        res = torch.empty((B, num_heads, Ntok, D), dtype=torch.float32, device=dev)
-        p.out = res.data_ptr()
-        p.out_strides[:] = (res.stride(0), res.stride(1), res.stride(2))
-    pjp = ctypes.byref(pj) if pj is not None else None
-    nbytes = lib().mxa_cross_attention_workspace_bytes(ctypes.byref(p), ctypes.byref(xc), pjp)
-    if nbytes < 0:
-        raise ValueError("bad shape")
-    ws = _workspace(dev, nbytes)
-    p.workspace, p.workspace_bytes = ws.data_ptr(), ws.numel()
-    check(lib().mxa_cross_attention(ctypes.byref(p), ctypes.byref(xc), pjp, stream_ptr(dev)), "mxa_cross_attention")
+        res = _bind_out(p, torch.empty((B, num_heads, Ntok, D), dtype=torch.float32, device=dev))
+    _call_with_workspace(lib().mxa_cross_attention_workspace_bytes, lib().mxa_cross_attention, "mxa_cross_attention", p,
+                         ctypes.byref(xc), ctypes.byref(pj) if pj is not None else None, dev=dev, bad="bad shape")
     return (res, idx, qo, kvo) if return_proj else (res, idx)
 
 

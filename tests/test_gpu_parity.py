@@ -953,3 +953,93 @@ def test_analysis_hooks_on_device_tensors(M):
     _, gidx = M.mx_topk_attention(dev(dt["q"]), dev(dt["k"]), dev(dt["v"]), float(dt["scale"]), k_top=20)
     assert A.total_chosen_k(gidx) == pytest.approx(A.total_chosen_k(torch.from_numpy(dt["ex_pred_k20/idx"])),
                                                    rel=1e-12)
+
+
+# ------------------------------------------------------------------ exact-size workspaces
+class _ExactWorkspace:
+    """Stands in for ops._workspace: the call's workspace is exactly the bytes its
+    *_workspace_bytes function reported, at the front of a buffer whose next 4096 bytes hold
+    0xA5 (ops._workspace itself never hands out less than 1 MB, so a region carved past the
+    reported size would go unnoticed)."""
+    TAIL = 4096
+
+    def __init__(self):
+        self.bufs = []
+
+    def __call__(self, device, nbytes):
+        assert nbytes > 0
+        buf = torch.full((nbytes + self.TAIL,), 0xA5, dtype=torch.uint8, device=device)
+        self.bufs.append((buf, nbytes))
+        return buf[:nbytes]
+
+    def check(self, what):
+        torch.cuda.synchronize()
+        assert self.bufs, f"{what}: the call took no workspace"
+        for buf, nbytes in self.bufs:
+            assert bool((buf[nbytes:] == 0xA5).all()), f"{what}: wrote past its {nbytes}-byte workspace"
+
+
+def _exact_ws_cases(M):
+    """{name: call} -- each call returns the tuple of tensors (or None) to compare."""
+    rng = np.random.default_rng(2024)
+    rnd = lambda *s, w=1.0: dev(rng.standard_normal(s, dtype=np.float32) * np.float32(w))
+    q40, k40, v40 = rnd(2, 2, 40, 64), rnd(2, 2, 40, 64), rnd(2, 2, 40, 64)
+    q96, k96, v96 = rnd(2, 2, 96, 64), rnd(2, 2, 96, 64), rnd(2, 2, 96, 64)
+    from mx_quantization_amd.funcs import _create_structured_orthogonal_matrix
+    torch.manual_seed(64)
+    eproj = _create_structured_orthogonal_matrix(64).cuda()
+    x = rnd(2, 40, 96)
+    w64, w48 = M.LinearWeightMX(rnd(3 * 128, 96, w=0.05), 64), M.LinearWeightMX(rnd(3 * 96, 96, w=0.05), 48)
+    b64 = rnd(3 * 128)
+    p64, p48, pb = rnd(80, 128, w=0.05), rnd(80, 96, w=0.05), rnd(80)
+    xq, cond = rnd(2, 45, 96), rnd(2, 70, 160)
+    wcq, wckv = M.LinearWeightMX(rnd(96, 96, w=0.05), 48), M.LinearWeightMX(rnd(192, 160, w=0.05), 48)
+    cbias = rnd(2, 1, 45, 70)
+    a, b = rnd(3, 45, 70), rnd(3, 70, 33)
+    xm, b1, b2 = rnd(65, 128), rnd(96), rnd(64)
+    w1, w2 = rnd(96, 128, w=0.05), rnd(64, 96, w=0.05)
+    w1_fused, w1_unfused, w2q = M.LinearWeightMX(w1, 96), M.LinearWeightMX(w1, 48), M.LinearWeightMX(w2, 64)
+    return {
+        "ex_pred_topk": lambda: M.mx_topk_attention(q40, k40, v40, 0.125, k_top=7),
+        "ex_pred_ws_mask": lambda: M.mx_topk_attention(q96, k96, v96, 0.125, k_top=70),
+        "true_ex": lambda: M.mx_topk_attention(q40, k40, v40, 0.125, k_top=7, pred_mode="true_ex"),
+        "elsa": lambda: M.mx_topk_attention(q40, k40, v40, 0.125, k_top=7, pred_mode="ELSA", elsa_proj=eproj),
+        "dense": lambda: M.mx_topk_attention(q40, k40, v40, 0.125, top_k=False),
+        "scores_only": lambda: (M.mx_approx_scores(q40, k40, pred_mode="ex_pred"),),
+        "qkv": lambda: M.mx_qkv_attention(x, w64, b64, 2, 0.125, k_top=7),
+        "qkv_proj_codes_direct": lambda: M.mx_qkv_attention(x, w64, b64, 2, 0.125, k_top=7, proj_weight=p64, proj_bias=pb),
+        "qkv_proj_fp32_copy": lambda: M.mx_qkv_attention(x, w48, None, 2, 48 ** -0.5, k_top=7, proj_weight=p48, proj_bias=pb),
+        "cross": lambda: M.mx_cross_attention(xq, cond, wcq, None, wckv, None, 2, 48 ** -0.5, k_top=7, bias=cbias),
+        "cross_proj": lambda: M.mx_cross_attention(xq, cond, wcq, None, wckv, None, 2, 48 ** -0.5, k_top=7, bias=cbias,
+                                                   proj_weight=p48, proj_bias=pb),
+        "matmul": lambda: (M.mx_matmul(a, b),),
+        "mlp_fused": lambda: (M.mx_mlp(xm, w1_fused, b1, w2q, b2),),
+        "mlp_unfused": lambda: (M.mx_mlp(xm, w1_unfused, b1, w2q, b2),),
+    }
+
+
+def test_attention_exact_workspace(M, monkeypatch):
+    """Every workspace-taking entry point with a workspace of exactly its *_workspace_bytes:
+    nothing is written past it, and the results are bitwise those of the same call with the
+    usual roomy workspace.  One case per region that can come last in a layout (tail records
+    and flags, the workspace mask, zero indicators, ELSA's key norms, the fused projections'
+    token codes, the proj Linear's codes with and without its fp32 copy, the matmul's and the
+    MLP's regions, fused and unfused fc1)."""
+    import mx_quantization_amd.ops as ops
+    cases = _exact_ws_cases(M)
+    roomy = {name: call() for name, call in cases.items()}
+    torch.cuda.synchronize()
+    sizes = {}
+    for name, call in cases.items():
+        guard = _ExactWorkspace()
+        monkeypatch.setattr(ops, "_workspace", guard)
+        got = call()
+        guard.check(name)
+        sizes[name] = guard.bufs[0][1]
+        assert len(got) == len(roomy[name])
+        for i, (g, w) in enumerate(zip(got, roomy[name])):
+            assert (g is None) == (w is None), (name, i)
+            if g is not None:
+                same(host(g.float()), host(w.float()), f"{name}[{i}] exact vs roomy workspace")
+    assert sizes["mlp_unfused"] > sizes["mlp_fused"]          # the fallback's fp32 hidden matrix
+    assert sizes["qkv_proj_fp32_copy"] > sizes["qkv"]
