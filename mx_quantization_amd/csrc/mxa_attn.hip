@@ -655,11 +655,11 @@ extern "C" int mxa_matmul_bt(const void* a, const void* bt, void* c, int64_t bat
 extern "C" int mxa_selftest_mfma32(const int8_t* a, const int8_t* b, int32_t* c, hipStream_t stream) {
   if (!a || !b || !c) return MXA_ERR_ARG;
   hipLaunchKernelGGL(selftest_mfma32_kernel, dim3(1), dim3(64), 0, stream, a, b, c);
-  return hipGetLastError() == hipSuccess ? MXA_OK : MXA_ERR_LAUNCH;
+  return launch_status();
 }
 
 extern "C" int mxa_selftest_mfma(const int8_t* a, const int8_t* b, int32_t* c, hipStream_t stream) {
   if (!a || !b || !c) return MXA_ERR_ARG;
   hipLaunchKernelGGL(selftest_mfma_kernel, dim3(1), dim3(64), 0, stream, a, b, c);
-  return hipGetLastError() == hipSuccess ? MXA_OK : MXA_ERR_LAUNCH;
+  return launch_status();
 }

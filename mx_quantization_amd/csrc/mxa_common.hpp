@@ -167,6 +167,21 @@ __device__ __forceinline__ int scale_exponent_dt(uint32_t maxbits, int scale_ema
   return e < -scale_emax ? -scale_emax : e;
 }
 
+// The MX block rule (mx_ops.py:276-300), from the bits of the block's max |x|: the scale
+// exponent es (kExpNaN for a NaN block), the NaN flag, and whether flush_subnormals zeroes the
+// block's elements (its raw shared exponent is not above -127).  Every quantizer and operand
+// builder of mxa_quant.hip and mxa_prep.hpp takes the three from here.  (The finishing and
+// dense kernels write the same lines out for their P blocks: p_block, mxa_finish.hpp.)
+struct BlkScale {
+  int es;
+  bool nan, flush;
+};
+__device__ __forceinline__ BlkScale blk_scale(uint32_t maxbits, int scale_emax, int dt, int flush) {
+  int e_raw;
+  const int es = scale_exponent_dt(maxbits, scale_emax, dt, &e_raw);
+  return {es, es == kExpNaN, flush && !(e_raw != kExpNaN && e_raw > -127)};
+}
+
 // Element rounding of x / 2^es * 2^(mbits-2) (elemwise_ops.py:45-65, :150-164);
 // returns the integer code as float, clamped to +-(2^(mbits-1)-1).
 // es is finite and in [-127, 127], so 2^-es is an exact float and x * 2^-es is

@@ -47,7 +47,7 @@ static int launch_dense_s(const Rows2Args& ra0, int BH, hipStream_t stream, bool
   ra.rows_per_wg = (ra.N + chunks - 1) / chunks;
   const unsigned gy = (unsigned)((ra.N + ra.rows_per_wg - 1) / ra.rows_per_wg);
   hipLaunchKernelGGL(dense_rows_kernel<S>, dim3((unsigned)BH, gy), dim3(64 * ra.waves), lds, stream, ra);
-  return hipGetLastError() == hipSuccess ? MXA_OK : MXA_ERR_LAUNCH;
+  return launch_status();
 }
 
 #endif  // MXA_FIN_PART == 0

@@ -168,8 +168,8 @@ __device__ __forceinline__ RowsPrepArgs xo_rows_args(int8_t* codes, int16_t* exp
 // ... and the 16 values xv of 32-block blk of output row orow (half sub, column c0) into
 // them.  Two consecutive lanes per block; every lane calls it (on: its row and block exist)
 __device__ __forceinline__ void xo_block(const RowsPrepArgs& ro, int64_t orow, int blk, int sub, int c0, float* xv, bool on) {
-  if (rows_prep_plain(ro)) rows_prep_block_plain<16, kF32>(ro, orow, blk, sub, c0, xv, on);
-  else rows_prep_block<16>(ro, orow, blk, sub, c0, xv, on);
+  if (rows_prep_plain(ro)) rows_prep_block_plain<kF32>(ro, orow, blk, sub, c0, xv, on);
+  else rows_prep_block(ro, orow, blk, sub, c0, xv, on);
 }
 
 // ---- the 32-row kernel ------------------------------------------------------------------

@@ -33,7 +33,7 @@ static int launch_gemm_shape(const GemmArgs& ga, int64_t batch, hipStream_t stre
     const dim3 grid((unsigned)((ga.M + 31) / 32));
     if (bits4) hipLaunchKernelGGL(mx_gemm_dig4_kernel<PLAIN>, grid, dim3(256), dl, stream, ga);
     else hipLaunchKernelGGL(mx_gemm_dig_kernel<PLAIN>, grid, dim3(256), dl, stream, ga);
-    return hipGetLastError() == hipSuccess ? MXA_OK : MXA_ERR_LAUNCH;
+    return launch_status();
   }
   const void* gk = reinterpret_cast<const void*>(&mx_gemm_kernel<PLAIN, SH>);
   if (hipFuncSetAttribute(gk, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return MXA_ERR_LAUNCH;
@@ -46,7 +46,7 @@ static int launch_gemm_shape(const GemmArgs& ga, int64_t batch, hipStream_t stre
     gs.c = static_cast<unsigned char*>(ga.c) + b0 * ga.c_bat * esz;
     const int64_t nb = std::min<int64_t>(65535, batch - b0);
     hipLaunchKernelGGL((mx_gemm_kernel<PLAIN, SH>), dim3((unsigned)gx, (unsigned)gy, (unsigned)nb), dim3(256), lds, stream, gs);
-    if (hipGetLastError() != hipSuccess) return MXA_ERR_LAUNCH;
+    if (launch_status() != MXA_OK) return MXA_ERR_LAUNCH;
   }
   return MXA_OK;
 }

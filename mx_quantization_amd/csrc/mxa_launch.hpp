@@ -9,6 +9,8 @@
 
 namespace mxa {
 
+// what a launcher returns after its launches: did the runtime take them?
+inline int launch_status() { return hipGetLastError() == hipSuccess ? MXA_OK : MXA_ERR_LAUNCH; }
 inline bool aligned16(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15u) == 0; }
 // the bfloat settings of include/mxa.h: 0 / 32 (no rounding) or bfloat10 .. bfloat31
 inline bool valid_bfloat(int bfloat) { return bfloat == 0 || bfloat == 32 || (bfloat >= 10 && bfloat <= 31); }
@@ -191,7 +193,7 @@ inline int launch_finish_tiles(const Rows2Args& ra, int BH, size_t lds, hipStrea
     return MXA_ERR_LAUNCH;
   const unsigned gy = (unsigned)((ra.N + ra.rows_per_wg - 1) / ra.rows_per_wg);
   hipLaunchKernelGGL(Kernel, dim3((unsigned)BH, gy), dim3(64 * ra.waves), lds, stream, ra);
-  return hipGetLastError() == hipSuccess ? MXA_OK : MXA_ERR_LAUNCH;
+  return launch_status();
 }
 
 // the MFMA finishing kernel's launches (mxa_fin_qk.hip): float32 inputs and scores (x0), float16 / bfloat16 (x1)

@@ -39,7 +39,7 @@ static int launch_mlp_fc1(const GemmArgs& ga, const MlpEpi<PLAIN>& e, bool bits4
   const dim3 grid((unsigned)((ga.M + 31) / 32));
   if (bits4) hipLaunchKernelGGL(mx_mlp_fc1_4_kernel<PLAIN>, grid, dim3(256), lds, stream, ga, e4);
   else hipLaunchKernelGGL(mx_mlp_fc1_kernel<PLAIN>, grid, dim3(256), lds, stream, ga, e);
-  return hipGetLastError() == hipSuccess ? MXA_OK : MXA_ERR_LAUNCH;
+  return launch_status();
 }
 
 }  // namespace mxa
@@ -104,7 +104,7 @@ extern "C" int mxa_mlp(const float* x, int64_t rows, int32_t in_features, int64_
     if (act_out) {
       hipLaunchKernelGGL(mlp_act_kernel, dim3((unsigned)std::min<int64_t>((n + 255) / 256, 65536)), dim3(256), 0, stream,
                          hf, act_out, n, act);
-      if (hipGetLastError() != hipSuccess) return MXA_ERR_LAUNCH;
+      if (launch_status() != MXA_OK) return MXA_ERR_LAUNCH;
     }
     RowsPrepArgs rh = flat_rows_prep(hf, rows, hidden_features, hidden_features, flush_subnormals, bfloat, hc, he, 1, bits);
     rh.act = 1 + act;

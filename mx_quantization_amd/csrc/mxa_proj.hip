@@ -180,7 +180,7 @@ static int launch_proj_kernel(const ProjArgs& pa, hipStream_t stream) {
   const int ng = (pa.H + p.hpg - 1) / p.hpg;
   hipLaunchKernelGGL(Kernel, dim3((unsigned)((pa.N + 31) / 32), (unsigned)pa.B, (unsigned)ng), dim3(kThreads), lds,
                      stream, p);
-  return hipGetLastError() == hipSuccess ? MXA_OK : MXA_ERR_LAUNCH;
+  return launch_status();
 }
 
 template <int NBD, bool PLAIN>
@@ -305,7 +305,7 @@ extern "C" int mxa_linear_weight_prep_bits(const float* w, int32_t out_features,
   hipLaunchKernelGGL(linear_pack_kernel, dim3((unsigned)((pcols * W.nbk + 255) / 256)), dim3(256), 0, stream,
                      rawc, rawe, out_features, group_width, W.NB32, W.nbk, W.Cpad, pcols,
                      reinterpret_cast<int8_t*>(wb + W.pk), reinterpret_cast<int16_t*>(wb + W.pe));
-  if (hipGetLastError() != hipSuccess) return MXA_ERR_LAUNCH;
+  if (launch_status() != MXA_OK) return MXA_ERR_LAUNCH;
   hipLaunchKernelGGL(linear_stats_kernel, dim3((unsigned)((pcols + 255) / 256)), dim3(256), 0, stream,
                      reinterpret_cast<const int16_t*>(wb + W.pe), pcols, W.nbk, reinterpret_cast<int16_t*>(wb + W.ps),
                      reinterpret_cast<int16_t*>(wb + W.pn));
@@ -325,7 +325,7 @@ extern "C" int mxa_linear_weight_prep_bits(const float* w, int32_t out_features,
       linear_weight_header(out_features, in_features, group_width, flush_subnormals, bfloat, hbits);
   hipLaunchKernelGGL(linear_header_kernel, dim3(1), dim3(64), 0, stream, reinterpret_cast<LinearWeightHeader*>(wb + W.hdr),
                      h);
-  if (hipGetLastError() != hipSuccess) return MXA_ERR_LAUNCH;
+  if (launch_status() != MXA_OK) return MXA_ERR_LAUNCH;
   linear_weight_note(wq, h);
   return MXA_OK;
 }

@@ -443,10 +443,10 @@ __device__ __forceinline__ void proj_block(const ProjArgs& a, int tb, int b, int
       for (int j = 0; j < 16; ++j) xv[j] = c0 + j < D ? ot[m * kOst + sk * 32 * NBD + c0 + j] : 0.0f;
       const RowsPrepArgs& ra = (PART == kPartKV || sk) ? a.rk : a.rq;
       if constexpr (PLAIN) {
-        rows_prep_block_plain<16, kF32>(ra, hrow0 + m, blk, sub, c0, xv, m < rows);
+        rows_prep_block_plain<kF32>(ra, hrow0 + m, blk, sub, c0, xv, m < rows);
       } else {
-        if (rows_prep_plain(ra)) rows_prep_block_plain<16>(ra, hrow0 + m, blk, sub, c0, xv, m < rows);
-        else rows_prep_block<16>(ra, hrow0 + m, blk, sub, c0, xv, m < rows);
+        if (rows_prep_plain(ra)) rows_prep_block_plain(ra, hrow0 + m, blk, sub, c0, xv, m < rows);
+        else rows_prep_block(ra, hrow0 + m, blk, sub, c0, xv, m < rows);
       }
     } else if (const int c = (int)threadIdx.x - kRowLanes; ProjParts<PART>::kHasV && c < D) {
       // V: cols_prep's per-column body over the 32 tokens

@@ -9,17 +9,35 @@
 //
 // All of it is HBM-bound byte work: coalesced fp32 loads, 32-element blocks
 // reduced with lane shuffles, int8 codes + int16 block exponents written out.
-#include "mxa_kernels.hpp"
+#include "mxa_launch.hpp"
 #include "mxa_prep.hpp"
 #include "mxa_act.hpp"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace mxa {
 
 // ---------------------------------------------------------------------------
-// generic MX quantize of a (outer, L, inner) tensor, one thread per block
+// quantize_mx: the element rule, and the two kernels that apply it
 // ---------------------------------------------------------------------------
+// element l of the tensor, bfloat-rounded, as the quantizer sees it
+__device__ __forceinline__ float quantize_mx_input(const QuantArgs& a, int64_t off) {
+  return round_bfloat(load_dt(a.x, off, a.dt), a.bfloat, kRoundNearest, 1, a.dt);
+}
+// The element rule: the code of x in a block of scale s and the output value
+// (code * 2^-(mbits-2)) * 2^es, which the store rounds once to the dtype; NaN, code 0 in a
+// NaN block
+struct MxElem {
+  float y, code;
+};
+__device__ __forceinline__ MxElem quantize_mx_elem(const QuantArgs& a, float x, const BlkScale& s) {
+  if (s.nan) return {__uint_as_float(0x7FC00000u), 0.0f};
+  const float cv = round_code(s.flush ? x * 0.0f : x, s.es, a.mbits, a.rnd, a.dt);
+  return {(cv * pow2f(2 - a.mbits)) * pow2f(s.es), cv};
+}
+
+// a (outer, L, inner) tensor in blocks of any size along L, one thread per block
 __global__ __launch_bounds__(256) void quantize_mx_kernel(QuantArgs a) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t nblocks = a.outer * a.nb * a.inner;
@@ -30,32 +48,47 @@ __global__ __launch_bounds__(256) void quantize_mx_kernel(QuantArgs a) {
   const int64_t o = ob / a.nb;
   const int64_t l0 = blk * a.bs;
   const int64_t l1 = (l0 + a.bs < a.L) ? l0 + a.bs : a.L;
-  const int64_t xp = (o * a.L) * a.inner + i;
   uint32_t mb = 0;
+  for (int64_t l = l0; l < l1; ++l)
+    mb = max(mb, __float_as_uint(quantize_mx_input(a, (o * a.L + l) * a.inner + i)) & 0x7FFFFFFFu);
+  const BlkScale s = blk_scale(mb, a.scale_emax, a.dt, a.flush);
   for (int64_t l = l0; l < l1; ++l) {
-    const float xv = round_bfloat(load_dt(a.x, xp + l * a.inner, a.dt), a.bfloat, kRoundNearest, 1, a.dt);
-    const uint32_t ub = __float_as_uint(xv) & 0x7FFFFFFFu;
-    mb = ub > mb ? ub : mb;
-  }
-  int e_raw;
-  const int es = scale_exponent_dt(mb, a.scale_emax, a.dt, &e_raw);
-  const bool flush = a.flush && !(e_raw != kExpNaN && e_raw > -127);
-  const int shift = a.mbits - 2;
-  for (int64_t l = l0; l < l1; ++l) {
-    float xv = round_bfloat(load_dt(a.x, xp + l * a.inner, a.dt), a.bfloat, kRoundNearest, 1, a.dt);
-    if (flush) xv = xv * 0.0f;
-    float yv, cv = 0.0f;
-    if (es == kExpNaN) {
-      yv = __uint_as_float(0x7FC00000u);
-    } else {
-      cv = round_code(xv, es, a.mbits, a.rnd, a.dt);
-      yv = (cv * pow2f(-shift)) * pow2f(es);
-    }
     const int64_t off = (o * a.L + l) * a.inner + i;
-    store_dt(a.y, off, yv, a.dt);  // (code * 2^(es-shift) rounded once to the dtype)
-    if (a.codes) a.codes[off] = (int8_t)cv;
+    const MxElem e = quantize_mx_elem(a, quantize_mx_input(a, off), s);
+    store_dt(a.y, off, e.y, a.dt);
+    if (a.codes) a.codes[off] = (int8_t)e.code;
   }
-  if (a.exps) a.exps[(o * a.nb + blk) * a.inner + i] = exp_to16(es);
+  if (a.exps) a.exps[(o * a.nb + blk) * a.inner + i] = exp_to16(s.es);
+}
+
+// maximum over each 32 consecutive lanes (one lane per element of a block)
+__device__ __forceinline__ uint32_t lanes32_max(uint32_t v) {
+#pragma unroll
+  for (int o = 1; o < 32; o <<= 1) {
+    const uint32_t w = (uint32_t)__shfl_xor((int)v, o);
+    v = v > w ? v : w;
+  }
+  return v;
+}
+
+// a contiguous axis in 32-element blocks (the mx ops' axes=[-1] case): one lane per element,
+// the block max by lane shuffles
+__global__ __launch_bounds__(256) void quantize_mx_row32_kernel(QuantArgs a) {
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t bid = t >> 5;
+  const int j = (int)(t & 31);
+  const bool live = bid < a.outer * a.nb;  // every lane takes part in the shuffles
+  const int64_t o = live ? bid / a.nb : 0, blk = live ? bid % a.nb : 0;
+  const int64_t l = blk * 32 + j;
+  const bool valid = live && l < a.L;
+  const int64_t off = o * a.L + l;
+  const float xv = valid ? quantize_mx_input(a, off) : 0.0f;
+  const BlkScale s = blk_scale(lanes32_max(__float_as_uint(xv) & 0x7FFFFFFFu), a.scale_emax, a.dt, a.flush);
+  if (!valid) return;
+  const MxElem e = quantize_mx_elem(a, xv, s);
+  store_dt(a.y, off, e.y, a.dt);
+  if (a.codes) a.codes[off] = (int8_t)e.code;
+  if (a.exps && j == 0) a.exps[o * a.nb + blk] = exp_to16(s.es);
 }
 
 // ---------------------------------------------------------------------------
@@ -116,7 +149,7 @@ __global__ __launch_bounds__(256) void bfloat_kernel(const void* __restrict__ x,
 
 // ---------------------------------------------------------------------------
 // attention operand builder for rows quantized along the last axis (Q, K):
-// 8 lanes per 32-element block, 4 floats (16 B) per lane (body: mxa_prep.hpp)
+// 2 lanes per 32-element block, 16 elements per lane (bodies: mxa_prep.hpp)
 // ---------------------------------------------------------------------------
 // 16 consecutive elements of a row (from element c0) of storage dtype DT as floats
 // (float32: 16-B loads at any 4-B alignment -- rows of a length that is not a multiple of 4,
@@ -187,8 +220,8 @@ __device__ __forceinline__ void rows_prep_body(const RowsPrepArgs& a, uint32_t b
     for (int j = 0; j < 16; ++j)
       if (valid && c0 + j < a.D) xv[j] = mlp_act(xv[j], a.act - 1);
   }
-  if (rows_prep_plain(a)) rows_prep_block_plain<16>(a, row, blk, sub, c0, xv, valid);
-  else rows_prep_block<16>(a, row, blk, sub, c0, xv, valid);
+  if (rows_prep_plain(a)) rows_prep_block_plain(a, row, blk, sub, c0, xv, valid);
+  else rows_prep_block(a, row, blk, sub, c0, xv, valid);
 }
 template <int DT>
 __global__ __launch_bounds__(256) void rows_prep_kernel(RowsPrepArgs a) { rows_prep_body<DT>(a, blockIdx.x); }
@@ -292,176 +325,99 @@ __global__ __launch_bounds__(64 * kElsaWaves) void elsa_prep_kernel(ElsaPrepArgs
 }
 
 // ---------------------------------------------------------------------------
-// approximator operand VALUES (what exponent_approximation's methods return)
-// one lane per element, 32 lanes per (row, 32-block): coalesced loads and stores, the
-// block's max |x| and max |code| by lane shuffles; exact fp32 op order of the reference.
+// approximator operand VALUES (what exponent_approximation's methods return), in the exact
+// fp32 op order of the reference
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ uint32_t lanes32_max(uint32_t v) {
-#pragma unroll
-  for (int o = 1; o < 32; o <<= 1) {
-    const uint32_t w = (uint32_t)__shfl_xor((int)v, o);
-    v = v > w ? v : w;
-  }
-  return v;
-}
-
-__global__ __launch_bounds__(256) void approx_values_kernel(ApproxArgs a) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int nb = (a.d + 31) / 32;
-  const int64_t bid = t >> 5;
-  const int j = (int)(t & 31);
-  const bool live = bid < a.rows * nb;  // every lane takes part in the shuffles
-  const int64_t row = live ? bid / nb : 0;
-  const int blk = live ? (int)(bid % nb) : 0;
-  const int c = blk * 32 + j;
-  const bool valid = live && c < a.d;
-  const int dt = a.dt;
-  const float xin = valid ? round_bfloat(load_dt(a.x, row * a.ld_x + c, dt), a.bfloat, kRoundNearest, 1, dt) : 0.0f;
-  const uint32_t mb = lanes32_max(__float_as_uint(xin) & 0x7FFFFFFFu);
-  int e_raw;
-  const int es = scale_exponent_dt(mb, 127, dt, &e_raw);
-  const bool nanblk = es == kExpNaN;
-  const bool flush = a.flush && !(e_raw != kExpNaN && e_raw > -127);
-  const float qnan = __uint_as_float(0x7FC00000u);
-  const float xv = flush ? xin * 0.0f : xin;
-  // the code as the float the reference holds (a negative x that rounds to code 0 is -0.0) and as an int
-  const float cf = nanblk ? 0.0f : round_code(xv, es, 8, kRoundNearest, dt);
-  const int cd = (int)cf;
-  const int maxc = (int)lanes32_max((uint32_t)(cd < 0 ? -cd : cd));
-  // exponent of the MX block (in the dtype: the MX max is a value of the dtype)
-  const int eA = nanblk ? kExpNaN
-                        : (maxc == 0 ? -126 : floor_log2_dt(__float_as_uint(round_dt((float)maxc * pow2f(es - 6), dt)), dt));
-  if (!valid) return;
-  float out;
-  if (nanblk) {
-    out = a.op_kind == MXA_OP_TRUE_EX ? 1.0f : qnan;  // true_ex: NaN -> exponent 0 -> +1 (examples :98-110)
-  } else if (a.op_kind == MXA_OP_MXINT4) {
-    out = (round_code(xv, es, 4, kRoundNearest, dt) * 0.25f) * pow2f(es);
-  } else {
-    const float mxv = round_dt((cf * pow2f(-6)) * pow2f(es), dt);  // MX int8 value
-    switch (a.op_kind) {
-      case MXA_OP_SIGN:  // (mx < 0 ? -1 : +1) * 2^eA
-        out = (mxv < 0.0f ? -1.0f : 1.0f) * pow2f(eA);
-        break;
-      case MXA_OP_EXION: {  // sign(mx) * eA * (2^l1 + 2^l2) / 64
-        const int m = exion_m(cd << (es - eA));
-        const float sg = cd > 0 ? 1.0f : (cd < 0 ? -1.0f : 0.0f);
-        out = ((sg * (float)eA) * (float)(m < 0 ? -m : m)) / 64.0f;
-        break;
-      }
-      case MXA_OP_TRUE_EX: {  // (mx < 0 ? -1 : +1) * 2^(floor(log2|mx|)), zeros -> 2^0
-        const float am = fabsf(mxv);
-        const int te = am > 0.0f ? floor_log2_dt(__float_as_uint(am), dt) : 0;
-        out = (mxv < 0.0f ? -1.0f : 1.0f) * pow2f(te);
-        break;
-      }
-      default:
-        out = mxv;
+// The value rule, for one element of a block of scale exponent es whose MX-quantized block has
+// the exponent eA: x the element (flushed where the block is), cf its MXINT8 code as the float
+// the reference holds (a negative x that rounds to code 0 is -0.0) and cd as an int
+__device__ __forceinline__ float approx_value(int op_kind, int dt, float x, float cf, int cd, int es, int eA, bool nan) {
+  // true_ex: NaN -> exponent 0 -> +1 (examples :98-110)
+  if (nan) return op_kind == MXA_OP_TRUE_EX ? 1.0f : __uint_as_float(0x7FC00000u);
+  if (op_kind == MXA_OP_MXINT4) return (round_code(x, es, 4, kRoundNearest, dt) * 0.25f) * pow2f(es);
+  const float mxv = round_dt((cf * pow2f(-6)) * pow2f(es), dt);  // MX int8 value
+  switch (op_kind) {
+    case MXA_OP_SIGN:  // (mx < 0 ? -1 : +1) * 2^eA
+      return (mxv < 0.0f ? -1.0f : 1.0f) * pow2f(eA);
+    case MXA_OP_EXION: {  // sign(mx) * eA * (2^l1 + 2^l2) / 64
+      const int m = exion_m(cd << (es - eA));
+      const float sg = cd > 0 ? 1.0f : (cd < 0 ? -1.0f : 0.0f);
+      return ((sg * (float)eA) * (float)(m < 0 ? -m : m)) / 64.0f;
     }
+    case MXA_OP_TRUE_EX: {  // (mx < 0 ? -1 : +1) * 2^(floor(log2|mx|)), zeros -> 2^0
+      const float am = fabsf(mxv);
+      const int te = am > 0.0f ? floor_log2_dt(__float_as_uint(am), dt) : 0;
+      return (mxv < 0.0f ? -1.0f : 1.0f) * pow2f(te);
+    }
+    default:  // MXA_OP_MXINT8
+      return mxv;
   }
-  store_dt(a.out, row * a.ld_out + c, round_dt(out, dt), dt);
 }
 
-// approx_values_kernel for float32 rows of whole 32-element blocks at 16-B aligned
-// strides: eight lanes per block, four elements per lane (one float4 load and store),
-// the block maxima over the eight lanes by DPP, 32-bit index math -- the same values
-// (it is HBM-bound: 8 bytes per element)
-template <int OPK>
-__global__ __launch_bounds__(256) void approx_values_v4_kernel(ApproxArgs a) {
-  const uint32_t t = blockIdx.x * 256u + threadIdx.x;
-  const uint32_t gid = t >> 3, nb = (uint32_t)(a.d >> 5);
-  const int sub = (int)(t & 7u);
-  const bool live = gid < (uint32_t)a.rows * nb;  // every lane takes part in the DPP steps
-  const uint32_t row = live ? gid / nb : 0u, blk = live ? gid - row * nb : 0u;
-  const int c = (int)blk * 32 + 4 * sub;
-  float xin[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-  if (live) {
-    const float4 x4 = *reinterpret_cast<const float4*>(static_cast<const float*>(a.x) + (int64_t)row * a.ld_x + c);
-    xin[0] = x4.x; xin[1] = x4.y; xin[2] = x4.z; xin[3] = x4.w;
-    if (a.bfloat != 0 && a.bfloat != 32)
+// 32 / EPL consecutive lanes per (row, 32-block), EPL elements per lane: coalesced loads and
+// stores, the block's max |x| and max |code| across the lanes.
+//   EPL 1: scalar loads and stores of any dtype, lane shuffles, 64-bit index math; the dtype
+//          and the operand kind are a's
+//   EPL 4: one float4 load and store, DPP, 32-bit index math (the launcher checks both);
+//          float32 and the operand kind OPK at compile time
+template <int EPL, int OPK = -1>
+__device__ __forceinline__ void approx_values_body(const ApproxArgs& a) {
+  constexpr bool V4 = EPL == 4;
+  constexpr int LPB = 32 / EPL;
+  using index_t = std::conditional_t<V4, uint32_t, int64_t>;
+  const int op_kind = V4 ? OPK : a.op_kind, dt = V4 ? (int)kF32 : a.dt;
+  const index_t t = (index_t)blockIdx.x * 256u + threadIdx.x;
+  const index_t bid = t / LPB, nb = (uint32_t)(a.d + 31) >> 5;
+  const int sub = (int)(t % LPB);
+  const bool live = bid < (index_t)a.rows * nb;  // every lane takes part in the reductions
+  const index_t row = live ? bid / nb : 0, blk = live ? bid - row * nb : 0;
+  const int c = (int)blk * 32 + EPL * sub;
+  const bool valid = live && (V4 || c < a.d);
+  float xin[EPL] = {};
+  if (valid) {
+    if constexpr (V4) {
+      const float4 x4 = *reinterpret_cast<const float4*>(static_cast<const float*>(a.x) + (int64_t)row * a.ld_x + c);
+      xin[0] = x4.x; xin[1] = x4.y; xin[2] = x4.z; xin[3] = x4.w;
+    } else {
+      xin[0] = load_dt(a.x, (int64_t)row * a.ld_x + c, dt);
+    }
 #pragma unroll
-      for (int i = 0; i < 4; ++i) xin[i] = round_bfloat(xin[i], a.bfloat, kRoundNearest, 1);
+    for (int i = 0; i < EPL; ++i) xin[i] = round_bfloat(xin[i], a.bfloat, kRoundNearest, 1, dt);
   }
   auto umax = [](uint32_t p, uint32_t q) { return p > q ? p : q; };
-  uint32_t mb = 0u;
+  auto block_max = [&](uint32_t v) { return V4 ? oct_reduce(v, umax) : lanes32_max(v); };
+  uint32_t mb = 0u, mc = 0u;
 #pragma unroll
-  for (int i = 0; i < 4; ++i) mb = umax(mb, __float_as_uint(xin[i]) & 0x7FFFFFFFu);
-  mb = oct_reduce(mb, umax);
-  int e_raw;
-  const int es = scale_exponent(mb, 127, &e_raw);
-  const bool nanblk = es == kExpNaN;
-  const bool flush = a.flush && !(e_raw != kExpNaN && e_raw > -127);
-  float cf[4];  // the codes as floats: -0.0 where a negative x rounds to code 0
-  int cd[4];
-  uint32_t mc = 0u;
+  for (int i = 0; i < EPL; ++i) mb = umax(mb, __float_as_uint(xin[i]) & 0x7FFFFFFFu);
+  const BlkScale s = blk_scale(block_max(mb), 127, dt, a.flush);
+  float xv[EPL], cf[EPL];
+  int cd[EPL];
 #pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float xv = flush ? xin[i] * 0.0f : xin[i];
-    cf[i] = nanblk ? 0.0f : round_code(xv, es, 8, kRoundNearest);
+  for (int i = 0; i < EPL; ++i) {
+    xv[i] = s.flush ? xin[i] * 0.0f : xin[i];
+    cf[i] = s.nan ? 0.0f : round_code(xv[i], s.es, 8, kRoundNearest, dt);
     cd[i] = (int)cf[i];
-    mc = umax(mc, (uint32_t)(cd[i] < 0 ? -cd[i] : cd[i]));
+    mc = umax(mc, (uint32_t)abs(cd[i]));
   }
-  const int maxc = (int)oct_reduce(mc, umax);
-  const int eA = nanblk ? kExpNaN : (maxc == 0 ? -126 : floor_log2_pos((float)maxc * pow2f(es - 6)));
-  if (!live) return;
-  float out[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    if (nanblk) {
-      out[i] = OPK == MXA_OP_TRUE_EX ? 1.0f : __uint_as_float(0x7FC00000u);
-    } else if (OPK == MXA_OP_MXINT4) {
-      const float xv = flush ? xin[i] * 0.0f : xin[i];
-      out[i] = (round_code(xv, es, 4, kRoundNearest) * 0.25f) * pow2f(es);
-    } else {
-      const float mxv = (cf[i] * pow2f(-6)) * pow2f(es);
-      if (OPK == MXA_OP_SIGN) {
-        out[i] = (mxv < 0.0f ? -1.0f : 1.0f) * pow2f(eA);
-      } else if (OPK == MXA_OP_EXION) {
-        const int m = exion_m(cd[i] << (es - eA));
-        const float sg = cd[i] > 0 ? 1.0f : (cd[i] < 0 ? -1.0f : 0.0f);
-        out[i] = ((sg * (float)eA) * (float)(m < 0 ? -m : m)) / 64.0f;
-      } else if (OPK == MXA_OP_TRUE_EX) {
-        const float am = fabsf(mxv);
-        const int te = am > 0.0f ? floor_log2_pos(am) : 0;
-        out[i] = (mxv < 0.0f ? -1.0f : 1.0f) * pow2f(te);
-      } else {
-        out[i] = mxv;
-      }
-    }
-  }
-  *reinterpret_cast<float4*>(static_cast<float*>(a.out) + (int64_t)row * a.ld_out + c) =
-      make_float4(out[0], out[1], out[2], out[3]);
-}
-
-// quantize_mx along a contiguous axis in 32-element blocks (the mx ops' axes=[-1] case):
-// one lane per element, the block max by lane shuffles -- quantize_mx_kernel's result
-__global__ __launch_bounds__(256) void quantize_mx_row32_kernel(QuantArgs a) {
-  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int64_t bid = t >> 5;
-  const int j = (int)(t & 31);
-  const bool live = bid < a.outer * a.nb;
-  const int64_t o = live ? bid / a.nb : 0, blk = live ? bid % a.nb : 0;
-  const int64_t l = blk * 32 + j;
-  const bool valid = live && l < a.L;
-  const int64_t off = o * a.L + l;
-  float xv = valid ? round_bfloat(load_dt(a.x, off, a.dt), a.bfloat, kRoundNearest, 1, a.dt) : 0.0f;
-  const uint32_t mb = lanes32_max(__float_as_uint(xv) & 0x7FFFFFFFu);
-  int e_raw;
-  const int es = scale_exponent_dt(mb, a.scale_emax, a.dt, &e_raw);
+  const int eA = mx_block_exponent((int)block_max(mc), s.es, s.nan, dt);
   if (!valid) return;
-  if (a.flush && !(e_raw != kExpNaN && e_raw > -127)) xv = xv * 0.0f;
-  const int shift = a.mbits - 2;
-  float yv, cv = 0.0f;
-  if (es == kExpNaN) {
-    yv = __uint_as_float(0x7FC00000u);
+  float out[EPL];
+#pragma unroll
+  for (int i = 0; i < EPL; ++i) out[i] = round_dt(approx_value(op_kind, dt, xv[i], cf[i], cd[i], s.es, eA, s.nan), dt);
+  if constexpr (V4) {
+    *reinterpret_cast<float4*>(static_cast<float*>(a.out) + (int64_t)row * a.ld_out + c) =
+        make_float4(out[0], out[1], out[2], out[3]);
   } else {
-    cv = round_code(xv, es, a.mbits, a.rnd, a.dt);
-    yv = (cv * pow2f(-shift)) * pow2f(es);
+    store_dt(a.out, (int64_t)row * a.ld_out + c, out[0], dt);
   }
-  store_dt(a.y, off, yv, a.dt);  // (code * 2^(es-shift) rounded once to the dtype)
-  if (a.codes) a.codes[off] = (int8_t)cv;
-  if (a.exps && j == 0) a.exps[o * a.nb + blk] = exp_to16(es);
 }
+// any dtype, operand kind, row length and alignment: one lane per element, both read from
+// the arguments
+__global__ __launch_bounds__(256) void approx_values_kernel(ApproxArgs a) { approx_values_body<1>(a); }
+// float32 rows of whole 32-element blocks at 16-B aligned strides, the operand kind known:
+// eight lanes per block, four elements per lane (it is HBM-bound: 8 bytes per element)
+template <int OPK>
+__global__ __launch_bounds__(256) void approx_values_v4_kernel(ApproxArgs a) { approx_values_body<4, OPK>(a); }
 
 }  // namespace mxa
 
@@ -471,6 +427,17 @@ using namespace mxa;
 // C ABI
 // ---------------------------------------------------------------------------
 static bool dtype_ok(int dt) { return dt == kF32 || dt == kF16 || dt == kBF16; }
+static_assert(kF32 == 0 && kF16 == 1 && kBF16 == 2, "with_constant<3> takes the storage dtypes as 0 .. 2");
+// f(std::integral_constant<int, v>) for v in [0, N): a storage dtype (N = 3) or an operand
+// kind (N = 5) as the template argument of the kernel that f launches.  The callers checked
+// the range.
+template <int N, class F>
+static void with_constant(int v, F f) {
+  if constexpr (N > 1) {
+    if (v != N - 1) return with_constant<N - 1>(v, f);
+  }
+  f(std::integral_constant<int, N - 1>{});
+}
 
 extern "C" int mxa_quantize_mx(const void* x, void* y, int8_t* codes, int16_t* exps, int64_t outer,
                                int64_t axis_len, int64_t inner, int32_t block_size, int32_t elem_mbits,
@@ -479,7 +446,7 @@ extern "C" int mxa_quantize_mx(const void* x, void* y, int8_t* codes, int16_t* e
   if (!x || !y || outer < 0 || axis_len < 0 || inner < 0 || block_size < 0 || !dtype_ok(dtype)) return MXA_ERR_ARG;
   if (elem_mbits != 8 && elem_mbits != 4 && elem_mbits != 2) return MXA_ERR_UNSUPPORTED;
   if (scale_bits < 2 || scale_bits > 8 || round_mode < 0 || round_mode > 2) return MXA_ERR_ARG;
-  if (bfloat != 0 && bfloat != 32 && (bfloat < 10 || bfloat > 31)) return MXA_ERR_ARG;
+  if (!valid_bfloat(bfloat)) return MXA_ERR_ARG;
   if (outer == 0 || axis_len == 0 || inner == 0) return MXA_OK;
   QuantArgs a{};
   a.x = x; a.y = y; a.codes = codes; a.exps = exps;
@@ -491,10 +458,10 @@ extern "C" int mxa_quantize_mx(const void* x, void* y, int8_t* codes, int16_t* e
   const int64_t nblocks = outer * a.nb * inner;
   if (inner == 1 && a.bs == 32) {  // contiguous 32-blocks: one lane per element
     hipLaunchKernelGGL(quantize_mx_row32_kernel, dim3((unsigned)((nblocks * 32 + 255) / 256)), dim3(256), 0, stream, a);
-    return hipGetLastError() == hipSuccess ? MXA_OK : MXA_ERR_LAUNCH;
+    return launch_status();
   }
   hipLaunchKernelGGL(quantize_mx_kernel, dim3((unsigned)((nblocks + 255) / 256)), dim3(256), 0, stream, a);
-  return hipGetLastError() == hipSuccess ? MXA_OK : MXA_ERR_LAUNCH;
+  return launch_status();
 }
 
 extern "C" int mxa_shared_exponents(const void* x, void* out, int64_t outer, int64_t axis_len, int64_t inner,
@@ -510,20 +477,20 @@ extern "C" int mxa_shared_exponents(const void* x, void* out, int64_t outer, int
   a.method = method; a.ebits = ebits; a.dt = dtype;
   const int64_t n = method == 1 ? outer * axis_len * inner : outer * a.nb * inner;
   hipLaunchKernelGGL(shared_exp_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
-  return hipGetLastError() == hipSuccess ? MXA_OK : MXA_ERR_LAUNCH;
+  return launch_status();
 }
 
 extern "C" int mxa_quantize_bfloat(const void* x, void* y, int64_t n, int32_t bfloat, int32_t round_mode,
                                    int32_t allow_denorm, int32_t dtype, hipStream_t stream) {
   if (!x || !y || n < 0 || !dtype_ok(dtype)) return MXA_ERR_ARG;
-  if (bfloat != 0 && bfloat != 32 && (bfloat < 10 || bfloat > 31)) return MXA_ERR_ARG;
+  if (!valid_bfloat(bfloat)) return MXA_ERR_ARG;
   if (round_mode < 0 || round_mode > 2) return MXA_ERR_ARG;
   if (n == 0) return MXA_OK;
   int64_t blocks = (n + 255) / 256;
   if (blocks > 256 * 16) blocks = 256 * 16;
   hipLaunchKernelGGL(bfloat_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, x, y, n, bfloat, round_mode,
                      allow_denorm, dtype);
-  return hipGetLastError() == hipSuccess ? MXA_OK : MXA_ERR_LAUNCH;
+  return launch_status();
 }
 
 extern "C" int mxa_approx_values(const void* x, void* out, int64_t rows, int32_t d, int64_t ld_x, int64_t ld_out,
@@ -539,19 +506,16 @@ extern "C" int mxa_approx_values(const void* x, void* out, int64_t rows, int32_t
   if (dtype == MXA_DT_F32 && d % 32 == 0 && ld_x % 4 == 0 && ld_out % 4 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(out)) & 15u) == 0 &&
       nbk * 8 < ((int64_t)1 << 31)) {  // eight lanes per block, float4 in and out
     const dim3 grid((unsigned)((nbk * 8 + 255) / 256));
-    switch (op_kind) {
-      case MXA_OP_SIGN: hipLaunchKernelGGL(approx_values_v4_kernel<MXA_OP_SIGN>, grid, dim3(256), 0, stream, a); break;
-      case MXA_OP_EXION: hipLaunchKernelGGL(approx_values_v4_kernel<MXA_OP_EXION>, grid, dim3(256), 0, stream, a); break;
-      case MXA_OP_MXINT4: hipLaunchKernelGGL(approx_values_v4_kernel<MXA_OP_MXINT4>, grid, dim3(256), 0, stream, a); break;
-      case MXA_OP_TRUE_EX: hipLaunchKernelGGL(approx_values_v4_kernel<MXA_OP_TRUE_EX>, grid, dim3(256), 0, stream, a); break;
-      default: hipLaunchKernelGGL(approx_values_v4_kernel<MXA_OP_MXINT8>, grid, dim3(256), 0, stream, a); break;
-    }
-    return hipGetLastError() == hipSuccess ? MXA_OK : MXA_ERR_LAUNCH;
+    static_assert(MXA_OP_SIGN == 0 && MXA_OP_TRUE_EX == 4, "the operand kinds are 0 .. 4");
+    with_constant<5>(op_kind, [&](auto opk) {
+      hipLaunchKernelGGL(approx_values_v4_kernel<decltype(opk)::value>, grid, dim3(256), 0, stream, a);
+    });
+    return launch_status();
   }
   const int64_t n = nbk * 32;  // one lane per element of the padded blocks
   if (n / 256 >= ((int64_t)1 << 31)) return MXA_ERR_UNSUPPORTED;
   hipLaunchKernelGGL(approx_values_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
-  return hipGetLastError() == hipSuccess ? MXA_OK : MXA_ERR_LAUNCH;
+  return launch_status();
 }
 
 namespace mxa {
@@ -563,10 +527,12 @@ int launch_rows_prep(const RowsPrepArgs& a, hipStream_t stream) {
   if (a.act != kActNone) {
     if (a.dt != kF32 || (a.act != 1 + MXA_ACT_GELU && a.act != 1 + MXA_ACT_GELU_TANH)) return MXA_ERR_ARG;
     hipLaunchKernelGGL(rows_prep_act_kernel, grid, dim3(256), 0, stream, a);
-  } else if (a.dt == kF16) hipLaunchKernelGGL(rows_prep_kernel<kF16>, grid, dim3(256), 0, stream, a);
-  else if (a.dt == kBF16) hipLaunchKernelGGL(rows_prep_kernel<kBF16>, grid, dim3(256), 0, stream, a);
-  else hipLaunchKernelGGL(rows_prep_kernel<kF32>, grid, dim3(256), 0, stream, a);
-  return hipGetLastError() == hipSuccess ? MXA_OK : MXA_ERR_LAUNCH;
+  } else {
+    with_constant<3>(a.dt, [&](auto dt) {
+      hipLaunchKernelGGL(rows_prep_kernel<decltype(dt)::value>, grid, dim3(256), 0, stream, a);
+    });
+  }
+  return launch_status();
 }
 int launch_elsa_prep(const ElsaPrepArgs& a, hipStream_t stream) {
   if (a.rows == 0) return MXA_OK;
@@ -577,7 +543,7 @@ int launch_elsa_prep(const ElsaPrepArgs& a, hipStream_t stream) {
     return MXA_ERR_LAUNCH;
   const int64_t blocks = std::min<int64_t>((a.rows + kElsaWaves - 1) / kElsaWaves, 2048);
   hipLaunchKernelGGL(elsa_prep_kernel, dim3((unsigned)blocks), dim3(64 * kElsaWaves), lds, stream, a);
-  return hipGetLastError() == hipSuccess ? MXA_OK : MXA_ERR_LAUNCH;
+  return launch_status();
 }
 int launch_attn_prep(const RowsPrepArgs& q, const RowsPrepArgs& k, const ColsPrepArgs& v, hipStream_t stream) {
   if (q.rows * q.nb >= ((int64_t)1 << 30) || k.rows * k.nb >= ((int64_t)1 << 30) ||
@@ -588,19 +554,20 @@ int launch_attn_prep(const RowsPrepArgs& q, const RowsPrepArgs& k, const ColsPre
   const int64_t nv = (v.mats * v.nb * v.C + 255) / 256;
   if (nq + nk + nv == 0) return MXA_OK;
   const dim3 grid((unsigned)(nq + nk + nv));
-  if (q.dt == kF16) hipLaunchKernelGGL(attn_prep_kernel<kF16>, grid, dim3(256), 0, stream, q, k, v, (uint32_t)nq, (uint32_t)nk);
-  else if (q.dt == kBF16) hipLaunchKernelGGL(attn_prep_kernel<kBF16>, grid, dim3(256), 0, stream, q, k, v, (uint32_t)nq, (uint32_t)nk);
-  else hipLaunchKernelGGL(attn_prep_kernel<kF32>, grid, dim3(256), 0, stream, q, k, v, (uint32_t)nq, (uint32_t)nk);
-  return hipGetLastError() == hipSuccess ? MXA_OK : MXA_ERR_LAUNCH;
+  with_constant<3>(q.dt, [&](auto dt) {
+    hipLaunchKernelGGL(attn_prep_kernel<decltype(dt)::value>, grid, dim3(256), 0, stream, q, k, v, (uint32_t)nq,
+                       (uint32_t)nk);
+  });
+  return launch_status();
 }
 int launch_cols_prep(const ColsPrepArgs& a, hipStream_t stream) {
   const int64_t threads = a.mats * a.nb * a.C;
   if (threads == 0) return MXA_OK;
   if (threads >= ((int64_t)1 << 31)) return MXA_ERR_UNSUPPORTED;  // 32-bit thread indices
   const dim3 grid((unsigned)((threads + 255) / 256));
-  if (a.dt == kF16) hipLaunchKernelGGL(cols_prep_kernel<kF16>, grid, dim3(256), 0, stream, a);
-  else if (a.dt == kBF16) hipLaunchKernelGGL(cols_prep_kernel<kBF16>, grid, dim3(256), 0, stream, a);
-  else hipLaunchKernelGGL(cols_prep_kernel<kF32>, grid, dim3(256), 0, stream, a);
-  return hipGetLastError() == hipSuccess ? MXA_OK : MXA_ERR_LAUNCH;
+  with_constant<3>(a.dt, [&](auto dt) {
+    hipLaunchKernelGGL(cols_prep_kernel<decltype(dt)::value>, grid, dim3(256), 0, stream, a);
+  });
+  return launch_status();
 }
 }  // namespace mxa

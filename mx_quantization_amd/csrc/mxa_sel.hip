@@ -34,7 +34,7 @@ static int launch_select_w(const Rows2Args& ra0, int BH, hipStream_t stream, boo
     grid = dim3((unsigned)(((int64_t)BH * gy + kFbItems - 1) / kFbItems), 1);
   }
   hipLaunchKernelGGL((select_kernel<NP, MODE, W, El, QM, TW>), grid, dim3(64 * W), lds, stream, ra);
-  return hipGetLastError() == hipSuccess ? MXA_OK : MXA_ERR_LAUNCH;
+  return launch_status();
 }
 // the one-lane tail (mxa_tail.hpp) over every row of the call: the rows the packed pass
 // handed over (the fused selection's, and the standalone mxa_topk_ws')
@@ -46,7 +46,7 @@ static int launch_tail(const TailArgs& ta, hipStream_t stream) {
     return MXA_ERR_LAUNCH;
   const int64_t per = 64 * kTailWaves;
   hipLaunchKernelGGL(topk_tail_kernel<TW>, dim3((unsigned)((ta.rows + per - 1) / per)), dim3(64 * kTailWaves), lds, stream, ta);
-  return hipGetLastError() == hipSuccess ? MXA_OK : MXA_ERR_LAUNCH;
+  return launch_status();
 }
 template <int NP, int MODE, int W>
 static int launch_select_packed(const Rows2Args& ra, int BH, hipStream_t stream, bool plan) {
@@ -120,7 +120,7 @@ static int launch_topk_wave(const GrpTopkArgs& ga, hipStream_t stream) {
                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
     return MXA_ERR_LAUNCH;
   hipLaunchKernelGGL(topk_wave_kernel<NP>, dim3((unsigned)((ga.rows + 3) / 4)), dim3(256), lds, stream, ga);
-  return hipGetLastError() == hipSuccess ? MXA_OK : MXA_ERR_LAUNCH;
+  return launch_status();
 }
 template <int NP, typename El = uint64_t, int QM = 0, int TW = 0>
 static int launch_topk_grp(const GrpTopkArgs& ga, const TopkWs& w, unsigned grid, hipStream_t stream) {
@@ -128,7 +128,7 @@ static int launch_topk_grp(const GrpTopkArgs& ga, const TopkWs& w, unsigned grid
   const void* fn = reinterpret_cast<const void*>(&topk_grp_kernel<NP, El, QM, TW>);
   if (hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return MXA_ERR_LAUNCH;
   hipLaunchKernelGGL((topk_grp_kernel<NP, El, QM, TW>), dim3(grid), dim3(256), lds, stream, ga, w);
-  return hipGetLastError() == hipSuccess ? MXA_OK : MXA_ERR_LAUNCH;
+  return launch_status();
 }
 
 // the workspace path of the standalone top-k: the packed pass for rows of <= 256 values

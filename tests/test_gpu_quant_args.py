@@ -192,6 +192,75 @@ def test_approx_values_f32_bfloat16(M, F32, kind):
     same_bits(np.ascontiguousarray(to_bits(got)[:, :32]), want, f"approx_values({kind}, bfloat=16), d = 40")
 
 
+def special_values(x):
+    """The special blocks of test_gpu_parity's test_approximator_operands_special_blocks_vs_oracle
+    into the six (i, j) slices of a standard normal x of shape (2, 3, rows, D): a NaN, a +Inf and a
+    -Inf element, every fifth column of a slice zero, an all-zero row, slices scaled by 2^-120 and
+    2^90, and one by 2^-130: subnormal blocks, where the flush decides something."""
+    x[0, 0, 3, 5], x[0, 1, 4, 40], x[1, 2, 6, x.shape[-1] - 2] = np.nan, np.inf, -np.inf
+    x[1, 0, :, ::5] = 0.0
+    x[0, 2, 9, :] = 0.0
+    x[1, 1] *= np.float32(2.0 ** -120)
+    x[1, 2] *= np.float32(2.0 ** 90)
+    x[0, 2] *= np.float32(2.0 ** -130)
+    return x
+
+
+APPROX_MODES = {"sign": "ex_pred", "exion": "two_step_leading_ones", "true_ex": "true_ex"}
+
+
+@pytest.mark.parametrize("D", [64, 72])
+def test_approx_values_kinds_on_both_kernels(M, D):
+    """Every operand kind, with and without the subnormal flush, on NaN / Inf / zero / tiny / huge /
+    subnormal blocks: the float4 kernel (D = 64, aligned) and the one-lane-per-element kernel
+    (D = 72; D = 64 at a data pointer 4 bytes off 16-byte alignment) against the oracle, and
+    against each other, bit for bit."""
+    x = special_values(np.random.default_rng(17).standard_normal((2, 3, 40, D), dtype=np.float32))
+    xd = dev(x)
+    assert xd.data_ptr() % 16 == 0
+    rows = x.size // D
+    buf = torch.empty(rows * D + 1, dtype=torch.float32, device="cuda")
+    off = buf[1:].view(rows, D)  # contiguous, 4 bytes off: the general kernel whatever D
+    off.copy_(xd.view(rows, D))
+    assert off.is_contiguous() and off.data_ptr() % 16 == 4
+    for kind in M.ops.OP_KINDS:
+        for flush in (False, True):
+            what = f"approx_values({kind}, flush={flush}), D = {D}"
+            if kind in APPROX_MODES:
+                want = O.approx_operands(x, x, APPROX_MODES[kind], flush=flush)[0]
+            else:
+                want = O.quantize_mx(x, "int8" if kind == "mxint8" else "int4", 32, -1, flush=flush)[0]
+            got = to_bits(M.approx_values(xd, kind, flush=flush))
+            same_bits(got, want, what, x=x)
+            if D == 64:
+                gen = to_bits(M.approx_values(off, kind, flush=flush)).reshape(x.shape)
+                same_bits(gen, want, what + ", general kernel", x=x)
+                same_bits(gen, got, what + ", general against float4 kernel", x=x)
+
+
+@pytest.mark.parametrize("rnd", QC.ROUNDS)
+@pytest.mark.parametrize("mbits", [8, 4, 2])
+def test_quantize_mx_row32_matches_generic(M, mbits, rnd):
+    """quantize_mx along a contiguous last axis in 32-blocks (one lane per element) and the same
+    blocks along axis 0 of the transpose (inner = 96: one thread per block): values, codes and
+    block exponents transposes of each other, bit for bit; MXINT8 nearest also against the oracle."""
+    x = special_values(np.random.default_rng(17).standard_normal((2, 3, 16, 64), dtype=np.float32)).reshape(96, 64)
+    xd = dev(x)
+    xt = xd.T.contiguous()
+    for flush in (False, True):
+        for sb in (8, 5):
+            what = f"quantize_mx(int{mbits}, {rnd}, flush={flush}, scale_bits={sb})"
+            y, c, e = M.quantize_mx(xd, mbits, 32, -1, sb, rnd, flush, want_codes=True)
+            yt, ct, et = M.quantize_mx(xt, mbits, 32, 0, sb, rnd, flush, want_codes=True)
+            assert e.shape == (96, 2, 1) and et.shape == (1, 2, 96)
+            same_bits(host(yt).T, host(y), what + " values", x=x)
+            same_ints(host(ct).T, host(c), what + " codes")
+            same_ints(host(et)[0].T, host(e)[:, :, 0], what + " exponents")
+            if mbits == 8 and rnd == "nearest":
+                want = O.quantize_mx(x, "int8", 32, -1, sb, flush=flush)[0]
+                same_bits(host(y), want, what + " against the oracle", x=x)
+
+
 # ------------------------------------------------------------------ the shared callers
 def out_close(got, ref, tol, what):
     same_ints(np.isnan(got), np.isnan(ref), what + " NaN pattern")
