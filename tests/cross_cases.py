@@ -3,7 +3,8 @@ tests/test_gpu_cross.py): M.mx_cross_attention is PixArt's MXCrossAttention.forw
 q = to_q(x), k = to_k(cond), v = to_v(cond) through mx.Linear, heads split as the module
 splits them, then the masked top-k attention core.
 
-The CPU file proves with the oracle alone that each input sits in the regime its GPU test is
+Exponents, the gate and the block normalisation are those of tests/gate_cases.py.  The CPU
+file proves with the oracle alone that each input sits in the regime its GPU test is
 about (the NaN rows, the accumulation path of every (tile, head) of the spread case, the
 subnormal gate); the GPU file repeats nothing of that and only compares."""
 import functools
@@ -81,20 +82,12 @@ SPREAD_SHAPE = (2, 70, 70, 256, 256)  # (B, N, T, C, C_kv); H = 4 and 2
 TILE_SHIFTS = {0: (0, 3, 8), 1: (12, 16, 20), 2: (9,)}  # per 32-token tile: the shifts of its rows' odd blocks
 
 
-def _unit_blocks(a):
-    """every 32-block along the last axis scaled by a power of two to max |.| in [1, 2)"""
-    sh = a.shape
-    b = a.reshape(sh[:-1] + (sh[-1] // 32, 32))
-    e = np.floor(np.log2(np.abs(b).max(-1, keepdims=True)))
-    return (b * np.float32(2.0) ** -e).reshape(sh).astype(np.float32)
-
-
 def spread_tokens(rng, B, N, C):
     """(B, N, C) tokens with every 32-channel block normalised to one exponent, then the odd
     blocks of each row scaled by 2^s, s from the row's tile (TILE_SHIFTS, five rows per
     value): a tile's largest row spread is then exactly its largest shift -- 8 (the digit
     limit), 20 and 9."""
-    x = _unit_blocks(rng.standard_normal((B, N, C), dtype=np.float32))
+    x = GC.blocks_to_unit(rng.standard_normal((B, N, C), dtype=np.float32))
     odd = (np.arange(C) // 32) % 2 == 1
     for t in range(N):
         sh = TILE_SHIFTS[t // 32]
@@ -114,8 +107,8 @@ def spread_case(H):
     D = C // H
     rng = np.random.default_rng(31 + H)
     x, cond = spread_tokens(rng, B, N, C), spread_tokens(rng, B, T, Ckv)
-    Wq = (_unit_blocks(rng.standard_normal((C, C), dtype=np.float32)) * np.float32(2.0 ** -5)).astype(np.float32)
-    Wkv = (_unit_blocks(rng.standard_normal((2 * C, Ckv), dtype=np.float32)) * np.float32(2.0 ** -5)).astype(np.float32)
+    Wq = (GC.blocks_to_unit(rng.standard_normal((C, C), dtype=np.float32)) * np.float32(2.0 ** -5)).astype(np.float32)
+    Wkv = (GC.blocks_to_unit(rng.standard_normal((2 * C, Ckv), dtype=np.float32)) * np.float32(2.0 ** -5)).astype(np.float32)
     bq = (rng.standard_normal(C, dtype=np.float32) * np.float32(0.1)).astype(np.float32)
     bkv = (rng.standard_normal(2 * C, dtype=np.float32) * np.float32(0.1)).astype(np.float32)
     oddq, oddk = (np.arange(C) // 32) % 2 == 1, (np.arange(Ckv) // 32) % 2 == 1

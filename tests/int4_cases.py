@@ -3,24 +3,26 @@ mxa_gemm.hpp mx_gemm_dig4_kernel, mxa_mlp.hpp mx_mlp_fc1_4_kernel), shared by th
 (test_gpu_int4.py) and by the CPU test that proves with the oracle alone on which side of the
 one-digit kernel's gate every row block of every case sits (test_int4_cpu.py).
 
-The device keeps an MXINT4 block as codes in [-7, 7] and the exponent of a code unit, e = es - 2
-(es: the oracle's shared exponent, quantize_mx(A, "int4")[2]; value = code * 2^e).  The
-one-digit kernel takes a 32-row block when
+Exponents and the gate are those of tests/gate_cases.py at elem="int4" (bound below under this
+module's names): codes in [-7, 7], the code unit's exponent e = es - 2.  The one-digit kernel
+takes a 32-row block when
     the largest spread (max - min of e, all-zero blocks left out) of its rows  <= 4,
     the largest spread of every weight column of the launch                   <= 4   and
     min e over the rows' blocks + min e over the weight's blocks              >= -126;
 any other row block is summed block by block in fp64 in the same workgroup.  Beyond 144
 K-blocks (K = 4,608), or for a weight without digits over the output columns (groups that are
 neither out_features nor a multiple of 32 columns), the tile kernel runs."""
-import warnings
+import functools
 
 import numpy as np
 
+import gate_cases as GC
+from gate_cases import DIGIT4_SPREAD  # noqa: F401
+from gpu_support import same_bits  # noqa: F401
+from mlp_cases import case as mlp_case  # noqa: F401
 from oracle import mx_oracle as O
 
 F32 = np.float32
-GATE = -126
-DIGIT4_SPREAD = 4   # mxa_proj_args.hpp kDigit4Spread: 7 * 2^4 = 112 <= 127
 DIG4_NBK_MAX = 144  # mxa_gemm.hpp kGemmDig4NbkMax = mxa_mlp.hpp kMlp4NbkMax
 SPECS = {  # the reference's workloads/PixArt/scripts/mx_inference.py:106-122
     'w_elem_format': 'int4', 'a_elem_format': 'int4', 'scale_bits': 8,
@@ -54,71 +56,14 @@ def linear_case(rows, inf, outf, seed):
     return rnd((rows, inf), seed), rnd((outf, inf), seed + 1, 0.15), rnd((outf,), seed + 2, 0.5)
 
 
-# ---- the gate restated from the oracle's block exponents -----------------------------------
-def unit_exps(A, bfloat=32, flush=False):
-    """(rows, nb) code-unit exponents es - 2 of A's 32-blocks as float64; NaN for a NaN block"""
-    A = O.quantize_bfloat(np.asarray(A, F32), bfloat)
-    return O.quantize_mx(A, "int4", 32, -1, flush=flush)[2][..., 0].astype(np.float64) - 2.0
-
-
-def zero_blocks(A):
-    A = np.asarray(A, F32)
-    nb = (A.shape[-1] + 31) // 32
-    P = np.zeros(A.shape[:-1] + (nb * 32,), F32)
-    P[..., : A.shape[-1]] = A
-    return (P.reshape(A.shape[:-1] + (nb, 32)) == 0).all(-1)
-
-
-def row_stats(A, skip_zero_blocks, bfloat=32):
-    e = unit_exps(A, bfloat)
-    if skip_zero_blocks:
-        e = np.where(zero_blocks(A), np.nan, e)
-    with warnings.catch_warnings():  # (a row of NaN / left-out blocks only: its min is NaN)
-        warnings.simplefilter("ignore", RuntimeWarning)
-        lo, hi = np.nanmin(e, -1), np.nanmax(e, -1)
-    return lo, hi - lo
-
-
-def gate(x, W, bfloat=32):
-    """(per 32-row block: rows' min + weight's min [NaN: no block left], per 32-row block the
-    largest row spread, the largest weight column spread)"""
-    lo, sp = row_stats(x, True, bfloat)
-    wlo, wsp = row_stats(W, False, bfloat)
-    nrb = (x.shape[0] + 31) // 32
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore", RuntimeWarning)
-        q = np.array([np.nanmin(lo[32 * r: 32 * r + 32]) for r in range(nrb)]) + np.nanmin(wlo)
-    smx = np.array([np.nanmax(np.nan_to_num(sp[32 * r: 32 * r + 32])) for r in range(nrb)])
-    return q, smx, np.nanmax(np.nan_to_num(wsp))
-
-
-def on_digits(x, W, bfloat=32):
-    """per 32-row block: does the one-digit K loop take it?"""
-    q, smx, wsp = gate(x, W, bfloat)
-    return (smx <= DIGIT4_SPREAD) & (wsp <= DIGIT4_SPREAD) & ~(q < GATE)
-
-
-def assert_side(x, W, want, bfloat=32, what=""):
-    """every row block on the wanted side ("digits" / "fp64"); returns (digit blocks, blocks)"""
-    d = on_digits(x, W, bfloat)
-    assert (d.all() if want == "digits" else not d.any()), (what, want, gate(x, W, bfloat))
-    return int(d.sum()), d.size
-
-
-# ---- gate edges: every 32-block normalised to one binade, block b scaled by 2^(s_b) -----------
-def blocks_to_unit(a):
-    """every 32-block of the rows normalised to max |.| in [1, 2): shared exponent 0"""
-    n = a.shape[1]
-    nb = (n + 31) // 32
-    p = np.zeros((a.shape[0], nb * 32), F32)
-    p[:, :n] = a
-    bm = np.abs(p.reshape(a.shape[0], nb, 32)).max(-1)
-    return (a * np.repeat(np.exp2(-np.floor(np.log2(bm))).astype(F32), 32, axis=1)[:, :n]).astype(F32)
-
-
-def scaled(a, shifts):
-    """block b of row r of the normalised a times 2^shifts[r, b]"""
-    return (a * np.repeat(np.exp2(shifts.astype(np.float64)).astype(F32), 32, axis=1)[:, : a.shape[1]]).astype(F32)
+# ---- the gate: tests/gate_cases.py at elem="int4" ------------------------------------------------
+unit_exps = functools.partial(GC.unit_exps, elem="int4")
+zero_blocks = GC.zero_blocks
+row_stats = functools.partial(GC.row_stats, elem="int4")
+gate = functools.partial(GC.gemm_gate, elem="int4")
+on_digits = functools.partial(GC.on_digits, elem="int4")
+assert_side = functools.partial(GC.assert_side, elem="int4")
+blocks_to_unit, scaled = GC.blocks_to_unit, GC.scaled  # the gate edges are built from these
 
 
 EDGE_ROWS, EDGE_IN, EDGE_OUT = 70, 256, 64
@@ -204,10 +149,7 @@ K_EDGE_IN = (4608, 4640)  # 144 K-blocks: the one-digit kernel's last; 145: the 
 def k_edge(inf):
     """every block of x and W normalised, x's blocks scaled by 2^0 .. 2^3 (each K-block at its own
     scale), W by 2^-6"""
-    rng = np.random.default_rng(inf)
-    nb = (inf + 31) // 32
-    x = scaled(blocks_to_unit(rng.standard_normal((K_EDGE_ROWS, inf), dtype=F32)), rng.integers(0, 4, size=(K_EDGE_ROWS, nb)))
-    W = scaled(blocks_to_unit(rng.standard_normal((K_EDGE_OUT, inf), dtype=F32)), np.full((K_EDGE_OUT, nb), -6))
+    x, W = GC.k_edge_operands(np.random.default_rng(inf), K_EDGE_ROWS, K_EDGE_OUT, inf, -6)
     return x, W, rnd((K_EDGE_OUT,), inf + 1, 0.5)
 
 
@@ -219,25 +161,3 @@ def assert_k_edge(inf, x, W):
 
 # ---- the MLP ----------------------------------------------------------------------------------
 MLP_SHAPES = ((70, 96, 160, 40), (33, 100, 136, 96), (45, 64, 4608, 40), (45, 64, 4640, 40), (5, 32, 32, 7))
-
-
-def mlp_case(rows, inf, hid, outf, seed):
-    rng = np.random.default_rng(seed)
-    x = rng.standard_normal((rows, inf), dtype=F32)
-    W1 = (rng.standard_normal((hid, inf), dtype=F32) * F32(0.15)).astype(F32)
-    b1 = (rng.standard_normal(hid, dtype=F32) * F32(0.5)).astype(F32)
-    W2 = (rng.standard_normal((outf, hid), dtype=F32) * F32(0.1)).astype(F32)
-    b2 = (rng.standard_normal(outf, dtype=F32) * F32(0.1)).astype(F32)
-    return x, W1, b1, W2, b2
-
-
-def same_bits(a, b, what=""):
-    """float32 arrays equal as uint32 (the sign of zero counts), NaN against NaN allowed"""
-    a, b = np.ascontiguousarray(a, dtype=F32), np.ascontiguousarray(b, dtype=F32)
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    ok = (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))
-    if not ok.all():
-        bad = np.argwhere(~ok)
-        i = tuple(bad[0])
-        raise AssertionError(f"{what}: {bad.shape[0]}/{ok.size} mismatches, first {bad[:4].tolist()}: "
-                             f"{a[i]!r} ({a.view(np.uint32)[i]:#010x}) vs {b[i]!r} ({b.view(np.uint32)[i]:#010x})")

@@ -3,10 +3,11 @@ epilogue quantizer (mxa_mlp.hpp MlpEpi -> xo_block), of the GELU (mxa_act.hpp) o
 digit kernel, shared by the GPU tests (test_gpu_mlp.py) and by the CPU test that proves with
 the oracle alone that each input is where it is meant to be (test_mlp_cases_cpu.py).
 
-Exponents are those of tests/gate_cases.py: the oracle's shared exponent es of a 32-block
-(quantize_mx(...)[2]), the code unit's exponent es - 6, the digit kernel's gate on the sum
-of the rows' and the weight's smallest code-unit exponents (>= -126: the digit fast path;
-below, or with a spread beyond kDigitSpread = 8, the fp64 block sums).  The regimes of the
+Exponents, the gate and the block construction are those of tests/gate_cases.py at its
+default elem="int8": the oracle's shared exponent es of a 32-block (quantize_mx(...)[2]), the
+code unit's exponent es - 6, the digit kernel's gate on the sum of the rows' and the weight's
+smallest code-unit exponents (>= -126: the digit fast path; below, or with a spread beyond
+kDigitSpread = 8, the fp64 block sums).  same_bits is tests/gpu_support.py's.  The regimes of the
 hidden matrix are asserted on pre = O.mx_linear(x, W1, b1) and on torch's CPU GELU of it:
 they hold with a margin of many ulps, the device's own GELU may differ in the last bits."""
 import math
@@ -15,6 +16,7 @@ import numpy as np
 import torch
 
 import gate_cases as GC
+from gpu_support import same_bits
 from oracle import mx_oracle as O
 
 F32 = np.float32
@@ -23,7 +25,8 @@ MLP_NBK_MAX = 72  # mxa_mlp.hpp kMlpNbkMax: the K-blocks the fused fc1 stages in
 
 
 def case(rows, inf, hid, outf, seed):
-    """ordinary data: x ~ N(0, 1), pre of standard deviation about 0.15 sqrt(inf)"""
+    """ordinary data: x ~ N(0, 1), pre of standard deviation about 0.15 sqrt(inf) (the MXINT4
+    tests' too: int4_cases.mlp_case)"""
     rng = np.random.default_rng(seed)
     x = rng.standard_normal((rows, inf), dtype=F32)
     W1 = (rng.standard_normal((hid, inf), dtype=F32) * F32(0.15)).astype(F32)
@@ -92,26 +95,11 @@ K_EDGE_ROWS, K_EDGE_HID, K_EDGE_OUT = 33, 64, 40
 K_EDGE_INF = (2304, 2290, 2336)  # 72 blocks; 72 blocks, 18 valid columns in the last; 73 blocks
 
 
-def _blocks_to_unit(a):
-    """every 32-block of the rows normalised to max |.| in [1, 2) (a ragged last block by its
-    valid columns)"""
-    n = a.shape[1]
-    nb = (n + 31) // 32
-    p = np.zeros((a.shape[0], nb * 32), F32)
-    p[:, :n] = a
-    bm = np.abs(p.reshape(a.shape[0], nb, 32)).max(-1)
-    return (a * np.repeat(np.exp2(-np.floor(np.log2(bm))).astype(F32), 32, axis=1)[:, :n]).astype(F32)
-
-
 def k_edge(inf):
     """test_mx_linear_long_k_tile_vs_oracle's operands: every block of x and W1 normalised, x's
     blocks then scaled by 2^0 .. 2^3 (each K-block contributes at its own scale); W1 by 2^-6 so
     that pre stays of order 1 and the GELU is not saturated."""
-    rng = np.random.default_rng(inf)
-    nb = (inf + 31) // 32
-    x = _blocks_to_unit(rng.standard_normal((K_EDGE_ROWS, inf), dtype=F32))
-    x *= np.repeat(np.exp2(rng.integers(0, 4, size=(K_EDGE_ROWS, nb))).astype(F32), 32, axis=1)[:, :inf]
-    W1 = (_blocks_to_unit(rng.standard_normal((K_EDGE_HID, inf), dtype=F32)) * F32(2.0 ** -6)).astype(F32)
+    x, W1 = GC.k_edge_operands(np.random.default_rng(inf), K_EDGE_ROWS, K_EDGE_HID, inf, -6)
     _, _, b1, W2, b2 = case(K_EDGE_ROWS, 32, K_EDGE_HID, K_EDGE_OUT, inf + 1)
     return x, W1, b1, W2, b2
 
@@ -308,18 +296,6 @@ def gelu_closed_form(pre):
     tiny = np.abs(pre) <= F32(2.0 ** -30)
     out[tiny] = (pre[tiny] * F32(0.5)).astype(F32)
     return out
-
-
-def same_bits(a, b, what=""):
-    """float32 arrays equal as uint32 (the sign of zero counts), NaN against NaN allowed"""
-    a, b = np.ascontiguousarray(a, dtype=F32), np.ascontiguousarray(b, dtype=F32)
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    ok = (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))
-    if not ok.all():
-        bad = np.argwhere(~ok)
-        i = tuple(bad[0])
-        raise AssertionError(f"{what}: {bad.shape[0]}/{ok.size} mismatches, first {bad[:4].tolist()}: "
-                             f"{a[i]!r} ({a.view(np.uint32)[i]:#010x}) vs {b[i]!r} ({b.view(np.uint32)[i]:#010x})")
 
 
 def assert_gelu_pinned(kind, x, W1, b1, t):

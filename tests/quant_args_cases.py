@@ -2,11 +2,16 @@
 tests/golden/gen_quant_args_golden.py (the reference's _quantize_bfloat, _quantize_mx and
 _shared_exponents over all their arguments), the bit comparison, and the codes that the
 three top-binade / zero-sign classes of DESIGN.md §2 are witnessed at."""
+import functools
 import os
 
 import numpy as np
 
-G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+import gpu_support
+from gpu_support import G
+
+# every comparison here is one of bit patterns: the fixtures hold uint32 / uint16 arrays
+same_bits = functools.partial(gpu_support.same_bits, patterns=True)
 ROUNDS = ("nearest", "floor", "even")
 F32_BFLOATS = (10, 13, 16, 19, 24, 31)
 # (bfloat, round, allow_denorm) stored for every 16-bit pattern
@@ -35,34 +40,6 @@ def load(name):
     return _CACHE[name]
 
 
-def bits(a):
-    """float32 -> uint32 patterns; uint16 / uint32 patterns as they are."""
-    a = np.ascontiguousarray(a)
-    return a.view(np.uint32) if a.dtype == np.float32 else a
-
-
-def is_nan_bits(u):
-    if u.dtype == np.uint32:
-        return (u & 0x7FFFFFFF) > 0x7F800000
-    raise TypeError(u.dtype)
-
-
 def nan16(u, dt):
     inf = 0x7C00 if dt == "f16" else 0x7F80
     return (u & 0x7FFF) > inf
-
-
-def same_bits(got, ref, what, dt=None, x=None):
-    """Equal bit patterns; a NaN on both sides counts as equal.  Nothing else is left out."""
-    g, r = bits(got), bits(ref)
-    assert g.shape == r.shape and g.dtype == r.dtype, (what, g.shape, r.shape, g.dtype, r.dtype)
-    gn, rn = (is_nan_bits(g), is_nan_bits(r)) if g.dtype == np.uint32 else (nan16(g, dt), nan16(r, dt))
-    ok = (g == r) | (gn & rn)
-    if not ok.all():
-        bad = np.argwhere(~ok)
-        first = []
-        for i in bad[:4]:
-            i = tuple(i)
-            src = "" if x is None or np.shape(x) != g.shape else f" x={int(bits(x)[i]):#x}"
-            first.append(f"{list(i)}:{src} got {int(g[i]):#x} want {int(r[i]):#x}")
-        raise AssertionError(f"{what}: {bad.shape[0]}/{ok.size} mismatches; " + "; ".join(first))

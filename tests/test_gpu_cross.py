@@ -14,39 +14,11 @@ import pytest
 import torch
 
 import cross_cases as CC
+from gpu_support import OUT_TOL, M, dev, dev_opt, host, same  # noqa: F401
 from oracle import mx_oracle as O
 
 pytestmark = pytest.mark.gpu
-OUT_TOL = 1e-3
 MODES = ("ex_pred", "MXINT4", "two_step_leading_ones")
-
-
-def dev(x):
-    return torch.from_numpy(np.ascontiguousarray(x)).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
-def same(a, b, what=""):
-    a, b = np.asarray(a), np.asarray(b)
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    ok = (a == b) | (np.isnan(a) & np.isnan(b)) if a.dtype.kind == "f" else a == b
-    if not ok.all():
-        bad = np.argwhere(~ok)
-        raise AssertionError(f"{what}: {bad.shape[0]}/{ok.size} mismatches, first {bad[:4].tolist()}: "
-                             f"{a[tuple(bad[0])]} vs {b[tuple(bad[0])]}")
-
-
-@pytest.fixture(scope="module")
-def M():
-    import mx_quantization_amd as m
-    return m
-
-
-def _d(a):
-    return None if a is None else dev(a)
 
 
 def _check(M, name, mode, flush, bfloat=0, with_bias=True):
@@ -55,7 +27,7 @@ def _check(M, name, mode, flush, bfloat=0, with_bias=True):
     D = C // H
     x, cond, Wq, bq, Wkv, bkv, Wo, bo = CC.case(name)
     c = CC.chain(name, mode, flush, bfloat, with_bias)
-    r, bias = c["r"], _d(c["bias"])
+    r, bias = c["r"], dev_opt(c["bias"])
     kw = dict(k_top=k_top, pred_mode=mode, bias=bias, flush_subnormals=flush, bfloat=bfloat)
     args = (dev(x), dev(cond), dev(Wq), dev(bq), dev(Wkv), dev(bkv), H, D ** -0.5)
     out, idx, q, kv = M.mx_cross_attention(*args, return_proj=True, **kw)
@@ -173,7 +145,7 @@ def test_cross_projection_digit_subnormal_gate(M, which):
     pass (H = 2): cross_cases.subnormal_case, asserted in test_cross_cpu."""
     H, x, cond, Wq, bq, Wkv, bkv = CC.subnormal_case(which)
     D = x.shape[-1] // H
-    _, _, q, kv = M.mx_cross_attention(dev(x), dev(cond), dev(Wq), _d(bq), dev(Wkv), _d(bkv), H, D ** -0.5, k_top=10,
+    _, _, q, kv = M.mx_cross_attention(dev(x), dev(cond), dev(Wq), dev_opt(bq), dev(Wkv), dev_opt(bkv), H, D ** -0.5, k_top=10,
                                        return_proj=True)
     torch.cuda.synchronize()
     same(host(q), O.mx_linear(x, Wq, bq), "q behind the subnormal gate")

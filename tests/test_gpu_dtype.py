@@ -11,71 +11,24 @@ Bit-exact: MX values, shared exponents, true / approximate scores, top-k indices
 pattern of the output.  Tolerance: the output, normwise over its finite elements, within
 the dtype's rounding (float16 1e-3, bfloat16 8e-3: the reference's P.V order is unpinned,
 SURVEY.md F7, and bfloat16 carries 8 significant bits)."""
+import functools
 import os
 
 import numpy as np
 import pytest
 import torch
 
+import gpu_support
+from gpu_support import TDT, G, M, from_bits, out_close, same, same_bits, to_f32  # noqa: F401
+
 pytestmark = pytest.mark.gpu
-G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-TDT = {"f16": torch.float16, "bf16": torch.bfloat16}
 TOL = {"f16": 1e-3, "bf16": 8e-3}
+host = functools.partial(gpu_support.host, f32=True)  # every tensor here may be a 16-bit one
 
 
 @pytest.fixture(scope="module")
 def D():
     return np.load(os.path.join(G, "attn_dtype.npz"))
-
-
-@pytest.fixture(scope="module")
-def M():
-    import mx_quantization_amd as m
-    return m
-
-
-def from_bits(bits, dt):
-    return torch.from_numpy(np.ascontiguousarray(bits).view(np.int16)).view(TDT[dt]).cuda()
-
-
-def to_f32(bits, dt):
-    """uint16 bit patterns of the dtype -> float32 values (exact)."""
-    return torch.from_numpy(np.ascontiguousarray(bits).view(np.int16)).view(TDT[dt]).float().numpy()
-
-
-def host(t):
-    return t.detach().float().cpu().numpy()
-
-
-def same(a, b, what=""):
-    a, b = np.asarray(a), np.asarray(b)
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    ok = (a == b) | (np.isnan(a) & np.isnan(b)) if a.dtype.kind == "f" else a == b
-    if not ok.all():
-        bad = np.argwhere(~ok)
-        raise AssertionError(f"{what}: {bad.shape[0]}/{ok.size} mismatches, first {bad[:4].tolist()}: "
-                             f"{a[tuple(bad[0])]} vs {b[tuple(bad[0])]}")
-
-
-def same_bits(a, b, what=""):
-    """float32 arrays equal as bit patterns (-0.0 is not +0.0); NaN equals NaN"""
-    a, b = np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32)
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    ok = (a.view(np.uint32) == b.view(np.uint32)) | (np.isnan(a) & np.isnan(b))
-    if not ok.all():
-        bad = np.argwhere(~ok)
-        raise AssertionError(f"{what}: {bad.shape[0]}/{ok.size} mismatches, first {bad[:4].tolist()}: "
-                             f"{a[tuple(bad[0])]!r} vs {b[tuple(bad[0])]!r}")
-
-
-def out_close(got, ref, tol, what):
-    """the NaN pattern bit-exact, the finite elements within tol normwise"""
-    same(np.isnan(got), np.isnan(ref), what + " NaN pattern")
-    fin = ~np.isnan(ref)
-    if fin.any():
-        g, r = got[fin].astype(np.float64), ref[fin].astype(np.float64)
-        err = np.linalg.norm(g - r) / max(np.linalg.norm(r), 1e-30)
-        assert err <= tol, f"{what}: normwise error {err:.3e} > {tol}"
 
 
 @pytest.mark.parametrize("dt", ["f16", "bf16"])

@@ -4,22 +4,12 @@ standalone top-k, packed and 64-bit elements, and two fused calls, bit-exact aga
 libstdc++'s order."""
 import numpy as np
 import pytest
-import torch
 
 import exchange_cases as XC
+from gpu_support import M, dev  # noqa: F401
 from oracle import mx_oracle as O
 
 pytestmark = pytest.mark.gpu
-
-
-def dev(x):
-    return torch.from_numpy(np.ascontiguousarray(x)).cuda()
-
-
-@pytest.fixture(scope="module")
-def M():
-    import mx_quantization_amd as m
-    return m
 
 
 @pytest.fixture(scope="module")

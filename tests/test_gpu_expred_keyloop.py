@@ -6,8 +6,8 @@ import math
 
 import numpy as np
 import pytest
-import torch
 
+from gpu_support import M, dev, host, same  # noqa: F401
 from oracle import mx_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -15,29 +15,6 @@ pytestmark = pytest.mark.gpu
 B, H = 1, 2
 DS = (32, 64, 48)  # one block, two blocks, a second block of 16 elements
 TS = (1, 15, 16, 17, 31, 32, 33, 48, 49, 50, 64, 65, 127, 128, 129, 197, 224, 225, 256)
-
-
-@pytest.fixture(scope="module")
-def M():
-    import mx_quantization_amd as m
-    return m
-
-
-def dev(x):
-    return torch.from_numpy(np.ascontiguousarray(x)).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
-def same(a, b, what, signed=False):
-    a, b = np.asarray(a), np.asarray(b)
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    ok = (a == b) | (np.isnan(a) & np.isnan(b)) if a.dtype.kind == "f" else a == b
-    if signed:  # the zeros' signs too
-        ok &= (np.signbit(a) == np.signbit(b)) | np.isnan(a)
-    assert ok.all(), (what, np.argwhere(~ok)[:5].tolist())
 
 
 def inputs(case, T, D):

@@ -7,6 +7,7 @@ Bit-exact (compared as bits): against the reference's own mx.Linear outputs (lin
 tests/golden/gen_int4_golden.py) and against O.mx_linear(..., elem="int4").  Every input comes
 from tests/int4_cases.py, and before its first device call each test repeats the CPU
 assertion of tests/test_int4_cpu.py on which side of the gate every row block sits."""
+import functools
 import os
 
 import numpy as np
@@ -14,26 +15,11 @@ import pytest
 import torch
 
 import int4_cases as C
-from int4_cases import same_bits
+from gpu_support import G, M, check_mlp_chain, dev, host, quantize_bfloat_in_dtype, same_bits  # noqa: F401
 from oracle import mx_oracle as O
 
 pytestmark = pytest.mark.gpu
-G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 ACTS = ("gelu", "gelu_tanh")
-
-
-def dev(x):
-    return torch.from_numpy(np.ascontiguousarray(x)).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
-@pytest.fixture(scope="module")
-def M():
-    import mx_quantization_amd as m
-    return m
 
 
 @pytest.fixture(scope="module")
@@ -99,18 +85,6 @@ def test_linear_plain_vs_oracle(M, rows, inf, outf, kw, bias):
     same_bits(lin4(M, x, W, b, **kw), want, f"{rows, inf, outf} {kw}")
 
 
-def _quantize_bfloat_in_dtype(A, bfloat):
-    """_quantize_bfloat (elemwise_ops.py:201-216) on a float16 / bfloat16 tensor, every step in
-    the tensor's own dtype as torch computes it (test_gpu_proj.py)."""
-    if bfloat in (0, 32):
-        return A
-    bits = bfloat - 7
-    pe = torch.floor(torch.log2(torch.abs(A) + (A == 0).type(A.dtype))).clip(min=-126)
-    out = A / (2 ** pe) * (2 ** (bits - 2))
-    out = torch.sign(out) * torch.floor(torch.abs(out) + 0.5)
-    return out / (2 ** (bits - 2)) * (2 ** pe)
-
-
 @pytest.mark.parametrize("dt", [torch.float16, torch.bfloat16])
 @pytest.mark.parametrize("bfloat", [0, 16])
 def test_linear_autocast(M, dt, bfloat):
@@ -125,7 +99,7 @@ def test_linear_autocast(M, dt, bfloat):
     qx = O.quantize_mx(O.quantize_bfloat(x, bfloat), "int4", 32, -1)[0]
     qw = O.quantize_mx(O.quantize_bfloat(W, bfloat), "int4", 32, -1)[0]
     exact = O.exact_matmul_f32(qx, np.swapaxes(qw, -1, -2))
-    want = _quantize_bfloat_in_dtype(torch.from_numpy(exact).to(dt), bfloat)
+    want = quantize_bfloat_in_dtype(torch.from_numpy(exact).to(dt), bfloat)
     y = M.mx_linear(dev(x), dev(W), None, bfloat=bfloat, autocast=dt, elem_bits=4)
     assert y.dtype == dt
     same_bits(host(y.float()), host(want.float()), f"autocast, no bias, bfloat={bfloat}")
@@ -189,21 +163,7 @@ def test_linear_grouped_weight_tile_kernel(M, bf):
 
 
 # ---- the MLP ----------------------------------------------------------------------------------------
-def _check_chain(M, x, W1, b1, W2, b2, act, bfloat=0, w1=None, what="", flush=False):
-    """test_gpu_mlp.py's equalities at elem_bits=4: pre is mx_linear's and the oracle's fc1; y is
-    mx_linear's and the oracle's fc2 of the activation the device produced."""
-    d = lambda a: None if a is None else dev(a)  # noqa: E731
-    kw = dict(flush_subnormals=flush, bfloat=bfloat, elem_bits=4)
-    ok = dict(elem="int4", flush=flush, bfloat=bfloat or 32)
-    y, pre, a = M.mx_mlp(dev(x), dev(W1) if w1 is None else w1, d(b1), dev(W2), d(b2), act=act, return_hidden=True, **kw)
-    torch.cuda.synchronize()
-    same_bits(host(pre), host(M.mx_linear(dev(x), dev(W1), d(b1), **kw)), f"{what} pre vs mx_linear")
-    same_bits(host(pre), O.mx_linear(x, W1, b1, **ok), f"{what} pre vs oracle")
-    same_bits(host(y), host(M.mx_linear(a, dev(W2), d(b2), **kw)), f"{what} y vs mx_linear(act)")
-    same_bits(host(y), O.mx_linear(host(a), W2, b2, **ok), f"{what} y vs the oracle's Linear of act")
-    y2 = M.mx_mlp(dev(x), dev(W1) if w1 is None else w1, d(b1), dev(W2), d(b2), act=act, **kw)
-    same_bits(host(y2), host(y), f"{what} y without the hidden copies")
-    return host(y), host(pre), host(a)
+_check_chain = functools.partial(check_mlp_chain, elem_bits=4, cmp=same_bits)  # test_gpu_mlp.py's equalities, as bits
 
 
 @pytest.mark.parametrize("bias", [True, False])

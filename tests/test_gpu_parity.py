@@ -5,51 +5,16 @@ Bit-exact: MX codes/values/exponents, approximator operands, true and
 approximate scores, top-k indices in torch's CPU order, prune masks.
 Tolerance: the attention output, normwise relative error <= 1e-3 (north star;
 SURVEY.md F7)."""
-import os
-
 import numpy as np
 import pytest
 import torch
 
 import gate_cases as GC
 import topk_cases as TC
+from gpu_support import OUT_TOL, M, dev, host, load, same  # noqa: F401
 from oracle import mx_oracle as O
 
 pytestmark = pytest.mark.gpu
-G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-OUT_TOL = 1e-3
-
-
-def load(name):
-    return np.load(os.path.join(G, name))
-
-
-def dev(x):
-    return torch.from_numpy(np.ascontiguousarray(x)).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
-
-
-def same(a, b, what=""):
-    a = np.asarray(a)
-    b = np.asarray(b)
-    assert a.shape == b.shape, (what, a.shape, b.shape)
-    if a.dtype.kind == "f":
-        ok = (a == b) | (np.isnan(a) & np.isnan(b))
-    else:
-        ok = a == b
-    if not ok.all():
-        bad = np.argwhere(~ok)
-        raise AssertionError(f"{what}: {bad.shape[0]}/{ok.size} mismatches, first {bad[:4].tolist()}: "
-                             f"{a[tuple(bad[0])]} vs {b[tuple(bad[0])]}")
-
-
-@pytest.fixture(scope="module")
-def M():
-    import mx_quantization_amd as m
-    return m
 
 
 # ------------------------------------------------------------------ MFMA lane maps
@@ -810,6 +775,26 @@ def test_qkv_attention_vs_oracle_chain(M, mode, B, N, C, H, k_top):
     same(host(out), host(o2), "out vs unfused op")
 
 
+def _first_tile_digits(seed):
+    """(rng, x, W, odd) for the two projection tests below: x (2, 70, 256) ~ N(0, 1) and W
+    (768, 256) = 0.05 N(0, 1) drawn in this order from default_rng(seed).  The first 32-token
+    tile has every 32-channel block normalised to one exponent (GC.blocks_to_unit); then row t
+    scales its odd blocks by 2^s, s <= 8 in the first tile -- its row spreads are the shifts
+    themselves: the digit operands -- and up to 30 behind it (fp64 block sums are exact to a
+    34-bit span).  odd: the channels of the odd blocks."""
+    B, N, C = 2, 70, 256
+    rng = np.random.default_rng(seed)
+    x = rng.standard_normal((B, N, C), dtype=np.float32)
+    W = (rng.standard_normal((3 * C, C), dtype=np.float32) * np.float32(0.05)).astype(np.float32)
+    odd = (np.arange(C) // 32) % 2 == 1
+    x[:, :32] = GC.blocks_to_unit(x[:, :32])
+    shifts = [0, 3, 8, 9, 12, 20, 30]
+    for t in range(N):
+        s = shifts[(t // 5) % 3] if t < 32 else shifts[(t // 5) % len(shifts)]  # first tile: s <= 8
+        x[:, t, odd] *= np.float32(2.0 ** s)
+    return rng, x, W, odd
+
+
 @pytest.mark.parametrize("H", [4, 2])
 def test_qkv_projection_spread_paths(M, H):
     """The fused projection's three accumulations in one launch, bit-exact against the
@@ -821,20 +806,10 @@ def test_qkv_projection_spread_paths(M, H):
     32-token tile has every 32-channel block normalised to one exponent before its shift
     (s <= 8), so its row spreads are the shifts themselves: the digit path for the head
     groups whose weight columns spread <= 8; later tiles spread 9 .. 30."""
-    B, N, C = 2, 70, 256
+    C = 256
     D = C // H
-    rng = np.random.default_rng(11 + H)
-    x = rng.standard_normal((B, N, C), dtype=np.float32)
-    W = (rng.standard_normal((3 * C, C), dtype=np.float32) * np.float32(0.05)).astype(np.float32)
+    rng, x, W, odd = _first_tile_digits(11 + H)
     bias = (rng.standard_normal(3 * C, dtype=np.float32) * np.float32(0.1)).astype(np.float32)
-    odd = (np.arange(C) // 32) % 2 == 1
-    blk = x[:, :32].reshape(B, 32, C // 32, 32)
-    e = np.floor(np.log2(np.abs(blk).max(-1, keepdims=True)))
-    x[:, :32] = (blk * np.float32(2.0) ** -e).reshape(B, 32, C).astype(np.float32)  # block max in [1, 2)
-    shifts = [0, 3, 8, 9, 12, 20, 30]  # fp64 block sums are exact to a 34-bit span
-    for t in range(N):
-        s = shifts[(t // 5) % 3] if t < 32 else shifts[(t // 5) % len(shifts)]  # first tile: s <= 8
-        x[:, t, odd] *= np.float32(2.0 ** s)
     W[0 * C + 0 * D: 0 * C + 0 * D + D][:, odd] *= np.float32(2.0 ** 10)  # head 0's q columns
     hk = min(1, H - 1)
     W[1 * C + hk * D: 1 * C + hk * D + D][:, odd] *= np.float32(2.0 ** 8)  # a head's k columns
@@ -861,17 +836,7 @@ def test_qkv_projection_digit_subnormal_gate(M, H, regime):
     qkv bit-exact against the oracle, idx and out against the unfused op on the same qkv."""
     B, N, C = 2, 70, 256
     D = C // H
-    rng = np.random.default_rng(23 + H)
-    x = rng.standard_normal((B, N, C), dtype=np.float32)
-    W = (rng.standard_normal((3 * C, C), dtype=np.float32) * np.float32(0.05)).astype(np.float32)
-    odd = (np.arange(C) // 32) % 2 == 1
-    blk = x[:, :32].reshape(B, 32, C // 32, 32)
-    e = np.floor(np.log2(np.abs(blk).max(-1, keepdims=True)))
-    x[:, :32] = (blk * np.float32(2.0) ** -e).reshape(B, 32, C).astype(np.float32)  # block max in [1, 2)
-    shifts = [0, 3, 8, 9, 12, 20, 30]
-    for t in range(N):
-        s = shifts[(t // 5) % 3] if t < 32 else shifts[(t // 5) % len(shifts)]  # first tile: s <= 8
-        x[:, t, odd] *= np.float32(2.0 ** s)
+    rng, x, W, _ = _first_tile_digits(23 + H)
     if regime == "subnormal":
         sx = sw = -70
     else:

@@ -16,30 +16,12 @@ import pytest
 import torch
 
 import quant_args_cases as QC
+from gpu_support import TDT, M, dev, from_bits, host, out_close, to_bits  # noqa: F401
 from oracle import mx_oracle as O
 from quant_args_cases import same_bits
 
 pytestmark = pytest.mark.gpu
-TDT = {"f16": torch.float16, "bf16": torch.bfloat16}
 FLT_MAX = np.float32(3.4028234663852886e38)
-
-
-@pytest.fixture(scope="module")
-def M():
-    import mx_quantization_amd as m
-    return m
-
-
-def dev(x):
-    return torch.from_numpy(np.ascontiguousarray(x)).cuda()
-
-
-def from_bits(u16, dt):
-    return torch.from_numpy(np.ascontiguousarray(u16).view(np.int16)).view(TDT[dt]).cuda()
-
-
-def host(t):
-    return t.detach().cpu().numpy()
 
 
 def same_ints(got, want, what):
@@ -49,13 +31,6 @@ def same_ints(got, want, what):
         bad = np.argwhere(got != want)
         raise AssertionError(f"{what}: {bad.shape[0]}/{got.size} mismatches, first {bad[:4].tolist()}: "
                              f"{got[tuple(bad[0])]} vs {want[tuple(bad[0])]}")
-
-
-def to_bits(t):
-    """device tensor -> float32 array, or the uint16 patterns of a 16-bit tensor"""
-    if t.dtype == torch.float32:
-        return host(t)
-    return host(t.contiguous().view(torch.int16)).view(np.uint16)
 
 
 @pytest.fixture(scope="module")
@@ -262,14 +237,6 @@ def test_quantize_mx_row32_matches_generic(M, mbits, rnd):
 
 
 # ------------------------------------------------------------------ the shared callers
-def out_close(got, ref, tol, what):
-    same_ints(np.isnan(got), np.isnan(ref), what + " NaN pattern")
-    fin = ~np.isnan(ref)
-    g, r = got[fin].astype(np.float64), ref[fin].astype(np.float64)
-    err = np.linalg.norm(g - r) / max(np.linalg.norm(r), 1e-30)
-    assert err <= tol, f"{what}: normwise error {err:.3e} > {tol}"
-
-
 def test_mx_linear_bfloat16_top_code(M):
     """mx_linear(bfloat=16) with one FLT_MAX in x: bf16(FLT_MAX) is NaN (class A), so its
     block, and with it the output row, are NaN; the other rows bit-exact."""

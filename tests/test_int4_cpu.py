@@ -9,9 +9,9 @@ import pytest
 import torch
 
 import int4_cases as C
+from gpu_support import G
 from oracle import mx_oracle as O
 
-G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 

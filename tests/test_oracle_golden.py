@@ -9,25 +9,8 @@ import os
 import numpy as np
 import pytest
 
+from gpu_support import G, load, same
 from oracle import mx_oracle as O
-
-G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-def load(name):
-    return np.load(os.path.join(G, name))
-
-
-def same(a, b):
-    a = np.asarray(a)
-    b = np.asarray(b)
-    assert a.shape == b.shape, (a.shape, b.shape)
-    if a.dtype.kind == "f":
-        ok = (a == b) | (np.isnan(a) & np.isnan(b))
-        bad = np.argwhere(~ok)
-        assert ok.all(), f"{bad.shape[0]} mismatches, first at {bad[:3].tolist()}: {a[tuple(bad[0])]} vs {b[tuple(bad[0])]}"
-    else:
-        assert np.array_equal(a, b)
 
 
 # ---------------------------------------------------------------- exponent rule
