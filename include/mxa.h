@@ -211,6 +211,24 @@ int mxa_attention(const mxa_attn_params* p, hipStream_t stream);
 int mxa_approx_scores(const mxa_attn_params* p, hipStream_t stream);
 
 /*
+ * mxa_attention / mxa_approx_scores / mxa_attention_workspace_bytes for rows of up to 1,024
+ * keys: PixArt 512x512 self-attention, N = T = 1,024 tokens (MXSelfAttention.forward,
+ * workloads/PixArt/models/MX_transformer_block.py:624-717).  The same parameter struct,
+ * strides, outputs (out, idx_out, mask_out, true_out, pred_out) and workspace rules.  With
+ * T <= 512 they run exactly what their short siblings run.  With 513 <= T <= 1,024: the top-k
+ * path with 1 <= k_top <= 64, every pred_mode (ELSA with N == T), approx = 0, bias,
+ * flush_subnormals and bfloat, on float32 tensors -- the selection runs one wave per query row
+ * (the engine of mxa_topk's long rows) and the finishing kernel reads the kept keys from the
+ * workspace.  MXA_ERR_UNSUPPORTED, before any HIP call, with T > 512 for: top_k == 0 (the dense
+ * branch), k_top > 64, float16 / bfloat16 tensors or a nonzero autocast score_dtype, and
+ * T > 1,024.  mxa_attention and the fused projections (mxa_qkv_attention, mxa_attention_proj,
+ * mxa_cross_attention) keep their T <= 512 rule.
+ */
+int64_t mxa_attention_long_workspace_bytes(const mxa_attn_params* p);
+int mxa_attention_long(const mxa_attn_params* p, hipStream_t stream);
+int mxa_approx_scores_long(const mxa_attn_params* p, hipStream_t stream);
+
+/*
  * Which kernels mxa_attention(p) runs (no launch; the workspace may be null):
  *   MXA_PATH_ROWS_SPLIT  selection kernel (scores + top-k) then finishing kernel
  *                        (gather, softmax, MX(P), P.V on int8 MFMA) -- top_k != 0

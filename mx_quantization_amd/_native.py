@@ -90,6 +90,9 @@ _SIGS = {
     "mxa_attention_workspace_bytes": (c_i64, [ctypes.POINTER(AttnParams)]),
     "mxa_attention": (c_i32, [ctypes.POINTER(AttnParams), c_vp]),
     "mxa_approx_scores": (c_i32, [ctypes.POINTER(AttnParams), c_vp]),
+    "mxa_attention_long_workspace_bytes": (c_i64, [ctypes.POINTER(AttnParams)]),
+    "mxa_attention_long": (c_i32, [ctypes.POINTER(AttnParams), c_vp]),
+    "mxa_approx_scores_long": (c_i32, [ctypes.POINTER(AttnParams), c_vp]),
     "mxa_attention_path": (c_i32, [ctypes.POINTER(AttnParams)]),
     "mxa_attention_finish_kernel": (c_i32, [ctypes.POINTER(AttnParams)]),
     "mxa_attention_timed": (c_i32, [ctypes.POINTER(AttnParams), c_vp, c_i32, ctypes.POINTER(c_f32)]),

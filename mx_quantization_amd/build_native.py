@@ -21,6 +21,10 @@ UNITS += [("mxa_sel.hip", f"_p{i}", (f"MXA_SEL_PART={i}",)) for i in range(1, 7)
 UNITS += [("mxa_fin.hip", "", ("MXA_FIN_PART=0",))] + [("mxa_fin.hip", f"_p{i}", (f"MXA_FIN_PART={i}",)) for i in range(1, 5)]
 # the 16-row finishing kernel: float32 and float16 / bfloat16 instantiations (MXA_F16_XDT)
 UNITS += [("mxa_fin16.hip", f"_x{i}", (f"MXA_F16_XDT={i}",)) for i in range(2)]
+# ... and its float32 instantiations for rows of 513 .. 1,024 keys (MXA_F16_LONG)
+UNITS += [("mxa_fin16.hip", "_l0", ("MXA_F16_LONG=1",))]
+# the long rows' selection kernel: the dispatcher and one score mode each (MXA_SELL_PART)
+UNITS += [("mxa_sel_long.hip", "", ("MXA_SELL_PART=0",))] + [("mxa_sel_long.hip", f"_p{i}", (f"MXA_SELL_PART={i}",)) for i in range(1, 7)]
 UNITS += [("mxa_proj.hip", "", ()), ("mxa_gemm.hip", "", ())]
 # the MLP's fc1 (the digit kernel's body with the GELU + quantizing epilogue) in a unit of its own
 UNITS += [("mxa_mlp.hip", "", ())]
@@ -28,7 +32,7 @@ UNITS += [("mxa_mlp.hip", "", ())]
 UNITS += [("mxa_fin_qk.hip", f"_x{i}", (f"MXA_FQ_XDT={i}",)) for i in range(2)]
 SOURCES = sorted({u[0] for u in UNITS})
 HEADERS = ["mxa_common.hpp", "mxa_kernels.hpp", "mxa_prep.hpp", "mxa_proj.hpp", "mxa_proj_args.hpp", "mxa_gemm_parts.hpp", "mxa_finish.hpp",
-           "mxa_order.hpp", "mxa_topk_grp.hpp", "mxa_topk_wave.hpp", "mxa_finish16.hpp", "mxa_finish_qk.hpp", "mxa_tail.hpp", "mxa_gemm.hpp", "mxa_dot.hpp", "mxa_select.hpp", "mxa_rows2.hpp", "mxa_modes.hpp", "mxa_launch.hpp", "mxa_act.hpp", "mxa_mlp.hpp",
+           "mxa_order.hpp", "mxa_topk_grp.hpp", "mxa_topk_wave.hpp", "mxa_finish16.hpp", "mxa_finish_qk.hpp", "mxa_tail.hpp", "mxa_gemm.hpp", "mxa_dot.hpp", "mxa_select.hpp", "mxa_select_long.hpp", "mxa_rows2.hpp", "mxa_modes.hpp", "mxa_launch.hpp", "mxa_act.hpp", "mxa_mlp.hpp",
            "../../include/mxa.h"]
 ARCH = os.environ.get("MXA_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

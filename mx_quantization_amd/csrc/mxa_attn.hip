@@ -6,6 +6,9 @@
 //   select_kernel               approximate scores + torch-CPU-order top-k, four query
 //                               rows per wave (mxa_select.hpp, mxa_topk_grp.hpp), the
 //                               one-lane tail (mxa_tail.hpp)
+//   select_long_kernel          rows of 513 .. 1,024 keys (mxa_attention_long): one wave per query
+//                               row, the scores into the wave top-k's mirror (mxa_select_long.hpp);
+//                               finish16_kernel then reads the kept keys from the workspace
 //   finish16_kernel / finish_kernel / finish_qk_kernel
 //                               the kept keys' true scores, softmax, MX(P), P.V on int8
 //                               MFMA (mxa_finish16.hpp, mxa_finish.hpp, mxa_finish_qk.hpp)
@@ -184,6 +187,7 @@ struct AttnCall {
   const mxa_cross_params* xc;  // cross-attention's projections (q from x, k and v from cond; N and T independent)
   const mxa_proj_params* pj;   // the proj Linear behind it (y = mx.Linear(out.transpose(1,2).reshape(B,N,C)))
   bool scores_only;  // the approximate (or true) scores into p->pred_out / true_out, no top-k
+  bool long_rows;    // the *_long entry points: rows of up to kLongRowsT keys (else 512)
   hipEvent_t* ev;    // the timed entry points' stage events
   int *plan, *fin;   // plan: only report the kernel path (MXA_PATH_*), launch nothing; fin (with plan): the
                      // finishing kernel (MXA_FIN_*, 0 for the scores alone)
@@ -192,7 +196,7 @@ struct AttnCall {
 // the refusals of a call, in their order; every one before the prepared weights' header
 // checks returns without a HIP call
 int attn_validate(const AttnCall& c) {
-  const auto [p, stream, xq, xc, pj, scores_only, ev, plan, fin] = c;
+  const auto [p, stream, xq, xc, pj, scores_only, long_ok, ev, plan, fin] = c;
   if (!p) return MXA_ERR_ARG;
   if (pj) {
     if (scores_only || !p->top_k || !pj->wq || !pj->y || pj->out_features <= 0 || pj->y_row_stride < pj->out_features)
@@ -225,7 +229,12 @@ int attn_validate(const AttnCall& c) {
       (p->pred_mode == MXA_PRED_EXION || p->pred_mode == MXA_PRED_TRUE_EX || p->pred_mode == MXA_PRED_ELSA))
     return MXA_ERR_UNSUPPORTED;
   if (!valid_bfloat(p->bfloat)) return MXA_ERR_ARG;
-  if (p->T > 512 || p->D > 32 * kMaxNB) return MXA_ERR_UNSUPPORTED;
+  if (p->T > (long_ok ? kLongRowsT : kShortRowsT) || p->D > 32 * kMaxNB) return MXA_ERR_UNSUPPORTED;
+  // rows over 512 keys: the top-k path with k <= 64 (the 16-row finishing kernel without its K
+  // table) or the scores alone; float32; no fused projection
+  if (long_rows(p->T) && (xq || xc || pj || (!scores_only && (!p->top_k || p->k_top > 64)) || p->dtype != MXA_DT_F32 ||
+                          p->score_dtype > MXA_DT_F32))
+    return MXA_ERR_UNSUPPORTED;
   // the prepared weights must have been prepared for this geometry and these settings
   const int HD = p->H * p->D, fl = p->flush_subnormals, bf = p->bfloat;
   if (xq && !linear_weight_verify(xq->wq, linear_weight_header(3 * HD, xq->C, p->D, fl, bf), stream)) return MXA_ERR_ARG;
@@ -415,8 +424,13 @@ int attention_impl(const AttnCall& c) {
   const int S = S0 <= 1 ? 1 : (S0 <= 2 ? 2 : (S0 <= 4 ? 4 : 8));
   Rows2Args r2 = rows2_shape(pp, L);
   // feasibility of the path's kernels (LDS budgets), before any pointer is bound
+  // (rows over 512 keys: the one-wave-per-row selection kernel, mxa_select_long.hpp)
+  auto select = [&](bool plan) {
+    return c.long_rows && long_rows(pp.T) ? launch_select_long(r2, mode, BH, c.stream, plan)
+                                          : launch_select(r2, mode, BH, c.stream, plan);
+  };
   rc = c.scores_only ? MXA_OK : launch_rows(r2, topk, mode == kModeTrue, S, BH, c.stream, true);
-  if (!rc && ranked) rc = launch_select(r2, mode, BH, c.stream, true);
+  if (!rc && ranked) rc = select(true);
   if (rc) return rc;
   if (c.plan) {
     *c.plan = topk ? MXA_PATH_ROWS_SPLIT : MXA_PATH_ROWS_FUSED;
@@ -433,7 +447,7 @@ int attention_impl(const AttnCall& c) {
   if (rc) return rc;
   mark(1), mark(2), mark(3);  // stages 1 and 2 are empty: the operand builders run as stage 0
   rc = rows2_bind(r2, pp, L, c.pj, direct);
-  if (!rc && ranked) rc = launch_select(r2, mode, BH, c.stream, false);
+  if (!rc && ranked) rc = select(false);
   if (rc) return rc;
   mark(4);
   if (!c.scores_only) {
@@ -517,6 +531,18 @@ extern "C" int mxa_attention(const mxa_attn_params* p, hipStream_t stream) {
 
 extern "C" int mxa_approx_scores(const mxa_attn_params* p, hipStream_t stream) {
   return attention_impl({.p = p, .stream = stream, .scores_only = true});
+}
+
+extern "C" int64_t mxa_attention_long_workspace_bytes(const mxa_attn_params* p) {
+  return mxa_attention_workspace_bytes(p);  // one layout (attn_layout): no region has a 512-key limit
+}
+
+extern "C" int mxa_attention_long(const mxa_attn_params* p, hipStream_t stream) {
+  return attention_impl({.p = p, .stream = stream, .long_rows = true});
+}
+
+extern "C" int mxa_approx_scores_long(const mxa_attn_params* p, hipStream_t stream) {
+  return attention_impl({.p = p, .stream = stream, .scores_only = true, .long_rows = true});
 }
 
 extern "C" int mxa_qkv_attention(const mxa_attn_params* p, const mxa_qkv_params* xq, hipStream_t stream) {

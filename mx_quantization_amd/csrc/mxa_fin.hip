@@ -106,6 +106,8 @@ static int launch_finish(const Rows2Args& ra, int BH, hipStream_t stream, bool p
   if (kind == MXA_FIN_MFMA) return xdt ? launch_finish_qk_x1(ra, BH, stream, plan) : launch_finish_qk_x0(ra, BH, stream, plan);
   // k <= 64 (DeiT's 20 / 30, PixArt's 20): 16-row tiles, four lanes per row (also with the
   // proj's MX input codes for k <= 32); larger k with T > 256: the 32-row kernel.
+  // (rows over 512 keys, float32 only: its LONG instantiations, which stage no K table)
+  if (kind == MXA_FIN_GATHER16 && long_rows(ra.T) && !xdt) return launch_finish16_l0(ra, BH, stream, plan);
   if (kind == MXA_FIN_GATHER16) return xdt ? launch_finish16_x1(ra, BH, stream, plan) : launch_finish16_x0(ra, BH, stream, plan);
   switch (ra.nbd) {
     case 1: return launch_finish32_p1(ra, BH, stream, plan);

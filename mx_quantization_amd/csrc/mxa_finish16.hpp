@@ -33,6 +33,7 @@ namespace mxa {
 
 constexpr int kFin16 = 16;  // query rows per MFMA tile (one wave)
 constexpr int kFin16Occ = 4;  // waves per SIMD the register allocation aims at
+constexpr int kFin16LongKS = 64;  // finish16_kernel's KSL of a LONG instantiation: KS + this
 // Measured (DeiT-base, same box): the V^T codes staged in LDS per workgroup instead of read
 // from L2: 0.172 vs 0.166 ms (3 workgroups per CU instead of 4; PixArt 0.019 vs 0.021); the
 // next tile's query codes loaded one tile ahead: 0.193 ms (registers).  Phase timing (tools
@@ -48,15 +49,17 @@ struct Fin16Lds {
 };
 // xo: the per-wave area also holds the 16 x (D + 1) fp32 output tile being MX-quantized for
 // the proj Linear (over the code tile, sP and bm, which are rewritten afterwards)
+// long_k: rows of more than 512 keys -- no K tables (the kept keys' rows are read from the
+// workspace), so the size does not grow with T D
 __host__ __device__ inline Fin16Lds fin16_lds(int T, int D, int kst, int nbd, int vst, int ntb, int waves,
-                                              bool xo = false) {
+                                              bool xo = false, bool long_k = false) {
   Fin16Lds L;
   size_t o = 0;
   auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
   L.kc = o;
-  o += al((size_t)T * kst);
+  if (!long_k) o += al((size_t)T * kst);
   L.ke = o;
-  o += al((size_t)T * nbd * 2);
+  if (!long_k) o += al((size_t)T * nbd * 2);
   L.ve = o;
   o += al((size_t)ntb * D * 4);
   L.vt = o;
@@ -74,9 +77,17 @@ __host__ __device__ inline Fin16Lds fin16_lds(int T, int D, int kst, int nbd, in
 // output or bfloatX rounding (else the scores and P are plain float32); XO: the output rows
 // go to the proj Linear as MX codes along C (Rows2Args::xo_codes; float32, D % 32 == 0):
 // the tile's 16 x D block is transposed through LDS and every 32-column block of every row
-// quantized by rows_prep's per-block body (two lanes per block, all 64 lanes for D = 64)
-template <int NB, int KS, bool XDT, bool EXTRA, bool XO = false>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NB <= 2 && KS <= 12 ? kFin16Occ : (NB * KS <= 64 ? 3 : 2), 8))) void finish16_kernel(Rows2Args a) {
+// quantized by rows_prep's per-block body (two lanes per block, all 64 lanes for D = 64);
+// LONG: rows of 513 .. 1,024 keys -- the head's K table is not staged: a kept key's codes and
+// exponents are read where rows_prep left them (k of T rows per query row, L2-resident)
+// (LONG travels in the slot count, KSL = KS + kFin16LongKS: the short rows' instantiations keep
+// the names and the code they had -- a kernel of its own around a shared body changed the
+// register allocation of 49 of them, and the committed profiles name them)
+template <int NB, int KSL, bool XDT, bool EXTRA, bool XO = false>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NB <= 2 && KSL % kFin16LongKS <= 12 ? kFin16Occ : (NB * (KSL % kFin16LongKS) <= 64 ? 3 : 2), 8))) void finish16_kernel(Rows2Args a) {
+  constexpr int KS = KSL % kFin16LongKS;
+  constexpr bool LONG = KSL >= kFin16LongKS;
+  static_assert(!(LONG && (XDT || XO)), "long rows: float32, no proj codes");
   constexpr bool kRound = XDT || EXTRA;
   const int sdt = XDT ? a.s_dt : (int)kF32, idt = XDT ? a.in_dt : (int)kF32;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -85,7 +96,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NB <= 2 && 
   const int T = a.T, D = a.D, kst = a.kst, vst = a.vst, ntb = a.ntb, k = a.k_top;
   constexpr int nbd = NB;
   const int b_ = bh / a.H, h_ = bh % a.H;
-  const Fin16Lds L = fin16_lds(T, D, kst, nbd, vst, ntb, a.waves, XO);
+  const Fin16Lds L = fin16_lds(T, D, kst, nbd, vst, ntb, a.waves, XO, LONG);
   int8_t* tkc = reinterpret_cast<int8_t*>(smem + L.kc);
   int16_t* tke = reinterpret_cast<int16_t*>(smem + L.ke);
   float* tvs = reinterpret_cast<float*>(smem + L.ve);
@@ -124,7 +135,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NB <= 2 && 
   // ---- stage the head's K table and V block scales; clear the code tile ---------------
   const int64_t kb = (int64_t)bh * T;
   {
-    stage_k_table<NB>(a, kb, tkc, tke);
+    if constexpr (!LONG) stage_k_table<NB>(a, kb, tkc, tke);
     const int16_t* vssrc = a.vs + (int64_t)bh * ntb * D;
     for (int i = threadIdx.x; i < ntb * D; i += blockDim.x) tvs[i] = scale_f(exp_from16(vssrc[i]));
     for (int i = lane; i < kFin16 * vst / 16; i += 64) reinterpret_cast<uint4*>(ptile)[i] = make_uint4(0, 0, 0, 0);
@@ -152,7 +163,8 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NB <= 2 && 
       ix[t] = ixn[t];
     }
     auto true_of = [&](int j) -> float {  // the true score of key j (+ bias: EXTRA only)
-      const float acc = true_dot<NB>(qv, qe, tkc + (size_t)j * kst, tke + j * nbd);
+      const float acc = LONG ? true_dot<NB>(qv, qe, a.kc + (kb + j) * a.dpad, a.ksT + (kb + j) * nbd)
+                             : true_dot<NB>(qv, qe, tkc + (size_t)j * kst, tke + j * nbd);
       const float t = true_score<kRound>(acc, a.scale, a.bfloat, sdt);
       return kRound && brow >= 0 ? true_score_bias(t, a.bias, brow + (int64_t)j * a.bs3, idt, sdt) : t;
     };

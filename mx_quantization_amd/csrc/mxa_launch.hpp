@@ -69,8 +69,15 @@ inline RowsPrepArgs flat_rows_prep(const void* x, int64_t rows, int cols, int64_
   return r;
 }
 
+// rows of 513 .. 1,024 keys (the *_long entry points of include/mxa.h): the selection runs one
+// wave per query row (mxa_select_long.hpp) and the 16-row finishing kernel reads the kept keys
+// from the workspace instead of staging the head's K table (mxa_finish16.hpp)
+constexpr int kShortRowsT = 512, kLongRowsT = 1024;
+inline bool long_rows(int T) { return T > kShortRowsT; }
 // selection kernel (mxa_sel.hip); plan: only check the LDS budget, launch nothing
 int launch_select(const Rows2Args& ra, int mode, int BH, hipStream_t stream, bool plan);
+// ... for long rows (mxa_sel_long.hip)
+int launch_select_long(const Rows2Args& ra, int mode, int BH, hipStream_t stream, bool plan);
 // the one-lane tail's prefix (measured, DeiT-base: 48 positions 0.575-0.583 ms against 0.585-0.599
 // for 64 -- 12 KB of LDS per wave, 3 waves per SIMD instead of 2, outweighs the selection kernel's
 // extra step -- and 0.573-0.584 for 56; a 32-position prefix is slower: the selection kernel then
@@ -202,6 +209,7 @@ int launch_finish_qk_x1(const Rows2Args& ra, int BH, hipStream_t stream, bool pl
 // the 16-row finishing kernel (mxa_fin16.hip): float32 (x0), float16 / bfloat16 (x1)
 int launch_finish16_x0(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 int launch_finish16_x1(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
+int launch_finish16_l0(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);  // long rows, float32
 // the 32-row finishing kernel for NB blocks per head dim (mxa_fin.hip parts 1..4)
 int launch_finish32_p1(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 int launch_finish32_p2(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);

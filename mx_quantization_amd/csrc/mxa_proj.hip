@@ -236,9 +236,11 @@ static bool linear_weight_fetch_header(const void* wq, hipStream_t stream, Linea
   return hipStreamSynchronize(stream) == hipSuccess;
 }
 
+// (a note that does not match may be that of a buffer since freed whose address this one has
+// taken -- a framework's caching allocator hands addresses out again: the device's copy decides)
 bool linear_weight_verify(const void* wq, const LinearWeightHeader& want, hipStream_t stream) {
   LinearWeightHeader h{};
-  if (linear_weight_known_header(wq, &h)) return h == want;
+  if (linear_weight_known_header(wq, &h) && h == want) return true;
   if (!linear_weight_fetch_header(wq, stream, &h) || !(h == want)) return false;
   linear_weight_note(wq, h);
   return true;
@@ -247,15 +249,17 @@ bool linear_weight_verify(const void* wq, const LinearWeightHeader& want, hipStr
 bool linear_weight_verify_any_group(const void* wq, int out_f, int in_f, int flush, int bfloat, hipStream_t stream,
                                     int* elem_bits) {
   LinearWeightHeader h{};
-  if (!linear_weight_known_header(wq, &h)) {
+  auto fits = [&](const LinearWeightHeader& x) {
+    return x == linear_weight_header(out_f, in_f, x.gw, flush, bfloat, elem_bits ? x.elem_bits : 0);
+  };
+  if (!(linear_weight_known_header(wq, &h) && fits(h))) {  // unknown, or a stale note (linear_weight_verify)
     if (!linear_weight_fetch_header(wq, stream, &h)) return false;
     if (h.magic != kLinearWeightMagic || h.gw <= 0 || h.out_f % h.gw || (h.elem_bits != 0 && h.elem_bits != 4))
       return false;
+    if (!fits(h)) return false;
     linear_weight_note(wq, h);
   }
-  const int bits = elem_bits ? h.elem_bits : 0;
-  if (!(h == linear_weight_header(out_f, in_f, h.gw, flush, bfloat, bits))) return false;
-  if (elem_bits) *elem_bits = bits;
+  if (elem_bits) *elem_bits = elem_bits ? h.elem_bits : 0;
   return true;
 }
 

@@ -337,6 +337,9 @@ def _bind_out(p, out: torch.Tensor) -> torch.Tensor:
     return out
 
 
+LONG_ROWS_T = 512  # longer rows (up to 1,024 keys) go to mxa_attention_long / mxa_approx_scores_long
+
+
 def _new_idx(p, B, H, Nq, k_top, top_k, dev):
     """The kept indices (B, H, N, k) int64 bound to p.idx_out; None without top-k."""
     idx = torch.empty((B, H, Nq, k_top), dtype=torch.int64, device=dev) if top_k else None
@@ -390,7 +393,11 @@ def mx_topk_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: 
         true_s = torch.empty((B, H, Nq, T), dtype=torch.float32, device=dev)
         pred_s = torch.full((B, H, Nq, T), float("nan"), dtype=torch.float32, device=dev)
         p.true_out, p.pred_out = true_s.data_ptr(), pred_s.data_ptr()
-    _call_with_workspace(lib().mxa_attention_workspace_bytes, lib().mxa_attention, "mxa_attention", p, dev=dev)
+    if T > LONG_ROWS_T:  # rows of 513 .. 1,024 keys: the sibling entry points (include/mxa.h)
+        _call_with_workspace(lib().mxa_attention_long_workspace_bytes, lib().mxa_attention_long, "mxa_attention_long", p,
+                             dev=dev)
+    else:
+        _call_with_workspace(lib().mxa_attention_workspace_bytes, lib().mxa_attention, "mxa_attention", p, dev=dev)
     return (out, idx) + ((true_s, pred_s) if return_scores else ()) + ((mask,) if return_mask else ())
 
 
@@ -403,8 +410,12 @@ def mx_approx_scores(q: torch.Tensor, k: torch.Tensor, pred_mode: str = "ex_pred
                                                   flush_subnormals, bfloat, elsa_proj, autocast)
     pred = torch.empty((B, H, Nq, T), dtype=torch.float32, device=dev)
     p.pred_out = pred.data_ptr()
-    _call_with_workspace(lib().mxa_attention_workspace_bytes, lib().mxa_approx_scores, "mxa_approx_scores", p, dev=dev,
-                         bad=None)
+    if T > LONG_ROWS_T:
+        _call_with_workspace(lib().mxa_attention_long_workspace_bytes, lib().mxa_approx_scores_long,
+                             "mxa_approx_scores_long", p, dev=dev, bad=None)
+    else:
+        _call_with_workspace(lib().mxa_attention_workspace_bytes, lib().mxa_approx_scores, "mxa_approx_scores", p, dev=dev,
+                             bad=None)
     odt = _out_dtype(q, autocast)
     return pred if odt == torch.float32 else pred.to(odt)  # the values are exact in odt
 
