@@ -81,8 +81,11 @@ int launch_select_long(const Rows2Args& ra, int mode, int BH, hipStream_t stream
 // the one-lane tail's prefix (measured, DeiT-base: 48 positions 0.575-0.583 ms against 0.585-0.599
 // for 64 -- 12 KB of LDS per wave, 3 waves per SIMD instead of 2, outweighs the selection kernel's
 // extra step -- and 0.573-0.584 for 56; a 32-position prefix is slower: the selection kernel then
-// runs one more lockstep step per row).  MXA_TAIL_PREF: a tools-only
-// build of another width for same-box A/Bs (build_native defines)
+// runs one more lockstep step per row).  Measured again with the tail's block stores
+// (profiles/ab_tail_blocks.txt, libraries ld0 / p56l0 / p64l0, select stage of four alternating
+// runs): 48 positions 0.502-0.506 ms, 56 0.510-0.512, 64 0.519-0.520 -- the tail still pays for
+// record size (its LDS per wave sets the waves per SIMD), so 48 stays.  MXA_TAIL_PREF: a
+// tools-only build of another width for same-box A/Bs (build_native defines)
 #ifndef MXA_TAIL_PREF
 #define MXA_TAIL_PREF 48
 #endif

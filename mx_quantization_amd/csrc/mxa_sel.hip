@@ -39,7 +39,14 @@ static int launch_select_w(const Rows2Args& ra0, int BH, hipStream_t stream, boo
 // the one-lane tail (mxa_tail.hpp) over every row of the call: the rows the packed pass
 // handed over (the fused selection's, and the standalone mxa_topk_ws')
 template <int TW>
-static int launch_tail(const TailArgs& ta, hipStream_t stream) {
+static int launch_tail(const TailArgs& ta0, hipStream_t stream) {
+  TailArgs ta = ta0;
+  // the block stores (mxa_tail.hpp) need 16-byte aligned bases (a view one int64 into a buffer
+  // keeps the per-lane stores); the standalone values output stays per lane (ntw <= kTailMaskWords
+  // holds for every row the tail takes, 8-bit indices: it is the bound of the kernel's staging array)
+  const auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; };
+  ta.blk_st = !ta.out_vals && ta.ntw <= kTailMaskWords && al16(ta.idx_out ? (const void*)ta.idx_out : (const void*)ta.idx16) &&
+              (!ta.mask_out || al16(ta.mask_out));
   const size_t lds = tail_lds(TW);
   if (hipFuncSetAttribute(reinterpret_cast<const void*>(&topk_tail_kernel<TW>), hipFuncAttributeMaxDynamicSharedMemorySize,
                           (int)lds) != hipSuccess)

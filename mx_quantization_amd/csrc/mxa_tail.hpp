@@ -20,6 +20,12 @@
 //
 // The row's prefix lives in LDS lane-interleaved, element z of lane i at [z][i]: every
 // lane addresses its own row with a per-lane position and no two lanes ever share a bank.
+//
+// Output: a wave whose 64 rows are all pending owns three contiguous runs (64 k indices, 64 ntw
+// mask words); it stages them linearly in its LDS area and writes them as 16-byte chunks, one
+// per lane and instruction (64 cache lines per store instruction become 8).  Any other wave (a
+// row finished in the selection kernel or left for the 64-bit pass, rows past the end, outputs
+// that are only 8-byte aligned, the standalone values output) stores one row per lane.
 #pragma once
 #include "mxa_topk_grp.hpp"
 
@@ -206,7 +212,16 @@ struct TailArgs {
   int64_t ld;
   int dt;
   void* out_vals;
+  // set by launch_tail: the index and mask outputs are 16-byte aligned and there is no values
+  // output, so a wave of 64 pending rows may write its runs as 16-byte block stores
+  int blk_st;
 };
+
+// 16-byte chunks of the wave's LDS area and of global memory (the block stores)
+typedef uint32_t tv4 __attribute__((ext_vector_type(4)));
+typedef uint32_t tv2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(3))) tv4 tl128;
+typedef __attribute__((address_space(3))) tv2 tl64;
 
 // The introsort stack of a lane, in registers: 16-bit entries (cut | depth << 8), the top in
 // the low bits of s0.  A pushed segment [cut, l) always ends where the entry below it starts
@@ -234,6 +249,9 @@ struct TStack {
 // (TW words per lane: the introsort stack lives in registers, the prune-mask words are set
 // in the prefix's positions [k, k + ntw) once the kept elements are in registers)
 constexpr int kTailWaves = 1;
+// the prune-mask words of a tail row: its indices are the packed element's low byte (& 0xFF),
+// so rows of at most 256 keys
+constexpr int kTailMaskWords = 256 / 32;
 constexpr int kTailMaxK = 33;  // k handed to the tail (k - 1 <= 32: the final rank's width)
 // the record's positions the tail reads: [0, l) of an introselect hand-over (nothing past the
 // range is read again: the window loads beyond l are masked out of the stop masks), [0, k) of
@@ -251,6 +269,10 @@ __global__ __launch_bounds__(64 * kTailWaves) void topk_tail_kernel(TailArgs a) 
   const TPtr A{(tl32*)(lu32*)(smem) + (size_t)wave * 64 * TW + lane};
   const int k = a.k, nth = k - 1, m = k - 1;
   uint32_t st = 0u;
+  tl32* const S = A.p - lane;  // the wave's area, linear
+  const int64_t row0 = row - lane;
+  // (the records stay one per lane, length-limited: reading a full wave's contiguous run in
+  // 16-byte chunks and scattering it to [z][row] measured no better)
   if (row < a.rows) {
     const uint32_t* src = a.rec + row * tail_rec_words(TW);
     st = src[0];
@@ -338,6 +360,9 @@ __global__ __launch_bounds__(64 * kTailWaves) void topk_tail_kernel(TailArgs a) 
       if (ph == 3) t_rank<32>(A, m);
     }
   }
+  // a full wave of pending rows (none finished in the selection kernel, none left for the 64-bit
+  // pass, none past a.rows) owns its outputs' contiguous runs: block stores
+  const bool blk = a.blk_st && __builtin_amdgcn_ballot_w64(pend) == ~0ull;
   if (!pend) return;
   // the kept elements (k <= kTailMaxK: tail_width_for) into registers, then the
   // prune-mask words (zeros.scatter_(-1, idx, 1) as bits) set by LDS ORs in the prefix's free
@@ -349,15 +374,55 @@ __global__ __launch_bounds__(64 * kTailWaves) void topk_tail_kernel(TailArgs a) 
   for (int p = 0; p < kTailMaxK; ++p) x[p] = p < k ? (uint32_t)A[p] : 0u;
   const int ntw = a.mask_out ? a.ntw : 0;
   for (int w = 0; w < ntw; ++w) A[k + w] = 0u;
+  if (ntw)
 #pragma unroll
-  for (int p = 0; p < kTailMaxK; ++p) {
+    for (int p = 0; p < kTailMaxK; ++p)
+      if (p < k) {
+        const uint32_t ix = x[p] & 0xFFu;
+        __hip_atomic_fetch_or(A[k + (int)(ix >> 5)].p, 1u << (ix & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+      }
+  if (blk) {
+    // the indices staged at word lane k + p of the area and the mask words behind them at
+    // 64 k + lane ntw + w (k + ntw <= TW: tail_width_for; ntw <= kTailMaskWords), then
+    // each run goes out in 16-byte chunks, chunk c to lane c % 64 (64 k and 64 ntw words: whole
+    // chunks; a block's runs start at multiples of 64 rows, so they are aligned as the bases are)
+    uint32_t mw[kTailMaskWords];
+#pragma unroll
+    for (int w = 0; w < kTailMaskWords; ++w) mw[w] = w < ntw ? (uint32_t)A[k + w] : 0u;
+    wave_lds_sync();  // every lane holds its kept elements and mask words
+#pragma unroll
+    for (int p = 0; p < kTailMaxK; ++p)
+      if (p < k) S[lane * k + p] = x[p] & 0xFFu;
+#pragma unroll
+    for (int w = 0; w < kTailMaskWords; ++w)
+      if (w < ntw) S[64 * k + lane * ntw + w] = mw[w];
+    wave_lds_sync();
+    if (a.idx_out) {  // two staged words widened per chunk
+      tv4* dst = reinterpret_cast<tv4*>(a.idx_out + row0 * k);
+      for (int c = lane; c < 32 * k; c += 64) {
+        const tv2 u = *reinterpret_cast<tl64*>(S + 2 * c);
+        dst[c] = tv4{u.x, 0u, u.y, 0u};
+      }
+    } else {  // eight per chunk
+      tv4* dst = reinterpret_cast<tv4*>(a.idx16 + row0 * k);
+      for (int c = lane; c < 8 * k; c += 64) {
+        const tv4 u = *reinterpret_cast<tl128*>(S + 8 * c), w = *reinterpret_cast<tl128*>(S + 8 * c + 4);
+        dst[c] = tv4{u.x | (u.y << 16), u.z | (u.w << 16), w.x | (w.y << 16), w.z | (w.w << 16)};
+      }
+    }
+    if (ntw) {  // four mask words per chunk
+      tv4* dst = reinterpret_cast<tv4*>(a.mask_out + row0 * ntw);
+      for (int c = lane; c < 16 * ntw; c += 64) dst[c] = *reinterpret_cast<tl128*>(S + 64 * k + 4 * c);
+    }
+    return;
+  }
+#pragma unroll
+  for (int p = 0; p < kTailMaxK; ++p)
     if (p < k) {
       const uint32_t ix = x[p] & 0xFFu;
       if (a.idx_out) a.idx_out[row * k + p] = (int64_t)ix;
       else a.idx16[row * k + p] = (uint16_t)ix;
-      if (ntw) __hip_atomic_fetch_or(A[k + (int)(ix >> 5)].p, 1u << (ix & 31), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
     }
-  }
   for (int w = 0; w < ntw; ++w) a.mask_out[row * ntw + w] = (uint32_t)A[k + w];
   if (a.out_vals)  // (the packed pass sent no row with a NaN or -0 value: q_val_bad)
 #pragma unroll
