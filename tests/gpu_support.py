@@ -113,6 +113,107 @@ def out_close(got, ref, tol, what):
     assert err <= tol, f"{what}: normwise error {err:.3e} > {tol}"
 
 
+# ---- the row-wise bound on the attention output ("The attention output") ----
+ELIGIBLE_ELEMS, ELIGIBLE_ROWS = 0.005, 0.15  # the largest eligible shares a test may have
+EXACT_GAP = 150.0  # a kept score this far below the row's maximum has p = 0 on both sides
+TAU_C0 = 5.5  # ulps: exp on the device 1, numpy's exp 3, the quotients 1 (device) and 1/2 (numpy)
+
+
+def ref_chain(n):
+    """the longest chain of float32 additions in numpy's sum of n contiguous terms: in order
+    below 8; else 8 accumulators over blocks of at most 128 (16 each), 3 to combine them, one
+    per level of the pairwise recursion above 128"""
+    return n - 1 if n < 8 else -(-min(n, 128) // 8) + 3 + max(0, int(np.ceil(np.log2(n / 128))))
+
+
+def finish_kernel_of(T, D, k):
+    """mxa_launch.hpp rows_kernel_kind for a float32 call without proj codes; k = 0: dense"""
+    mfma = T <= 256 and (D + 31) // 32 <= 4
+    if not k:
+        return "dense_qk" if mfma else "dense_rows"
+    return "qk" if k >= 65 and mfma else ("fin16" if k <= 64 else "fin32")
+
+
+def n_add_and_chain(kernel, T, k):
+    """(fp32 additions per output element, longest chain of fp32 additions in the row sum) of a
+    finishing kernel, read from its code.  The three MFMA kernels add one fmaf of an exact int32
+    block sum per key block; dense_rows_kernel accumulates in fp64 and converts once.  Row sums:
+    finish16_kernel its KS slots per lane (mxa_fin16.hip: 5 / 8 / 12 / 16 for ceil(k / 4)) and two
+    quad steps; finish_kernel KS slots (mxa_fin.hip: 8 / 16 / 32 for ceil(k / 16)) and the four
+    steps of a 16-lane reduction; finish_qk_kernel 8 keys of every block per lane and two
+    steps; dense_rows_kernel ceil(T / 64) per lane and the six steps of a wave reduction."""
+    ntb = (T + 31) // 32
+    if kernel == "fin16":
+        return ntb, min(s for s in (5, 8, 12, 16) if 4 * s >= k) + 2
+    if kernel == "fin32":
+        return ntb, min(s for s in (8, 16, 32) if 16 * s >= k) + 4
+    return {"qk": (ntb, 8 * ntb + 2), "dense_qk": (ntb, 8 * ntb + 2), "dense_rows": (1, (T + 63) // 64 + 6)}[kernel]
+
+
+def out_row_bound(r, v, kernel=None):
+    """From the oracle's result r (true, attn, out; idx on the top-k path) and v alone: the
+    elementwise bound A + F on |got - r["out"]| of the kernel that runs the call, the finite
+    rows, the eligible shares (elements, rows), the kernel's name and the eligible set.
+    A = (n_add + 1) 2^-24 |Pq| @ |Vq| is the accumulation; F = sum over the eligible kept
+    elements of one code step 2^(eP - 6) |Vq|: the elements whose p lies within a relative tau
+    of a rounding tie of its block's code grid, and every non-zero element of a block whose
+    maximum lies within 2 tau of a binade boundary.  tau_j = (TAU_C0 + (chain + ref_chain) / 2 +
+    2 |x_j - max|) 2^-23 (an addition rounds by half an ulp).  A row whose kept scores all
+    equal the maximum or lie EXACT_GAP below it has no eligible element: its p are 1/m,
+    correctly rounded, on both sides."""
+    attn, true = np.asarray(r["attn"], np.float64), np.asarray(r["true"], np.float64)
+    T, D = attn.shape[-1], v.shape[-1]
+    k = r["idx"].shape[-1] if "idx" in r else 0
+    kernel = kernel or finish_kernel_of(T, D, k)
+    n_add, chain = n_add_and_chain(kernel, T, k)
+    kept = O.prune_mask(r["idx"], T) if k else np.ones(attn.shape, bool)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        pq, _, pe = O.quantize_mx(r["attn"], "int8", 32, -1)
+        vq = np.abs(O.quantize_mx(np.asarray(v, np.float32), "int8", 32, -2)[0].astype(np.float64))
+        S = np.matmul(np.abs(pq.astype(np.float64)), vq)
+        fin = np.isfinite(attn).all(-1) & np.isfinite(r["out"]).all(-1) & np.isfinite(S).all(-1)
+        gap = np.where(kept, np.abs(true - np.max(np.where(kept, true, -np.inf), -1, keepdims=True)), np.inf)
+        gap = np.where(fin[..., None], gap, np.inf)
+        loose = ((gap > 0) & (gap < EXACT_GAP)).any(-1, keepdims=True)  # (else the row is exact)
+        tau = (TAU_C0 + (chain + ref_chain(k or T)) / 2 + 2.0 * gap) * 2.0 ** -23
+        pb, _ = O.to_blocks(r["attn"], -1, 32)
+        pb = pb.astype(np.float64)
+        tb = O.to_blocks(np.where(np.isfinite(tau), tau, 0).astype(np.float32), -1, 32)[0].astype(np.float64)
+        live = O.to_blocks((kept & loose & fin[..., None] & (attn > 0)).astype(np.float32), -1, 32)[0] > 0
+        step = np.exp2(pe.astype(np.float64) - 6)  # (..., nb, 1): one code step of the block
+        y = pb / step
+        tie = np.abs(y - np.floor(y) - 0.5) <= tb * y
+        pmax = pb.max(-1, keepdims=True)
+        tmax = np.take_along_axis(tb, pb.argmax(-1)[..., None], -1)
+        mant = pmax / (64 * step)  # in [1, 2)
+        edge = (mant * (1 - 2 * tmax) < 1) | (mant * (1 + 2 * tmax) >= 2)
+        elig = live & (tie | edge)
+        F = np.matmul(O.from_blocks(np.where(elig, step, 0.0), T, -1), np.where(np.isfinite(vq), vq, 0.0))
+    shares = (elig.sum() / max(1, (kept & fin[..., None]).sum()), elig.any((-1, -2))[fin].mean() if fin.any() else 0.0)
+    return (n_add + 1) * 2.0 ** -24 * S + F, fin, shares, kernel, O.from_blocks(elig, T, -1)
+
+
+def out_rows_close(got, r, v, what, kernel=None):
+    """The attention output of a float32 call with bfloat 0 / 32 against the oracle's, row by
+    row: |got - ref| <= A + F elementwise on the finite rows (out_row_bound), the NaN pattern
+    equal everywhere.  The eligible shares are asserted first, from the oracle alone.  Prints
+    the kernel, the shares and the worst ratio; on failure its row and column."""
+    bound, fin, (se, sr), kernel, _ = out_row_bound(r, v, kernel)
+    assert se <= ELIGIBLE_ELEMS and sr <= ELIGIBLE_ROWS, f"{what}: eligible elements {se:.4%}, rows {sr:.2%}"
+    ref = np.asarray(r["out"])
+    same(np.isnan(got), np.isnan(ref), what + " NaN pattern")
+    err = np.abs(got[fin].astype(np.float64) - ref[fin].astype(np.float64))
+    b = bound[fin]
+    ratio = np.where(err == 0, 0.0, err / np.where(b > 0, b, 1e-300))
+    worst = float(ratio.max()) if ratio.size else 0.0
+    print(f"out_rows_close {what}: {kernel}, eligible elements {se:.4%} rows {sr:.2%}, worst |got - ref| / (A + F) {worst:.3f}")
+    if worst > 1:
+        i = np.unravel_index(np.argmax(ratio), ratio.shape)
+        row = np.argwhere(fin)[i[0]].tolist()
+        raise AssertionError(f"{what}: |got - ref| / (A + F) = {worst:.3f} at row {row} column {i[1]}: "
+                             f"got {got[fin][i]!r} want {ref[fin][i]!r} bound {b[i]:.3e}")
+
+
 def quantize_bfloat_in_dtype(A, bfloat):
     """_quantize_bfloat (elemwise_ops.py:201-216 -> _quantize_elemwise_core :144-160) on a
     float16 / bfloat16 tensor, every step in the tensor's own dtype as torch computes it:

@@ -10,7 +10,7 @@ import pytest
 import torch
 
 import topk_cases as TC
-from gpu_support import OUT_TOL, M, dev, host, load, out_close, same  # noqa: F401
+from gpu_support import OUT_TOL, M, dev, host, load, out_close, out_rows_close, same  # noqa: F401
 from oracle import mx_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -33,8 +33,10 @@ def run(M, q, kk, v, scale, **kw):
                 mask=host(M.unpack_mask(mask, kk.shape[-2])))
 
 
-def check(got, ref, what):
-    """ref: the oracle's (or the reference's) true, pred (absent with approx off), idx, out"""
+def check(got, ref, what, v=None):
+    """ref: the oracle's (or the reference's) true, pred (absent with approx off), idx, out; v: of
+    a float32 call with bfloat 0 / 32 and no flush checked against the oracle -- the row-wise
+    bound beside the norm"""
     T = got["true"].shape[-1]
     same(got["true"], ref["true"], what + " true")
     if "pred" in ref:
@@ -46,6 +48,8 @@ def check(got, ref, what):
     same(got["idx"], idx, what + " idx")
     same(got["mask"], O.prune_mask(idx, T), what + " mask")
     out_close(got["out"], ref["out"], OUT_TOL, what + " out")
+    if v is not None:
+        out_rows_close(got["out"], ref, v, what + " out")
 
 
 # ---- 1. the reference's own arrays --------------------------------------------------------------
@@ -63,7 +67,7 @@ def test_long_rows_vs_reference(M, mode):
 def test_long_rows_expred_grid(M, D, T, k):
     q, kk, v = qkv(1, 2, 20, T, D, 1000 * D + T)
     scale = float(D) ** -0.5
-    check(run(M, q, kk, v, scale, k_top=k), O.attention(q, kk, v, scale, k_top=k), f"D{D} T{T} k{k}")
+    check(run(M, q, kk, v, scale, k_top=k), O.attention(q, kk, v, scale, k_top=k), f"D{D} T{T} k{k}", v)
 
 
 # ---- 3. the other approximators, and the true scores ranked --------------------------------------
@@ -74,7 +78,8 @@ def test_long_rows_modes(M, mode, D, T):
     q[0, 0, :, ::7] = 0.0  # zero elements (true_ex's zero indicators)
     kw = dict(approx=False) if mode == "true" else dict(pred_mode=mode)
     scale = float(D) ** -0.5
-    check(run(M, q, kk, v, scale, k_top=20, **kw), O.attention(q, kk, v, scale, k_top=20, **kw), f"{mode} D{D} T{T}")
+    check(run(M, q, kk, v, scale, k_top=20, **kw), O.attention(q, kk, v, scale, k_top=20, **kw), f"{mode} D{D} T{T}",
+          v)
 
 
 @pytest.mark.parametrize("D,T", [(72, 600), (64, 1024)])  # (the head dims the structured matrix exists for)
@@ -86,7 +91,7 @@ def test_long_rows_elsa(M, D, T):
     kk[0, 0, 5, :] = 0.0  # a zero key row: zero norm scales query row 5
     scale = float(D) ** -0.5
     got = run(M, q, kk, v, scale, k_top=20, pred_mode="ELSA", elsa_proj=proj)
-    check(got, O.attention(q, kk, v, scale, k_top=20, pred_mode="ELSA", elsa_proj=proj), f"ELSA D{D} T{T}")
+    check(got, O.attention(q, kk, v, scale, k_top=20, pred_mode="ELSA", elsa_proj=proj), f"ELSA D{D} T{T}", v)
 
 
 # ---- 4. special rows -----------------------------------------------------------------------------
@@ -112,7 +117,7 @@ def test_long_rows_special_rows(M, D):
     q[1, 3, 40:80, :] *= (np.float32(2.0) ** -np.arange(49, 54, dtype=np.float32).repeat(8))[:, None]
     kk[1, 3, 100, 32:] *= np.float32(2.0 ** -60)
     kk[1, 3, 590, 32:] *= np.float32(2.0 ** -60)
-    check(run(M, q, kk, v, 0.125, k_top=20), O.attention(q, kk, v, 0.125, k_top=20), f"special D{D}")
+    check(run(M, q, kk, v, 0.125, k_top=20), O.attention(q, kk, v, 0.125, k_top=20), f"special D{D}", v)
 
 
 # ---- 5. bias -------------------------------------------------------------------------------------
@@ -126,7 +131,8 @@ def test_long_rows_bias(M, mode, flush):
     bias[1, 0, 2, :] = -np.inf  # every key masked: the row's softmax is NaN
     scale = float(D) ** -0.5
     got = run(M, q, kk, v, scale, k_top=20, pred_mode=mode, bias=bias, flush_subnormals=flush)
-    check(got, O.attention(q, kk, v, scale, k_top=20, pred_mode=mode, bias=bias, flush=flush), f"bias {mode} flush={flush}")
+    check(got, O.attention(q, kk, v, scale, k_top=20, pred_mode=mode, bias=bias, flush=flush), f"bias {mode} flush={flush}",
+          None if flush else v)
 
 
 # ---- 6. the depth limit and ties ------------------------------------------------------------------
@@ -138,7 +144,7 @@ def test_long_rows_depth_limit(M, T, k, mode):
     rows are random, full of ties.  Every query row's pred, idx and mask."""
     q, kk, v, _, _ = TC.fused_inputs(T, k)
     check(run(M, q, kk, v, 0.125, k_top=k, pred_mode=mode), O.attention(q, kk, v, 0.125, k_top=k, pred_mode=mode),
-          f"adversary T{T} k{k} {mode}")
+          f"adversary T{T} k{k} {mode}", v)
 
 
 # ---- 7. one full-size head group -------------------------------------------------------------------

@@ -11,7 +11,7 @@ import torch
 
 import gate_cases as GC
 import topk_cases as TC
-from gpu_support import OUT_TOL, M, dev, host, load, same  # noqa: F401
+from gpu_support import OUT_TOL, M, dev, host, load, out_rows_close, same  # noqa: F401
 from oracle import mx_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -410,7 +410,7 @@ def test_trueex_elsa_vs_oracle(M, mode, D):
                               elsa_proj=None if proj is None else dev(proj))
     got = [host(t) for t in res]
     r = O.attention(q, kk, v, D ** -0.5, k_top=30, pred_mode=mode, elsa_proj=proj)
-    _check_vs_oracle(got, r, mode)
+    _check_vs_oracle(got, r, mode, v)
 
 
 def test_fused_attention_strided_qkv_views(M):
@@ -455,6 +455,7 @@ def test_fused_attention_full_size_vs_oracle(M, cfg):
         same(pred_h[b:b + 1], r["pred"], "pred")
         same(host(idx[b:b + 1]), r["idx"], "idx")
         assert O.normwise_rel_err(host(out[b:b + 1]), r["out"]) <= OUT_TOL
+        out_rows_close(host(out[b:b + 1]), r, host(v[b:b + 1]), f"{cfg} image {b}")
 
 
 PATHS = ("split",)
@@ -467,7 +468,7 @@ def _attn_all_paths(M, q, k, v, scale, **kw):
     return [[host(t) for t in r] for r in res]
 
 
-def _check_vs_oracle(got, r, what):
+def _check_vs_oracle(got, r, what, v):
     out, idx, true_s, pred_s = got
     same(true_s, r["true"], what + " true")
     same(pred_s, r["pred"], what + " pred")
@@ -476,6 +477,7 @@ def _check_vs_oracle(got, r, what):
     same(nan_o, nan_r, what + " NaN rows")
     fin = ~nan_r.any(-1)
     assert O.normwise_rel_err(out[fin], r["out"][fin]) <= OUT_TOL, what
+    out_rows_close(out, r, v, what + " out")
 
 
 @pytest.mark.parametrize("D", [32, 64, 72, 128])
@@ -492,7 +494,7 @@ def test_expred_paths_vs_oracle(M, D, N, T, k):
     outs = _attn_all_paths(M, q, kk, v, scale, k_top=k)
     r = O.attention(q, kk, v, scale, k_top=k)
     for got, name in zip(outs, PATHS):
-        _check_vs_oracle(got, r, name)
+        _check_vs_oracle(got, r, name, v)
 
 
 @pytest.mark.parametrize("k", [20, 100])
@@ -523,7 +525,7 @@ def test_expred_special_rows(M, k):
     outs = _attn_all_paths(M, q, kk, v, 0.125, k_top=k)
     r = O.attention(q, kk, v, 0.125, k_top=k)
     for got, name in zip(outs, PATHS):
-        _check_vs_oracle(got, r, name)
+        _check_vs_oracle(got, r, name, v)
 
 
 @pytest.mark.parametrize("D", [32, 64, 72, 128])
@@ -557,6 +559,7 @@ def test_dense_branch_vs_oracle(M, D, N, T):
         same(np.isnan(o), np.isnan(ro), "NaN rows")
         fin = ~np.isnan(ro).any(-1)
         assert O.normwise_rel_err(o[fin], ro[fin]) <= OUT_TOL
+        out_rows_close(o, r, v, f"dense D{D} N{N} T{T} bias={bb is not None}")
     if T <= 256:
         import ctypes
         p, _, _, _ = M.ops._attn_params(dev(q), dev(kk), dev(v), D ** -0.5, 0, "ex_pred", False, False, None, False, 0,
@@ -595,7 +598,7 @@ def test_finish32_paths_vs_oracle(M, D, k):
         (got,) = _attn_all_paths(M, q, kk, v, D ** -0.5, k_top=k, bias=bd, return_mask=True)
         r = O.attention(q, kk, v, D ** -0.5, k_top=k, bias=bb)
         what = f"D{D} k{k} bias={bb is not None}"
-        _check_vs_oracle(got[:4], r, what)
+        _check_vs_oracle(got[:4], r, what, v)
         same(host(M.unpack_mask(torch.from_numpy(got[4]), T)), O.prune_mask(r["idx"], T), what + " mask")
 
 
@@ -642,7 +645,7 @@ def test_approx_modes_all_paths_vs_oracle(M, mode, N, T, k):
     outs = _attn_all_paths(M, q, kk, v, 72 ** -0.5, k_top=k, pred_mode=mode)
     r = O.attention(q, kk, v, 72 ** -0.5, k_top=k, pred_mode=mode)
     for got, name in zip(outs, PATHS):
-        _check_vs_oracle(got, r, name)
+        _check_vs_oracle(got, r, name, v)
 
 
 def test_pixart_cross_full_batch(M):

@@ -18,7 +18,7 @@ import pytest
 import torch
 
 import topk_cases as TC
-from gpu_support import OUT_TOL, M, dev, host, same, same_bits  # noqa: F401
+from gpu_support import OUT_TOL, M, dev, host, out_rows_close, same, same_bits  # noqa: F401
 from oracle import mx_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -100,6 +100,7 @@ def test_fused_blocks(M, shape, T, k):
     if k == 20:
         ro = O.attention(q, kk, v, 0.125, k_top=k, pred_mode="ex_pred")
         assert O.normwise_rel_err(out, ro["out"]) <= OUT_TOL
+        out_rows_close(out, ro, v, f"{shape} T{T} k{k} out")
 
 
 @pytest.mark.parametrize("r", [0, 31, 63])
