@@ -121,6 +121,15 @@ int mxa_quantize_bfloat(const void* x, void* y, int64_t n, int32_t bfloat, int32
 int mxa_approx_values(const void* x, void* out, int64_t rows, int32_t d, int64_t ld_x,
                       int64_t ld_out, int32_t op_kind, int32_t flush_subnormals, int32_t bfloat,
                       int32_t dtype, hipStream_t stream);
+/*
+ * The same with the element width of the MX codes the operands are derived from: elem_bits 8 is
+ * mxa_approx_values; 4: every op_kind from MXINT4 codes (exponent_approximation at a_elem_format
+ * "int4": MXA_OP_SIGN, MXA_OP_EXION and MXA_OP_TRUE_EX of the MXINT4 tensor, MXA_OP_MXINT8 and
+ * MXA_OP_MXINT4 both that tensor); any other width: MXA_ERR_ARG.
+ */
+int mxa_approx_values_bits(const void* x, void* out, int64_t rows, int32_t d, int64_t ld_x,
+                           int64_t ld_out, int32_t op_kind, int32_t flush_subnormals, int32_t bfloat,
+                           int32_t dtype, int32_t elem_bits, hipStream_t stream);
 
 /*
  * torch.topk(vals, k, dim=-1, largest=True, sorted=True) with torch's CPU index
@@ -227,6 +236,36 @@ int mxa_approx_scores(const mxa_attn_params* p, hipStream_t stream);
 int64_t mxa_attention_long_workspace_bytes(const mxa_attn_params* p);
 int mxa_attention_long(const mxa_attn_params* p, hipStream_t stream);
 int mxa_approx_scores_long(const mxa_attn_params* p, hipStream_t stream);
+
+/*
+ * The same three with the element width of the attention core as an argument (W4A4: the
+ * reference's PixArt inference, workloads/PixArt/scripts/mx_inference.py:106-122, runs
+ * MXSelfAttention / MXCrossAttention.forward, MX_transformer_block.py:648-717, :792-859, at
+ * w_elem_format = a_elem_format = "int4").  The same parameter struct and workspace rules.
+ *   elem_bits 8: exactly mxa_attention_long / mxa_approx_scores_long /
+ *                mxa_attention_long_workspace_bytes -- the same kernels, bytes, statuses, size.
+ *   elem_bits 4: Q and K (along D), P (along the keys) and V (along the tokens) are MXINT4 --
+ *                codes in [-7, 7], one per byte, code unit 2^(es - 2) -- and every approximator
+ *                is built from the MXINT4 MX_Q / MX_K, as exponent_approximation does at
+ *                a_elem_format "int4" (funcs/exponent_based_prediction.py:18-31): a value that
+ *                rounds to the int4 code 0 has the exp-sign "+", partial_*'s MX side is the
+ *                MXINT4 tensor, EXION's integer is MX / 2^e * 64 of the int4 value.
+ *                Float32 tensors; bfloat, flush_subnormals, bias, approx = 0, pred_mode ex_pred,
+ *                partial_Q, partial_K, MXINT4, EXION and true_ex, every optional output, D <= 128;
+ *                the top-k path with k_top <= 64 at T <= 1,024 (finish16_kernel, above 512 keys
+ *                behind select_long_kernel), and k_top > 64 or the dense branch at T <= 256
+ *                (finish_qk_kernel): PixArt's self-attention at 256 / 1,024 tokens, its 120-token
+ *                cross-attention and the dense steps of exclude_timesteps.
+ *                MXA_ERR_UNSUPPORTED, before any HIP call: MXA_PRED_ELSA (with approx), float16 /
+ *                bfloat16 tensors or a nonzero score_dtype, k_top > 64 or the dense branch with
+ *                T > 256 (finish_kernel, dense_rows_kernel), T > 1,024.
+ *   any other width: -1 / MXA_ERR_ARG before any HIP call.
+ * The fused projections have no 4-bit form (they return MXA_ERR_ARG for a 4-bit weight): a W4A4
+ * block is mxa_linear x 3, mxa_attention_bits(p, 4), mxa_linear.
+ */
+int64_t mxa_attention_bits_workspace_bytes(const mxa_attn_params* p, int32_t elem_bits);
+int mxa_attention_bits(const mxa_attn_params* p, int32_t elem_bits, hipStream_t stream);
+int mxa_approx_scores_bits(const mxa_attn_params* p, int32_t elem_bits, hipStream_t stream);
 
 /*
  * Which kernels mxa_attention(p) runs (no launch; the workspace may be null):

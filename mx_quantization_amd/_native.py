@@ -84,6 +84,7 @@ _SIGS = {
     "mxa_shared_exponents": (c_i32, [c_vp, c_vp, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "mxa_quantize_bfloat": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "mxa_approx_values": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "mxa_approx_values_bits": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "mxa_topk": (c_i32, [c_vp, c_i64, c_i32, c_i64, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp]),
     "mxa_topk_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32]),
     "mxa_topk_ws": (c_i32, [c_vp, c_i64, c_i32, c_i64, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp]),
@@ -93,6 +94,10 @@ _SIGS = {
     "mxa_attention_long_workspace_bytes": (c_i64, [ctypes.POINTER(AttnParams)]),
     "mxa_attention_long": (c_i32, [ctypes.POINTER(AttnParams), c_vp]),
     "mxa_approx_scores_long": (c_i32, [ctypes.POINTER(AttnParams), c_vp]),
+    # AttnParams by reference, elem_bits[, stream]
+    "mxa_attention_bits_workspace_bytes": (c_i64, [c_vp, c_i32]),
+    "mxa_attention_bits": (c_i32, [c_vp, c_i32, c_vp]),
+    "mxa_approx_scores_bits": (c_i32, [c_vp, c_i32, c_vp]),
     "mxa_attention_path": (c_i32, [ctypes.POINTER(AttnParams)]),
     "mxa_attention_finish_kernel": (c_i32, [ctypes.POINTER(AttnParams)]),
     "mxa_attention_timed": (c_i32, [ctypes.POINTER(AttnParams), c_vp, c_i32, ctypes.POINTER(c_f32)]),

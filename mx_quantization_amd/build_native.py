@@ -23,6 +23,8 @@ UNITS += [("mxa_fin.hip", "", ("MXA_FIN_PART=0",))] + [("mxa_fin.hip", f"_p{i}",
 UNITS += [("mxa_fin16.hip", f"_x{i}", (f"MXA_F16_XDT={i}",)) for i in range(2)]
 # ... and its float32 instantiations for rows of 513 .. 1,024 keys (MXA_F16_LONG)
 UNITS += [("mxa_fin16.hip", "_l0", ("MXA_F16_LONG=1",))]
+# ... and its MXINT4-P instantiations (mxa_attention_bits at width 4), short and long rows
+UNITS += [("mxa_fin16.hip", "_x0w4", ("MXA_F16_W4=1",)), ("mxa_fin16.hip", "_l0w4", ("MXA_F16_LONG=1", "MXA_F16_W4=1"))]
 # the long rows' selection kernel: the dispatcher and one score mode each (MXA_SELL_PART)
 UNITS += [("mxa_sel_long.hip", "", ("MXA_SELL_PART=0",))] + [("mxa_sel_long.hip", f"_p{i}", (f"MXA_SELL_PART={i}",)) for i in range(1, 7)]
 UNITS += [("mxa_proj.hip", "", ()), ("mxa_gemm.hip", "", ())]
@@ -30,6 +32,7 @@ UNITS += [("mxa_proj.hip", "", ()), ("mxa_gemm.hip", "", ())]
 UNITS += [("mxa_mlp.hip", "", ())]
 # the MFMA finishing kernel's float32 and float16 / bfloat16 instantiations (MXA_FQ_XDT)
 UNITS += [("mxa_fin_qk.hip", f"_x{i}", (f"MXA_FQ_XDT={i}",)) for i in range(2)]
+UNITS += [("mxa_fin_qk.hip", "_x0w4", ("MXA_FQ_W4=1",))]  # ... and its MXINT4-P ones
 SOURCES = sorted({u[0] for u in UNITS})
 HEADERS = ["mxa_common.hpp", "mxa_kernels.hpp", "mxa_prep.hpp", "mxa_proj.hpp", "mxa_proj_args.hpp", "mxa_gemm_parts.hpp", "mxa_finish.hpp",
            "mxa_order.hpp", "mxa_topk_grp.hpp", "mxa_topk_wave.hpp", "mxa_finish16.hpp", "mxa_finish_qk.hpp", "mxa_tail.hpp", "mxa_gemm.hpp", "mxa_dot.hpp", "mxa_select.hpp", "mxa_select_long.hpp", "mxa_rows2.hpp", "mxa_modes.hpp", "mxa_launch.hpp", "mxa_act.hpp", "mxa_mlp.hpp",

@@ -191,12 +191,15 @@ struct AttnCall {
   hipEvent_t* ev;    // the timed entry points' stage events
   int *plan, *fin;   // plan: only report the kernel path (MXA_PATH_*), launch nothing; fin (with plan): the
                      // finishing kernel (MXA_FIN_*, 0 for the scores alone)
+  int elem_bits;     // the *_bits entry points: 0 / 8 MXINT8; 4 MXINT4 for Q, K, P and V and for the codes
+                     // every approximator is derived from (include/mxa.h mxa_attention_bits)
 };
 
 // the refusals of a call, in their order; every one before the prepared weights' header
 // checks returns without a HIP call
 int attn_validate(const AttnCall& c) {
-  const auto [p, stream, xq, xc, pj, scores_only, long_ok, ev, plan, fin] = c;
+  const auto [p, stream, xq, xc, pj, scores_only, long_ok, ev, plan, fin, elem_bits] = c;
+  if (elem_bits != 0 && elem_bits != 8 && elem_bits != 4) return MXA_ERR_ARG;
   if (!p) return MXA_ERR_ARG;
   if (pj) {
     if (scores_only || !p->top_k || !pj->wq || !pj->y || pj->out_features <= 0 || pj->y_row_stride < pj->out_features)
@@ -235,6 +238,14 @@ int attn_validate(const AttnCall& c) {
   if (long_rows(p->T) && (xq || xc || pj || (!scores_only && (!p->top_k || p->k_top > 64)) || p->dtype != MXA_DT_F32 ||
                           p->score_dtype > MXA_DT_F32))
     return MXA_ERR_UNSUPPORTED;
+  // MXINT4 (mxa_attention_bits at width 4): float32; the approximators of exponent_approximation
+  // (ELSA's hashes would need the width too); the finishing kernels with an MXINT4-P
+  // instantiation -- finish16_kernel (k <= 64) and finish_qk_kernel (T <= 256); no fused projection
+  if (elem_bits == 4 &&
+      (xq || xc || pj || p->dtype != MXA_DT_F32 || p->score_dtype > MXA_DT_F32 ||
+       (p->approx && p->pred_mode == MXA_PRED_ELSA) ||
+       (!scores_only && p->T > 256 && (!p->top_k || p->k_top > 64))))
+    return MXA_ERR_UNSUPPORTED;
   // the prepared weights must have been prepared for this geometry and these settings
   const int HD = p->H * p->D, fl = p->flush_subnormals, bf = p->bfloat;
   if (xq && !linear_weight_verify(xq->wq, linear_weight_header(3 * HD, xq->C, p->D, fl, bf), stream)) return MXA_ERR_ARG;
@@ -247,7 +258,7 @@ int attn_validate(const AttnCall& c) {
 
 // the operand builder's arguments for one side: x at strides s (B, H, row), R rows per head
 RowsPrepArgs attn_rows_prep(const mxa_attn_params& pp, const AttnLayout& L, const AttnOperands& o, const void* x,
-                            const int64_t* s, int R, int op_kind) {
+                            const int64_t* s, int R, int op_kind, int elem_bits) {
   RowsPrepArgs r{};
   r.x = x; r.s0 = s[0]; r.s1 = s[1]; r.s2 = s[2];
   r.H = pp.H; r.R = R; r.rows = (int64_t)pp.B * pp.H * R; r.D = pp.D; r.nb = L.nbd; r.dpad = L.dpad;
@@ -256,6 +267,7 @@ RowsPrepArgs attn_rows_prep(const mxa_attn_params& pp, const AttnLayout& L, cons
   r.dt = pp.dtype;  // (the fused projections, which write these operands themselves, take float32 only)
   r.codes = o.codes; r.sT = o.sT; r.op = o.op; r.zind = o.z; r.sA = o.sA;
   r.signs = L.needs.prep_signs ? o.sg : nullptr;
+  r.mbits = elem_bits;
   return r;
 }
 
@@ -307,12 +319,13 @@ int launch_proj_pass(const mxa_attn_params& pp, int part, const ProjTokens& t, c
 // -> the q operands, then its key / value tokens -> the k operands and V (two launches of
 // the projection kernel by parts)
 int attn_build_operands(const AttnCall& c, const mxa_attn_params& pp, const AttnLayout& L, int opq, int opk) {
-  const RowsPrepArgs rq = attn_rows_prep(pp, L, L.q, pp.q, pp.q_strides, pp.N, opq);
-  const RowsPrepArgs rk = attn_rows_prep(pp, L, L.k, pp.k, pp.k_strides, pp.T, opk);
+  const int bits = c.elem_bits == 4 ? 4 : 8;
+  const RowsPrepArgs rq = attn_rows_prep(pp, L, L.q, pp.q, pp.q_strides, pp.N, opq, bits);
+  const RowsPrepArgs rk = attn_rows_prep(pp, L, L.k, pp.k, pp.k_strides, pp.T, opk, bits);
   ColsPrepArgs cv{};
   cv.x = pp.v; cv.s0 = pp.v_strides[0]; cv.s1 = pp.v_strides[1]; cv.s2 = pp.v_strides[2];
   cv.H = pp.H; cv.mats = (int64_t)pp.B * pp.H; cv.R = pp.T; cv.C = pp.D; cv.nb = L.ntb; cv.rpad = L.tpad;
-  cv.mbits = 8; cv.flush = pp.flush_subnormals; cv.bfloat = pp.bfloat; cv.dt = pp.dtype;
+  cv.mbits = bits; cv.flush = pp.flush_subnormals; cv.bfloat = pp.bfloat; cv.dt = pp.dtype;
   cv.codes_t = L.vt; cv.tb_major = 1; cv.scale = L.vs;
   if (c.xq) {
     const mxa_qkv_params& xq = *c.xq;
@@ -429,7 +442,8 @@ int attention_impl(const AttnCall& c) {
     return c.long_rows && long_rows(pp.T) ? launch_select_long(r2, mode, BH, c.stream, plan)
                                           : launch_select(r2, mode, BH, c.stream, plan);
   };
-  rc = c.scores_only ? MXA_OK : launch_rows(r2, topk, mode == kModeTrue, S, BH, c.stream, true);
+  const int bits = c.elem_bits == 4 ? 4 : 8;
+  rc = c.scores_only ? MXA_OK : launch_rows(r2, topk, mode == kModeTrue, S, BH, c.stream, true, bits);
   if (!rc && ranked) rc = select(true);
   if (rc) return rc;
   if (c.plan) {
@@ -451,7 +465,7 @@ int attention_impl(const AttnCall& c) {
   if (rc) return rc;
   mark(4);
   if (!c.scores_only) {
-    rc = launch_rows(r2, topk, mode == kModeTrue, S, BH, c.stream, false);
+    rc = launch_rows(r2, topk, mode == kModeTrue, S, BH, c.stream, false, bits);
     if (rc) return rc;
   }
   mark(5);
@@ -543,6 +557,23 @@ extern "C" int mxa_attention_long(const mxa_attn_params* p, hipStream_t stream) 
 
 extern "C" int mxa_approx_scores_long(const mxa_attn_params* p, hipStream_t stream) {
   return attention_impl({.p = p, .stream = stream, .scores_only = true, .long_rows = true});
+}
+
+extern "C" int64_t mxa_attention_bits_workspace_bytes(const mxa_attn_params* p, int32_t elem_bits) {
+  if (elem_bits != 8 && elem_bits != 4) return -1;
+  return mxa_attention_long_workspace_bytes(p);  // codes stay one byte each: the same regions at either width
+}
+
+extern "C" int mxa_attention_bits(const mxa_attn_params* p, int32_t elem_bits, hipStream_t stream) {
+  if (elem_bits != 8 && elem_bits != 4) return MXA_ERR_ARG;
+  if (elem_bits == 8) return mxa_attention_long(p, stream);
+  return attention_impl({.p = p, .stream = stream, .long_rows = true, .elem_bits = 4});
+}
+
+extern "C" int mxa_approx_scores_bits(const mxa_attn_params* p, int32_t elem_bits, hipStream_t stream) {
+  if (elem_bits != 8 && elem_bits != 4) return MXA_ERR_ARG;
+  if (elem_bits == 8) return mxa_approx_scores_long(p, stream);
+  return attention_impl({.p = p, .stream = stream, .scores_only = true, .long_rows = true, .elem_bits = 4});
 }
 
 extern "C" int mxa_qkv_attention(const mxa_attn_params* p, const mxa_qkv_params* xq, hipStream_t stream) {

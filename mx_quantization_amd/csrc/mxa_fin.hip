@@ -100,9 +100,15 @@ int MXA_FIN_FN(MXA_FIN_PART)(const Rows2Args& ra, int BH, hipStream_t stream, bo
   return launch_finish_nb<MXA_FIN_PART>(ra, BH, stream);
 }
 #else
-static int launch_finish(const Rows2Args& ra, int BH, hipStream_t stream, bool plan) {
+static int launch_finish(const Rows2Args& ra, int BH, hipStream_t stream, bool plan, int elem_bits) {
   const int kind = rows_kernel_kind(true, ra.k_top, ra.T, ra.nbd, ra.xo_codes != nullptr);
   const bool xdt = ra.s_dt != kF32 || ra.in_dt != kF32;
+  if (elem_bits == 4) {  // MXINT4 P: the 16-row kernel (short and LONG) and the MFMA kernel, float32
+    if (xdt || ra.xo_codes) return MXA_ERR_UNSUPPORTED;
+    if (kind == MXA_FIN_MFMA) return launch_finish_qk_x0w4(ra, BH, stream, plan);
+    if (kind != MXA_FIN_GATHER16) return MXA_ERR_UNSUPPORTED;
+    return long_rows(ra.T) ? launch_finish16_l0w4(ra, BH, stream, plan) : launch_finish16_x0w4(ra, BH, stream, plan);
+  }
   if (kind == MXA_FIN_MFMA) return xdt ? launch_finish_qk_x1(ra, BH, stream, plan) : launch_finish_qk_x0(ra, BH, stream, plan);
   // k <= 64 (DeiT's 20 / 30, PixArt's 20): 16-row tiles, four lanes per row (also with the
   // proj's MX input codes for k <= 32); larger k with T > 256: the 32-row kernel.
@@ -118,12 +124,13 @@ static int launch_finish(const Rows2Args& ra, int BH, hipStream_t stream, bool p
 }
 
 // the row kernel of the path: the finishing kernel (top-k) or the dense kernel
-int launch_rows(const Rows2Args& ra, bool topk, bool true_mode, int S, int BH, hipStream_t stream, bool plan) {
+int launch_rows(const Rows2Args& ra, bool topk, bool true_mode, int S, int BH, hipStream_t stream, bool plan,
+                int elem_bits) {
   if (topk) {
     // the selection kernel already wrote the true scores when it ranked them
     Rows2Args rf = ra;
     if (true_mode) rf.true_out = nullptr;
-    return launch_finish(rf, BH, stream, plan);
+    return launch_finish(rf, BH, stream, plan, elem_bits);
   }
   // the dense branch: the MFMA finishing kernel with every key kept (T <= 256: a row's scores
   // in registers); longer rows: the v_dot4 row kernel
@@ -131,9 +138,11 @@ int launch_rows(const Rows2Args& ra, bool topk, bool true_mode, int S, int BH, h
     Rows2Args rd = ra;
     rd.dense = 1;
     rd.mask_out = nullptr;
+    if (elem_bits == 4) return launch_finish_qk_x0w4(rd, BH, stream, plan);  // (refuses float16 / bfloat16)
     if (rd.s_dt != kF32 || rd.in_dt != kF32) return launch_finish_qk_x1(rd, BH, stream, plan);
     return launch_finish_qk_x0(rd, BH, stream, plan);
   }
+  if (elem_bits == 4) return MXA_ERR_UNSUPPORTED;  // dense_rows_kernel: MXINT8 P only
   switch (S) {
     case 1: return launch_dense_s<1>(ra, BH, stream, plan);
     case 2: return launch_dense_s<2>(ra, BH, stream, plan);

@@ -3,6 +3,8 @@
 // MXA_F16_XDT=1 the float16 / bfloat16 ones (launch_finish16_x1), so that they build in
 // parallel with the other finishing kernels.  A third compilation, MXA_F16_LONG=1 (float32
 // only), holds the LONG instantiations for rows of 513 .. 1,024 keys (launch_finish16_l0).
+// MXA_F16_W4=1 (float32 only, with or without MXA_F16_LONG): the MXINT4-P instantiations of
+// mxa_attention_bits at width 4 (launch_finish16_x0w4, launch_finish16_l0w4).
 #include "mxa_finish16.hpp"
 #include "mxa_launch.hpp"
 
@@ -12,7 +14,14 @@
 #ifndef MXA_F16_LONG
 #define MXA_F16_LONG 0
 #endif
-#if MXA_F16_LONG
+#ifndef MXA_F16_W4
+#define MXA_F16_W4 0
+#endif
+#if MXA_F16_W4 && MXA_F16_LONG
+#define MXA_F16_FN launch_finish16_l0w4
+#elif MXA_F16_W4
+#define MXA_F16_FN launch_finish16_x0w4
+#elif MXA_F16_LONG
 #define MXA_F16_FN launch_finish16_l0
 #elif MXA_F16_XDT
 #define MXA_F16_FN launch_finish16_x1
@@ -24,7 +33,8 @@ namespace mxa {
 
 constexpr bool kF16Xdt = MXA_F16_XDT != 0;
 constexpr bool kF16Long = MXA_F16_LONG != 0;
-static_assert(!(kF16Xdt && kF16Long), "long rows: float32 only");
+constexpr bool kF16W4 = MXA_F16_W4 != 0;
+static_assert(!(kF16Xdt && (kF16Long || kF16W4)), "long rows, MXINT4 P: float32 only");
 
 // waves per workgroup by finish_tile_plan (mxa_launch.hpp) from the waves per SIMD the
 // kernel's registers allow
@@ -36,7 +46,7 @@ static int finish16_plan(const Rows2Args& ra, int BH, int regs_waves_per_simd, i
 template <int NB, int KS, bool EXTRA, bool XO = false>
 static int launch_finish16_x(const Rows2Args& ra0, int BH, hipStream_t stream) {
   Rows2Args ra = ra0;
-  constexpr auto kernel = &finish16_kernel<NB, KS + (kF16Long ? kFin16LongKS : 0), kF16Xdt, EXTRA, XO>;
+  constexpr auto kernel = &finish16_kernel<NB, KS + (kF16Long ? kFin16LongKS : 0) + (kF16W4 ? kFin16Bits4KS : 0), kF16Xdt, EXTRA, XO>;
   int rc = finish16_plan(ra, BH, kernel_waves_per_simd<kernel>(), &ra.waves, &ra.rows_per_wg);
   if (rc) return rc;
   const size_t lds = fin16_lds(ra.T, ra.D, ra.kst, ra.nbd, ra.vst, ra.ntb, ra.waves, XO, kF16Long).total;
@@ -47,7 +57,7 @@ static int launch_finish16_ks(const Rows2Args& ra, int BH, hipStream_t stream) {
   // EXTRA: a bias, the debug true scores or bfloatX rounding (float16 / bfloat16 always round)
   const bool extra = kF16Xdt || ra.bias || ra.true_out || (ra.bfloat != 0 && ra.bfloat != 32);
   if (ra.xo_codes) {  // the proj Linear's MX input codes: float32, D % 32 == 0, k <= 32
-    if constexpr (!kF16Xdt && !kF16Long && KS <= 8) {
+    if constexpr (!kF16Xdt && !kF16Long && !kF16W4 && KS <= 8) {
       if (ra.D % 32) return MXA_ERR_UNSUPPORTED;
       return extra ? launch_finish16_x<NB, KS, true, true>(ra, BH, stream) : launch_finish16_x<NB, KS, false, true>(ra, BH, stream);
     }
@@ -69,7 +79,8 @@ static int launch_finish16_nb(const Rows2Args& ra, int BH, hipStream_t stream) {
 }
 
 int MXA_F16_FN(const Rows2Args& ra, int BH, hipStream_t stream, bool plan) {
-  if (ra.xo_codes && (kF16Xdt || kF16Long || ra.k_top > 32 || ra.D % 32)) return MXA_ERR_UNSUPPORTED;
+  if (ra.xo_codes && (kF16Xdt || kF16Long || kF16W4 || ra.k_top > 32 || ra.D % 32)) return MXA_ERR_UNSUPPORTED;
+  if (kF16W4 && (ra.s_dt != kF32 || ra.in_dt != kF32)) return MXA_ERR_UNSUPPORTED;
   if (kF16Long != long_rows(ra.T)) return MXA_ERR_UNSUPPORTED;
   if (plan) {
     int w, r;

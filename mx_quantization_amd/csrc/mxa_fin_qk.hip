@@ -1,14 +1,20 @@
 // Launches of the finishing kernel with every key's score on MFMA (mxa_finish_qk.hpp).
 // Compiled twice (build_native.py): MXA_FQ_XDT=0 the float32 instantiations
 // (launch_finish_qk_x0), MXA_FQ_XDT=1 the float16 / bfloat16 ones (launch_finish_qk_x1),
-// so that the two build in parallel.
+// so that the two build in parallel.  MXA_FQ_W4=1 (float32 only): the MXINT4-P instantiations
+// of mxa_attention_bits at width 4 (launch_finish_qk_x0w4).
 #include "mxa_finish_qk.hpp"
 #include "mxa_launch.hpp"
 
 #ifndef MXA_FQ_XDT
 #define MXA_FQ_XDT 0
 #endif
-#if MXA_FQ_XDT
+#ifndef MXA_FQ_W4
+#define MXA_FQ_W4 0
+#endif
+#if MXA_FQ_W4
+#define MXA_FQ_FN launch_finish_qk_x0w4
+#elif MXA_FQ_XDT
 #define MXA_FQ_FN launch_finish_qk_x1
 #else
 #define MXA_FQ_FN launch_finish_qk_x0
@@ -17,6 +23,8 @@
 namespace mxa {
 
 constexpr bool kXdt = MXA_FQ_XDT != 0;
+constexpr bool kW4 = MXA_FQ_W4 != 0;
+static_assert(!(kXdt && kW4), "MXINT4 P: float32 only");
 
 // ---- finishing kernel, every key's score on MFMA (mxa_finish_qk.hpp) ------------------
 // key blocks the kernel's registers hold (template NTB): 4 or 8
@@ -29,7 +37,7 @@ static int finish_qk_plan(const Rows2Args& ra, int nb, int BH, int regs_waves_pe
 }
 template <int NB, int NTB, bool XDT, bool EXTRA>
 static int launch_finish_qk_x(Rows2Args ra, int BH, hipStream_t stream) {
-  constexpr auto kernel = &finish_qk_kernel<NB, NTB, XDT, EXTRA>;
+  constexpr auto kernel = &finish_qk_kernel<NB, NTB + (kW4 ? kFqBits4NTB : 0), XDT, EXTRA>;
   int rc = finish_qk_plan(ra, NB, BH, kernel_waves_per_simd<kernel>(), &ra.waves, &ra.rows_per_wg);
   if (rc) return rc;
   return launch_finish_tiles<kernel>(ra, BH, fq_lds(ra.ntb, NB, NTB, ra.D).total, stream);
@@ -48,6 +56,7 @@ static int launch_finish_qk_nb(const Rows2Args& ra, int BH, hipStream_t stream) 
 }
 
 int MXA_FQ_FN(const Rows2Args& ra, int BH, hipStream_t stream, bool plan) {
+  if (kW4 && (ra.s_dt != kF32 || ra.in_dt != kF32)) return MXA_ERR_UNSUPPORTED;
   if (plan) {
     int w, r;
     return finish_qk_plan(ra, ra.nbd, BH, 2, &w, &r);

@@ -110,11 +110,12 @@ struct PBlock {
   bool flush;
   float sP;
 };
-__device__ __forceinline__ PBlock p_block(uint32_t maxbits, int flush_p, int sdt) {
+// (unit: the code unit is 2^(es - unit): 6 for MXINT8 codes, 2 for MXINT4 ones)
+__device__ __forceinline__ PBlock p_block(uint32_t maxbits, int flush_p, int sdt, int unit = 6) {
   int e_raw;
   const int es = scale_exponent_dt(maxbits, 127, sdt, &e_raw);
   const bool fl = flush_p && !(e_raw != kExpNaN && e_raw > -127);
-  return {es, fl, scale_f(es == kExpNaN ? kExpNaN : es - 6)};
+  return {es, fl, scale_f(es == kExpNaN ? kExpNaN : es - unit)};
 }
 // the gather kernels pass a block to the lanes that code its elements as one LDS word: es +
 // 1024 (0 = a NaN block: no codes), the flush flag in bit 16.  The code of p from that
@@ -129,6 +130,19 @@ __device__ __forceinline__ float p_code_f32(float p, float mult) {
   const float y = (p * mult) * 64.0f;
   return fminf(floorf(y + 0.5f), 127.0f);
 }
+// the same for MXINT4 P (mxa_attention_bits at width 4): floor(p 2^-es 4 + 0.5), <= 7, with the
+// block scale sP = 2^(es - 2); the block rule (es, flush) does not depend on the width
+__device__ __forceinline__ float p_code4_f32(float p, float mult) {
+  const float y = (p * mult) * 4.0f;
+  return fminf(floorf(y + 0.5f), 7.0f);
+}
+// W4 ? the MXINT4 rule : the MXINT8 rule, and the exponent of a code unit below es
+template <bool W4>
+__device__ __forceinline__ float p_code_bits_f32(float p, float mult) {
+  return W4 ? p_code4_f32(p, mult) : p_code_f32(p, mult);
+}
+template <bool W4>
+constexpr int kPUnit = W4 ? 2 : 6;
 
 // a query row's codes (two 16-byte halves per 32-block) and block exponents
 template <int NB>

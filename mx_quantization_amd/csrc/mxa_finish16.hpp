@@ -34,6 +34,7 @@ namespace mxa {
 constexpr int kFin16 = 16;  // query rows per MFMA tile (one wave)
 constexpr int kFin16Occ = 4;  // waves per SIMD the register allocation aims at
 constexpr int kFin16LongKS = 64;  // finish16_kernel's KSL of a LONG instantiation: KS + this
+constexpr int kFin16Bits4KS = 128;  // ... and of an MXINT4-P instantiation: + this
 // Measured (DeiT-base, same box): the V^T codes staged in LDS per workgroup instead of read
 // from L2: 0.172 vs 0.166 ms (3 workgroups per CU instead of 4; PixArt 0.019 vs 0.021); the
 // next tile's query codes loaded one tile ahead: 0.193 ms (registers).  Phase timing (tools
@@ -83,11 +84,15 @@ __host__ __device__ inline Fin16Lds fin16_lds(int T, int D, int kst, int nbd, in
 // (LONG travels in the slot count, KSL = KS + kFin16LongKS: the short rows' instantiations keep
 // the names and the code they had -- a kernel of its own around a shared body changed the
 // register allocation of 49 of them, and the committed profiles name them)
+// W4: P is MXINT4 (mxa_attention_bits at width 4: codes floor(p 2^(2 - es) + 1/2) <= 7, block
+// scale 2^(es - 2); the int8 MFMA and its epilogue as they are) -- it travels in the slot count
+// too, KSL = KS (+ kFin16LongKS) + kFin16Bits4KS; float32, no proj codes
 template <int NB, int KSL, bool XDT, bool EXTRA, bool XO = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NB <= 2 && KSL % kFin16LongKS <= 12 ? kFin16Occ : (NB * (KSL % kFin16LongKS) <= 64 ? 3 : 2), 8))) void finish16_kernel(Rows2Args a) {
   constexpr int KS = KSL % kFin16LongKS;
-  constexpr bool LONG = KSL >= kFin16LongKS;
-  static_assert(!(LONG && (XDT || XO)), "long rows: float32, no proj codes");
+  constexpr bool LONG = KSL % kFin16Bits4KS >= kFin16LongKS;
+  constexpr bool W4 = KSL >= kFin16Bits4KS;
+  static_assert(!((LONG || W4) && (XDT || XO)), "long rows, MXINT4 P: float32, no proj codes");
   constexpr bool kRound = XDT || EXTRA;
   const int sdt = XDT ? a.s_dt : (int)kF32, idt = XDT ? a.in_dt : (int)kF32;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -220,7 +225,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NB <= 2 && 
       int e_raw;
       const int es = scale_exponent_dt(bm[bk], 127, sdt, &e_raw);
       const bool fl = a.flush_p && !(e_raw != kExpNaN && e_raw > -127);
-      sP[bk * kFin16 + pr] = scale_f(es == kExpNaN ? kExpNaN : es - 6);
+      sP[bk * kFin16 + pr] = scale_f(es == kExpNaN ? kExpNaN : es - kPUnit<W4>);
       if (XDT) bm[bk] = (es == kExpNaN ? 0u : (uint32_t)(es + 1024)) | (fl ? 0x10000u : 0u);
       else bm[bk] = __float_as_uint(es == kExpNaN || fl ? 0.0f : pow2f(-es));
     }
@@ -229,7 +234,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NB <= 2 && 
     for (int t = 0; t < KS; ++t) {
       const uint32_t e = bm[ix[t] >> 5];
       // (float32: a NaN block's codes do not matter, its sP is NaN)
-      const int code = XDT ? p_code_word(v[t], e, sdt) : (int)p_code_f32(v[t], __uint_as_float(e));
+      const int code = XDT ? p_code_word(v[t], e, sdt) : (int)p_code_bits_f32<W4>(v[t], __uint_as_float(e));
       ptile[pr * vst + (on[t] ? ix[t] : pad)] = (int8_t)code;
     }
     wave_lds_sync();

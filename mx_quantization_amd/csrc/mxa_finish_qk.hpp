@@ -33,6 +33,7 @@
 namespace mxa {
 
 constexpr int kFqRows = 16;  // query rows per tile (one wave)
+constexpr int kFqBits4NTB = 16;  // finish_qk_kernel's NTBW of an MXINT4-P instantiation: NTB + this
 
 typedef int v4iq_ __attribute__((ext_vector_type(4)));
 
@@ -131,8 +132,14 @@ __device__ __forceinline__ float fq_exact(const int* I, const int* e) {
 // XDT: float16 / bfloat16 inputs or scores (the dtype roundings at run time); EXTRA: a bias,
 // the debug true-score output or bfloatX rounding (the bias / output addresses per key are
 // loop invariants the compiler would otherwise hoist into 64 register pairs)
-template <int NB, int NTB, bool XDT, bool EXTRA>
+// W4: P is MXINT4 (mxa_attention_bits at width 4; the rule of p_code4_f32, mxa_finish.hpp).  It
+// travels in the key-block slot, NTBW = NTB + kFqBits4NTB, so that the MXINT8 instantiations keep
+// their names and code (as LONG does in finish16_kernel); float32 only
+template <int NB, int NTBW, bool XDT, bool EXTRA>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 8))) void finish_qk_kernel(Rows2Args a) {
+  constexpr int NTB = NTBW % kFqBits4NTB;
+  constexpr bool W4 = NTBW >= kFqBits4NTB;
+  static_assert(!(W4 && XDT), "MXINT4 P: float32");
   const int sdt = XDT ? a.s_dt : (int)kF32, idt = XDT ? a.in_dt : (int)kF32;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -393,7 +400,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
 #pragma unroll
         for (int j = 0; j < 8; ++j) bm = max(bm, __float_as_uint(v[blk][j]) & 0x7FFFFFFFu);
         bm = fq_umax4(bm);
-        const PBlock pb = p_block(bm, a.flush_p, sdt);
+        const PBlock pb = p_block(bm, a.flush_p, sdt, kPUnit<W4>);
         const int es = pb.es;
         const bool fl = pb.flush;
         const float sP = pb.sP;
@@ -404,7 +411,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
             uint32_t code;
             const float x = fl ? v[blk][j] * 0.0f : v[blk][j];
             if (XDT) code = (uint32_t)(int)round_code(x, es, 8, kRoundNearest, sdt) & 0xFFu;
-            else code = (uint32_t)p_code_f32(x, pow2f(-es));
+            else code = (uint32_t)p_code_bits_f32<W4>(x, pow2f(-es));
             if (j < 4) lo |= code << (8 * j);
             else hi |= code << (8 * (j - 4));
           }

@@ -41,7 +41,7 @@ struct RowsPrepArgs {
   int op_kind, flush, bfloat;
   int dt;         // storage dtype of x (MXA_DT_*): loads and the shared-exponent rule
   int8_t* codes;  // [rows][dpad] MXINT8 codes (nullable)
-  int16_t* sT;    // [rows][nb] exponent of a code unit: es - 6 (nullable)
+  int16_t* sT;    // [rows][nb] exponent of a code unit: es - 6; es - 2 at mbits 4 (nullable)
   int8_t* op;     // [rows][dpad] approximator operand (nullable)
   int16_t* sA;    // [rows][nb] approximator scale (nullable)
   uint32_t* signs;  // [rows][nb] bit i = (MX code i < 0) (nullable)
@@ -51,6 +51,9 @@ struct RowsPrepArgs {
                     // (one coalesced 1-KB load per wave and K-block; rows padded to 32)
   int act;          // 0: none; 1 + MXA_ACT_*: the MLP's activation (mxa_act.hpp) applied to the float32
                     // values as they are loaded (launch_rows_prep only: rows_prep_act_kernel)
+  int mbits;        // element width of the codes: 0 / 8 MXINT8; 4 MXINT4 (codes in [-7, 7], code unit
+                    // 2^(es - 2), every approximator operand from those codes; float32 rows).  The
+                    // launchers pick the kernel by it; the block body has it as a template argument
 };
 
 // ELSA sign hashes (and key norms) of rows already quantized by rows_prep:

@@ -209,17 +209,23 @@ inline int launch_finish_tiles(const Rows2Args& ra, int BH, size_t lds, hipStrea
 // the MFMA finishing kernel's launches (mxa_fin_qk.hip): float32 inputs and scores (x0), float16 / bfloat16 (x1)
 int launch_finish_qk_x0(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 int launch_finish_qk_x1(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
+int launch_finish_qk_x0w4(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);  // float32, MXINT4 P
 // the 16-row finishing kernel (mxa_fin16.hip): float32 (x0), float16 / bfloat16 (x1)
 int launch_finish16_x0(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 int launch_finish16_x1(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 int launch_finish16_l0(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);  // long rows, float32
+int launch_finish16_x0w4(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);  // float32, MXINT4 P
+int launch_finish16_l0w4(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);  // ... on long rows
 // the 32-row finishing kernel for NB blocks per head dim (mxa_fin.hip parts 1..4)
 int launch_finish32_p1(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 int launch_finish32_p2(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 int launch_finish32_p3(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 int launch_finish32_p4(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 // the row kernel of the path: finishing kernel (top-k) or dense row kernel (mxa_fin.hip)
-int launch_rows(const Rows2Args& ra, bool topk, bool true_mode, int S, int BH, hipStream_t stream, bool plan);
+// elem_bits 4 (mxa_attention_bits): P is MXINT4 -- the MXINT4-P instantiations of the 16-row and
+// the MFMA kernel; MXA_ERR_UNSUPPORTED where the call would take the 32-row or the dense row kernel
+int launch_rows(const Rows2Args& ra, bool topk, bool true_mode, int S, int BH, hipStream_t stream, bool plan,
+                int elem_bits = 8);
 // fused projection kernel (mxa_proj.hip): part 0 the self-attention q, k, v of one token
 // matrix, 1 / 2 cross-attention's q and k, v passes (mxa_proj.hpp ProjPart)
 int launch_proj(const ProjArgs& pa, hipStream_t stream, int part = 0);

@@ -26,10 +26,11 @@ __device__ __forceinline__ int exion_m(int raw) {
 // exponent of the MX-quantized block (funcs/exponent_based_prediction.py:35-36):
 // floor(log2(max |MX|)), unclamped, in the dtype; MX max = maxc * 2^(es-6) (a value of the
 // dtype: exact in float32 / bfloat16, and in float16 for es >= -18), maxc the largest |code|
-__device__ __forceinline__ int mx_block_exponent(int maxc, int es, bool nan, int dt) {
+// (unit: the code unit is 2^(es - unit) -- 6 for MXINT8, 2 for MXINT4)
+__device__ __forceinline__ int mx_block_exponent(int maxc, int es, bool nan, int dt, int unit = 6) {
   if (nan) return kExpNaN;
   if (maxc == 0) return -126;
-  return floor_log2_dt(__float_as_uint(round_dt((float)maxc * pow2f(es - 6), dt)), dt);
+  return floor_log2_dt(__float_as_uint(round_dt((float)maxc * pow2f(es - unit), dt)), dt);
 }
 
 // ---------------------------------------------------------------------------
@@ -79,9 +80,18 @@ __device__ __forceinline__ void store_block_words(const RowsPrepArgs& a, int64_t
 // mfma_base, store_block_words.  Written out here, because as shared helpers they cost the
 // general-argument projection kernels SGPR spills (qkv_proj_kernel<2..4, false> 196 -> 350
 // with all of them): the rounding + maximum loop, and the packing of codes, operand and zero
-// indicators word by word
+// indicators word by word.
+// MB: the element width.  8: MXINT8.  4: MXINT4 -- codes in [-7, 7] in the same int8 containers,
+// code unit 2^(es - 2), and every approximator operand derived from those codes, as the
+// reference's exponent_approximation does at a_elem_format = "int4" (its MX_Q / MX_K are MXINT4
+// then: funcs/exponent_based_prediction.py:18-31): a value that rounds to the int4 code 0 has
+// the sign "+", EXION's raw integer MX / 2^eA * 64 is code << (es - eA + 4) (at most 112), and
+// the MXINT8 kind (partial_*'s MX side) is the int4 code itself
+template <int MB = 8>
 __device__ __forceinline__ void rows_prep_block(const RowsPrepArgs& a, int64_t row, int blk, int sub, int c0,
                                                 float xv[16], bool valid) {
+  static_assert(MB == 8 || MB == 4, "MXINT8 or MXINT4");
+  constexpr int U = MB - 2;  // the code unit is 2^(es - U)
   uint32_t mb = 0;
 #pragma unroll
   for (int j = 0; j < 16; ++j) {
@@ -99,9 +109,9 @@ __device__ __forceinline__ void rows_prep_block(const RowsPrepArgs& a, int64_t r
   }
   int code[16];
 #pragma unroll
-  for (int j = 0; j < 16; ++j) code[j] = nanblk ? 0 : (int)round_code(xv[j], es, 8, kRoundNearest, a.dt);
+  for (int j = 0; j < 16; ++j) code[j] = nanblk ? 0 : (int)round_code(xv[j], es, MB, kRoundNearest, a.dt);
   const int maxc = row_block_codes(code, sub).maxc;
-  const int eA = mx_block_exponent(maxc, es, nanblk, a.dt);
+  const int eA = mx_block_exponent(maxc, es, nanblk, a.dt, U);
   int op[16];
   int sA;
   switch (a.op_kind) {
@@ -116,7 +126,7 @@ __device__ __forceinline__ void rows_prep_block(const RowsPrepArgs& a, int64_t r
       sA = nanblk ? kExpNaN : es - 2;
       break;
     case MXA_OP_EXION: {
-      const int sh = nanblk ? 0 : es - eA;  // MX / 2^eA * 64 = code * 2^(es-eA), an integer < 128
+      const int sh = nanblk ? 0 : es - eA + (6 - U);  // MX / 2^eA * 64 = code * 2^(es-eA+6-U), an integer < 128
 #pragma unroll
       for (int j = 0; j < 16; ++j) op[j] = nanblk ? 0 : exion_m(code[j] << sh);
       sA = eA;
@@ -125,7 +135,7 @@ __device__ __forceinline__ void rows_prep_block(const RowsPrepArgs& a, int64_t r
     case MXA_OP_TRUE_EX:
       // exponent_based_sign_leading_ones (examples/deit/exponent_based_prediction.py:163-178):
       // (mx < 0 ? -1 : 1) * 2^floor(log2|mx|), zeros -> +1.  Nonzero elements as the
-      // power-of-two code sign * 2^floor(log2|code|) in units of 2^(es-6); zeros in zind
+      // power-of-two code sign * 2^floor(log2|code|) in units of 2^(es-U); zeros in zind
 #pragma unroll
       for (int j = 0; j < 16; ++j) {
         const int ac = code[j] < 0 ? -code[j] : code[j];
@@ -134,12 +144,12 @@ __device__ __forceinline__ void rows_prep_block(const RowsPrepArgs& a, int64_t r
       }
       // a NaN block's MX values are NaN, and get_true_exponents maps them like zeros
       // (mask |x| > 0 is false: exponent 0, value +1; examples :98-110): codes 0, zind 1
-      sA = nanblk ? 0 : es - 6;
+      sA = nanblk ? 0 : es - U;
       break;
-    default:  // MXA_OP_MXINT8
+    default:  // MXA_OP_MXINT8 (the MX codes themselves, at either width)
 #pragma unroll
       for (int j = 0; j < 16; ++j) op[j] = code[j];
-      sA = nanblk ? kExpNaN : es - 6;
+      sA = nanblk ? kExpNaN : es - U;
       break;
   }
   if (valid) {
@@ -163,7 +173,7 @@ __device__ __forceinline__ void rows_prep_block(const RowsPrepArgs& a, int64_t r
   // before the operand switch it stays live across it, which costs the prep kernels 15 VGPRs
   // and with them a wave per SIMD
   const uint32_t sw = row_block_codes(code, sub).signs;
-  if (valid && sub == 0) store_block_words(a, row, blk, nanblk ? kExpNaN : es - 6, sA, sw);
+  if (valid && sub == 0) store_block_words(a, row, blk, nanblk ? kExpNaN : es - U, sA, sw);
 }
 
 // rows_prep_block for the plain case -- no bfloat rounding, no subnormal flush, no
@@ -224,6 +234,64 @@ __device__ __forceinline__ void rows_prep_block_plain(const RowsPrepArgs& a, int
       if (dt != kF32 && !nanblk && maxc != 0)
         eA = floor_log2_dt(__float_as_uint(round_dt((float)maxc * pow2f(es - 6), dt)), dt);
       const int sT = nanblk ? kExpNaN : es - 6;
+      store_block_words(a, row, blk, sT, a.op_kind == MXA_OP_SIGN ? eA : sT, rc.signs);
+    }
+  }
+}
+
+// The plain case at 4 bits (rows_prep_block<4> with no bfloat rounding, no flush, no zero
+// indicators; operand the sign, or the MXINT4 code under either of its kinds), float32 rows:
+// the kernel trace of the PixArt shapes had the general body at 21.8 us against the plain 8-bit
+// one's 16.4 (profiles/r10_attn4_bench.txt).  A body of its own, so that rows_prep_block_plain
+// and the kernels that inline it stay what they are.  The code: x * 2^(2 - es) is exact and
+// equals (x * 2^-es) * 4 (for es < -125, where 2^(2 - es) is no float, 2^-es and then * 4),
+// floor(|y| + 1/2) clipped to 7, the sign copied back (-0 converts to 0).  The block exponent:
+// floor(log2(maxc * 2^(es - 2))) = floor(log2 maxc) + es - 2 exactly (maxc <= 7).
+__device__ __forceinline__ bool rows_prep_plain4(const RowsPrepArgs& a) {
+  return (a.bfloat == 0 || a.bfloat == 32) && !a.flush && !a.zind &&
+         (a.op_kind == MXA_OP_MXINT8 || a.op_kind == MXA_OP_MXINT4 || (a.op_kind == MXA_OP_SIGN && !a.op));
+}
+__device__ __forceinline__ void rows_prep_block_plain4(const RowsPrepArgs& a, int64_t row, int blk, int sub, int c0,
+                                                       const float xv[16], bool valid) {
+  uint32_t mb = 0;
+#pragma unroll
+  for (int j = 0; j < 16; ++j) mb = max(mb, __float_as_uint(xv[j]) & 0x7FFFFFFFu);
+  mb = max(mb, pair_swap(mb));
+  int e_raw;
+  const int es = scale_exponent(mb, 127, &e_raw);
+  const bool nanblk = es == kExpNaN;
+  int code[16];
+  auto quant = [&](auto tiny) {
+    const float sc = pow2f(decltype(tiny)::value ? -es : 2 - es);
+#pragma unroll
+    for (int j = 0; j < 16; ++j) {
+      float y = xv[j] * sc;
+      if (decltype(tiny)::value) y = y * 4.0f;
+      code[j] = (int)__builtin_copysignf(fminf(floorf(fabsf(y) + 0.5f), 7.0f), y);
+    }
+  };
+  if (nanblk) {
+#pragma unroll
+    for (int j = 0; j < 16; ++j) code[j] = 0;
+  } else if (es >= -125) {
+    quant(std::false_type{});
+  } else {
+    quant(std::true_type{});
+  }
+  const RowCodes rc = row_block_codes(code, sub);
+  if (valid) {
+    uint32_t pc[4];
+#pragma unroll
+    for (int w = 0; w < 4; ++w)
+      pc[w] = (uint32_t)(code[4 * w] & 0xFF) | (uint32_t)(code[4 * w + 1] & 0xFF) << 8 |
+              (uint32_t)(code[4 * w + 2] & 0xFF) << 16 | (uint32_t)code[4 * w + 3] << 24;
+    const int64_t base = mfma_base(a, row, blk, sub, c0);
+    const uint4 v = make_uint4(pc[0], pc[1], pc[2], pc[3]);
+    if (a.codes) *reinterpret_cast<uint4*>(a.codes + base) = v;
+    if (a.op) *reinterpret_cast<uint4*>(a.op + base) = v;  // the MXINT4 code (SIGN has none)
+    if (sub == 0) {
+      const int eA = nanblk ? kExpNaN : (rc.maxc == 0 ? -126 : 31 - __clz(rc.maxc) + es - 2);
+      const int sT = nanblk ? kExpNaN : es - 2;
       store_block_words(a, row, blk, sT, a.op_kind == MXA_OP_SIGN ? eA : sT, rc.signs);
     }
   }

@@ -191,7 +191,8 @@ __device__ __forceinline__ void load_row16(const void* xr, int c0, int D, bool v
   }
 }
 
-template <int DT, bool ACT = false>
+// MB: the element width (rows_prep_block; 4: MXINT4 -- its own plain body, rows_prep_block_plain4)
+template <int DT, bool ACT = false, int MB = 8>
 __device__ __forceinline__ void rows_prep_body(const RowsPrepArgs& a, uint32_t bid) {
   // two lanes per 32-element block, 16 elements per lane; 32-bit index math
   // (the launcher checks rows * nb < 2^31): a 64-bit division is a ~50-instruction
@@ -220,11 +221,19 @@ __device__ __forceinline__ void rows_prep_body(const RowsPrepArgs& a, uint32_t b
     for (int j = 0; j < 16; ++j)
       if (valid && c0 + j < a.D) xv[j] = mlp_act(xv[j], a.act - 1);
   }
-  if (rows_prep_plain(a)) rows_prep_block_plain(a, row, blk, sub, c0, xv, valid);
-  else rows_prep_block(a, row, blk, sub, c0, xv, valid);
+  if constexpr (MB == 8) {
+    if (rows_prep_plain(a)) rows_prep_block_plain(a, row, blk, sub, c0, xv, valid);
+    else rows_prep_block(a, row, blk, sub, c0, xv, valid);
+  } else {
+    static_assert(DT == kF32, "MXINT4 rows: float32");
+    if (rows_prep_plain4(a)) rows_prep_block_plain4(a, row, blk, sub, c0, xv, valid);
+    else rows_prep_block<MB>(a, row, blk, sub, c0, xv, valid);
+  }
 }
 template <int DT>
 __global__ __launch_bounds__(256) void rows_prep_kernel(RowsPrepArgs a) { rows_prep_body<DT>(a, blockIdx.x); }
+// RowsPrepArgs::mbits == 4: MXINT4 rows (float32); a kernel of its own, as rows_prep_act_kernel is
+__global__ __launch_bounds__(256) void rows_prep4_kernel(RowsPrepArgs a) { rows_prep_body<kF32, false, 4>(a, blockIdx.x); }
 // RowsPrepArgs::act: the MLP's activation on the float32 values as they are loaded (the
 // fallback of mxa_mlp: fc1's fp32 output -> fc2's MX input codes); a kernel of its own, so
 // that rows_prep_kernel stays what it is
@@ -278,6 +287,14 @@ __global__ __launch_bounds__(256) void attn_prep_kernel(RowsPrepArgs q, RowsPrep
   else if (b < nq + nk) rows_prep_body<DT>(k, b - nq);
   else cols_prep_body<DT>(v, b - nq - nk);
 }
+// ... at 4 bits (mxa_attention_bits): MXINT4 Q and K rows; V's width is ColsPrepArgs::mbits
+__global__ __launch_bounds__(256) void attn_prep4_kernel(RowsPrepArgs q, RowsPrepArgs k, ColsPrepArgs v, uint32_t nq,
+                                                         uint32_t nk) {
+  const uint32_t b = blockIdx.x;
+  if (b < nq) rows_prep_body<kF32, false, 4>(q, b);
+  else if (b < nq + nk) rows_prep_body<kF32, false, 4>(k, b - nq);
+  else cols_prep_body<kF32>(v, b - nq - nk);
+}
 
 // ---------------------------------------------------------------------------
 // ELSA hashes / key norms (funcs/elsa_approximation.py:105-112, :126), one wave
@@ -330,17 +347,20 @@ __global__ __launch_bounds__(64 * kElsaWaves) void elsa_prep_kernel(ElsaPrepArgs
 // ---------------------------------------------------------------------------
 // The value rule, for one element of a block of scale exponent es whose MX-quantized block has
 // the exponent eA: x the element (flushed where the block is), cf its MXINT8 code as the float
-// the reference holds (a negative x that rounds to code 0 is -0.0) and cd as an int
-__device__ __forceinline__ float approx_value(int op_kind, int dt, float x, float cf, int cd, int es, int eA, bool nan) {
+// the reference holds (a negative x that rounds to code 0 is -0.0) and cd as an int.  unit: the
+// code unit is 2^(es - unit) -- 6: the codes are MXINT8; 2: MXINT4 (mxa_approx_values_bits at
+// width 4: the reference's MX_Q / MX_K at a_elem_format "int4")
+__device__ __forceinline__ float approx_value(int op_kind, int dt, float x, float cf, int cd, int es, int eA, bool nan,
+                                              int unit = 6) {
   // true_ex: NaN -> exponent 0 -> +1 (examples :98-110)
   if (nan) return op_kind == MXA_OP_TRUE_EX ? 1.0f : __uint_as_float(0x7FC00000u);
   if (op_kind == MXA_OP_MXINT4) return (round_code(x, es, 4, kRoundNearest, dt) * 0.25f) * pow2f(es);
-  const float mxv = round_dt((cf * pow2f(-6)) * pow2f(es), dt);  // MX int8 value
+  const float mxv = round_dt((cf * pow2f(-unit)) * pow2f(es), dt);  // the MX value
   switch (op_kind) {
     case MXA_OP_SIGN:  // (mx < 0 ? -1 : +1) * 2^eA
       return (mxv < 0.0f ? -1.0f : 1.0f) * pow2f(eA);
     case MXA_OP_EXION: {  // sign(mx) * eA * (2^l1 + 2^l2) / 64
-      const int m = exion_m(cd << (es - eA));
+      const int m = exion_m(cd << (es - eA + 6 - unit));
       const float sg = cd > 0 ? 1.0f : (cd < 0 ? -1.0f : 0.0f);
       return ((sg * (float)eA) * (float)(m < 0 ? -m : m)) / 64.0f;
     }
@@ -360,7 +380,8 @@ __device__ __forceinline__ float approx_value(int op_kind, int dt, float x, floa
 //          and the operand kind are a's
 //   EPL 4: one float4 load and store, DPP, 32-bit index math (the launcher checks both);
 //          float32 and the operand kind OPK at compile time
-template <int EPL, int OPK = -1>
+//   MB:    the element width of the codes every kind is derived from (8, or 4: MXINT4)
+template <int EPL, int OPK = -1, int MB = 8>
 __device__ __forceinline__ void approx_values_body(const ApproxArgs& a) {
   constexpr bool V4 = EPL == 4;
   constexpr int LPB = 32 / EPL;
@@ -395,15 +416,15 @@ __device__ __forceinline__ void approx_values_body(const ApproxArgs& a) {
 #pragma unroll
   for (int i = 0; i < EPL; ++i) {
     xv[i] = s.flush ? xin[i] * 0.0f : xin[i];
-    cf[i] = s.nan ? 0.0f : round_code(xv[i], s.es, 8, kRoundNearest, dt);
+    cf[i] = s.nan ? 0.0f : round_code(xv[i], s.es, MB, kRoundNearest, dt);
     cd[i] = (int)cf[i];
     mc = umax(mc, (uint32_t)abs(cd[i]));
   }
-  const int eA = mx_block_exponent((int)block_max(mc), s.es, s.nan, dt);
+  const int eA = mx_block_exponent((int)block_max(mc), s.es, s.nan, dt, MB - 2);
   if (!valid) return;
   float out[EPL];
 #pragma unroll
-  for (int i = 0; i < EPL; ++i) out[i] = round_dt(approx_value(op_kind, dt, xv[i], cf[i], cd[i], s.es, eA, s.nan), dt);
+  for (int i = 0; i < EPL; ++i) out[i] = round_dt(approx_value(op_kind, dt, xv[i], cf[i], cd[i], s.es, eA, s.nan, MB - 2), dt);
   if constexpr (V4) {
     *reinterpret_cast<float4*>(static_cast<float*>(a.out) + (int64_t)row * a.ld_out + c) =
         make_float4(out[0], out[1], out[2], out[3]);
@@ -418,6 +439,10 @@ __global__ __launch_bounds__(256) void approx_values_kernel(ApproxArgs a) { appr
 // eight lanes per block, four elements per lane (it is HBM-bound: 8 bytes per element)
 template <int OPK>
 __global__ __launch_bounds__(256) void approx_values_v4_kernel(ApproxArgs a) { approx_values_body<4, OPK>(a); }
+// the same two from MXINT4 codes (mxa_approx_values_bits at width 4)
+__global__ __launch_bounds__(256) void approx_values4_kernel(ApproxArgs a) { approx_values_body<1, -1, 4>(a); }
+template <int OPK>
+__global__ __launch_bounds__(256) void approx_values4_v4_kernel(ApproxArgs a) { approx_values_body<4, OPK, 4>(a); }
 
 }  // namespace mxa
 
@@ -493,9 +518,9 @@ extern "C" int mxa_quantize_bfloat(const void* x, void* y, int64_t n, int32_t bf
   return launch_status();
 }
 
-extern "C" int mxa_approx_values(const void* x, void* out, int64_t rows, int32_t d, int64_t ld_x, int64_t ld_out,
-                                 int32_t op_kind, int32_t flush_subnormals, int32_t bfloat, int32_t dtype,
-                                 hipStream_t stream) {
+static int approx_values_impl(const void* x, void* out, int64_t rows, int32_t d, int64_t ld_x, int64_t ld_out,
+                              int32_t op_kind, int32_t flush_subnormals, int32_t bfloat, int32_t dtype, bool bits4,
+                              hipStream_t stream) {
   if (!x || !out || rows < 0 || d <= 0 || ld_x < d || ld_out < d || !dtype_ok(dtype)) return MXA_ERR_ARG;
   if (op_kind < MXA_OP_SIGN || op_kind > MXA_OP_TRUE_EX) return MXA_ERR_ARG;
   if (rows == 0) return MXA_OK;
@@ -508,14 +533,30 @@ extern "C" int mxa_approx_values(const void* x, void* out, int64_t rows, int32_t
     const dim3 grid((unsigned)((nbk * 8 + 255) / 256));
     static_assert(MXA_OP_SIGN == 0 && MXA_OP_TRUE_EX == 4, "the operand kinds are 0 .. 4");
     with_constant<5>(op_kind, [&](auto opk) {
-      hipLaunchKernelGGL(approx_values_v4_kernel<decltype(opk)::value>, grid, dim3(256), 0, stream, a);
+      if (bits4) hipLaunchKernelGGL(approx_values4_v4_kernel<decltype(opk)::value>, grid, dim3(256), 0, stream, a);
+      else hipLaunchKernelGGL(approx_values_v4_kernel<decltype(opk)::value>, grid, dim3(256), 0, stream, a);
     });
     return launch_status();
   }
   const int64_t n = nbk * 32;  // one lane per element of the padded blocks
   if (n / 256 >= ((int64_t)1 << 31)) return MXA_ERR_UNSUPPORTED;
-  hipLaunchKernelGGL(approx_values_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
+  if (bits4) hipLaunchKernelGGL(approx_values4_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
+  else hipLaunchKernelGGL(approx_values_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, a);
   return launch_status();
+}
+
+extern "C" int mxa_approx_values(const void* x, void* out, int64_t rows, int32_t d, int64_t ld_x, int64_t ld_out,
+                                 int32_t op_kind, int32_t flush_subnormals, int32_t bfloat, int32_t dtype,
+                                 hipStream_t stream) {
+  return approx_values_impl(x, out, rows, d, ld_x, ld_out, op_kind, flush_subnormals, bfloat, dtype, false, stream);
+}
+
+extern "C" int mxa_approx_values_bits(const void* x, void* out, int64_t rows, int32_t d, int64_t ld_x, int64_t ld_out,
+                                      int32_t op_kind, int32_t flush_subnormals, int32_t bfloat, int32_t dtype,
+                                      int32_t elem_bits, hipStream_t stream) {
+  if (elem_bits != 8 && elem_bits != 4) return MXA_ERR_ARG;
+  return approx_values_impl(x, out, rows, d, ld_x, ld_out, op_kind, flush_subnormals, bfloat, dtype, elem_bits == 4,
+                            stream);
 }
 
 namespace mxa {
@@ -524,7 +565,10 @@ int launch_rows_prep(const RowsPrepArgs& a, hipStream_t stream) {
   if (threads == 0) return MXA_OK;
   if (a.rows * a.nb >= ((int64_t)1 << 30)) return MXA_ERR_UNSUPPORTED;  // 32-bit thread indices (x2 lanes)
   const dim3 grid((unsigned)((threads + 255) / 256));
-  if (a.act != kActNone) {
+  if (a.mbits == 4) {  // MXINT4 rows: float32, no activation
+    if (a.dt != kF32 || a.act != kActNone) return MXA_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(rows_prep4_kernel, grid, dim3(256), 0, stream, a);
+  } else if (a.act != kActNone) {
     if (a.dt != kF32 || (a.act != 1 + MXA_ACT_GELU && a.act != 1 + MXA_ACT_GELU_TANH)) return MXA_ERR_ARG;
     hipLaunchKernelGGL(rows_prep_act_kernel, grid, dim3(256), 0, stream, a);
   } else {
@@ -554,6 +598,11 @@ int launch_attn_prep(const RowsPrepArgs& q, const RowsPrepArgs& k, const ColsPre
   const int64_t nv = (v.mats * v.nb * v.C + 255) / 256;
   if (nq + nk + nv == 0) return MXA_OK;
   const dim3 grid((unsigned)(nq + nk + nv));
+  if (q.mbits == 4 || k.mbits == 4) {  // MXINT4 Q and K rows (V: v.mbits): float32
+    if (q.mbits != k.mbits || q.dt != kF32) return MXA_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(attn_prep4_kernel, grid, dim3(256), 0, stream, q, k, v, (uint32_t)nq, (uint32_t)nk);
+    return launch_status();
+  }
   with_constant<3>(q.dt, [&](auto dt) {
     hipLaunchKernelGGL(attn_prep_kernel<decltype(dt)::value>, grid, dim3(256), 0, stream, q, k, v, (uint32_t)nq,
                        (uint32_t)nk);

@@ -36,6 +36,9 @@ class exponent_approximation:
         self.K = quantize_elemwise_op(K, mx_specs, round=mx_specs["round_output"])
         self.shared_exponent_method = mx_specs.get("shared_exp_method", "max")
         self._flush = bool(mx_specs["mx_flush_fp32_subnorms"])
+        # the width of MX_Q / MX_K, from which every approximator but MXINT4() is derived (:18-31)
+        # ("int4": the MXINT4 codes; every other spec as before, from MXINT8 codes)
+        self._bits = 4 if mx_specs["a_elem_format"] == "int4" else 8
 
     # MXINT8 copies (funcs/exponent_based_prediction.py:18-31): built on first use -- the
     # approximators that do not read them (exp-sign, EXION, MXINT4, true_ex) skip two
@@ -85,7 +88,9 @@ class exponent_approximation:
 
     # -- approximators -----------------------------------------------------------
     def _vals(self, X, kind):
-        return ops.approx_values(X, kind, flush=self._flush)
+        if self._bits == 8 or kind == "mxint4":  # MXINT4() quantizes Q and K itself: int4 whatever the spec
+            return ops.approx_values(X, kind, flush=self._flush)
+        return ops.approx_values(X, kind, flush=self._flush, elem_bits=4)
 
     def exponent_based_sign(self):
         """Proposed exp-sign: (mx < 0 ? -1 : +1) * 2^(shared exponent of the MX block)."""

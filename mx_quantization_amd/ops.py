@@ -128,17 +128,30 @@ OP_KINDS = {"sign": N.MXA_OP_SIGN, "mxint8": N.MXA_OP_MXINT8, "mxint4": N.MXA_OP
             "exion": N.MXA_OP_EXION, "true_ex": N.MXA_OP_TRUE_EX}
 
 
-def approx_values(X: torch.Tensor, kind: str, flush: bool = False, bfloat: int = 0) -> torch.Tensor:
-    """Approximator operand values along the last axis (funcs/exponent_based_prediction.py)."""
+def _elem_bits(elem_bits) -> int:
+    """8 (MXINT8) or 4 (MXINT4); any other width is a ValueError"""
+    if elem_bits not in (8, 4):
+        raise ValueError(f"elem_bits must be 8 or 4 (got {elem_bits!r})")
+    return int(elem_bits)
+
+
+def approx_values(X: torch.Tensor, kind: str, flush: bool = False, bfloat: int = 0, elem_bits: int = 8) -> torch.Tensor:
+    """Approximator operand values along the last axis (funcs/exponent_based_prediction.py).
+    elem_bits: the width of the MX codes the values are derived from -- 8, or 4: the MXINT4
+    MX_Q / MX_K of a_elem_format "int4" (include/mxa.h mxa_approx_values_bits)."""
+    bits = _elem_bits(elem_bits)
     dev = require_device(X)
     dt = _dt(X, "X")
     X = X.contiguous()
     out = torch.empty_like(X)
     d = X.shape[-1]
     rows = X.numel() // d if d else 0
-    if rows:
+    if rows and bits == 8:
         check(lib().mxa_approx_values(X.data_ptr(), out.data_ptr(), rows, d, d, d, OP_KINDS[kind], int(flush),
                                       int(bfloat), dt, stream_ptr(dev)), "mxa_approx_values")
+    elif rows:
+        check(lib().mxa_approx_values_bits(X.data_ptr(), out.data_ptr(), rows, d, d, d, OP_KINDS[kind], int(flush),
+                                           int(bfloat), dt, bits, stream_ptr(dev)), "mxa_approx_values_bits")
     return out
 
 
@@ -364,13 +377,17 @@ def mx_topk_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: 
                       bias: Optional[torch.Tensor] = None, flush_subnormals: bool = False, bfloat: int = 0,
                       return_scores: bool = False, out: Optional[torch.Tensor] = None,
                       return_mask: bool = False, elsa_proj: Optional[torch.Tensor] = None,
-                      autocast: Optional[torch.dtype] = None):
+                      autocast: Optional[torch.dtype] = None, elem_bits: int = 8):
     """The fused hot path (include/mxa.h mxa_attention): q (B,H,N,D), k/v (B,H,T,D)
     float32, float16 or bfloat16 (strided views of a packed qkv are fine; the ops follow
     the tensors' dtype as the reference's do).  autocast: the torch.autocast dtype the
     reference's matmuls would return (scores, P and out in it).  Returns (out (B,H,N,D),
     idx (B,H,N,k_top) int64 or None[, true, pred][, mask words (B,H,N,ceil(T/32))]);
-    true / pred are float32 tensors holding the score-dtype values."""
+    true / pred are float32 tensors holding the score-dtype values.
+    elem_bits: 8, or 4 -- Q, K, P and V as MXINT4 and every approximator from the MXINT4 codes
+    (the reference at a_elem_format = w_elem_format = "int4"; include/mxa.h mxa_attention_bits:
+    float32, no autocast, no ELSA -- the library refuses those)."""
+    bits = _elem_bits(elem_bits)
     p, dev, (B, H, Nq, T, D), keep = _attn_params(q, k, v, scale, k_top, pred_mode, top_k, approx and top_k, bias,
                                                   flush_subnormals, bfloat, elsa_proj, autocast)
     odt = _out_dtype(q, autocast)
@@ -393,7 +410,10 @@ def mx_topk_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: 
         true_s = torch.empty((B, H, Nq, T), dtype=torch.float32, device=dev)
         pred_s = torch.full((B, H, Nq, T), float("nan"), dtype=torch.float32, device=dev)
         p.true_out, p.pred_out = true_s.data_ptr(), pred_s.data_ptr()
-    if T > LONG_ROWS_T:  # rows of 513 .. 1,024 keys: the sibling entry points (include/mxa.h)
+    if bits == 4:
+        _call_with_workspace(lib().mxa_attention_bits_workspace_bytes, lib().mxa_attention_bits, "mxa_attention_bits", p,
+                             bits, dev=dev)
+    elif T > LONG_ROWS_T:  # rows of 513 .. 1,024 keys: the sibling entry points (include/mxa.h)
         _call_with_workspace(lib().mxa_attention_long_workspace_bytes, lib().mxa_attention_long, "mxa_attention_long", p,
                              dev=dev)
     else:
@@ -403,14 +423,20 @@ def mx_topk_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: 
 
 def mx_approx_scores(q: torch.Tensor, k: torch.Tensor, pred_mode: str = "ex_pred",
                      bias: Optional[torch.Tensor] = None, flush_subnormals: bool = False, bfloat: int = 0,
-                     elsa_proj: Optional[torch.Tensor] = None, autocast: Optional[torch.dtype] = None) -> torch.Tensor:
+                     elsa_proj: Optional[torch.Tensor] = None, autocast: Optional[torch.dtype] = None,
+                     elem_bits: int = 8) -> torch.Tensor:
     """pred = aQ @ aK^T (+ bias) of the approximator `pred_mode` (or ELSA's
-    approximation_scores), (B,H,N,T) in the score dtype -- include/mxa.h mxa_approx_scores."""
+    approximation_scores), (B,H,N,T) in the score dtype -- include/mxa.h mxa_approx_scores.
+    elem_bits 4: the approximators of the MXINT4 Q and K (mxa_approx_scores_bits)."""
+    bits = _elem_bits(elem_bits)
     p, dev, (B, H, Nq, T, D), keep = _attn_params(q, k, None, 1.0, 0, pred_mode, False, True, bias,
                                                   flush_subnormals, bfloat, elsa_proj, autocast)
     pred = torch.empty((B, H, Nq, T), dtype=torch.float32, device=dev)
     p.pred_out = pred.data_ptr()
-    if T > LONG_ROWS_T:
+    if bits == 4:
+        _call_with_workspace(lib().mxa_attention_bits_workspace_bytes, lib().mxa_approx_scores_bits,
+                             "mxa_approx_scores_bits", p, bits, dev=dev, bad=None)
+    elif T > LONG_ROWS_T:
         _call_with_workspace(lib().mxa_attention_long_workspace_bytes, lib().mxa_approx_scores_long,
                              "mxa_approx_scores_long", p, dev=dev, bad=None)
     else:

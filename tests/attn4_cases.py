@@ -1,0 +1,293 @@
+"""What the MXINT4 attention tests share (test_attn4_cpu.py, test_gpu_attn4.py): the oracle's
+attention restated at elem="int4", the row-wise output bound at that width, the exact-result
+cases with a V that is its own MXINT4, and the GPU cases with their references (computed once,
+left unchanged).  Nothing here touches the device.
+
+The reference is the caller glue of the PixArt modules (MX_transformer_block.py:648-717,
+:792-859) at a_elem_format = w_elem_format = "int4": matmul(q, k^T) and matmul(attn, v) quantize
+their operands to MXINT4 and exponent_approximation builds every approximator from the MXINT4
+MX_Q / MX_K.  attention4 assembles it from the oracle's pieces, which take the width already."""
+import collections
+import functools
+
+import numpy as np
+
+import exact_out_cases as EC
+import gpu_support as GS
+from oracle import mx_oracle as O
+
+F32 = np.float32
+MODES = ("ex_pred", "partial_Q", "partial_K", "MXINT4", "two_step_leading_ones", "true_ex")
+
+
+def operands4(q, k, mode, flush=False, bfloat=32):
+    ea = O.ExponentApproximation(q, k, 32, elem="int4", flush=flush, bfloat=bfloat)
+    return {"ex_pred": ea.exponent_based_sign, "partial_Q": ea.partial_Q, "partial_K": ea.partial_K,
+            "MXINT4": ea.MXINT4, "two_step_leading_ones": ea.two_step_leading_ones,
+            "true_ex": ea.exponent_based_sign_leading_ones}[mode]()
+
+
+def attention4(q, k, v, scale, k_top=20, pred_mode="ex_pred", top_k=True, approx=True, bias=None, flush=False,
+               bfloat=32):
+    """O.attention with every MX operand at int4 (same keys in the result)"""
+    q, k, v = (np.asarray(x, F32) for x in (q, k, v))
+    res = {}
+    true = O.mx_matmul(q, np.swapaxes(k, -1, -2), elem="int4", flush=flush, bfloat=bfloat)
+    true = (true * F32(scale)).astype(F32)
+    if bias is not None:
+        bias = np.broadcast_to(np.asarray(bias, F32), true.shape)
+        true = (true + bias).astype(F32)
+    res["true"] = true
+    if top_k:
+        if approx:
+            aq, ak = operands4(q, k, pred_mode, flush, bfloat)
+            pred = O.exact_matmul_f32(aq, np.swapaxes(ak, -1, -2))
+            if bias is not None:
+                pred = (pred + bias).astype(F32)
+            res["aq"], res["ak"], res["pred"] = aq, ak, pred
+            _, idx = O.topk(pred, k_top)
+            vals = np.take_along_axis(true, idx, axis=-1)
+        else:
+            vals, idx = O.topk(true, k_top)
+        res["idx"], res["vals"] = idx, vals
+        attn = np.zeros_like(true)
+        np.put_along_axis(attn, idx, O.softmax_f32(vals), axis=-1)
+    else:
+        attn = O.softmax_f32(true)
+    res["attn"] = attn
+    res["out"] = O.mx_matmul(attn, v, elem="int4", flush=flush, bfloat=bfloat)
+    return res
+
+
+# ---- the row-wise bound at width 4 (gpu_support.out_row_bound restated) -------------------------
+def out_row_bound4(r, v, kernel=None):
+    """gpu_support.out_row_bound for MXINT4 P and V: one code step is 2^(eP - 2), the block
+    maximum's mantissa pmax / (4 step), and a rounding tie at y >= 7 (between the codes 7 and 8)
+    is no tie: both sides clip to 7.  n_add and chain are the same kernels'."""
+    attn, true = np.asarray(r["attn"], np.float64), np.asarray(r["true"], np.float64)
+    T, D = attn.shape[-1], v.shape[-1]
+    k = r["idx"].shape[-1] if "idx" in r else 0
+    kernel = kernel or GS.finish_kernel_of(T, D, k)
+    assert kernel in ("fin16", "qk", "dense_qk"), kernel  # the kernels with an MXINT4-P form
+    n_add, chain = GS.n_add_and_chain(kernel, T, k)
+    kept = O.prune_mask(r["idx"], T) if k else np.ones(attn.shape, bool)
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        pq, _, pe = O.quantize_mx(r["attn"], "int4", 32, -1)
+        vq = np.abs(O.quantize_mx(np.asarray(v, F32), "int4", 32, -2)[0].astype(np.float64))
+        S = np.matmul(np.abs(pq.astype(np.float64)), vq)
+        fin = np.isfinite(attn).all(-1) & np.isfinite(r["out"]).all(-1) & np.isfinite(S).all(-1)
+        gap = np.where(kept, np.abs(true - np.max(np.where(kept, true, -np.inf), -1, keepdims=True)), np.inf)
+        gap = np.where(fin[..., None], gap, np.inf)
+        loose = ((gap > 0) & (gap < GS.EXACT_GAP)).any(-1, keepdims=True)
+        tau = (GS.TAU_C0 + (chain + GS.ref_chain(k or T)) / 2 + 2.0 * gap) * 2.0 ** -23
+        pb = O.to_blocks(r["attn"], -1, 32)[0].astype(np.float64)
+        tb = O.to_blocks(np.where(np.isfinite(tau), tau, 0).astype(F32), -1, 32)[0].astype(np.float64)
+        live = O.to_blocks((kept & loose & fin[..., None] & (attn > 0)).astype(F32), -1, 32)[0] > 0
+        step = np.exp2(pe.astype(np.float64) - 2)  # (..., nb, 1): one code step of the block
+        y = pb / step
+        tie = (np.abs(y - np.floor(y) - 0.5) <= tb * y) & (np.floor(y) < 7)
+        pmax = pb.max(-1, keepdims=True)
+        tmax = np.take_along_axis(tb, pb.argmax(-1)[..., None], -1)
+        mant = pmax / (4 * step)  # in [1, 2)
+        edge = (mant * (1 - 2 * tmax) < 1) | (mant * (1 + 2 * tmax) >= 2)
+        elig = live & (tie | edge)
+        F = np.matmul(O.from_blocks(np.where(elig, step, 0.0), T, -1), np.where(np.isfinite(vq), vq, 0.0))
+    shares = (elig.sum() / max(1, (kept & fin[..., None]).sum()), elig.any((-1, -2))[fin].mean() if fin.any() else 0.0)
+    return (n_add + 1) * 2.0 ** -24 * S + F, fin, shares, kernel, O.from_blocks(elig, T, -1)
+
+
+def shares_within_caps(r, v):
+    se, sr = out_row_bound4(r, v)[2]
+    return se <= GS.ELIGIBLE_ELEMS and sr <= GS.ELIGIBLE_ROWS, (se, sr)
+
+
+def out_rows_close4(got, r, v, what):
+    """gpu_support.out_rows_close against out_row_bound4"""
+    bound, fin, (se, sr), kernel, _ = out_row_bound4(r, v)
+    assert se <= GS.ELIGIBLE_ELEMS and sr <= GS.ELIGIBLE_ROWS, f"{what}: eligible elements {se:.4%}, rows {sr:.2%}"
+    ref = np.asarray(r["out"])
+    GS.same(np.isnan(got), np.isnan(ref), what + " NaN pattern")
+    err = np.abs(got[fin].astype(np.float64) - ref[fin].astype(np.float64))
+    b = bound[fin]
+    ratio = np.where(err == 0, 0.0, err / np.where(b > 0, b, 1e-300))
+    worst = float(ratio.max()) if ratio.size else 0.0
+    print(f"out_rows_close4 {what}: {kernel}, eligible elements {se:.4%} rows {sr:.2%}, worst |got - ref| / (A + F) {worst:.3f}")
+    if worst > 1:
+        i = np.unravel_index(np.argmax(ratio), ratio.shape)
+        raise AssertionError(f"{what}: |got - ref| / (A + F) = {worst:.3f} at row {np.argwhere(fin)[i[0]].tolist()} "
+                             f"column {i[1]}: got {got[fin][i]!r} want {ref[fin][i]!r} bound {b[i]:.3e}")
+
+
+def eligible_bf16(r, v, flush=False):
+    """bfloat = 16: the P blocks whose MXINT4 codes or exponent may differ between two correct
+    implementations.  P enters the output through its codes alone; the codes come from
+    bf16(p), and two float32 softmaxes within tau of each other (out_row_bound4's tau) round to
+    different bfloat16 values only where p lies within tau of a bfloat16 rounding midpoint.
+    Those elements are moved to their lower, then to their upper bfloat16 neighbour; a block whose
+    codes or exponent change, or that holds two such elements, is eligible.  Returns the number of
+    eligible blocks, the number of near-midpoint elements and the rows (..., N) with an eligible block."""
+    k = r["idx"].shape[-1] if "idx" in r else 0
+    T, D = r["attn"].shape[-1], v.shape[-1]
+    _, chain = GS.n_add_and_chain(GS.finish_kernel_of(T, D, k), T, k)
+    attn, true = r["attn"].astype(np.float64), r["true"].astype(np.float64)
+    kept = O.prune_mask(r["idx"], T) if k else np.ones(attn.shape, bool)
+    with np.errstate(invalid="ignore", over="ignore"):
+        gap = np.where(kept, np.abs(true - np.max(np.where(kept, true, -np.inf), -1, keepdims=True)), 0.0)
+        tau = (GS.TAU_C0 + (chain + GS.ref_chain(k or T)) / 2 + 2.0 * gap) * 2.0 ** -23
+        bits = r["attn"].view(np.uint32)
+        lo = (bits & np.uint32(0xFFFF0000)).view(F32).astype(np.float64)  # the bfloat16 value below p
+        hi = ((bits & np.uint32(0xFFFF0000)) + np.uint32(0x10000)).view(F32).astype(np.float64)
+        mid = (lo + hi) / 2
+        near = kept & (attn > 0) & np.isfinite(attn) & (np.abs(attn - mid) <= tau * attn)
+        a_lo = np.where(near, lo, O.quantize_bfloat(r["attn"], 16)).astype(F32)
+        a_hi = np.where(near, hi, O.quantize_bfloat(r["attn"], 16)).astype(F32)
+        _, c_lo, e_lo = O.quantize_mx(a_lo, "int4", 32, -1, flush=flush)
+        _, c_hi, e_hi = O.quantize_mx(a_hi, "int4", 32, -1, flush=flush)
+    changed = (c_lo != c_hi).any(-1) | (e_lo[..., 0] != e_hi[..., 0])
+    crowded = O.to_blocks(near.astype(F32), -1, 32)[0].sum(-1) > 1
+    return int((changed | crowded).sum()), int(near.sum()), (changed | crowded).any(-1)
+
+
+# ---- exact-result cases at 4 bits (the construction of exact_out_cases.py) ----------------------
+# q, k and the bias are exact_out_cases' (8.0 and 256 / width are MXINT4 values: code 4); V is
+# integers |n| <= 7 times 2^e per (32-token block, column), so that V is its own MXINT4
+_c = EC._c
+EXACT = []
+EXACT += [_c(EC.GATHER16, 1, 2, 20, T, D, k) for T in (70, 197) for D in (32, 72, 128) for k in (1, 20, 64)]
+EXACT += [_c(EC.GATHER16, 1, 2, 20, T, D, k) for T, D, k in ((513, 32, 20), (513, 72, 64), (1000, 72, 20), (1000, 128, 64))]
+EXACT += [_c(EC.MFMA, 1, 2, 70, 130, 64, 65), _c(EC.MFMA, 1, 2, 33, 256, 72, 154)]
+EXACT += [_c(EC.DENSE_MFMA, 1, 2, 5, 20, 64, 0), _c(EC.DENSE_MFMA, 1, 2, 77, 120, 72, 0), _c(EC.DENSE_MFMA, 1, 2, 256, 256, 64, 0)]
+EXACT += [_c(EC.GATHER16, 2, 2, 20, 197, 72, 20, True), _c(EC.GATHER16, 2, 2, 20, 1000, 72, 20, True),
+          _c(EC.MFMA, 2, 2, 33, 256, 72, 65, True), _c(EC.DENSE_MFMA, 2, 2, 77, 120, 72, 0, True)]
+EXACT += [_c(EC.GATHER16, 1, 2, 20, 197, 64, 20, approx=False), _c(EC.GATHER16, 1, 2, 20, 197, 64, 20, pred_mode="MXINT4")]
+EXACT += [_c(EC.GATHER16, 1, 2, 20, 197, 64, 20, bfloat=16), _c(EC.MFMA, 1, 2, 77, 120, 72, 77, bfloat=16),
+          _c(EC.GATHER16, 1, 2, 20, 513, 72, 20, bfloat=16)]
+
+
+@functools.lru_cache(maxsize=None)
+def exact_inputs(c):
+    q, k, _, bias = EC.inputs(c)
+    rng = np.random.default_rng([4, c.kind, c.N, c.T, c.D, c.k, int(c.bias)])
+    n = rng.integers(-7, 8, (c.B, c.H, c.T, c.D)).astype(F32)
+    e = rng.integers(0, 4, (c.B, c.H, (c.T + 31) // 32, c.D)).astype(F32)
+    v = (n * np.exp2(np.repeat(e, 32, axis=2)[:, :, :c.T])).astype(F32)
+    return q, k, v, bias
+
+
+@functools.lru_cache(maxsize=None)
+def exact_reference(c):
+    q, k, v, bias = exact_inputs(c)
+    return attention4(q, k, v, EC.SCALE, bias=bias, **EC.oracle_kw(c))
+
+
+# ---- the random GPU cases -----------------------------------------------------------------------
+def rnd(shape, seed, mult=1.0):
+    return (np.random.default_rng(seed).standard_normal(shape, dtype=F32) * F32(mult)).astype(F32)
+
+
+def pixart_bias(B, N, T, valid):
+    """(1 - mask) * -10000 over the text tokens, (B, 1, 1, T)"""
+    b = np.zeros((B, 1, 1, T), F32)
+    b[..., valid:] = -10000.0
+    return b
+
+
+# k = 0: dense; mode None: approx=False; scores: the call also takes the true / approximate scores
+RCase = collections.namedtuple("RCase", "N T D k mode scores bias flush bfloat seed")
+
+
+def rcase_id(c):
+    return (f"N{c.N}T{c.T}D{c.D}" + (f"k{c.k}" if c.k else "dense") + f"-{c.mode or 'trueK'}" +
+            ("-scores" if c.scores else "") + ("-bias" if c.bias else "") + ("-flush" if c.flush else "") +
+            (f"-bf{c.bfloat}" if c.bfloat != 32 else "") + f"-s{c.seed}")
+
+
+def _r(N, T, D, k, mode="ex_pred", scores=False, bias=False, flush=False, bfloat=32, seed=0):
+    return RCase(N, T, D, k, mode, scores, bias, flush, bfloat, seed)
+
+
+def _grid():
+    out, i = [], 0
+    seven = MODES + (None,)
+    for D in (32, 64, 72, 128):
+        for N, T, bias in ((70, 70, False), (33, 197, False), (40, 120, True)):
+            for k in (1, 7, 20, 64):
+                # the modes thinned over the grid: each of the seven with every D, shape and k class
+                out.append(_r(N, T, D, k, seven[i % 7], scores=(i // 7) % 2 == 0, bias=bias, flush=bias, seed=i))
+                i += 1
+    return out
+
+
+GRID = _grid()
+LONG = [_r(33, T, D, k, mode, scores=(j % 2 == 0), seed=100 + j)
+        for j, (T, D, k, mode) in enumerate((T, D, k, m) for T in (513, 1000) for D in (32, 72) for k in (20, 64)
+                                            for m in ("ex_pred", "MXINT4"))]
+QK = [_r(70, 130, 64, 65, "ex_pred", True, seed=200), _r(70, 130, 72, 65, "true_ex", seed=201),
+      _r(33, 256, 64, 154, "MXINT4", seed=202), _r(33, 256, 72, 154, "ex_pred", True, seed=203),
+      _r(5, 20, 64, 0, seed=204), _r(5, 20, 72, 0, scores=True, seed=205), _r(77, 120, 64, 0, seed=206),
+      _r(77, 120, 72, 0, scores=True, bias=True, flush=True, seed=207), _r(256, 256, 64, 0, seed=208),
+      _r(256, 256, 72, 0, seed=209)]
+# one random bfloat = 16 case whose eligible set is empty (asserted on the CPU): by the norm
+BF16 = _r(40, 120, 72, 20, "ex_pred", True, bias=True, flush=True, bfloat=16, seed=300)
+ROWS_CASES = GRID + LONG + QK
+
+
+@functools.lru_cache(maxsize=None)
+def r_inputs(c):
+    """q, k, v as strided views of one packed (B, N, 3, H, D) qkv where N == T, bias or None"""
+    B, H = 1, 2
+    if c.N == c.T:
+        qkv = rnd((B, c.N, 3, H, c.D), c.seed)
+        q, k, v = (qkv[:, :, j].transpose(0, 2, 1, 3) for j in range(3))
+    else:
+        q, k, v = rnd((B, H, c.N, c.D), c.seed), rnd((B, H, c.T, c.D), c.seed + 1000), rnd((B, H, c.T, c.D), c.seed + 2000)
+    bias = pixart_bias(B, c.N, c.T, c.T // 2) if c.bias else None
+    return q, k, v, bias
+
+
+def r_scale(c):
+    return float(F32(c.D ** -0.5))
+
+
+@functools.lru_cache(maxsize=None)
+def r_reference(c):
+    q, k, v, bias = r_inputs(c)
+    kw = dict(k_top=c.k) if c.k else dict(top_k=False)
+    if c.mode is None:
+        kw["approx"] = False
+    else:
+        kw["pred_mode"] = c.mode
+    return attention4(q, k, v, r_scale(c), bias=bias, flush=c.flush, bfloat=c.bfloat, **kw)
+
+
+# ---- special blocks: NaN, +-Inf, all-zero and 2^+-100 blocks in Q, K and V ------------------------
+SPECIAL_K, SPECIAL_SCALE = 7, 0.125
+
+
+@functools.lru_cache(maxsize=None)
+def special_inputs():
+    q, k, v = rnd((1, 2, 40, 72), 400), rnd((1, 2, 70, 72), 401), rnd((1, 2, 70, 72), 402)
+    q[0, 0, 3, 5], q[0, 1, 5, 40], k[0, 1, 6, 70] = np.nan, np.inf, -np.inf
+    q[0, 0, 7, :] = 0.0
+    q[0, 1, :, ::5] = 0.0  # zero elements, and the negative ones that round to the int4 code 0 elsewhere
+    # (whole rows: a dot product whose blocks lie 2^100 apart leaves the range in which the oracle's
+    # float64 sum of the approximate scores is exact)
+    q[0, 0, 9, :] *= F32(2.0 ** 100)
+    q[0, 0, 11, :] *= F32(2.0 ** -100)
+    q[0, 0, 13, :] *= F32(2.0 ** -120)  # (head 0: true_ex maps the zero elements of head 1 to +1, 2^120 above)
+    k[0, 0, 2, :] = 0.0
+    k[0, 0, 4, :] *= F32(2.0 ** -100)
+    k[0, 1, 8, :] *= F32(2.0 ** 90)
+    v[0, 1, 33, 5] = np.nan  # (head 1: a NaN or Inf V block makes its output column NaN in every row)
+    v[0, 1, 2, 7] = -np.inf
+    v[0, 0, 32:64, 9] = 0.0
+    v[0, 0, 0:32, 11] *= F32(2.0 ** 100)
+    v[0, 1, 64:, 13] *= F32(2.0 ** -100)
+    return q, k, v
+
+
+@functools.lru_cache(maxsize=None)
+def special_reference(mode):
+    q, k, v = special_inputs()
+    return attention4(q, k, v, SPECIAL_SCALE, SPECIAL_K, mode)
+

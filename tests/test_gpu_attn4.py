@@ -1,0 +1,240 @@
+"""The MXINT4 attention core on the device (mx_topk_attention / mx_approx_scores / approx_values
+with elem_bits=4: mxa_attention_bits and its siblings) against the reference's fixture at
+a_elem_format = "int4" and against attention4 (tests/attn4_cases.py): true and approximate
+scores, kept indices and mask words bit for bit; out bit for bit on the exact-result cases, by
+the row-wise bound at width 4 elsewhere, by the norm on the bfloat = 16 rows that
+test_attn4_cpu.py shows to have no eligible P block.  The references are computed once in
+attn4_cases.py and shared with the CPU file, which asserts the eligible-share caps from the oracle
+alone."""
+import numpy as np
+import pytest
+import torch
+
+import attn4_cases as A
+import exact_out_cases as EC
+from gpu_support import M, OUT_TOL, dev, dev_opt, host, load, out_close, same, same_bits  # noqa: F401
+from oracle import mx_oracle as O
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module")
+def gold():
+    return load("attn_int4.npz")
+
+
+def _run(M, q, k, v, scale, c_k, mode, bias, flush, bfloat, scores, T):
+    """the op at elem_bits=4 -> (out, idx, mask as bools, true, pred) on the host (None where absent)"""
+    kw = dict(k_top=c_k) if c_k else dict(top_k=False)
+    if mode is None:
+        kw["approx"] = False
+    else:
+        kw["pred_mode"] = mode
+    res = M.mx_topk_attention(q, k, v, scale, bias=bias, flush_subnormals=flush, bfloat=0 if bfloat == 32 else bfloat,
+                              return_scores=scores, return_mask=c_k > 0, elem_bits=4, **kw)
+    torch.cuda.synchronize()
+    mask = host(M.unpack_mask(res[-1], T)) if c_k else None
+    return (host(res[0]), host(res[1]) if c_k else None, mask, host(res[2]) if scores else None,
+            host(res[3]) if scores else None)
+
+
+def _check_scores(got, r, what, approx):
+    out, idx, mask, true, pred = got
+    if "idx" in r:
+        same(idx, r["idx"], what + " idx")
+        same(mask, O.prune_mask(r["idx"], r["true"].shape[-1]), what + " mask")
+    else:
+        assert idx is None
+    if true is not None:
+        same_bits(true, r["true"], what + " true")
+        if approx and "pred" in r:
+            same_bits(pred, r["pred"], what + " pred")
+
+
+# ---- the reference's fixture --------------------------------------------------------------------
+FIXTURE = [(f"{m}_k20", 20, m) for m in A.MODES] + [("trueK_k30", 30, None), ("dense", 0, "ex_pred")]
+
+
+@pytest.mark.parametrize("tag,k,mode", FIXTURE, ids=[f[0] for f in FIXTURE])
+def test_fixture_self(M, gold, tag, k, mode):
+    q, kk, v, sc = gold["self/q"], gold["self/k"], gold["self/v"], float(gold["self/scale"])
+    kw = dict(top_k=False) if not k else (dict(k_top=k, approx=False) if mode is None else dict(k_top=k, pred_mode=mode))
+    r = A.attention4(q, kk, v, sc, **kw)  # (test_attn4_cpu.py: equal to the fixture bit for bit)
+    if k:
+        same(r["idx"], gold[f"self/{tag}/idx"].astype(np.int64), "oracle idx vs fixture")
+    got = _run(M, dev(q), dev(kk), dev(v), sc, k, mode, None, False, 32, True, 70)
+    same_bits(got[3], gold["self/true"], tag + " true vs fixture")
+    if k and mode is not None:
+        same_bits(got[4], gold[f"self/{tag}/pred"], tag + " pred vs fixture")
+    _check_scores(got, r, tag, mode is not None)
+    A.out_rows_close4(got[0], dict(r, out=gold[f"self/{tag}/out"]), v, tag)
+
+
+@pytest.mark.parametrize("tag,k,mode", [("ex_pred_k20", 20, "ex_pred"), ("MXINT4_k20", 20, "MXINT4"), ("dense", 0, "ex_pred")])
+def test_fixture_cross_bf16(M, gold, tag, k, mode):
+    """the PixArt cross slice: mask bias, flush, bfloat = 16; out by the norm on the rows without
+    an eligible P block (attn4_cases.eligible_bf16; at most 2 % of the rows have one)"""
+    q, kk, v, sc = gold["cross/q"], gold["cross/k"], gold["cross/v"], float(gold["cross/scale"])
+    bias = gold["cross/bias"][:, None]
+    kw = dict(k_top=k, pred_mode=mode) if k else dict(top_k=False)
+    r = A.attention4(q, kk, v, sc, bias=bias, flush=True, bfloat=16, **kw)
+    rows = ~A.eligible_bf16(r, v, True)[2]
+    got = _run(M, dev(q), dev(kk), dev(v), sc, k, mode, dev(bias), True, 16, True, 120)
+    same_bits(got[3], gold["cross/true"], tag + " true vs fixture")
+    if k:
+        same_bits(got[4], gold[f"cross/{tag}/pred"], tag + " pred vs fixture")
+        same(got[1], gold[f"cross/{tag}/idx"].astype(np.int64), tag + " idx vs fixture")
+    _check_scores(got, r, tag, True)
+    out_close(got[0][rows], gold[f"cross/{tag}/out"][rows], OUT_TOL, tag + " out")
+
+
+# ---- the grid, the long rows and finish_qk_kernel against attention4 ---------------------------------
+@pytest.mark.parametrize("c", A.ROWS_CASES, ids=A.rcase_id)
+def test_rows_vs_attention4(M, c):
+    q, k, v, bias = A.r_inputs(c)
+    r = A.r_reference(c)
+    tq, tk, tv = dev(q), dev(k), dev(v)
+    if c.N == c.T:  # strided views of one packed qkv on the device
+        qkv = torch.stack([tq.permute(0, 2, 1, 3), tk.permute(0, 2, 1, 3), tv.permute(0, 2, 1, 3)], 2).contiguous()
+        tq, tk, tv = (qkv[:, :, j].permute(0, 2, 1, 3) for j in range(3))
+        assert not tq.is_contiguous()
+    got = _run(M, tq, tk, tv, A.r_scale(c), c.k, c.mode, dev_opt(bias), c.flush, c.bfloat, c.scores, c.T)
+    _check_scores(got, r, A.rcase_id(c), c.mode is not None)
+    A.out_rows_close4(got[0], r, v, A.rcase_id(c))
+
+
+def test_random_bf16_case_by_the_norm(M):
+    c = A.BF16
+    q, k, v, bias = A.r_inputs(c)
+    r = A.r_reference(c)
+    got = _run(M, dev(q), dev(k), dev(v), A.r_scale(c), c.k, c.mode, dev_opt(bias), c.flush, c.bfloat, c.scores, c.T)
+    _check_scores(got, r, "bf16", True)
+    out_close(got[0], r["out"], OUT_TOL, "bf16 out")
+
+
+def test_approx_scores_bits(M, gold):
+    q, kk = gold["self/q"], gold["self/k"]
+    for mode in A.MODES:
+        pred = M.mx_approx_scores(dev(q), dev(kk), mode, elem_bits=4)
+        same_bits(host(pred), gold[f"self/{mode}_k20/pred"], mode)
+    c = A.LONG[0]
+    q, k, _, _ = A.r_inputs(c)
+    same_bits(host(M.mx_approx_scores(dev(q), dev(k), c.mode, elem_bits=4)), A.r_reference(c)["pred"], "long rows")
+
+
+# ---- exact-result cases: out, idx and mask bit for bit ------------------------------------------------
+@pytest.mark.parametrize("c", A.EXACT, ids=EC.case_id)
+def test_exact_out4(M, c):
+    q, kk, v, bias = A.exact_inputs(c)
+    r = A.exact_reference(c)
+    kw = dict(c.kw)
+    for scores in (False, True):
+        got = _run(M, dev(q), dev(kk), dev(v), EC.SCALE, c.k, kw.get("pred_mode", "ex_pred") if kw.get("approx", True) else None,
+                   dev_opt(bias), False, kw.get("bfloat", 32), scores, c.T)
+        w = f"{EC.case_id(c)} scores={scores}"
+        if c.k:
+            same(got[1], r["idx"], w + " idx")
+            same(got[2], O.prune_mask(r["idx"], c.T), w + " mask")
+        if scores:
+            same(got[3], r["true"], w + " true")
+        same_bits(got[0], r["out"], w + " out")
+
+
+# ---- special blocks ------------------------------------------------------------------------------
+def test_special_blocks_operands(M):
+    """approx_values(.., elem_bits=4) against ExponentApproximation(elem="int4") bit for bit, -0.0
+    (a negative element that rounds to the code 0) included"""
+    q, k, _ = A.special_inputs()
+    ea = O.ExponentApproximation(q, k, 32, elem="int4")
+    want = {"sign": ea.exponent_based_sign(), "mxint8": (ea.MX_Q, ea.MX_K), "mxint4": ea.MXINT4(),
+            "exion": ea.two_step_leading_ones(), "true_ex": ea.exponent_based_sign_leading_ones()}
+    assert (np.signbit(ea.MX_Q) & (ea.MX_Q == 0)).any()  # the fixture holds a -0.0
+    for kind, (wq, wk) in want.items():
+        same_bits(host(M.ops.approx_values(dev(q), kind, elem_bits=4)), wq, kind + " q")
+        same_bits(host(M.ops.approx_values(dev(k), kind, elem_bits=4)), wk, kind + " k")
+    # an unaligned view and a ragged row length take the one-lane-per-element kernel
+    same_bits(host(M.ops.approx_values(dev(q)[..., 1:71], "exion", elem_bits=4)),
+              O.ExponentApproximation(q[..., 1:71], k, 32, elem="int4").two_step_leading_ones()[0], "exion ragged")
+    # flush and bfloat
+    eb = O.ExponentApproximation(q, k, 32, elem="int4", flush=True, bfloat=16)
+    same_bits(host(M.ops.approx_values(dev(q), "sign", flush=True, bfloat=16, elem_bits=4)), eb.exponent_based_sign()[0],
+              "sign flush bf16")
+
+
+@pytest.mark.parametrize("mode", ["ex_pred", "two_step_leading_ones", "MXINT4"])
+def test_special_blocks_fused(M, mode):
+    """(not true_ex: it maps an element that rounds to the code 0 to +1, 2^100 above the other
+    elements of a 2^-100 row, so the float64 sum of such a score is exact in neither the oracle
+    nor the device; its operands on these blocks are pinned by test_special_blocks_operands)"""
+    q, k, v = A.special_inputs()
+    r = A.special_reference(mode)
+    got = _run(M, dev(q), dev(k), dev(v), A.SPECIAL_SCALE, A.SPECIAL_K, mode, None, False, 32, True, 70)
+    same_bits(got[3], r["true"], mode + " true")
+    same_bits(got[4], r["pred"], mode + " pred")
+    same(got[1], r["idx"], mode + " idx")  # (NaN scores rank first, in torch's order)
+    same(got[2], O.prune_mask(r["idx"], 70), mode + " mask")
+    A.out_rows_close4(got[0], r, v, mode)  # the NaN pattern (a NaN V block poisons its column) and the finite rows
+
+
+# ---- width 8 through the new entry points ------------------------------------------------------------
+@pytest.mark.parametrize("T", [70, 600])
+def test_width_8_is_byte_identical(M, T):
+    import ctypes
+    q, k, v = (dev(A.rnd((2, 2, T, 64), 500 + j)) for j in range(3))
+    ref = M.mx_topk_attention(q, k, v, 0.125, 20, return_scores=True, return_mask=True)
+    # the same call through mxa_attention_bits(p, 8)
+    p, dv, (B, H, Nq, T_, D), _ = M.ops._attn_params(q, k, v, 0.125, 20, "ex_pred", True, True, None, False, 0, None)
+    out = torch.empty_like(ref[0])
+    M.ops._bind_out(p, out)
+    idx = M.ops._new_idx(p, B, H, Nq, 20, True, dv)
+    mask = torch.empty_like(ref[4])
+    true_s, pred_s = torch.empty_like(ref[2]), torch.empty_like(ref[3])
+    p.mask_out, p.true_out, p.pred_out = mask.data_ptr(), true_s.data_ptr(), pred_s.data_ptr()
+    lib = M._native.lib()
+    M.ops._call_with_workspace(lib.mxa_attention_bits_workspace_bytes, lib.mxa_attention_bits, "mxa_attention_bits", p, 8,
+                               dev=dv)
+    torch.cuda.synchronize()
+    for a, b, what in zip((out, idx, true_s, pred_s, mask), ref, ("out", "idx", "true", "pred", "mask")):
+        assert torch.equal(a.view(torch.int32) if a.dtype == torch.float32 else a,
+                           b.view(torch.int32) if b.dtype == torch.float32 else b), what
+    pred8 = torch.empty_like(ref[3])
+    p.pred_out = pred8.data_ptr()
+    M.ops._call_with_workspace(lib.mxa_attention_bits_workspace_bytes, lib.mxa_approx_scores_bits, "mxa_approx_scores_bits",
+                               p, 8, dev=dv)
+    torch.cuda.synchronize()
+    assert torch.equal(pred8.view(torch.int32), ref[3].view(torch.int32))
+    assert torch.equal(M.ops.approx_values(q, "sign", elem_bits=8), M.ops.approx_values(q, "sign"))
+
+
+def test_library_refuses_at_width_4(M):
+    q = dev(A.rnd((1, 2, 70, 64), 510))
+    with pytest.raises(M._native.NativeError):
+        M.mx_topk_attention(q.half(), q.half(), q.half(), 0.125, 20, elem_bits=4)
+    with pytest.raises(M._native.NativeError):
+        M.mx_topk_attention(q, q, q, 0.125, 20, autocast=torch.float16, elem_bits=4)
+    with pytest.raises(M._native.NativeError):
+        M.mx_topk_attention(q, q, q, 0.125, 20, pred_mode="ELSA", elsa_proj=torch.eye(64, device="cuda"), elem_bits=4)
+
+
+# ---- the drop-in under an int4 spec --------------------------------------------------------------------
+def test_dropin_int4_operands_and_matmul(M, gold):
+    """exponent_approximation at a_elem_format = "int4": the six operand pairs equal the
+    reference's bit for bit (from MXINT8 codes the sign, EXION and true_ex pairs differ);
+    mx.matmul(q, k^T) at that spec is the fused call's true score before the scale"""
+    M.install_dropin()
+    import mx
+    from funcs import exponent_approximation
+    from mx.specs import apply_mx_specs
+    specs = apply_mx_specs({"a_elem_format": "int4", "w_elem_format": "int4", "block_size": 32, "scale_bits": 8, "bfloat": 32})
+    q, k, v = dev(gold["self/q"]), dev(gold["self/k"]), dev(gold["self/v"])
+    for mode in A.MODES:
+        obj = exponent_approximation(q, k, specs)
+        fn = {"ex_pred": obj.exponent_based_sign, "true_ex": obj.exponent_based_sign_leading_ones}.get(mode, getattr(obj, mode, None))
+        aq, ak = fn()
+        same_bits(host(aq)[..., :32, :], gold[f"self/{mode}_k20/aq"], mode + " aq")
+        same_bits(host(ak)[..., :32, :], gold[f"self/{mode}_k20/ak"], mode + " ak")
+    s = mx.matmul(q, k.transpose(-2, -1), mx_specs=specs, mode_config="aa")
+    sc = float(gold["self/scale"])
+    true = M.mx_topk_attention(q, k, v, sc, 20, return_scores=True, elem_bits=4)[2]
+    same_bits(host(s * sc), host(true), "mx.matmul * scale vs the fused call's true scores")
+    same_bits(host(s * sc), gold["self/true"], "... vs the fixture")
