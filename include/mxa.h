@@ -268,6 +268,30 @@ int mxa_attention_bits(const mxa_attn_params* p, int32_t elem_bits, hipStream_t 
 int mxa_approx_scores_bits(const mxa_attn_params* p, int32_t elem_bits, hipStream_t stream);
 
 /*
+ * mxa_attention_bits with the whole of the 513 .. 1,024-key rows: the dense branch and every k_top.
+ * The reference's MXSelfAttention.forward takes attn = softmax(true scores)
+ * (workloads/PixArt/models/MX_transformer_block.py:704-705) when the model runs with
+ * self_top_k=False, in the exclude_timesteps and in the exclude_blocks -- at 512 x 512 a dense
+ * row of 1,024 keys -- and its self_k is a free parameter (the top-k branch, :700-702: gather,
+ * softmax, scatter).  The same parameter struct, strides, outputs and workspace rules.
+ *   - every call mxa_attention_bits(p, elem_bits) accepts runs exactly what that runs: the same
+ *     kernels, bytes, statuses and workspace size;
+ *   - with 513 <= T <= 1,024 also top_k == 0 and 65 <= k_top <= T, at elem_bits 8 and 4, on
+ *     finish_qk_long_kernel: every key's score and P.V on v_mfma_i32_16x16x32_i8, three passes
+ *     over the key blocks (maximum, sum, codes and P.V) with the arithmetic of finish_qk_kernel;
+ *     the top-k case behind select_long_kernel, whose prune-mask words it reads (a workspace
+ *     region when the caller takes no mask_out: the size does not depend on mask_out).
+ * MXA_ERR_UNSUPPORTED, before any HIP call: T > 1,024; with T > 512 float16 / bfloat16 tensors
+ * or a nonzero score_dtype; at elem_bits 4 what mxa_attention_bits refuses at T <= 512, and
+ * MXA_PRED_ELSA (with approx).  Any other width: -1 / MXA_ERR_ARG.  The fused projections keep
+ * their T <= 512 rule.  mxa_attention_full_finish_kernel: the MXA_FIN_* kind of the call
+ * (no launch; the workspace may be null), as mxa_attention_finish_kernel for mxa_attention.
+ */
+int64_t mxa_attention_full_workspace_bytes(const mxa_attn_params* p, int32_t elem_bits);
+int mxa_attention_full(const mxa_attn_params* p, int32_t elem_bits, hipStream_t stream);
+int mxa_attention_full_finish_kernel(const mxa_attn_params* p, int32_t elem_bits);
+
+/*
  * Which kernels mxa_attention(p) runs (no launch; the workspace may be null):
  *   MXA_PATH_ROWS_SPLIT  selection kernel (scores + top-k) then finishing kernel
  *                        (gather, softmax, MX(P), P.V on int8 MFMA) -- top_k != 0
@@ -288,6 +312,9 @@ int mxa_attention_path(const mxa_attn_params* p);
  *                       (the prune mask applied in the softmax)
  *   MXA_FIN_DENSE_MFMA  the dense branch (top_k == 0) on finish_qk_kernel, every key kept
  *   MXA_FIN_DENSE_ROWS  the dense branch on dense_rows_kernel (T > 256): v_dot4 for both
+ * and, reported by mxa_attention_full_finish_kernel for mxa_attention_full alone:
+ *   MXA_FIN_MFMA_LONG        finish_qk_long_kernel: top-k with k >= 65 on rows over 512 keys
+ *   MXA_FIN_DENSE_MFMA_LONG  finish_qk_long_kernel: top_k == 0 on rows over 512 keys
  * or a negative MXA_ERR_* for invalid parameters.
  */
 #define MXA_FIN_GATHER16 1
@@ -295,6 +322,8 @@ int mxa_attention_path(const mxa_attn_params* p);
 #define MXA_FIN_MFMA 3
 #define MXA_FIN_DENSE_MFMA 4
 #define MXA_FIN_DENSE_ROWS 5
+#define MXA_FIN_MFMA_LONG 6
+#define MXA_FIN_DENSE_MFMA_LONG 7
 int mxa_attention_finish_kernel(const mxa_attn_params* p);
 
 /*

@@ -32,6 +32,10 @@ FIN_KERNELS = {1: ("finish16_kernel", "v_dot4 (kept keys)", "v_mfma_i32_16x16x32
                    "v_mfma_i32_16x16x32_i8"),
                4: ("finish_qk_kernel (dense: every key kept)", "v_mfma_i32_16x16x32_i8", "v_mfma_i32_16x16x32_i8"),
                5: ("dense_rows_kernel", "v_dot4", "v_dot4")}
+# mxa_attention_full_finish_kernel reports these two besides: rows of 513 .. 1,024 keys
+FIN_KERNELS_FULL = {6: ("finish_qk_long_kernel", "v_mfma_i32_16x16x32_i8 (every key, prune mask in the softmax)",
+                   "v_mfma_i32_16x16x32_i8"),
+                    7: ("finish_qk_long_kernel (dense: every key kept)", "v_mfma_i32_16x16x32_i8", "v_mfma_i32_16x16x32_i8")}
 PRED_MODES = {"ex_pred": 0, "partial_Q": 1, "partial_K": 2, "MXINT4": 3, "two_step_leading_ones": 4,
               "true_ex": 5, "ELSA": 6}
 ROUND_MODES = {"nearest": 0, "floor": 1, "even": 2}
@@ -98,6 +102,9 @@ _SIGS = {
     "mxa_attention_bits_workspace_bytes": (c_i64, [c_vp, c_i32]),
     "mxa_attention_bits": (c_i32, [c_vp, c_i32, c_vp]),
     "mxa_approx_scores_bits": (c_i32, [c_vp, c_i32, c_vp]),
+    "mxa_attention_full_workspace_bytes": (c_i64, [c_vp, c_i32]),
+    "mxa_attention_full": (c_i32, [c_vp, c_i32, c_vp]),
+    "mxa_attention_full_finish_kernel": (c_i32, [c_vp, c_i32]),
     "mxa_attention_path": (c_i32, [ctypes.POINTER(AttnParams)]),
     "mxa_attention_finish_kernel": (c_i32, [ctypes.POINTER(AttnParams)]),
     "mxa_attention_timed": (c_i32, [ctypes.POINTER(AttnParams), c_vp, c_i32, ctypes.POINTER(c_f32)]),

@@ -33,9 +33,11 @@ UNITS += [("mxa_mlp.hip", "", ())]
 # the MFMA finishing kernel's float32 and float16 / bfloat16 instantiations (MXA_FQ_XDT)
 UNITS += [("mxa_fin_qk.hip", f"_x{i}", (f"MXA_FQ_XDT={i}",)) for i in range(2)]
 UNITS += [("mxa_fin_qk.hip", "_x0w4", ("MXA_FQ_W4=1",))]  # ... and its MXINT4-P ones
+# its tiled sibling for rows of 513 .. 1,024 keys: MXINT8-P and MXINT4-P instantiations (MXA_FQL_W4)
+UNITS += [("mxa_fin_qkl.hip", f"_w{8 - 4 * i}", (f"MXA_FQL_W4={i}",)) for i in range(2)]
 SOURCES = sorted({u[0] for u in UNITS})
 HEADERS = ["mxa_common.hpp", "mxa_kernels.hpp", "mxa_prep.hpp", "mxa_proj.hpp", "mxa_proj_args.hpp", "mxa_gemm_parts.hpp", "mxa_finish.hpp",
-           "mxa_order.hpp", "mxa_topk_grp.hpp", "mxa_topk_wave.hpp", "mxa_finish16.hpp", "mxa_finish_qk.hpp", "mxa_tail.hpp", "mxa_gemm.hpp", "mxa_dot.hpp", "mxa_select.hpp", "mxa_select_long.hpp", "mxa_rows2.hpp", "mxa_modes.hpp", "mxa_launch.hpp", "mxa_act.hpp", "mxa_mlp.hpp",
+           "mxa_order.hpp", "mxa_topk_grp.hpp", "mxa_topk_wave.hpp", "mxa_finish16.hpp", "mxa_finish_qk.hpp", "mxa_finish_qk_long.hpp", "mxa_tail.hpp", "mxa_gemm.hpp", "mxa_dot.hpp", "mxa_select.hpp", "mxa_select_long.hpp", "mxa_rows2.hpp", "mxa_modes.hpp", "mxa_launch.hpp", "mxa_act.hpp", "mxa_mlp.hpp",
            "../../include/mxa.h"]
 ARCH = os.environ.get("MXA_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

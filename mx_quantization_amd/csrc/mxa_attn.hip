@@ -14,6 +14,8 @@
 //                               MFMA (mxa_finish16.hpp, mxa_finish.hpp, mxa_finish_qk.hpp)
 //   dense (top_k=False)         finish_qk_kernel with every key kept (T <= 256), else
 //                               dense_rows_kernel (mxa_rows2.hpp)
+//   finish_qk_long_kernel       mxa_attention_full on rows of 513 .. 1,024 keys: the dense branch and
+//                               k > 64, three passes over the key blocks (mxa_finish_qk_long.hpp)
 //
 // This is the mx_quant branch of the patched attention forward:
 //   workloads/deit/scripts/main.py:100-152, workloads/DiT/models.py:168-225,
@@ -130,7 +132,7 @@ struct AttnLayout {
 
 // workspace: the call's, or null to size it
 AttnLayout attn_layout(const mxa_attn_params* p, int mode, const mxa_qkv_params* xq, const mxa_cross_params* xc,
-                       const mxa_proj_params* pj, void* workspace) {
+                       const mxa_proj_params* pj, void* workspace, bool full = false) {
   AttnLayout L{};
   Carver ws(workspace);
   const int64_t BH = (int64_t)p->B * p->H;
@@ -153,7 +155,9 @@ AttnLayout attn_layout(const mxa_attn_params* p, int mode, const mxa_qkv_params*
   }
   // the prune-mask words for the MFMA finishing kernel when the caller takes none
   // (reserved whatever mask_out is: the size must not depend on it)
-  L.mask = ws.take<uint32_t>(p->top_k && finish_qk_wanted(p->k_top, p->T, L.nbd, pj && proj_codes_direct(p))
+  // (mxa_attention_full: also for the tiled MFMA kernel of the long rows)
+  L.mask = ws.take<uint32_t>(p->top_k && (finish_qk_wanted(p->k_top, p->T, L.nbd, pj && proj_codes_direct(p)) ||
+                                          finish_qk_long_wanted(full, true, p->k_top, p->T))
                                  ? qrows * (int64_t)L.ntb
                                  : 0);
   const int64_t qtok = (int64_t)p->B * p->N;
@@ -175,8 +179,8 @@ bool attn_shape_ok(const mxa_attn_params* p) { return p && p->B > 0 && p->H > 0 
 // the workspace of a call; sized for the approximator whenever it may run (the proj Linear
 // and top-k run the selection kernel, pred_out the scores alone)
 int64_t attn_workspace_total(const mxa_attn_params* p, const mxa_qkv_params* xq, const mxa_cross_params* xc,
-                             const mxa_proj_params* pj) {
-  return attn_layout(p, score_mode(p, pj || p->top_k || p->pred_out), xq, xc, pj, nullptr).total;
+                             const mxa_proj_params* pj, bool full = false) {
+  return attn_layout(p, score_mode(p, pj || p->top_k || p->pred_out), xq, xc, pj, nullptr, full).total;
 }
 
 // One attention call
@@ -193,12 +197,15 @@ struct AttnCall {
                      // finishing kernel (MXA_FIN_*, 0 for the scores alone)
   int elem_bits;     // the *_bits entry points: 0 / 8 MXINT8; 4 MXINT4 for Q, K, P and V and for the codes
                      // every approximator is derived from (include/mxa.h mxa_attention_bits)
+  bool full;         // mxa_attention_full: rows over 512 keys also take the dense branch and k_top > 64
 };
 
 // the refusals of a call, in their order; every one before the prepared weights' header
 // checks returns without a HIP call
 int attn_validate(const AttnCall& c) {
-  const auto [p, stream, xq, xc, pj, scores_only, long_ok, ev, plan, fin, elem_bits] = c;
+  const auto [p, stream, xq, xc, pj, scores_only, long_ok, ev, plan, fin, elem_bits, full] = c;
+  // the long rows' dense branch and k_top > 64: mxa_attention_full's tiled MFMA kernel
+  const bool fql = !scores_only && finish_qk_long_wanted(full, p && p->top_k, p ? p->k_top : 0, p ? p->T : 0);
   if (elem_bits != 0 && elem_bits != 8 && elem_bits != 4) return MXA_ERR_ARG;
   if (!p) return MXA_ERR_ARG;
   if (pj) {
@@ -235,7 +242,7 @@ int attn_validate(const AttnCall& c) {
   if (p->T > (long_ok ? kLongRowsT : kShortRowsT) || p->D > 32 * kMaxNB) return MXA_ERR_UNSUPPORTED;
   // rows over 512 keys: the top-k path with k <= 64 (the 16-row finishing kernel without its K
   // table) or the scores alone; float32; no fused projection
-  if (long_rows(p->T) && (xq || xc || pj || (!scores_only && (!p->top_k || p->k_top > 64)) || p->dtype != MXA_DT_F32 ||
+  if (long_rows(p->T) && (xq || xc || pj || (!scores_only && !fql && (!p->top_k || p->k_top > 64)) || p->dtype != MXA_DT_F32 ||
                           p->score_dtype > MXA_DT_F32))
     return MXA_ERR_UNSUPPORTED;
   // MXINT4 (mxa_attention_bits at width 4): float32; the approximators of exponent_approximation
@@ -244,7 +251,7 @@ int attn_validate(const AttnCall& c) {
   if (elem_bits == 4 &&
       (xq || xc || pj || p->dtype != MXA_DT_F32 || p->score_dtype > MXA_DT_F32 ||
        (p->approx && p->pred_mode == MXA_PRED_ELSA) ||
-       (!scores_only && p->T > 256 && (!p->top_k || p->k_top > 64))))
+       (!scores_only && !fql && p->T > 256 && (!p->top_k || p->k_top > 64))))
     return MXA_ERR_UNSUPPORTED;
   // the prepared weights must have been prepared for this geometry and these settings
   const int HD = p->H * p->D, fl = p->flush_subnormals, bf = p->bfloat;
@@ -420,7 +427,7 @@ int attention_impl(const AttnCall& c) {
   const bool ranked = topk || c.scores_only;  // the selection kernel runs
   const int mode = score_mode(&pp, ranked);
   if (mode == kModeElsa && (!pp.elsa_proj || pp.N != pp.T)) return MXA_ERR_ARG;  // elsa_approximation.py:126, :142
-  const AttnLayout L = attn_layout(&pp, mode, c.xq, c.xc, c.pj, pp.workspace);
+  const AttnLayout L = attn_layout(&pp, mode, c.xq, c.xc, c.pj, pp.workspace, c.full);
   const int BH = (int)((int64_t)pp.B * pp.H);
   const bool direct = c.pj && proj_codes_direct(&pp);
 
@@ -443,12 +450,12 @@ int attention_impl(const AttnCall& c) {
                                           : launch_select(r2, mode, BH, c.stream, plan);
   };
   const int bits = c.elem_bits == 4 ? 4 : 8;
-  rc = c.scores_only ? MXA_OK : launch_rows(r2, topk, mode == kModeTrue, S, BH, c.stream, true, bits);
+  rc = c.scores_only ? MXA_OK : launch_rows(r2, topk, mode == kModeTrue, S, BH, c.stream, true, bits, c.full);
   if (!rc && ranked) rc = select(true);
   if (rc) return rc;
   if (c.plan) {
     *c.plan = topk ? MXA_PATH_ROWS_SPLIT : MXA_PATH_ROWS_FUSED;
-    if (c.fin) *c.fin = c.scores_only ? 0 : rows_kernel_kind(topk, r2.k_top, r2.T, r2.nbd, direct);
+    if (c.fin) *c.fin = c.scores_only ? 0 : rows_kernel_kind(topk, r2.k_top, r2.T, r2.nbd, direct, c.full);
     return MXA_OK;
   }
   if (!pp.workspace || pp.workspace_bytes < L.total) return MXA_ERR_WORKSPACE;
@@ -465,7 +472,7 @@ int attention_impl(const AttnCall& c) {
   if (rc) return rc;
   mark(4);
   if (!c.scores_only) {
-    rc = launch_rows(r2, topk, mode == kModeTrue, S, BH, c.stream, false, bits);
+    rc = launch_rows(r2, topk, mode == kModeTrue, S, BH, c.stream, false, bits, c.full);
     if (rc) return rc;
   }
   mark(5);
@@ -568,6 +575,25 @@ extern "C" int mxa_attention_bits(const mxa_attn_params* p, int32_t elem_bits, h
   if (elem_bits != 8 && elem_bits != 4) return MXA_ERR_ARG;
   if (elem_bits == 8) return mxa_attention_long(p, stream);
   return attention_impl({.p = p, .stream = stream, .long_rows = true, .elem_bits = 4});
+}
+
+// mxa_attention_bits plus, on rows over 512 keys, the dense branch and k_top > 64
+// (MX_transformer_block.py:704-705, :700-702) on finish_qk_long_kernel
+extern "C" int64_t mxa_attention_full_workspace_bytes(const mxa_attn_params* p, int32_t elem_bits) {
+  if (elem_bits != 8 && elem_bits != 4) return -1;
+  return attn_shape_ok(p) ? attn_workspace_total(p, nullptr, nullptr, nullptr, true) : -1;
+}
+
+extern "C" int mxa_attention_full(const mxa_attn_params* p, int32_t elem_bits, hipStream_t stream) {
+  if (elem_bits != 8 && elem_bits != 4) return MXA_ERR_ARG;
+  return attention_impl({.p = p, .stream = stream, .long_rows = true, .elem_bits = elem_bits == 4 ? 4 : 0, .full = true});
+}
+
+extern "C" int mxa_attention_full_finish_kernel(const mxa_attn_params* p, int32_t elem_bits) {
+  if (elem_bits != 8 && elem_bits != 4) return MXA_ERR_ARG;
+  int plan = -1, fin = -1;
+  const int rc = attention_impl({.p = p, .long_rows = true, .plan = &plan, .fin = &fin, .elem_bits = elem_bits == 4 ? 4 : 0, .full = true});
+  return rc ? rc : fin;
 }
 
 extern "C" int mxa_approx_scores_bits(const mxa_attn_params* p, int32_t elem_bits, hipStream_t stream) {

@@ -125,7 +125,18 @@ static int launch_finish(const Rows2Args& ra, int BH, hipStream_t stream, bool p
 
 // the row kernel of the path: the finishing kernel (top-k) or the dense kernel
 int launch_rows(const Rows2Args& ra, bool topk, bool true_mode, int S, int BH, hipStream_t stream, bool plan,
-                int elem_bits) {
+                int elem_bits, bool full) {
+  // mxa_attention_full on rows over 512 keys, the dense branch or k > 64: the tiled MFMA kernel
+  // (mxa_finish_qk_long.hpp), which reads the selection's prune-mask words or keeps every key
+  if (finish_qk_long_wanted(full, topk, ra.k_top, ra.T)) {
+    Rows2Args rl = ra;
+    if (topk && true_mode) rl.true_out = nullptr;  // (the selection kernel wrote them)
+    if (!topk) {
+      rl.dense = 1;
+      rl.mask_out = nullptr;
+    }
+    return elem_bits == 4 ? launch_finish_qk_long_w4(rl, BH, stream, plan) : launch_finish_qk_long_w8(rl, BH, stream, plan);
+  }
   if (topk) {
     // the selection kernel already wrote the true scores when it ranked them
     Rows2Args rf = ra;

@@ -137,7 +137,11 @@ inline bool finish_qk_wanted(int k, int T, int nbd, bool xo) { return k >= MXA_F
 inline bool finish_qk_dense_ok(int T, int nbd) { return T <= 256 && nbd <= 4; }
 // the finishing kernel of a call (include/mxa.h MXA_FIN_*): the single decision launch_rows
 // (mxa_fin.hip) dispatches on and mxa_attention_finish_kernel reports
-inline int rows_kernel_kind(bool topk, int k, int T, int nbd, bool xo) {
+// full (mxa_attention_full): rows over 512 keys also take the dense branch and k > 64, on the
+// tiled MFMA kernel (mxa_finish_qk_long.hpp); every other call is decided as without it
+inline bool finish_qk_long_wanted(bool full, bool topk, int k, int T) { return full && long_rows(T) && (!topk || k > 64); }
+inline int rows_kernel_kind(bool topk, int k, int T, int nbd, bool xo, bool full = false) {
+  if (finish_qk_long_wanted(full, topk, k, T)) return topk ? MXA_FIN_MFMA_LONG : MXA_FIN_DENSE_MFMA_LONG;
   if (!topk) return finish_qk_dense_ok(T, nbd) ? MXA_FIN_DENSE_MFMA : MXA_FIN_DENSE_ROWS;
   if (finish_qk_wanted(k, T, nbd, xo)) return MXA_FIN_MFMA;
   // k <= 64 (DeiT's 20 / 30, PixArt's 20): 16-row tiles, four lanes per row (with the proj's
@@ -210,6 +214,9 @@ inline int launch_finish_tiles(const Rows2Args& ra, int BH, size_t lds, hipStrea
 int launch_finish_qk_x0(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 int launch_finish_qk_x1(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 int launch_finish_qk_x0w4(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);  // float32, MXINT4 P
+// its tiled sibling for rows of 513 .. 1,024 keys (mxa_fin_qkl.hip): float32, MXINT8 / MXINT4 P
+int launch_finish_qk_long_w8(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
+int launch_finish_qk_long_w4(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 // the 16-row finishing kernel (mxa_fin16.hip): float32 (x0), float16 / bfloat16 (x1)
 int launch_finish16_x0(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 int launch_finish16_x1(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
@@ -224,8 +231,9 @@ int launch_finish32_p4(const Rows2Args& ra, int BH, hipStream_t stream, bool pla
 // the row kernel of the path: finishing kernel (top-k) or dense row kernel (mxa_fin.hip)
 // elem_bits 4 (mxa_attention_bits): P is MXINT4 -- the MXINT4-P instantiations of the 16-row and
 // the MFMA kernel; MXA_ERR_UNSUPPORTED where the call would take the 32-row or the dense row kernel
+// full (mxa_attention_full): rows_kernel_kind's
 int launch_rows(const Rows2Args& ra, bool topk, bool true_mode, int S, int BH, hipStream_t stream, bool plan,
-                int elem_bits = 8);
+                int elem_bits = 8, bool full = false);
 // fused projection kernel (mxa_proj.hip): part 0 the self-attention q, k, v of one token
 // matrix, 1 / 2 cross-attention's q and k, v passes (mxa_proj.hpp ProjPart)
 int launch_proj(const ProjArgs& pa, hipStream_t stream, int part = 0);

@@ -386,7 +386,9 @@ def mx_topk_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: 
     true / pred are float32 tensors holding the score-dtype values.
     elem_bits: 8, or 4 -- Q, K, P and V as MXINT4 and every approximator from the MXINT4 codes
     (the reference at a_elem_format = w_elem_format = "int4"; include/mxa.h mxa_attention_bits:
-    float32, no autocast, no ELSA -- the library refuses those)."""
+    float32, no autocast, no ELSA -- the library refuses those).
+    Rows of 513 .. 1,024 keys (float32): top_k=False and k_top > 64 go to mxa_attention_full, at
+    either width; k_top <= 64 to mxa_attention_long / mxa_attention_bits."""
     bits = _elem_bits(elem_bits)
     p, dev, (B, H, Nq, T, D), keep = _attn_params(q, k, v, scale, k_top, pred_mode, top_k, approx and top_k, bias,
                                                   flush_subnormals, bfloat, elsa_proj, autocast)
@@ -410,7 +412,12 @@ def mx_topk_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: 
         true_s = torch.empty((B, H, Nq, T), dtype=torch.float32, device=dev)
         pred_s = torch.full((B, H, Nq, T), float("nan"), dtype=torch.float32, device=dev)
         p.true_out, p.pred_out = true_s.data_ptr(), pred_s.data_ptr()
-    if bits == 4:
+    if T > LONG_ROWS_T and (not top_k or k_top > 64):
+        # the dense branch and k > 64 on rows of 513 .. 1,024 keys (PixArt 512 x 512 with self_top_k=False,
+        # exclude_timesteps or exclude_blocks; a large self_k): finish_qk_long_kernel, either width
+        _call_with_workspace(lib().mxa_attention_full_workspace_bytes, lib().mxa_attention_full, "mxa_attention_full", p,
+                             bits, dev=dev)
+    elif bits == 4:
         _call_with_workspace(lib().mxa_attention_bits_workspace_bytes, lib().mxa_attention_bits, "mxa_attention_bits", p,
                              bits, dev=dev)
     elif T > LONG_ROWS_T:  # rows of 513 .. 1,024 keys: the sibling entry points (include/mxa.h)
