@@ -16,6 +16,9 @@
 //                               dense_rows_kernel (mxa_rows2.hpp)
 //   finish_qk_long_kernel       mxa_attention_full on rows of 513 .. 1,024 keys: the dense branch and
 //                               k > 64, three passes over the key blocks (mxa_finish_qk_long.hpp)
+// Which of these finishes a call is finish_choice's answer (mxa_launch.hpp) to the call's facts
+// (attn_fin_facts): attn_validate takes its refusal, attn_layout whether to hold mask words,
+// launch_rows (mxa_fin.hip) the kernel, the *_finish_kernel entry points the kind they report.
 //
 // This is the mx_quant branch of the patched attention forward:
 //   workloads/deit/scripts/main.py:100-152, workloads/DiT/models.py:168-225,
@@ -102,6 +105,12 @@ bool proj_codes_direct(const mxa_attn_params* p) {
   return p->D % 32 == 0 && p->dtype == MXA_DT_F32 && p->score_dtype <= MXA_DT_F32;
 }
 
+// what finish_choice (mxa_launch.hpp) decides a call's finishing kernel from
+FinFacts attn_fin_facts(const mxa_attn_params* p, const mxa_proj_params* pj, int elem_bits, bool full) {
+  return {p->top_k != 0, p->top_k ? p->k_top : 0, p->T, (p->D + 31) / 32, pj && proj_codes_direct(p),
+          p->dtype != MXA_DT_F32 || p->score_dtype > MXA_DT_F32, elem_bits, full};
+}
+
 // one side's (Q's or K's) row operands; null: the score mode does not read it
 struct AttnOperands { int8_t *codes, *op, *z; int16_t *sT, *sA; uint32_t* sg; };
 AttnOperands carve_operands(Carver& ws, int64_t rows, int nbd, const ModeNeeds& n) {
@@ -132,7 +141,7 @@ struct AttnLayout {
 
 // workspace: the call's, or null to size it
 AttnLayout attn_layout(const mxa_attn_params* p, int mode, const mxa_qkv_params* xq, const mxa_cross_params* xc,
-                       const mxa_proj_params* pj, void* workspace, bool full = false) {
+                       const mxa_proj_params* pj, void* workspace, bool full) {
   AttnLayout L{};
   Carver ws(workspace);
   const int64_t BH = (int64_t)p->B * p->H;
@@ -153,13 +162,9 @@ AttnLayout attn_layout(const mxa_attn_params* p, int mode, const mxa_qkv_params*
     L.tail = ws.take<uint32_t>(tw ? qrows * (int64_t)tail_rec_words(tw) : 0);
     L.fbf = ws.take<uint32_t>(pk ? BH * (int64_t)((p->N + 15) / 16) : 0);
   }
-  // the prune-mask words for the MFMA finishing kernel when the caller takes none
-  // (reserved whatever mask_out is: the size must not depend on it)
-  // (mxa_attention_full: also for the tiled MFMA kernel of the long rows)
-  L.mask = ws.take<uint32_t>(p->top_k && (finish_qk_wanted(p->k_top, p->T, L.nbd, pj && proj_codes_direct(p)) ||
-                                          finish_qk_long_wanted(full, true, p->k_top, p->T))
-                                 ? qrows * (int64_t)L.ntb
-                                 : 0);
+  // the prune-mask words for a finishing kernel that reads them, when the caller takes none
+  // (reserved whatever mask_out is: the size must not depend on it, nor on P's width)
+  L.mask = ws.take<uint32_t>(finish_choice(attn_fin_facts(p, pj, 8, full)).reads_mask ? qrows * (int64_t)L.ntb : 0);
   const int64_t qtok = (int64_t)p->B * p->N;
   if (xq) L.x = carve_mx_rows(ws, qtok, xq->C, false);
   if (xc) {
@@ -179,7 +184,7 @@ bool attn_shape_ok(const mxa_attn_params* p) { return p && p->B > 0 && p->H > 0 
 // the workspace of a call; sized for the approximator whenever it may run (the proj Linear
 // and top-k run the selection kernel, pred_out the scores alone)
 int64_t attn_workspace_total(const mxa_attn_params* p, const mxa_qkv_params* xq, const mxa_cross_params* xc,
-                             const mxa_proj_params* pj, bool full = false) {
+                             const mxa_proj_params* pj, bool full) {
   return attn_layout(p, score_mode(p, pj || p->top_k || p->pred_out), xq, xc, pj, nullptr, full).total;
 }
 
@@ -195,8 +200,8 @@ struct AttnCall {
   hipEvent_t* ev;    // the timed entry points' stage events
   int *plan, *fin;   // plan: only report the kernel path (MXA_PATH_*), launch nothing; fin (with plan): the
                      // finishing kernel (MXA_FIN_*, 0 for the scores alone)
-  int elem_bits;     // the *_bits entry points: 0 / 8 MXINT8; 4 MXINT4 for Q, K, P and V and for the codes
-                     // every approximator is derived from (include/mxa.h mxa_attention_bits)
+  int elem_bits = 8;  // 8 MXINT8; 4 (the *_bits / *_full entry points) MXINT4 for Q, K, P and V and for the
+                      // codes every approximator is derived from (include/mxa.h mxa_attention_bits)
   bool full;         // mxa_attention_full: rows over 512 keys also take the dense branch and k_top > 64
 };
 
@@ -204,9 +209,6 @@ struct AttnCall {
 // checks returns without a HIP call
 int attn_validate(const AttnCall& c) {
   const auto [p, stream, xq, xc, pj, scores_only, long_ok, ev, plan, fin, elem_bits, full] = c;
-  // the long rows' dense branch and k_top > 64: mxa_attention_full's tiled MFMA kernel
-  const bool fql = !scores_only && finish_qk_long_wanted(full, p && p->top_k, p ? p->k_top : 0, p ? p->T : 0);
-  if (elem_bits != 0 && elem_bits != 8 && elem_bits != 4) return MXA_ERR_ARG;
   if (!p) return MXA_ERR_ARG;
   if (pj) {
     if (scores_only || !p->top_k || !pj->wq || !pj->y || pj->out_features <= 0 || pj->y_row_stride < pj->out_features)
@@ -240,19 +242,14 @@ int attn_validate(const AttnCall& c) {
     return MXA_ERR_UNSUPPORTED;
   if (!valid_bfloat(p->bfloat)) return MXA_ERR_ARG;
   if (p->T > (long_ok ? kLongRowsT : kShortRowsT) || p->D > 32 * kMaxNB) return MXA_ERR_UNSUPPORTED;
-  // rows over 512 keys: the top-k path with k <= 64 (the 16-row finishing kernel without its K
-  // table) or the scores alone; float32; no fused projection
-  if (long_rows(p->T) && (xq || xc || pj || (!scores_only && !fql && (!p->top_k || p->k_top > 64)) || p->dtype != MXA_DT_F32 ||
-                          p->score_dtype > MXA_DT_F32))
+  // rows over 512 keys, and MXINT4 (mxa_attention_bits at width 4): float32, no fused projection;
+  // MXINT4: the approximators of exponent_approximation (ELSA's hashes would need the width too)
+  if ((long_rows(p->T) || elem_bits == 4) && (xq || xc || pj || p->dtype != MXA_DT_F32 || p->score_dtype > MXA_DT_F32))
     return MXA_ERR_UNSUPPORTED;
-  // MXINT4 (mxa_attention_bits at width 4): float32; the approximators of exponent_approximation
-  // (ELSA's hashes would need the width too); the finishing kernels with an MXINT4-P
-  // instantiation -- finish16_kernel (k <= 64) and finish_qk_kernel (T <= 256); no fused projection
-  if (elem_bits == 4 &&
-      (xq || xc || pj || p->dtype != MXA_DT_F32 || p->score_dtype > MXA_DT_F32 ||
-       (p->approx && p->pred_mode == MXA_PRED_ELSA) ||
-       (!scores_only && !fql && p->T > 256 && (!p->top_k || p->k_top > 64))))
-    return MXA_ERR_UNSUPPORTED;
+  if (elem_bits == 4 && p->approx && p->pred_mode == MXA_PRED_ELSA) return MXA_ERR_UNSUPPORTED;
+  // ... and a finishing kernel with an instantiation for them (finish_choice: the 16-row and the MFMA
+  // kernels), or the scores alone
+  if (!scores_only && finish_choice(attn_fin_facts(p, pj, elem_bits, full)).status) return MXA_ERR_UNSUPPORTED;
   // the prepared weights must have been prepared for this geometry and these settings
   const int HD = p->H * p->D, fl = p->flush_subnormals, bf = p->bfloat;
   if (xq && !linear_weight_verify(xq->wq, linear_weight_header(3 * HD, xq->C, p->D, fl, bf), stream)) return MXA_ERR_ARG;
@@ -326,7 +323,7 @@ int launch_proj_pass(const mxa_attn_params& pp, int part, const ProjTokens& t, c
 // -> the q operands, then its key / value tokens -> the k operands and V (two launches of
 // the projection kernel by parts)
 int attn_build_operands(const AttnCall& c, const mxa_attn_params& pp, const AttnLayout& L, int opq, int opk) {
-  const int bits = c.elem_bits == 4 ? 4 : 8;
+  const int bits = c.elem_bits;
   const RowsPrepArgs rq = attn_rows_prep(pp, L, L.q, pp.q, pp.q_strides, pp.N, opq, bits);
   const RowsPrepArgs rk = attn_rows_prep(pp, L, L.k, pp.k, pp.k_strides, pp.T, opk, bits);
   ColsPrepArgs cv{};
@@ -429,7 +426,8 @@ int attention_impl(const AttnCall& c) {
   if (mode == kModeElsa && (!pp.elsa_proj || pp.N != pp.T)) return MXA_ERR_ARG;  // elsa_approximation.py:126, :142
   const AttnLayout L = attn_layout(&pp, mode, c.xq, c.xc, c.pj, pp.workspace, c.full);
   const int BH = (int)((int64_t)pp.B * pp.H);
-  const bool direct = c.pj && proj_codes_direct(&pp);
+  const FinFacts ff = attn_fin_facts(&pp, c.pj, c.elem_bits, c.full);
+  const bool direct = ff.xo;
 
   int opq = MXA_OP_SIGN, opk = MXA_OP_SIGN;
   switch (pp.pred_mode) {
@@ -449,13 +447,12 @@ int attention_impl(const AttnCall& c) {
     return c.long_rows && long_rows(pp.T) ? launch_select_long(r2, mode, BH, c.stream, plan)
                                           : launch_select(r2, mode, BH, c.stream, plan);
   };
-  const int bits = c.elem_bits == 4 ? 4 : 8;
-  rc = c.scores_only ? MXA_OK : launch_rows(r2, topk, mode == kModeTrue, S, BH, c.stream, true, bits, c.full);
+  rc = c.scores_only ? MXA_OK : launch_rows(r2, ff, mode == kModeTrue, S, BH, c.stream, true);
   if (!rc && ranked) rc = select(true);
   if (rc) return rc;
   if (c.plan) {
     *c.plan = topk ? MXA_PATH_ROWS_SPLIT : MXA_PATH_ROWS_FUSED;
-    if (c.fin) *c.fin = c.scores_only ? 0 : rows_kernel_kind(topk, r2.k_top, r2.T, r2.nbd, direct, c.full);
+    if (c.fin) *c.fin = c.scores_only ? 0 : finish_choice(ff).kind;
     return MXA_OK;
   }
   if (!pp.workspace || pp.workspace_bytes < L.total) return MXA_ERR_WORKSPACE;
@@ -472,7 +469,7 @@ int attention_impl(const AttnCall& c) {
   if (rc) return rc;
   mark(4);
   if (!c.scores_only) {
-    rc = launch_rows(r2, topk, mode == kModeTrue, S, BH, c.stream, false, bits, c.full);
+    rc = launch_rows(r2, ff, mode == kModeTrue, S, BH, c.stream, false);
     if (rc) return rc;
   }
   mark(5);
@@ -526,24 +523,24 @@ extern "C" const char* mxa_status_string(int status) {
 }
 
 extern "C" int64_t mxa_attention_workspace_bytes(const mxa_attn_params* p) {
-  return attn_shape_ok(p) ? attn_workspace_total(p, nullptr, nullptr, nullptr) : -1;
+  return attn_shape_ok(p) ? attn_workspace_total(p, nullptr, nullptr, nullptr, false) : -1;
 }
 
 extern "C" int64_t mxa_qkv_attention_workspace_bytes(const mxa_attn_params* p, const mxa_qkv_params* xq) {
   if (!attn_shape_ok(p) || !xq || xq->C <= 0) return -1;
-  return attn_workspace_total(p, xq, nullptr, nullptr);
+  return attn_workspace_total(p, xq, nullptr, nullptr, false);
 }
 
 extern "C" int64_t mxa_attention_proj_workspace_bytes(const mxa_attn_params* p, const mxa_qkv_params* xq,
                                                       const mxa_proj_params* pj) {
   if (!attn_shape_ok(p) || !pj || pj->out_features <= 0 || (xq && xq->C <= 0)) return -1;
-  return attn_workspace_total(p, xq, nullptr, pj);
+  return attn_workspace_total(p, xq, nullptr, pj, false);
 }
 
 extern "C" int64_t mxa_cross_attention_workspace_bytes(const mxa_attn_params* p, const mxa_cross_params* xc,
                                                        const mxa_proj_params* pj) {
   if (!attn_shape_ok(p) || !xc || xc->C <= 0 || xc->C_kv <= 0 || (pj && pj->out_features <= 0)) return -1;
-  return attn_workspace_total(p, nullptr, xc, pj);
+  return attn_workspace_total(p, nullptr, xc, pj, false);
 }
 
 extern "C" int mxa_attention(const mxa_attn_params* p, hipStream_t stream) {
@@ -573,8 +570,7 @@ extern "C" int64_t mxa_attention_bits_workspace_bytes(const mxa_attn_params* p, 
 
 extern "C" int mxa_attention_bits(const mxa_attn_params* p, int32_t elem_bits, hipStream_t stream) {
   if (elem_bits != 8 && elem_bits != 4) return MXA_ERR_ARG;
-  if (elem_bits == 8) return mxa_attention_long(p, stream);
-  return attention_impl({.p = p, .stream = stream, .long_rows = true, .elem_bits = 4});
+  return attention_impl({.p = p, .stream = stream, .long_rows = true, .elem_bits = elem_bits});
 }
 
 // mxa_attention_bits plus, on rows over 512 keys, the dense branch and k_top > 64
@@ -586,20 +582,19 @@ extern "C" int64_t mxa_attention_full_workspace_bytes(const mxa_attn_params* p, 
 
 extern "C" int mxa_attention_full(const mxa_attn_params* p, int32_t elem_bits, hipStream_t stream) {
   if (elem_bits != 8 && elem_bits != 4) return MXA_ERR_ARG;
-  return attention_impl({.p = p, .stream = stream, .long_rows = true, .elem_bits = elem_bits == 4 ? 4 : 0, .full = true});
+  return attention_impl({.p = p, .stream = stream, .long_rows = true, .elem_bits = elem_bits, .full = true});
 }
 
 extern "C" int mxa_attention_full_finish_kernel(const mxa_attn_params* p, int32_t elem_bits) {
   if (elem_bits != 8 && elem_bits != 4) return MXA_ERR_ARG;
   int plan = -1, fin = -1;
-  const int rc = attention_impl({.p = p, .long_rows = true, .plan = &plan, .fin = &fin, .elem_bits = elem_bits == 4 ? 4 : 0, .full = true});
+  const int rc = attention_impl({.p = p, .long_rows = true, .plan = &plan, .fin = &fin, .elem_bits = elem_bits, .full = true});
   return rc ? rc : fin;
 }
 
 extern "C" int mxa_approx_scores_bits(const mxa_attn_params* p, int32_t elem_bits, hipStream_t stream) {
   if (elem_bits != 8 && elem_bits != 4) return MXA_ERR_ARG;
-  if (elem_bits == 8) return mxa_approx_scores_long(p, stream);
-  return attention_impl({.p = p, .stream = stream, .scores_only = true, .long_rows = true, .elem_bits = 4});
+  return attention_impl({.p = p, .stream = stream, .scores_only = true, .long_rows = true, .elem_bits = elem_bits});
 }
 
 extern "C" int mxa_qkv_attention(const mxa_attn_params* p, const mxa_qkv_params* xq, hipStream_t stream) {

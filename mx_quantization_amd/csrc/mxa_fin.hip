@@ -1,6 +1,8 @@
-// Row-kernel launches: the finishing kernel of the top-k path (mxa_finish.hpp) and the
-// dense (top_k=False) branch: the MFMA finishing kernel with every key kept
-// (mxa_finish_qk.hpp, T <= 256), else the row kernel (mxa_rows2.hpp).
+// Row-kernel launches.  launch_rows switches once on the kind finish_choice (mxa_launch.hpp)
+// gives for the call and hands over to that kernel's launcher: the MFMA finishing kernels
+// (mxa_fin_qk.hip, mxa_fin_qkl.hip), the 16-row gather kernel (mxa_fin16.hip), and the two
+// launched from this file: the 32-row gather kernel (mxa_finish.hpp) and the dense branch's
+// v_dot4 row kernel (mxa_rows2.hpp).
 #include "mxa_finish.hpp"
 #include "mxa_launch.hpp"
 
@@ -100,65 +102,47 @@ int MXA_FIN_FN(MXA_FIN_PART)(const Rows2Args& ra, int BH, hipStream_t stream, bo
   return launch_finish_nb<MXA_FIN_PART>(ra, BH, stream);
 }
 #else
-static int launch_finish(const Rows2Args& ra, int BH, hipStream_t stream, bool plan, int elem_bits) {
-  const int kind = rows_kernel_kind(true, ra.k_top, ra.T, ra.nbd, ra.xo_codes != nullptr);
-  const bool xdt = ra.s_dt != kF32 || ra.in_dt != kF32;
-  if (elem_bits == 4) {  // MXINT4 P: the 16-row kernel (short and LONG) and the MFMA kernel, float32
-    if (xdt || ra.xo_codes) return MXA_ERR_UNSUPPORTED;
-    if (kind == MXA_FIN_MFMA) return launch_finish_qk_x0w4(ra, BH, stream, plan);
-    if (kind != MXA_FIN_GATHER16) return MXA_ERR_UNSUPPORTED;
-    return long_rows(ra.T) ? launch_finish16_l0w4(ra, BH, stream, plan) : launch_finish16_x0w4(ra, BH, stream, plan);
+// the row kernel of the path: the one switch over finish_choice's kind (mxa_launch.hpp)
+int launch_rows(const Rows2Args& ra0, const FinFacts& f, bool true_mode, int S, int BH, hipStream_t stream, bool plan) {
+  const FinChoice c = finish_choice(f);
+  if (c.status) return c.status;
+  Rows2Args ra = ra0;
+  if (f.topk && true_mode) ra.true_out = nullptr;  // the selection kernel already wrote the true scores
+  if (c.kind == MXA_FIN_DENSE_MFMA || c.kind == MXA_FIN_DENSE_MFMA_LONG) {  // every key kept: no mask words
+    ra.dense = 1;
+    ra.mask_out = nullptr;
   }
-  if (kind == MXA_FIN_MFMA) return xdt ? launch_finish_qk_x1(ra, BH, stream, plan) : launch_finish_qk_x0(ra, BH, stream, plan);
-  // k <= 64 (DeiT's 20 / 30, PixArt's 20): 16-row tiles, four lanes per row (also with the
-  // proj's MX input codes for k <= 32); larger k with T > 256: the 32-row kernel.
-  // (rows over 512 keys, float32 only: its LONG instantiations, which stage no K table)
-  if (kind == MXA_FIN_GATHER16 && long_rows(ra.T) && !xdt) return launch_finish16_l0(ra, BH, stream, plan);
-  if (kind == MXA_FIN_GATHER16) return xdt ? launch_finish16_x1(ra, BH, stream, plan) : launch_finish16_x0(ra, BH, stream, plan);
-  switch (ra.nbd) {
-    case 1: return launch_finish32_p1(ra, BH, stream, plan);
-    case 2: return launch_finish32_p2(ra, BH, stream, plan);
-    case 3: return launch_finish32_p3(ra, BH, stream, plan);
-    default: return launch_finish32_p4(ra, BH, stream, plan);
-  }
-}
-
-// the row kernel of the path: the finishing kernel (top-k) or the dense kernel
-int launch_rows(const Rows2Args& ra, bool topk, bool true_mode, int S, int BH, hipStream_t stream, bool plan,
-                int elem_bits, bool full) {
-  // mxa_attention_full on rows over 512 keys, the dense branch or k > 64: the tiled MFMA kernel
-  // (mxa_finish_qk_long.hpp), which reads the selection's prune-mask words or keeps every key
-  if (finish_qk_long_wanted(full, topk, ra.k_top, ra.T)) {
-    Rows2Args rl = ra;
-    if (topk && true_mode) rl.true_out = nullptr;  // (the selection kernel wrote them)
-    if (!topk) {
-      rl.dense = 1;
-      rl.mask_out = nullptr;
-    }
-    return elem_bits == 4 ? launch_finish_qk_long_w4(rl, BH, stream, plan) : launch_finish_qk_long_w8(rl, BH, stream, plan);
-  }
-  if (topk) {
-    // the selection kernel already wrote the true scores when it ranked them
-    Rows2Args rf = ra;
-    if (true_mode) rf.true_out = nullptr;
-    return launch_finish(rf, BH, stream, plan, elem_bits);
-  }
-  // the dense branch: the MFMA finishing kernel with every key kept (T <= 256: a row's scores
-  // in registers); longer rows: the v_dot4 row kernel
-  if (rows_kernel_kind(false, 0, ra.T, ra.nbd, false) == MXA_FIN_DENSE_MFMA) {
-    Rows2Args rd = ra;
-    rd.dense = 1;
-    rd.mask_out = nullptr;
-    if (elem_bits == 4) return launch_finish_qk_x0w4(rd, BH, stream, plan);  // (refuses float16 / bfloat16)
-    if (rd.s_dt != kF32 || rd.in_dt != kF32) return launch_finish_qk_x1(rd, BH, stream, plan);
-    return launch_finish_qk_x0(rd, BH, stream, plan);
-  }
-  if (elem_bits == 4) return MXA_ERR_UNSUPPORTED;  // dense_rows_kernel: MXINT8 P only
-  switch (S) {
-    case 1: return launch_dense_s<1>(ra, BH, stream, plan);
-    case 2: return launch_dense_s<2>(ra, BH, stream, plan);
-    case 4: return launch_dense_s<4>(ra, BH, stream, plan);
-    default: return launch_dense_s<8>(ra, BH, stream, plan);
+  // the plan pass runs before the workspace is bound: the gather kernels' LDS plans read only whether the
+  // proj's code pointer is set, never the pointer
+  static int8_t plan_xo;
+  if (plan && f.xo) ra.xo_codes = &plan_xo;
+  const bool w4 = f.bits == 4;  // (finish_choice: float32 then)
+  switch (c.kind) {
+    case MXA_FIN_MFMA_LONG:
+    case MXA_FIN_DENSE_MFMA_LONG:
+      return w4 ? launch_finish_qk_long_w4(ra, BH, stream, plan) : launch_finish_qk_long_w8(ra, BH, stream, plan);
+    case MXA_FIN_MFMA:
+    case MXA_FIN_DENSE_MFMA:
+      if (w4) return launch_finish_qk_x0w4(ra, BH, stream, plan);
+      return f.xdt ? launch_finish_qk_x1(ra, BH, stream, plan) : launch_finish_qk_x0(ra, BH, stream, plan);
+    case MXA_FIN_GATHER16:  // (rows over 512 keys: the LONG instantiations, which stage no K table)
+      if (long_rows(ra.T)) return w4 ? launch_finish16_l0w4(ra, BH, stream, plan) : launch_finish16_l0(ra, BH, stream, plan);
+      if (w4) return launch_finish16_x0w4(ra, BH, stream, plan);
+      return f.xdt ? launch_finish16_x1(ra, BH, stream, plan) : launch_finish16_x0(ra, BH, stream, plan);
+    case MXA_FIN_GATHER32:
+      switch (ra.nbd) {
+        case 1: return launch_finish32_p1(ra, BH, stream, plan);
+        case 2: return launch_finish32_p2(ra, BH, stream, plan);
+        case 3: return launch_finish32_p3(ra, BH, stream, plan);
+        default: return launch_finish32_p4(ra, BH, stream, plan);
+      }
+    default:  // MXA_FIN_DENSE_ROWS
+      switch (S) {
+        case 1: return launch_dense_s<1>(ra, BH, stream, plan);
+        case 2: return launch_dense_s<2>(ra, BH, stream, plan);
+        case 4: return launch_dense_s<4>(ra, BH, stream, plan);
+        default: return launch_dense_s<8>(ra, BH, stream, plan);
+      }
   }
 }
 #endif  // MXA_FIN_PART

@@ -18,25 +18,12 @@ namespace mxa {
 
 constexpr bool kW4 = MXA_FQL_W4 != 0;
 
-// waves per workgroup by finish_tile_plan (mxa_launch.hpp): LDS per workgroup only, none per wave
-static int finish_qk_long_plan(const Rows2Args& ra, int BH, int regs_waves_per_simd, int* waves, int* rows_per_wg) {
-  const size_t t = fql_lds(ra.nbd, ra.D).total;
-  return finish_tile_plan(kFqRows, ra.N, BH, [t](int) { return t; }, finish_wave_cap(regs_waves_per_simd), waves,
-                          rows_per_wg);
-}
-template <int NB, bool EXTRA>
-static int launch_finish_qk_long_x(Rows2Args ra, int BH, hipStream_t stream) {
-  constexpr auto kernel = &finish_qk_long_kernel<NB, kW4, EXTRA>;
-  int rc = finish_qk_long_plan(ra, BH, kernel_waves_per_simd<kernel>(), &ra.waves, &ra.rows_per_wg);
-  if (rc) return rc;
-  return launch_finish_tiles<kernel>(ra, BH, fql_lds(NB, ra.D).total, stream);
-}
 template <int NB>
 static int launch_finish_qk_long_nb(const Rows2Args& ra, int BH, hipStream_t stream) {
   if ((!ra.mask_out && !ra.dense) || ra.dpad != 32 * NB) return MXA_ERR_ARG;
-  // EXTRA: a bias, the debug true scores or bfloatX rounding
-  const bool extra = ra.bias || ra.true_out || (ra.bfloat != 0 && ra.bfloat != 32);
-  return extra ? launch_finish_qk_long_x<NB, true>(ra, BH, stream) : launch_finish_qk_long_x<NB, false>(ra, BH, stream);
+  const size_t lds = fql_lds(NB, ra.D).total;
+  if (finish_mfma_extra(ra)) return launch_finish_mfma<&finish_qk_long_kernel<NB, kW4, true>>(ra, kFqRows, lds, BH, stream);
+  return launch_finish_mfma<&finish_qk_long_kernel<NB, kW4, false>>(ra, kFqRows, lds, BH, stream);
 }
 
 int MXA_FQL_FN(const Rows2Args& ra, int BH, hipStream_t stream, bool plan) {
@@ -44,14 +31,9 @@ int MXA_FQL_FN(const Rows2Args& ra, int BH, hipStream_t stream, bool plan) {
   if (ra.T > kFqlT || ra.ntb > kFqlNTB || ra.nbd < 1 || ra.nbd > 4 || ra.D > 32 * ra.nbd) return MXA_ERR_UNSUPPORTED;
   if (plan) {
     int w, r;
-    return finish_qk_long_plan(ra, BH, 2, &w, &r);
+    return finish_mfma_plan(ra, kFqRows, fql_lds(ra.nbd, ra.D).total, BH, 2, &w, &r);
   }
-  switch (ra.nbd) {
-    case 1: return launch_finish_qk_long_nb<1>(ra, BH, stream);
-    case 2: return launch_finish_qk_long_nb<2>(ra, BH, stream);
-    case 3: return launch_finish_qk_long_nb<3>(ra, BH, stream);
-    default: return launch_finish_qk_long_nb<4>(ra, BH, stream);
-  }
+  return dispatch_nbd(ra.nbd, [&](auto nb) { return launch_finish_qk_long_nb<decltype(nb)::value>(ra, BH, stream); });
 }
 
 }  // namespace mxa

@@ -1,7 +1,7 @@
 // Finishing kernel of the top-k path: for every query row and its k kept keys
 // (select_kernel's indices), the true scores, softmax, MX(P) along keys and P.V,
 // with P.V on int8 MFMA.  This is the 32-ROW kernel, for the calls the two 16-row kernels
-// do not take (mxa_launch.hpp rows_kernel_kind): k > 64 with rows of more than 256 keys
+// do not take (mxa_launch.hpp finish_choice): k > 64 with rows of more than 256 keys
 // (below that mxa_finish_qk.hpp scores every key on MFMA), and k > 32 when the output
 // goes to the proj Linear as MX codes (XO); k <= 64 (k <= 32 with XO) is
 // mxa_finish16.hpp's.  The rules the three kernels share -- the true-score roundings,

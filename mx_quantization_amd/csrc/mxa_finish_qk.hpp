@@ -128,6 +128,176 @@ __device__ __forceinline__ float fq_exact(const int* I, const int* e) {
   return (float)acc;
 }
 
+// ---- the parts finish_qk_kernel and finish_qk_long_kernel (mxa_finish_qk_long.hpp) share ------
+// What differs between the two is an argument or a template constant: the strides of the LDS
+// tables (KES keys per row of tke / tkx, NTBS key blocks per row of ttg / tvs), where a K or V^T
+// operand comes from (the caller hands the MFMA operands or accumulators over), W4, XDT, EXTRA.
+// A part takes the fields of Rows2Args it needs by value, as the shared rules of mxa_finish.hpp do:
+// with a reference to the kernel's argument struct the spill counts of float16 / bfloat16
+// instantiations at the 128-VGPR cap rise.
+// Two steps stay written out in both kernels, because the register allocation of instantiations at
+// the 128-VGPR cap moved upward with them as functions (profiles/r12_fq_parts_resources.txt): the P
+// block coding (fq_umax4, p_block, the eight packed codes) and the output store.  Both kernels must
+// keep them the same text.
+
+// The exact epilogue's per-key terms of the head's keys [0, tpad): the K exponents tke [NB][KES]
+// (int16, key order) and tkx [3][KES] (the key's smallest block exponent, its blocks' offsets from
+// it as bytes, its spread)
+template <int NB, int KES>
+__device__ __forceinline__ void fq_stage_key_terms(const int16_t* ksT, int T, int64_t kb, int tpad, int16_t* tke, int* tkx) {
+  for (int key = threadIdx.x; key < tpad; key += blockDim.x) {
+    int e[NB], emin = 1 << 20, emax = -(1 << 20);
+    bool nan = false;
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+      const int16_t raw = key < T ? ksT[(kb + key) * NB + b] : (int16_t)0;
+      tke[b * KES + key] = raw;
+      e[b] = exp_from16(raw);
+      nan = nan || e[b] == kExpNaN;
+      emin = min(emin, e[b]);
+      emax = max(emax, e[b]);
+    }
+    tkx[key] = nan ? -100000 : emin;
+    uint32_t dkp = 0u;  // offsets as bytes (the fast form needs them <= 10)
+#pragma unroll
+    for (int b = 0; b < NB; ++b) dkp |= (uint32_t)min(e[b] - emin, 255) << (8 * b);
+    tkx[KES + key] = (int)dkp;
+    tkx[2 * KES + key] = nan ? 1000 : emax - emin;
+  }
+}
+// The V block scales as floats, tvs [ceil(D / 16)][NTBS][16]
+template <int NTBS>
+__device__ __forceinline__ void fq_stage_v_scales(const int16_t* vs, int ntb, int D, int bh, float* tvs) {
+  const int16_t* vssrc = vs + (int64_t)bh * ntb * D;
+  for (int i = threadIdx.x; i < ntb * D; i += blockDim.x) {
+    const int tb = i / D, dd = i - tb * D;
+    tvs[((dd >> 4) * NTBS + tb) * 16 + (dd & 15)] = scale_f(exp_from16(vssrc[i]));
+  }
+}
+// Per 16-key tile, ttg [2][2 NTBS]: the smallest exponent and the largest spread of its keys (the
+// fast-path test); after a barrier behind fq_stage_key_terms, and one before the tiles read it
+template <int KES, int NTBS>
+__device__ __forceinline__ void fq_stage_tile_terms(int ntb, const int* tkx, int* ttg) {
+  if (threadIdx.x < 2 * ntb) {
+    const int tile = threadIdx.x;
+    int mn = 1 << 20, sp = 0;
+    for (int m = 0; m < 16; ++m) {
+      const int key = fq_key_of_row(16 * tile + m);
+      mn = min(mn, tkx[key]);
+      sp = max(sp, tkx[2 * KES + key]);
+    }
+    ttg[tile] = mn;
+    ttg[2 * NTBS + tile] = sp;
+  }
+}
+
+// A tile's query side in lane (q, g): the codes (B operand: row q, elements 32 b + 8 g ..), the
+// block exponents and the exact epilogue's query terms.  Fast form: sum_b I_b 2^(e_b) =
+// 2^(qmin + kmin) sum_b I_b 2^(dq_b + dk_b), an exact int32 while every shift dq_b + dk_b <= 10 --
+// the wave's largest query spread plus the key tile's largest spread -- and qmin + kmin >= -100 (no
+// subnormal result): the same float as true_dot's rule (fq_exact), which the tiles that fail it take
+template <int NB>
+struct FqQuery {
+  int64_t qb[NB];
+  int qe[NB];
+  int qmin;
+  uint32_t dqp;  // the query's offsets from qmin as bytes (<= 10 on the fast form: no carries)
+  int wq_spread, wq_min;
+};
+template <int NB>
+__device__ __forceinline__ FqQuery<NB> fq_load_query(const int8_t* qc, const int16_t* qsT, int64_t grow, int g) {
+  FqQuery<NB> Q;
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    Q.qb[b] = *reinterpret_cast<const int64_t*>(qc + grow * (32 * NB) + 32 * b + 8 * g);
+    Q.qe[b] = exp_from16(qsT[grow * NB + b]);
+  }
+  int qmin = Q.qe[0], qmax = Q.qe[0];
+  bool qnan = false;
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    qmin = min(qmin, Q.qe[b]);
+    qmax = max(qmax, Q.qe[b]);
+    qnan = qnan || Q.qe[b] == kExpNaN;
+  }
+  Q.qmin = qmin;
+  Q.dqp = 0u;
+#pragma unroll
+  for (int b = 0; b < NB; ++b) Q.dqp |= (uint32_t)min(Q.qe[b] - qmin, 255) << (8 * b);
+  Q.wq_spread = (int)wave_reduce((uint32_t)(qnan ? 1000 : qmax - qmin),
+                                 [](uint32_t x, uint32_t y) { return (int)x > (int)y ? x : y; });
+  Q.wq_min = (int)wave_reduce((uint32_t)(qnan ? -100000 : qmin),
+                              [](uint32_t x, uint32_t y) { return (int)x < (int)y ? x : y; });
+  return Q;
+}
+
+// The exact scores sc[0..3] of the lane's keys key0 .. key0 + 3 of key tile `tile` from its NB
+// MFMA accumulators c: the fast shifted-int32 form under its test, else fq_exact
+template <int NB, int KES, int NTBS>
+__device__ __forceinline__ void fq_tile_scores(const v4iq_* c, const FqQuery<NB>& Q, int tile, int key0, const int16_t* tke,
+                                               const int* tkx, const int* ttg, float* sc) {
+  const int tkm = __builtin_amdgcn_readfirstlane(ttg[tile]);
+  const int tsp = __builtin_amdgcn_readfirstlane(ttg[2 * NTBS + tile]);
+  if (Q.wq_spread + tsp <= 10 && Q.wq_min + tkm >= -100) {
+    const int4 km = *reinterpret_cast<const int4*>(tkx + key0);
+    const int4 dk = *reinterpret_cast<const int4*>(tkx + KES + key0);
+    auto comp = [](const int4& x, int i) { return i == 0 ? x.x : (i == 1 ? x.y : (i == 2 ? x.z : x.w)); };
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const uint32_t sh = Q.dqp + (uint32_t)comp(dk, i);  // byte b: the shift of block b
+      int sum = 0;
+#pragma unroll
+      for (int b = 0; b < NB; ++b) sum += c[b][i] << ((sh >> (8 * b)) & 31u);
+      sc[i] = ldexpf((float)sum, Q.qmin + comp(km, i));
+    }
+  } else {
+    int ke[NB][4];
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+      const uint2 w = *reinterpret_cast<const uint2*>(tke + b * KES + key0);
+      ke[b][0] = exp_from16((int16_t)(w.x & 0xFFFFu));
+      ke[b][1] = exp_from16((int16_t)(w.x >> 16));
+      ke[b][2] = exp_from16((int16_t)(w.y & 0xFFFFu));
+      ke[b][3] = exp_from16((int16_t)(w.y >> 16));
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      int I[NB], e[NB];
+#pragma unroll
+      for (int b = 0; b < NB; ++b) {
+        I[b] = c[b][i];
+        e[b] = Q.qe[b] + ke[b][i];
+      }
+      sc[i] = fq_exact<NB>(I, e);
+    }
+  }
+}
+
+// An exact score finished: the true score (scale, roundings), then with EXTRA the bias (brow: the
+// row's bias offset, < 0 none) and, write_true, the debug true-score output (row grow of true_out)
+template <bool EXTRA, bool ROUND>
+__device__ __forceinline__ float fq_finish_score(float sc, float scale, int bfloat, int T, const void* bias, int64_t bs3, float* true_out, int key,
+                                                 int64_t brow, int64_t grow, bool valid, bool write_true, int sdt, int idt) {
+  float s = true_score<ROUND>(sc, scale, bfloat, sdt);
+  if (EXTRA) {
+    if (brow >= 0 && key < T) s = true_score_bias(s, bias, brow + (int64_t)key * bs3, idt, sdt);
+    if (write_true && true_out && valid && key < T) true_out[grow * T + key] = s;
+  }
+  return s;
+}
+
+// acc += (V^T . P^T) * (sP * sV): one MFMA of 16 output columns (A operand va) by one key block (B
+// operand pc); sv4: the lane's four V block scales, acc: its four columns 4 g + i
+__device__ __forceinline__ void fq_pv_mfma(int64_t va, int64_t pc, float sP, const float* sv4, float* acc) {
+  const v4iq_ zero = {0, 0, 0, 0};
+  const v4iq_ c = __builtin_amdgcn_mfma_i32_16x16x32_i8(va, pc, zero, 0, 0, 0);
+  const float4 sv = *reinterpret_cast<const float4*>(sv4);
+  acc[0] = fmaf((float)c[0], sP * sv.x, acc[0]);
+  acc[1] = fmaf((float)c[1], sP * sv.y, acc[1]);
+  acc[2] = fmaf((float)c[2], sP * sv.z, acc[2]);
+  acc[3] = fmaf((float)c[3], sP * sv.w, acc[3]);
+}
+
 // NB: 32-element blocks per head dim; NTB: key blocks the registers hold (T <= 32 NTB);
 // XDT: float16 / bfloat16 inputs or scores (the dtype roundings at run time); EXTRA: a bias,
 // the debug true-score output or bfloatX rounding (the bias / output addresses per key are
@@ -169,49 +339,17 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
       if (key < T) x = *reinterpret_cast<const uint4*>(a.kc + (kb + key) * (32 * NB) + 16 * c);
       *reinterpret_cast<uint4*>(tkc + (size_t)p * kst + 16 * c) = x;
     }
-    for (int key = threadIdx.x; key < tpad; key += blockDim.x) {
-      int e[NB], emin = 1 << 20, emax = -(1 << 20);
-      bool nan = false;
-#pragma unroll
-      for (int b = 0; b < NB; ++b) {
-        const int16_t raw = key < T ? a.ksT[(kb + key) * NB + b] : (int16_t)0;
-        tke[b * kes + key] = raw;
-        e[b] = exp_from16(raw);
-        nan = nan || e[b] == kExpNaN;
-        emin = min(emin, e[b]);
-        emax = max(emax, e[b]);
-      }
-      tkx[key] = nan ? -100000 : emin;
-      uint32_t dkp = 0u;  // offsets as bytes (the fast form needs them <= 10)
-#pragma unroll
-      for (int b = 0; b < NB; ++b) dkp |= (uint32_t)min(e[b] - emin, 255) << (8 * b);
-      tkx[kes + key] = (int)dkp;
-      tkx[2 * kes + key] = nan ? 1000 : emax - emin;
-    }
+    fq_stage_key_terms<NB, kes>(a.ksT, T, kb, tpad, tke, tkx);
     const int8_t* vsrc = a.vt + (int64_t)bh * D * a.tpad;  // [ntb][D][32] in HBM
     for (int i = threadIdx.x; i < ntb * D * 2; i += blockDim.x) {
       const int half = i & 1, row = i >> 1, tb = row / D, dd = row - tb * D;
       *reinterpret_cast<uint4*>(tvt + (size_t)dd * vst + 32 * tb + 16 * half) =
           *reinterpret_cast<const uint4*>(vsrc + (int64_t)row * 32 + 16 * half);
     }
-    const int16_t* vssrc = a.vs + (int64_t)bh * ntb * D;
-    for (int i = threadIdx.x; i < ntb * D; i += blockDim.x) {
-      const int tb = i / D, dd = i - tb * D;
-      tvs[((dd >> 4) * NTB + tb) * 16 + (dd & 15)] = scale_f(exp_from16(vssrc[i]));
-    }
+    fq_stage_v_scales<NTB>(a.vs, ntb, D, bh, tvs);
   }
   __syncthreads();
-  if (threadIdx.x < 2 * ntb) {  // per key tile: the smallest exponent, the largest spread
-    const int tile = threadIdx.x;
-    int mn = 1 << 20, sp = 0;
-    for (int m = 0; m < 16; ++m) {
-      const int key = 32 * (tile >> 1) + 8 * (m >> 2) + 4 * (tile & 1) + (m & 3);
-      mn = min(mn, tkx[key]);
-      sp = max(sp, tkx[2 * kes + key]);
-    }
-    ttg[tile] = mn;
-    ttg[2 * NTB + tile] = sp;
-  }
+  fq_stage_tile_terms<kes, NTB>(ntb, tkx, ttg);
   __syncthreads();
 
   const int r_beg = (int)blockIdx.y * a.rows_per_wg, r_end = min(a.N, r_beg + a.rows_per_wg);
@@ -220,33 +358,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
     const bool valid = r < r_end;
     const int64_t grow = (int64_t)bh * a.N + (valid ? r : r0);
     const int64_t brow = EXTRA && a.bias ? b_ * a.bs0 + h_ * a.bs1 + (int64_t)(valid ? r : r0) * a.bs2 : -1;
-    // the tile's query codes (B operand: row q, elements 32 b + 8 g ..) and exponents
-    int64_t qb[NB];
-    int qe[NB];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      qb[b] = *reinterpret_cast<const int64_t*>(a.qc + grow * (32 * NB) + 32 * b + 8 * g);
-      qe[b] = exp_from16(a.qsT[grow * NB + b]);
-    }
-    // exact epilogue, fast form: sum_b I_b 2^(e_b) = 2^(qmin + kmin) sum_b I_b 2^(dq_b + dk_b),
-    // an exact int32 while every shift dq_b + dk_b <= 10 -- the wave's largest query spread
-    // plus the key tile's largest spread -- and qmin + kmin >= -100 (no subnormal result):
-    // the same float as true_dot's rule (fq_exact), which the tiles that fail it take
-    int qmin = qe[0], qmax = qe[0];
-    bool qnan = false;
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      qmin = min(qmin, qe[b]);
-      qmax = max(qmax, qe[b]);
-      qnan = qnan || qe[b] == kExpNaN;
-    }
-    uint32_t dqp = 0u;  // the query's offsets as bytes (<= 10 on the fast form: no carries)
-#pragma unroll
-    for (int b = 0; b < NB; ++b) dqp |= (uint32_t)min(qe[b] - qmin, 255) << (8 * b);
-    const int wq_spread = (int)wave_reduce((uint32_t)(qnan ? 1000 : qmax - qmin),
-                                           [](uint32_t x, uint32_t y) { return (int)x > (int)y ? x : y; });
-    const int wq_min = (int)wave_reduce((uint32_t)(qnan ? -100000 : qmin),
-                                        [](uint32_t x, uint32_t y) { return (int)x < (int)y ? x : y; });
+    const FqQuery<NB> Q = fq_load_query<NB>(a.qc, a.qsT, grow, g);
     // the row's kept bits of keys 32 blk + 8 g .. + 7: byte blk % 4 of kw[blk / 4]
     uint32_t kw[(NTB + 3) / 4];
 #pragma unroll
@@ -278,53 +390,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
           for (int b = 0; b < NB; ++b) {
             const int64_t ka = *reinterpret_cast<const int64_t*>(tkc + (size_t)(16 * tile + q) * kst + 32 * b + 8 * g);
             const v4iq_ zero = {0, 0, 0, 0};
-            c[b] = __builtin_amdgcn_mfma_i32_16x16x32_i8(ka, qb[b], zero, 0, 0, 0);
+            c[b] = __builtin_amdgcn_mfma_i32_16x16x32_i8(ka, Q.qb[b], zero, 0, 0, 0);
           }
           const int key0 = 32 * blk + 8 * g + 4 * t;
           float sc[4];
-          const int tkm = __builtin_amdgcn_readfirstlane(ttg[tile]);
-          const int tsp = __builtin_amdgcn_readfirstlane(ttg[2 * NTB + tile]);
-          if (wq_spread + tsp <= 10 && wq_min + tkm >= -100) {
-            const int4 km = *reinterpret_cast<const int4*>(tkx + key0);
-            const int4 dk = *reinterpret_cast<const int4*>(tkx + kes + key0);
-            auto comp = [](const int4& x, int i) { return i == 0 ? x.x : (i == 1 ? x.y : (i == 2 ? x.z : x.w)); };
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-              const uint32_t sh = dqp + (uint32_t)comp(dk, i);  // byte b: the shift of block b
-              int sum = 0;
-#pragma unroll
-              for (int b = 0; b < NB; ++b) sum += c[b][i] << ((sh >> (8 * b)) & 31u);
-              sc[i] = ldexpf((float)sum, qmin + comp(km, i));
-            }
-          } else {
-            int ke[NB][4];
-#pragma unroll
-            for (int b = 0; b < NB; ++b) {
-              const uint2 w = *reinterpret_cast<const uint2*>(tke + b * kes + key0);
-              ke[b][0] = exp_from16((int16_t)(w.x & 0xFFFFu));
-              ke[b][1] = exp_from16((int16_t)(w.x >> 16));
-              ke[b][2] = exp_from16((int16_t)(w.y & 0xFFFFu));
-              ke[b][3] = exp_from16((int16_t)(w.y >> 16));
-            }
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-              int I[NB], e[NB];
-#pragma unroll
-              for (int b = 0; b < NB; ++b) {
-                I[b] = c[b][i];
-                e[b] = qe[b] + ke[b][i];
-              }
-              sc[i] = fq_exact<NB>(I, e);
-            }
-          }
+          fq_tile_scores<NB, kes, NTB>(c, Q, tile, key0, tke, tkx, ttg, sc);
 #pragma unroll
           for (int i = 0; i < 4; ++i) {
-            float s = true_score<kRound>(sc[i], a.scale, a.bfloat, sdt);
-            const int key = key0 + i;
-            if (EXTRA) {
-              if (brow >= 0 && key < T) s = true_score_bias(s, a.bias, brow + (int64_t)key * a.bs3, idt, sdt);
-              if (a.true_out && valid && key < T) a.true_out[grow * T + key] = s;
-            }
+            const float s = fq_finish_score<EXTRA, kRound>(sc[i], a.scale, a.bfloat, T, a.bias, a.bs3, a.true_out, key0 + i, brow, grow, valid, true, sdt, idt);
             // a dropped key: -inf (the kept bit as an all-ones / zero mask, one bit select)
             const uint32_t m = (uint32_t)__builtin_amdgcn_sbfe((int)kw[blk >> 2], 8 * (blk & 3) + 4 * t + i, 1);
             uint32_t sv;
@@ -405,7 +478,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
         const bool fl = pb.flush;
         const float sP = pb.sP;
         uint32_t lo = 0u, hi = 0u;
-        if (es != kExpNaN) {  // (a NaN block has no codes; p_code_word's rule from registers)
+        if (es != kExpNaN) {
 #pragma unroll
           for (int j = 0; j < 8; ++j) {
             uint32_t code;
@@ -421,13 +494,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(4, 8))) voi
         for (int u = 0; u < NDT; ++u) {
           if (16 * u < D) {
             const int64_t va = *reinterpret_cast<const int64_t*>(tvt + (size_t)(16 * u + q) * vst + 32 * blk + 8 * g);
-            const v4iq_ zero = {0, 0, 0, 0};
-            const v4iq_ c = __builtin_amdgcn_mfma_i32_16x16x32_i8(va, pc, zero, 0, 0, 0);
-            const float4 sv = *reinterpret_cast<const float4*>(tvs + (u * NTB + blk) * 16 + 4 * g);
-            acc[u][0] = fmaf((float)c[0], sP * sv.x, acc[u][0]);
-            acc[u][1] = fmaf((float)c[1], sP * sv.y, acc[u][1]);
-            acc[u][2] = fmaf((float)c[2], sP * sv.z, acc[u][2]);
-            acc[u][3] = fmaf((float)c[3], sP * sv.w, acc[u][3]);
+            fq_pv_mfma(va, pc, sP, tvs + (u * NTB + blk) * 16 + 4 * g, acc[u]);
           }
         }
       }

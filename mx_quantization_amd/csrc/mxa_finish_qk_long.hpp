@@ -86,44 +86,10 @@ __global__ __launch_bounds__(512) MXA_FQL_ATTR void finish_qk_long_kernel(Rows2A
 
   // ---- stage the head's per-key terms and V block scales -------------------------------
   const int64_t kb = (int64_t)bh * T;
-  for (int key = threadIdx.x; key < tpad; key += blockDim.x) {
-    int e[NB], emin = 1 << 20, emax = -(1 << 20);
-    bool nan = false;
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      const int16_t raw = key < T ? a.ksT[(kb + key) * NB + b] : (int16_t)0;
-      tke[b * kes + key] = raw;
-      e[b] = exp_from16(raw);
-      nan = nan || e[b] == kExpNaN;
-      emin = min(emin, e[b]);
-      emax = max(emax, e[b]);
-    }
-    tkx[key] = nan ? -100000 : emin;
-    uint32_t dkp = 0u;  // offsets as bytes (the fast form needs them <= 10)
-#pragma unroll
-    for (int b = 0; b < NB; ++b) dkp |= (uint32_t)min(e[b] - emin, 255) << (8 * b);
-    tkx[kes + key] = (int)dkp;
-    tkx[2 * kes + key] = nan ? 1000 : emax - emin;
-  }
-  {
-    const int16_t* vssrc = a.vs + (int64_t)bh * ntb * D;
-    for (int i = threadIdx.x; i < ntb * D; i += blockDim.x) {
-      const int tb = i / D, dd = i - tb * D;
-      tvs[((dd >> 4) * kFqlNTB + tb) * 16 + (dd & 15)] = scale_f(exp_from16(vssrc[i]));
-    }
-  }
+  fq_stage_key_terms<NB, kes>(a.ksT, T, kb, tpad, tke, tkx);
+  fq_stage_v_scales<kFqlNTB>(a.vs, ntb, D, bh, tvs);
   __syncthreads();
-  if (threadIdx.x < 2 * ntb) {  // per key tile: the smallest exponent, the largest spread
-    const int tile = threadIdx.x;
-    int mn = 1 << 20, sp = 0;
-    for (int m = 0; m < 16; ++m) {
-      const int key = fq_key_of_row(16 * tile + m);
-      mn = min(mn, tkx[key]);
-      sp = max(sp, tkx[2 * kes + key]);
-    }
-    ttg[tile] = mn;
-    ttg[2 * kFqlNTB + tile] = sp;
-  }
+  fq_stage_tile_terms<kes, kFqlNTB>(ntb, tkx, ttg);
   __syncthreads();
 
   const int8_t* vbase = a.vt + (int64_t)bh * D * a.tpad + 8 * g;  // [ntb][D][32] per head
@@ -133,30 +99,7 @@ __global__ __launch_bounds__(512) MXA_FQL_ATTR void finish_qk_long_kernel(Rows2A
     const bool valid = r < r_end;
     const int64_t grow = (int64_t)bh * a.N + (valid ? r : r0);
     const int64_t brow = EXTRA && a.bias ? b_ * a.bs0 + h_ * a.bs1 + (int64_t)(valid ? r : r0) * a.bs2 : -1;
-    // the tile's query codes (B operand: row q, elements 32 b + 8 g ..) and exponents
-    int64_t qb[NB];
-    int qe[NB];
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      qb[b] = *reinterpret_cast<const int64_t*>(a.qc + grow * (32 * NB) + 32 * b + 8 * g);
-      qe[b] = exp_from16(a.qsT[grow * NB + b]);
-    }
-    // the exact epilogue's query terms (finish_qk_kernel)
-    int qmin = qe[0], qmax = qe[0];
-    bool qnan = false;
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      qmin = min(qmin, qe[b]);
-      qmax = max(qmax, qe[b]);
-      qnan = qnan || qe[b] == kExpNaN;
-    }
-    uint32_t dqp = 0u;
-#pragma unroll
-    for (int b = 0; b < NB; ++b) dqp |= (uint32_t)min(qe[b] - qmin, 255) << (8 * b);
-    const int wq_spread = (int)wave_reduce((uint32_t)(qnan ? 1000 : qmax - qmin),
-                                           [](uint32_t x, uint32_t y) { return (int)x > (int)y ? x : y; });
-    const int wq_min = (int)wave_reduce((uint32_t)(qnan ? -100000 : qmin),
-                                        [](uint32_t x, uint32_t y) { return (int)x < (int)y ? x : y; });
+    const FqQuery<NB> Q = fq_load_query<NB>(a.qc, a.qsT, grow, g);
 
     // the row's kept bits of keys 32 blk + 8 g .. + 7 (the dense branch: every key < T)
     auto kept_bits = [&](int blk) -> uint32_t {
@@ -182,53 +125,14 @@ __global__ __launch_bounds__(512) MXA_FQL_ATTR void finish_qk_long_kernel(Rows2A
 #pragma unroll
       for (int b = 0; b < NB; ++b) {
         const v4iq_ zero = {0, 0, 0, 0};
-        c[b] = __builtin_amdgcn_mfma_i32_16x16x32_i8(ka[b], qb[b], zero, 0, 0, 0);
+        c[b] = __builtin_amdgcn_mfma_i32_16x16x32_i8(ka[b], Q.qb[b], zero, 0, 0, 0);
       }
       const int key0 = 32 * blk + 8 * g + 4 * t;
       float sc[4];
-      const int tkm = __builtin_amdgcn_readfirstlane(ttg[tile]);
-      const int tsp = __builtin_amdgcn_readfirstlane(ttg[2 * kFqlNTB + tile]);
-      if (wq_spread + tsp <= 10 && wq_min + tkm >= -100) {
-        const int4 km = *reinterpret_cast<const int4*>(tkx + key0);
-        const int4 dk = *reinterpret_cast<const int4*>(tkx + kes + key0);
-        auto comp = [](const int4& x, int i) { return i == 0 ? x.x : (i == 1 ? x.y : (i == 2 ? x.z : x.w)); };
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const uint32_t sh = dqp + (uint32_t)comp(dk, i);  // byte b: the shift of block b
-          int sum = 0;
-#pragma unroll
-          for (int b = 0; b < NB; ++b) sum += c[b][i] << ((sh >> (8 * b)) & 31u);
-          sc[i] = ldexpf((float)sum, qmin + comp(km, i));
-        }
-      } else {
-        int ke[NB][4];
-#pragma unroll
-        for (int b = 0; b < NB; ++b) {
-          const uint2 w = *reinterpret_cast<const uint2*>(tke + b * kes + key0);
-          ke[b][0] = exp_from16((int16_t)(w.x & 0xFFFFu));
-          ke[b][1] = exp_from16((int16_t)(w.x >> 16));
-          ke[b][2] = exp_from16((int16_t)(w.y & 0xFFFFu));
-          ke[b][3] = exp_from16((int16_t)(w.y >> 16));
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          int I[NB], e[NB];
-#pragma unroll
-          for (int b = 0; b < NB; ++b) {
-            I[b] = c[b][i];
-            e[b] = qe[b] + ke[b][i];
-          }
-          sc[i] = fq_exact<NB>(I, e);
-        }
-      }
+      fq_tile_scores<NB, kes, kFqlNTB>(c, Q, tile, key0, tke, tkx, ttg, sc);
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        float s = true_score<kRound>(sc[i], a.scale, a.bfloat, sdt);
-        const int key = key0 + i;
-        if (EXTRA) {
-          if (brow >= 0 && key < T) s = true_score_bias(s, a.bias, brow + (int64_t)key * a.bs3, idt, sdt);
-          if (first && a.true_out && valid && key < T) a.true_out[grow * T + key] = s;
-        }
+        const float s = fq_finish_score<EXTRA, kRound>(sc[i], a.scale, a.bfloat, T, a.bias, a.bs3, a.true_out, key0 + i, brow, grow, valid, first, sdt, idt);
         sv[i] = (kbits >> (4 * t + i)) & 1u ? s : -INFINITY;
       }
     };
@@ -321,35 +225,26 @@ __global__ __launch_bounds__(512) MXA_FQL_ATTR void finish_qk_long_kernel(Rows2A
       }
       uint32_t bm = 0u;
 #pragma unroll
-      for (int j = 0; j < 8; ++j) bm = max(bm, __float_as_uint(p[j]) & 0x7FFFFFFFu);
-      bm = fq_umax4(bm);
-      const PBlock pb = p_block(bm, a.flush_p, sdt, kPUnit<W4>);
-      const int es = pb.es;
-      const bool fl = pb.flush;
-      const float sP = pb.sP;
-      uint32_t lo = 0u, hi = 0u;
-      if (es != kExpNaN) {  // (a NaN block has no codes)
+        for (int j = 0; j < 8; ++j) bm = max(bm, __float_as_uint(p[j]) & 0x7FFFFFFFu);
+        bm = fq_umax4(bm);
+        const PBlock pb = p_block(bm, a.flush_p, sdt, kPUnit<W4>);
+        const int es = pb.es;
+        const bool fl = pb.flush;
+        const float sP = pb.sP;
+        uint32_t lo = 0u, hi = 0u;
+        if (es != kExpNaN) {
 #pragma unroll
-        for (int j = 0; j < 8; ++j) {
-          const float x = fl ? p[j] * 0.0f : p[j];
-          const uint32_t code = (uint32_t)p_code_bits_f32<W4>(x, pow2f(-es));
-          if (j < 4) lo |= code << (8 * j);
-          else hi |= code << (8 * (j - 4));
+          for (int j = 0; j < 8; ++j) {
+            const float x = fl ? p[j] * 0.0f : p[j];
+            const uint32_t code = (uint32_t)p_code_bits_f32<W4>(x, pow2f(-es));
+            if (j < 4) lo |= code << (8 * j);
+            else hi |= code << (8 * (j - 4));
+          }
         }
-      }
-      const int64_t pc = (int64_t)(((uint64_t)hi << 32) | lo);
+        const int64_t pc = (int64_t)(((uint64_t)hi << 32) | lo);
 #pragma unroll
-      for (int u = 0; u < NDT; ++u) {
-        if (16 * u < D) {
-          const v4iq_ zero = {0, 0, 0, 0};
-          const v4iq_ c = __builtin_amdgcn_mfma_i32_16x16x32_i8(va[u], pc, zero, 0, 0, 0);
-          const float4 sv = *reinterpret_cast<const float4*>(tvs + (u * kFqlNTB + blk) * 16 + 4 * g);
-          acc[u][0] = fmaf((float)c[0], sP * sv.x, acc[u][0]);
-          acc[u][1] = fmaf((float)c[1], sP * sv.y, acc[u][1]);
-          acc[u][2] = fmaf((float)c[2], sP * sv.z, acc[u][2]);
-          acc[u][3] = fmaf((float)c[3], sP * sv.w, acc[u][3]);
-        }
-      }
+      for (int u = 0; u < NDT; ++u)
+        if (16 * u < D) fq_pv_mfma(va[u], pc, sP, tvs + (u * kFqlNTB + blk) * 16 + 4 * g, acc[u]);
     });
     // ---- the tile's output rows -------------------------------------------------------------
     if (valid) {

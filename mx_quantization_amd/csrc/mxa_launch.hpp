@@ -3,6 +3,7 @@
 #pragma once
 #include <algorithm>
 #include <atomic>
+#include <type_traits>
 
 #include "mxa_proj_args.hpp"
 #include "mxa_rows2.hpp"
@@ -124,29 +125,38 @@ inline int launch_select_mode(const Rows2Args& ra, int mode, int BH, hipStream_t
     default: return launch_select_p6(ra, BH, stream, plan);
   }
 }
-// the finishing kernel with the scores of every key on MFMA (mxa_finish_qk.hpp): k a large
-// share of T (above the 16-row gather kernel's k <= 64), T <= 256 (the scores of a row in
-// registers); not with the proj Linear's MX input codes (xo).  It reads the selection's
-// prune-mask words (the caller's mask_out, else a workspace copy), not the kept indices.
-// (MXA_FQ_KMIN: a tools-only build of the threshold for same-box A/Bs, build_native defines)
+// ---- the finishing kernel of a call: the one decision -------------------------------------
+// attn_validate, attn_layout, launch_rows and the *_finish_kernel entry points all read
+// finish_choice of the same facts; nothing else asks which kernel runs.
+// (MXA_FQ_KMIN: a tools-only build of the MFMA kernel's threshold for same-box A/Bs, build_native defines)
 #ifndef MXA_FQ_KMIN
 #define MXA_FQ_KMIN 65
 #endif
-inline bool finish_qk_wanted(int k, int T, int nbd, bool xo) { return k >= MXA_FQ_KMIN && T <= 256 && nbd <= 4 && !xo; }
-// the dense branch (top_k=False) on the same kernel with every key kept (Rows2Args::dense)
-inline bool finish_qk_dense_ok(int T, int nbd) { return T <= 256 && nbd <= 4; }
-// the finishing kernel of a call (include/mxa.h MXA_FIN_*): the single decision launch_rows
-// (mxa_fin.hip) dispatches on and mxa_attention_finish_kernel reports
-// full (mxa_attention_full): rows over 512 keys also take the dense branch and k > 64, on the
-// tiled MFMA kernel (mxa_finish_qk_long.hpp); every other call is decided as without it
-inline bool finish_qk_long_wanted(bool full, bool topk, int k, int T) { return full && long_rows(T) && (!topk || k > 64); }
-inline int rows_kernel_kind(bool topk, int k, int T, int nbd, bool xo, bool full = false) {
-  if (finish_qk_long_wanted(full, topk, k, T)) return topk ? MXA_FIN_MFMA_LONG : MXA_FIN_DENSE_MFMA_LONG;
-  if (!topk) return finish_qk_dense_ok(T, nbd) ? MXA_FIN_DENSE_MFMA : MXA_FIN_DENSE_ROWS;
-  if (finish_qk_wanted(k, T, nbd, xo)) return MXA_FIN_MFMA;
-  // k <= 64 (DeiT's 20 / 30, PixArt's 20): 16-row tiles, four lanes per row (with the proj's
-  // MX input codes: k <= 32); larger k: the 32-row kernel
-  return k <= (xo ? 32 : 64) ? MXA_FIN_GATHER16 : MXA_FIN_GATHER32;
+// topk, k (0 on the dense branch), xo: the finishing kernel writes the proj Linear's MX input codes
+// (the call's `direct`, known before any pointer is bound); xdt: float16 / bfloat16 inputs or scores;
+// bits: 8 or 4, P's element width; full: mxa_attention_full
+struct FinFacts { bool topk; int k, T, nbd; bool xo, xdt; int bits; bool full; };
+// kind: MXA_FIN_* (include/mxa.h); reads_mask: the kernel reads the selection's prune-mask words (the
+// caller's mask_out, else a workspace copy), not the kept indices; status: MXA_ERR_UNSUPPORTED where the
+// kind has no instantiation for the facts
+struct FinChoice { int kind; bool reads_mask; int status; };
+inline FinChoice finish_choice(const FinFacts& f) {
+  const bool lng = long_rows(f.T), w4 = f.bits == 4, regs = f.T <= 256 && f.nbd <= 4;  // regs: a row's scores in registers
+  FinChoice c{};
+  if (f.full && lng && (!f.topk || f.k > 64))  // the tiled MFMA kernel (mxa_finish_qk_long.hpp)
+    c.kind = f.topk ? MXA_FIN_MFMA_LONG : MXA_FIN_DENSE_MFMA_LONG;
+  else if (!f.topk)  // the dense branch: finish_qk_kernel with every key kept, else the v_dot4 row kernel
+    c.kind = regs ? MXA_FIN_DENSE_MFMA : MXA_FIN_DENSE_ROWS;
+  else if (f.k >= MXA_FQ_KMIN && regs && !f.xo)  // k a large share of T (mxa_finish_qk.hpp)
+    c.kind = MXA_FIN_MFMA;
+  else  // k <= 64 (DeiT's 20 / 30, PixArt's 20; with the proj's codes: k <= 32): 16-row tiles, else 32-row
+    c.kind = f.k <= (f.xo ? 32 : 64) ? MXA_FIN_GATHER16 : MXA_FIN_GATHER32;
+  c.reads_mask = c.kind == MXA_FIN_MFMA || c.kind == MXA_FIN_MFMA_LONG;
+  // long rows and MXINT4 P: float32 without the proj's codes, and not on the 32-row or the dense row
+  // kernel (a K table of <= 512 keys, MXINT8 P only)
+  if ((lng || w4) && (f.xdt || f.xo || c.kind == MXA_FIN_GATHER32 || c.kind == MXA_FIN_DENSE_ROWS))
+    c.status = MXA_ERR_UNSUPPORTED;
+  return c;
 }
 
 // ---- what the three finishing kernels' launches share (mxa_fin.hip, mxa_fin16.hip,
@@ -210,6 +220,32 @@ inline int launch_finish_tiles(const Rows2Args& ra, int BH, size_t lds, hipStrea
   return launch_status();
 }
 
+// ---- what the two MFMA finishing kernels' launches share (mxa_fin_qk.hip, mxa_fin_qkl.hip) ----
+// their plan: tiles of tile_rows query rows, lds bytes of LDS per workgroup and none per wave
+inline int finish_mfma_plan(const Rows2Args& ra, int tile_rows, size_t lds, int BH, int regs_waves_per_simd, int* waves,
+                            int* rows_per_wg) {
+  return finish_tile_plan(tile_rows, ra.N, BH, [lds](int) { return lds; }, finish_wave_cap(regs_waves_per_simd), waves,
+                          rows_per_wg);
+}
+// their EXTRA instantiations: a bias, the debug true scores or bfloatX rounding
+inline bool finish_mfma_extra(const Rows2Args& ra) { return ra.bias || ra.true_out || (ra.bfloat != 0 && ra.bfloat != 32); }
+// one instantiation planned by its own registers, then launched
+template <auto Kernel>
+inline int launch_finish_mfma(Rows2Args ra, int tile_rows, size_t lds, int BH, hipStream_t stream) {
+  const int rc = finish_mfma_plan(ra, tile_rows, lds, BH, kernel_waves_per_simd<Kernel>(), &ra.waves, &ra.rows_per_wg);
+  return rc ? rc : launch_finish_tiles<Kernel>(ra, BH, lds, stream);
+}
+// fn(std::integral_constant<int, NB>) for the NB = nbd blocks per head dim (1..4)
+template <class Fn>
+inline int dispatch_nbd(int nbd, Fn fn) {
+  switch (nbd) {
+    case 1: return fn(std::integral_constant<int, 1>{});
+    case 2: return fn(std::integral_constant<int, 2>{});
+    case 3: return fn(std::integral_constant<int, 3>{});
+    default: return fn(std::integral_constant<int, 4>{});
+  }
+}
+
 // the MFMA finishing kernel's launches (mxa_fin_qk.hip): float32 inputs and scores (x0), float16 / bfloat16 (x1)
 int launch_finish_qk_x0(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 int launch_finish_qk_x1(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
@@ -228,12 +264,9 @@ int launch_finish32_p1(const Rows2Args& ra, int BH, hipStream_t stream, bool pla
 int launch_finish32_p2(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 int launch_finish32_p3(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 int launch_finish32_p4(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
-// the row kernel of the path: finishing kernel (top-k) or dense row kernel (mxa_fin.hip)
-// elem_bits 4 (mxa_attention_bits): P is MXINT4 -- the MXINT4-P instantiations of the 16-row and
-// the MFMA kernel; MXA_ERR_UNSUPPORTED where the call would take the 32-row or the dense row kernel
-// full (mxa_attention_full): rows_kernel_kind's
-int launch_rows(const Rows2Args& ra, bool topk, bool true_mode, int S, int BH, hipStream_t stream, bool plan,
-                int elem_bits = 8, bool full = false);
+// the row kernel finish_choice(f) names (mxa_fin.hip); true_mode: the selection kernel ranked, and
+// wrote, the true scores; plan: f.xo stands for the proj's code pointers, which are not bound yet
+int launch_rows(const Rows2Args& ra, const FinFacts& f, bool true_mode, int S, int BH, hipStream_t stream, bool plan);
 // fused projection kernel (mxa_proj.hip): part 0 the self-attention q, k, v of one token
 // matrix, 1 / 2 cross-attention's q and k, v passes (mxa_proj.hpp ProjPart)
 int launch_proj(const ProjArgs& pa, hipStream_t stream, int part = 0);

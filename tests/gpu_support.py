@@ -127,7 +127,7 @@ def ref_chain(n):
 
 
 def finish_kernel_of(T, D, k):
-    """mxa_launch.hpp rows_kernel_kind for a float32 call without proj codes; k = 0: dense"""
+    """mxa_launch.hpp finish_choice for a float32 call without proj codes; k = 0: dense"""
     mfma = T <= 256 and (D + 31) // 32 <= 4
     if not k:
         return "dense_qk" if mfma else "dense_rows"

@@ -19,7 +19,7 @@ _c = EC._c
 
 
 def kind_of(T, k):
-    """mxa_launch.hpp rows_kernel_kind(full = true) on rows over 512 keys; k = 0: dense"""
+    """mxa_launch.hpp finish_choice(full = true) on rows over 512 keys; k = 0: dense"""
     assert T > 512
     return DENSE_MFMA_LONG if not k else (MFMA_LONG if k > 64 else EC.GATHER16)
 

@@ -1,7 +1,8 @@
 """The library's host-side decisions against a recorded table (tests/golden/host_table.json,
 written by tools/record_host_table.py): every workspace size, the kernel path and finishing
-kernel, and the first refusal of mxa_attention / mxa_approx_scores with a null workspace, over
-shapes x score modes x flags x dtypes.  Nothing launches, so it runs without a GPU.  The
+kernel, and the first refusal of mxa_attention / mxa_approx_scores and their *_long, *_bits and
+*_full siblings (at widths 8, 4 and an invalid one) with a null workspace, over shapes x score
+modes x flags x dtypes.  Nothing launches, so it runs without a GPU.  The
 table is a record of what the library answered when it was written: a change of the host code
 that is meant to leave sizes and refusals alone must reproduce it, one that is meant to change
 them re-records it."""
@@ -28,19 +29,24 @@ def test_table_covers_the_recorder(tables):
     rec, got, want = tables
     assert want["shapes"] == [list(s) for s in rec.SHAPES]
     assert set(got) == set(want)
+    assert len(want["attn"]) == len(rec.SHAPES) >= 26
     n_attn = 1
     for ax in rec.ATTN_AXES:
         n_attn *= len(ax)
-    assert all(len(rows) == n_attn and all(len(r) == 5 for r in rows) for rows in want["attn"])
+    assert all(len(rows) == n_attn and all(len(r) == rec.ATTN_COLS == 5 for r in rows) for rows in want["attn"])
+    assert len(want["attn_ext"]) == len(rec.SHAPES)
+    assert all(len(rows) == n_attn and all(len(r) == rec.ATTN_EXT_COLS == 21 for r in rows) for rows in want["attn_ext"])
+    assert len(want["fused"]) == len(rec.FUSED_SHAPES) >= 15
     assert all(rows and all(len(r) == 20 for r in rows) for rows in want["fused"])
     assert len(want["matmul"]) == len(rec.MATMUL_SHAPES) >= 20
     assert len(want["linear"]) == len(rec.LINEAR_SHAPES) >= 20
     assert len(want["mlp"]) == len(rec.MLP_SHAPES) >= 20
 
 
-@pytest.mark.parametrize("key", ["attn", "fused"])
+@pytest.mark.parametrize("key", ["attn", "attn_ext", "fused"])
 def test_attention_rows(tables, key):
     rec, got, want = tables
+    assert len(got[key]) == len(want[key])
     for shape, g, w in zip(rec.SHAPES, got[key], want[key]):
         assert len(g) == len(w), shape
         bad = [(i, a, b) for i, (a, b) in enumerate(zip(g, w)) if a != b]

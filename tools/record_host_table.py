@@ -9,7 +9,7 @@ No row reaches a launch: the attention calls carry a null workspace (the workspa
 earlier refusal, is what is recorded), and the entry points that read a prepared weight's
 header past validation are only sized, never called.
 
-The file holds each of the two big tables as its distinct rows plus, per shape, the run-length
+The file holds each of the three big tables as its distinct rows plus, per shape, the run-length
 coded row numbers (many argument sets get the same answers), and sizes in units of 256 bytes
 (every region is 256-B aligned): pack() / unpack().
 """
@@ -32,6 +32,13 @@ SHAPES = [(256, 12, 197, 197, 64, 20), (64, 16, 256, 256, 72, 154), (8, 16, 256,
           (2, 2, 40, 40, 64, 7), (2, 2, 40, 40, 64, 33), (2, 2, 40, 40, 64, 34), (2, 2, 96, 96, 64, 70),
           (2, 2, 45, 70, 48, 7), (1, 1, 1, 1, 32, 1), (1, 2, 300, 257, 72, 100), (1, 2, 64, 512, 128, 65),
           (1, 1, 8, 513, 64, 4), (1, 1, 8, 64, 129, 4)]
+# both sides of every threshold the finishing-kernel decision reads (T 256 / 257, 512 / 513, 1024 / 1025;
+# k 32 / 33, 64 / 65, k = T; D 128 / 129), on the short and the long rows
+SHAPES += [(1, 2, 40, 256, 64, 64), (1, 2, 40, 256, 64, 65), (1, 2, 40, 256, 72, 100), (1, 2, 40, 257, 64, 65),
+           (1, 2, 40, 200, 64, 200), (1, 2, 40, 513, 64, 64), (1, 2, 40, 513, 64, 65), (1, 2, 33, 513, 32, 32),
+           (1, 2, 33, 513, 32, 33), (1, 2, 40, 1024, 72, 154), (1, 2, 40, 1025, 72, 154), (1, 2, 40, 1000, 128, 1000),
+           (1, 2, 40, 600, 129, 65)]
+FUSED_SHAPES = SHAPES[:15]  # the fused entry points take no long rows: the shapes up to the k = 64 / 65 pair
 MODES = sorted(N.PRED_MODES.values())
 DTYPES = [(N.DT_F32, 0), (N.DT_F16, 0), (N.DT_BF16, 0), (N.DT_F32, N.DT_F16)]
 # the plain attention's axes, in row order: pred_mode, approx, top_k, pred_out, bias, (dtype, score_dtype)
@@ -40,6 +47,14 @@ ATTN_AXES = [MODES, [0, 1], [0, 1], [0, 1], [0, 1], DTYPES]
 # approx = 0 ignores the mode, so it is recorded for the first mode alone
 FUSED_AXES = [MODES, [0, 1], [0, 1], [0, 1], [0, 1], [DTYPES[0], DTYPES[3]]]
 CS, CKVS, OUTFS = (96, 1152), (160, 1152), (96, 1152)
+WIDTHS = (8, 4, 3)  # the *_bits / *_full entry points' elem_bits: MXINT8, MXINT4, an invalid width
+# an attention row's columns: size, path, finishing kernel, mxa_attention, mxa_approx_scores ("attn"), then
+# ("attn_ext", a table of its own so that the rows repeat) the *_long pair; per width (size, mxa_attention_bits,
+# mxa_approx_scores_bits); per width (size, mxa_attention_full, mxa_attention_full_finish_kernel);
+# mxa_attention_proj with a null weight pointer.  The *_bits and *_full sizes are recorded as their excess
+# over the row's first column (0: the same layout; mxa_attention_full on long rows: its prune-mask words),
+# the refusal -1 as it is
+ATTN_COLS, ATTN_EXT_COLS = 5, 2 + 3 * len(WIDTHS) + 3 * len(WIDTHS) + 1
 # (batch, M, K, Nc) for mxa_matmul; (rows, in, out) for mxa_linear; (rows, in, hidden, out) for mxa_mlp
 MATMUL_SHAPES = [(1, 1, 1, 1), (3, 45, 70, 33), (1, 32, 32, 32), (2, 31, 33, 65), (1, 197, 64, 197), (3072, 197, 64, 197),
                  (1024, 256, 72, 256), (128, 256, 72, 120), (1, 8, 256, 8), (1, 8, 257, 8), (4, 7, 31, 4), (2, 64, 96, 1),
@@ -73,10 +88,22 @@ def attn_params(shape, mode, approx, top_k, pred_out, bias, dt):
 def attn_rows(shape):
     lib = N.lib()
     rows = []
+    pj = N.ProjParams()  # a proj Linear without its weight: refused before anything reads one
+    pj.out_features, pj.y, pj.y_row_stride = 96, PH, 96
     for combo in itertools.product(*ATTN_AXES):
         p = ctypes.byref(attn_params(shape, *combo))
-        rows.append([lib.mxa_attention_workspace_bytes(p), lib.mxa_attention_path(p), lib.mxa_attention_finish_kernel(p),
-                     lib.mxa_attention(p, None), lib.mxa_approx_scores(p, None)])
+        excess = lambda v: v if v < 0 else v - row[0]
+        row = [lib.mxa_attention_workspace_bytes(p), lib.mxa_attention_path(p), lib.mxa_attention_finish_kernel(p),
+               lib.mxa_attention(p, None), lib.mxa_approx_scores(p, None),
+               lib.mxa_attention_long(p, None), lib.mxa_approx_scores_long(p, None)]
+        for w in WIDTHS:
+            row += [excess(lib.mxa_attention_bits_workspace_bytes(p, w)), lib.mxa_attention_bits(p, w, None),
+                    lib.mxa_approx_scores_bits(p, w, None)]
+        for w in WIDTHS:
+            row += [excess(lib.mxa_attention_full_workspace_bytes(p, w)), lib.mxa_attention_full(p, w, None),
+                    lib.mxa_attention_full_finish_kernel(p, w)]
+        row.append(lib.mxa_attention_proj(p, None, ctypes.byref(pj), None))
+        rows.append(row)
     return rows
 
 
@@ -108,10 +135,12 @@ def fused_rows(shape):
 
 def compute():
     lib = N.lib()
+    attn = [attn_rows(s) for s in SHAPES]
     return {
         "shapes": [list(s) for s in SHAPES],
-        "attn": [attn_rows(s) for s in SHAPES],
-        "fused": [fused_rows(s) for s in SHAPES],
+        "attn": [[r[:ATTN_COLS] for r in rows] for rows in attn],
+        "attn_ext": [[r[ATTN_COLS:] for r in rows] for rows in attn],
+        "fused": [fused_rows(s) for s in FUSED_SHAPES],
         "matmul": [lib.mxa_matmul_workspace_bytes(*s) for s in MATMUL_SHAPES],
         "linear": [lib.mxa_linear_workspace_bytes(*s) for s in LINEAR_SHAPES],
         "mlp": [lib.mxa_mlp_workspace_bytes(r, i, None, h, o) for r, i, h, o in MLP_SHAPES],
@@ -127,7 +156,7 @@ def pack(table):
     (sizes are > 0 or -1), so that unpack() is exact for whatever the library answers."""
     size = lambda v: _units(v) if v <= 0 or v % 256 == 0 else -v - 2
     out = dict(table)
-    for key, size_cols in (("attn", (0,)), ("fused", range(20))):
+    for key, size_cols in (("attn", (0,)), ("attn_ext", ()), ("fused", range(20))):
         rows, index = {}, []
         for per_shape in table[key]:
             runs = []
@@ -148,7 +177,9 @@ def pack(table):
 def unpack(stored):
     size = lambda v: v * 256 if v > 0 else (v if v >= -1 else -v - 2)
     out = dict(stored)
-    for key, size_cols in (("attn", (0,)), ("fused", range(20))):
+    for key, size_cols in (("attn", (0,)), ("attn_ext", ()), ("fused", range(20))):
+        if key not in stored:  # a file recorded before the table had this part
+            continue
         rows = [[size(v) if c in size_cols else v for c, v in enumerate(r)] for r in stored[key]["rows"]]
         out[key] = [[rows[i] for i, n in runs for _ in range(n)] for runs in stored[key]["index"]]
     for key in ("matmul", "linear", "mlp"):
