@@ -105,10 +105,33 @@ bool proj_codes_direct(const mxa_attn_params* p) {
   return p->D % 32 == 0 && p->dtype == MXA_DT_F32 && p->score_dtype <= MXA_DT_F32;
 }
 
-// what finish_choice (mxa_launch.hpp) decides a call's finishing kernel from
-FinFacts attn_fin_facts(const mxa_attn_params* p, const mxa_proj_params* pj, int elem_bits, bool full) {
-  return {p->top_k != 0, p->top_k ? p->k_top : 0, p->T, (p->D + 31) / 32, pj && proj_codes_direct(p),
-          p->dtype != MXA_DT_F32 || p->score_dtype > MXA_DT_F32, elem_bits, full};
+// How far an entry point reaches, in order: each value takes every call the one before it takes, on the
+// same kernels.  kReachShort: rows of at most 512 keys; kReachLong (the *_long and *_bits entry points):
+// rows of at most kLongRowsT keys on the kernels that existed before finish_qk_long_kernel; kReachFull
+// (mxa_attention_full): those rows' dense branch and k_top > 64 too
+enum Reach { kReachShort, kReachLong, kReachFull };
+
+// One attention call
+struct AttnCall {
+  const mxa_attn_params* p;
+  hipStream_t stream;
+  const mxa_qkv_params* xq;    // the fused qkv projection (q, k, v produced from x and the prepared weight)
+  const mxa_cross_params* xc;  // cross-attention's projections (q from x, k and v from cond; N and T independent)
+  const mxa_proj_params* pj;   // the proj Linear behind it (y = mx.Linear(out.transpose(1,2).reshape(B,N,C)))
+  bool scores_only;  // the approximate (or true) scores into p->pred_out / true_out, no top-k
+  Reach reach;       // the entry point's (kReachShort unless named)
+  hipEvent_t* ev;    // the timed entry points' stage events
+  int *plan, *fin;   // plan: only report the kernel path (MXA_PATH_*), launch nothing; fin (with plan): the
+                     // finishing kernel (MXA_FIN_*, 0 for the scores alone)
+  int elem_bits = 8;  // 8 MXINT8; 4 (the *_bits / *_full entry points) MXINT4 for Q, K, P and V and for the
+                      // codes every approximator is derived from (include/mxa.h mxa_attention_bits)
+};
+
+// what finish_choice (mxa_launch.hpp) decides a call's finishing kernel from; p: the call's parameters
+// as the kernels see them (attention_impl's copy)
+FinFacts attn_fin_facts(const AttnCall& c, const mxa_attn_params* p) {
+  return {p->top_k != 0, p->top_k ? p->k_top : 0, p->T, (p->D + 31) / 32, c.pj && proj_codes_direct(p),
+          p->dtype != MXA_DT_F32 || p->score_dtype > MXA_DT_F32, c.elem_bits, c.reach == kReachFull};
 }
 
 // one side's (Q's or K's) row operands; null: the score mode does not read it
@@ -139,9 +162,11 @@ struct AttnLayout {
   int64_t total;
 };
 
-// workspace: the call's, or null to size it
-AttnLayout attn_layout(const mxa_attn_params* p, int mode, const mxa_qkv_params* xq, const mxa_cross_params* xc,
-                       const mxa_proj_params* pj, void* workspace, bool full) {
+// p: as attn_fin_facts; workspace: the call's, or null to size it
+AttnLayout attn_layout(const AttnCall& c, const mxa_attn_params* p, int mode, void* workspace) {
+  const mxa_qkv_params* xq = c.xq;
+  const mxa_cross_params* xc = c.xc;
+  const mxa_proj_params* pj = c.pj;
   AttnLayout L{};
   Carver ws(workspace);
   const int64_t BH = (int64_t)p->B * p->H;
@@ -163,8 +188,9 @@ AttnLayout attn_layout(const mxa_attn_params* p, int mode, const mxa_qkv_params*
     L.fbf = ws.take<uint32_t>(pk ? BH * (int64_t)((p->N + 15) / 16) : 0);
   }
   // the prune-mask words for a finishing kernel that reads them, when the caller takes none
-  // (reserved whatever mask_out is: the size must not depend on it, nor on P's width)
-  L.mask = ws.take<uint32_t>(finish_choice(attn_fin_facts(p, pj, 8, full)).reads_mask ? qrows * (int64_t)L.ntb : 0);
+  // (reserved whatever mask_out is: the size must not depend on it; nor does it on P's width, which no
+  // kernel kind depends on)
+  L.mask = ws.take<uint32_t>(finish_choice(attn_fin_facts(c, p)).reads_mask ? qrows * (int64_t)L.ntb : 0);
   const int64_t qtok = (int64_t)p->B * p->N;
   if (xq) L.x = carve_mx_rows(ws, qtok, xq->C, false);
   if (xc) {
@@ -183,33 +209,15 @@ bool attn_shape_ok(const mxa_attn_params* p) { return p && p->B > 0 && p->H > 0 
 
 // the workspace of a call; sized for the approximator whenever it may run (the proj Linear
 // and top-k run the selection kernel, pred_out the scores alone)
-int64_t attn_workspace_total(const mxa_attn_params* p, const mxa_qkv_params* xq, const mxa_cross_params* xc,
-                             const mxa_proj_params* pj, bool full) {
-  return attn_layout(p, score_mode(p, pj || p->top_k || p->pred_out), xq, xc, pj, nullptr, full).total;
+int64_t attn_workspace_total(const AttnCall& c) {
+  return attn_layout(c, c.p, score_mode(c.p, c.pj || c.p->top_k || c.p->pred_out), nullptr).total;
 }
-
-// One attention call
-struct AttnCall {
-  const mxa_attn_params* p;
-  hipStream_t stream;
-  const mxa_qkv_params* xq;    // the fused qkv projection (q, k, v produced from x and the prepared weight)
-  const mxa_cross_params* xc;  // cross-attention's projections (q from x, k and v from cond; N and T independent)
-  const mxa_proj_params* pj;   // the proj Linear behind it (y = mx.Linear(out.transpose(1,2).reshape(B,N,C)))
-  bool scores_only;  // the approximate (or true) scores into p->pred_out / true_out, no top-k
-  bool long_rows;    // the *_long entry points: rows of up to kLongRowsT keys (else 512)
-  hipEvent_t* ev;    // the timed entry points' stage events
-  int *plan, *fin;   // plan: only report the kernel path (MXA_PATH_*), launch nothing; fin (with plan): the
-                     // finishing kernel (MXA_FIN_*, 0 for the scores alone)
-  int elem_bits = 8;  // 8 MXINT8; 4 (the *_bits / *_full entry points) MXINT4 for Q, K, P and V and for the
-                      // codes every approximator is derived from (include/mxa.h mxa_attention_bits)
-  bool full;         // mxa_attention_full: rows over 512 keys also take the dense branch and k_top > 64
-};
 
 // the refusals of a call, in their order; every one before the prepared weights' header
 // checks returns without a HIP call
 int attn_validate(const AttnCall& c) {
-  const auto [p, stream, xq, xc, pj, scores_only, long_ok, ev, plan, fin, elem_bits, full] = c;
-  if (!p) return MXA_ERR_ARG;
+  const auto [p, stream, xq, xc, pj, scores_only, reach, ev, plan, fin, elem_bits] = c;
+  if (!p || !mx_width_ok(elem_bits)) return MXA_ERR_ARG;
   if (pj) {
     if (scores_only || !p->top_k || !pj->wq || !pj->y || pj->out_features <= 0 || pj->y_row_stride < pj->out_features)
       return MXA_ERR_ARG;
@@ -241,7 +249,7 @@ int attn_validate(const AttnCall& c) {
       (p->pred_mode == MXA_PRED_EXION || p->pred_mode == MXA_PRED_TRUE_EX || p->pred_mode == MXA_PRED_ELSA))
     return MXA_ERR_UNSUPPORTED;
   if (!valid_bfloat(p->bfloat)) return MXA_ERR_ARG;
-  if (p->T > (long_ok ? kLongRowsT : kShortRowsT) || p->D > 32 * kMaxNB) return MXA_ERR_UNSUPPORTED;
+  if (p->T > (reach == kReachShort ? kShortRowsT : kLongRowsT) || p->D > 32 * kMaxNB) return MXA_ERR_UNSUPPORTED;
   // rows over 512 keys, and MXINT4 (mxa_attention_bits at width 4): float32, no fused projection;
   // MXINT4: the approximators of exponent_approximation (ELSA's hashes would need the width too)
   if ((long_rows(p->T) || elem_bits == 4) && (xq || xc || pj || p->dtype != MXA_DT_F32 || p->score_dtype > MXA_DT_F32))
@@ -249,7 +257,7 @@ int attn_validate(const AttnCall& c) {
   if (elem_bits == 4 && p->approx && p->pred_mode == MXA_PRED_ELSA) return MXA_ERR_UNSUPPORTED;
   // ... and a finishing kernel with an instantiation for them (finish_choice: the 16-row and the MFMA
   // kernels), or the scores alone
-  if (!scores_only && finish_choice(attn_fin_facts(p, pj, elem_bits, full)).status) return MXA_ERR_UNSUPPORTED;
+  if (!scores_only && finish_choice(attn_fin_facts(c, p)).status) return MXA_ERR_UNSUPPORTED;
   // the prepared weights must have been prepared for this geometry and these settings
   const int HD = p->H * p->D, fl = p->flush_subnormals, bf = p->bfloat;
   if (xq && !linear_weight_verify(xq->wq, linear_weight_header(3 * HD, xq->C, p->D, fl, bf), stream)) return MXA_ERR_ARG;
@@ -424,9 +432,9 @@ int attention_impl(const AttnCall& c) {
   const bool ranked = topk || c.scores_only;  // the selection kernel runs
   const int mode = score_mode(&pp, ranked);
   if (mode == kModeElsa && (!pp.elsa_proj || pp.N != pp.T)) return MXA_ERR_ARG;  // elsa_approximation.py:126, :142
-  const AttnLayout L = attn_layout(&pp, mode, c.xq, c.xc, c.pj, pp.workspace, c.full);
+  const AttnLayout L = attn_layout(c, &pp, mode, pp.workspace);
   const int BH = (int)((int64_t)pp.B * pp.H);
-  const FinFacts ff = attn_fin_facts(&pp, c.pj, c.elem_bits, c.full);
+  const FinFacts ff = attn_fin_facts(c, &pp);
   const bool direct = ff.xo;
 
   int opq = MXA_OP_SIGN, opk = MXA_OP_SIGN;
@@ -444,8 +452,7 @@ int attention_impl(const AttnCall& c) {
   // feasibility of the path's kernels (LDS budgets), before any pointer is bound
   // (rows over 512 keys: the one-wave-per-row selection kernel, mxa_select_long.hpp)
   auto select = [&](bool plan) {
-    return c.long_rows && long_rows(pp.T) ? launch_select_long(r2, mode, BH, c.stream, plan)
-                                          : launch_select(r2, mode, BH, c.stream, plan);
+    return long_rows(pp.T) ? launch_select_long(r2, mode, BH, c.stream, plan) : launch_select(r2, mode, BH, c.stream, plan);
   };
   rc = c.scores_only ? MXA_OK : launch_rows(r2, ff, mode == kModeTrue, S, BH, c.stream, true);
   if (!rc && ranked) rc = select(true);
@@ -523,24 +530,24 @@ extern "C" const char* mxa_status_string(int status) {
 }
 
 extern "C" int64_t mxa_attention_workspace_bytes(const mxa_attn_params* p) {
-  return attn_shape_ok(p) ? attn_workspace_total(p, nullptr, nullptr, nullptr, false) : -1;
+  return attn_shape_ok(p) ? attn_workspace_total({.p = p}) : -1;
 }
 
 extern "C" int64_t mxa_qkv_attention_workspace_bytes(const mxa_attn_params* p, const mxa_qkv_params* xq) {
   if (!attn_shape_ok(p) || !xq || xq->C <= 0) return -1;
-  return attn_workspace_total(p, xq, nullptr, nullptr, false);
+  return attn_workspace_total({.p = p, .xq = xq});
 }
 
 extern "C" int64_t mxa_attention_proj_workspace_bytes(const mxa_attn_params* p, const mxa_qkv_params* xq,
                                                       const mxa_proj_params* pj) {
   if (!attn_shape_ok(p) || !pj || pj->out_features <= 0 || (xq && xq->C <= 0)) return -1;
-  return attn_workspace_total(p, xq, nullptr, pj, false);
+  return attn_workspace_total({.p = p, .xq = xq, .pj = pj});
 }
 
 extern "C" int64_t mxa_cross_attention_workspace_bytes(const mxa_attn_params* p, const mxa_cross_params* xc,
                                                        const mxa_proj_params* pj) {
   if (!attn_shape_ok(p) || !xc || xc->C <= 0 || xc->C_kv <= 0 || (pj && pj->out_features <= 0)) return -1;
-  return attn_workspace_total(p, nullptr, xc, pj, false);
+  return attn_workspace_total({.p = p, .xc = xc, .pj = pj});
 }
 
 extern "C" int mxa_attention(const mxa_attn_params* p, hipStream_t stream) {
@@ -556,45 +563,40 @@ extern "C" int64_t mxa_attention_long_workspace_bytes(const mxa_attn_params* p) 
 }
 
 extern "C" int mxa_attention_long(const mxa_attn_params* p, hipStream_t stream) {
-  return attention_impl({.p = p, .stream = stream, .long_rows = true});
+  return attention_impl({.p = p, .stream = stream, .reach = kReachLong});
 }
 
 extern "C" int mxa_approx_scores_long(const mxa_attn_params* p, hipStream_t stream) {
-  return attention_impl({.p = p, .stream = stream, .scores_only = true, .long_rows = true});
+  return attention_impl({.p = p, .stream = stream, .scores_only = true, .reach = kReachLong});
 }
 
 extern "C" int64_t mxa_attention_bits_workspace_bytes(const mxa_attn_params* p, int32_t elem_bits) {
-  if (elem_bits != 8 && elem_bits != 4) return -1;
-  return mxa_attention_long_workspace_bytes(p);  // codes stay one byte each: the same regions at either width
+  // codes stay one byte each: the same regions at either width
+  return mx_width_ok(elem_bits) ? mxa_attention_long_workspace_bytes(p) : -1;
 }
 
 extern "C" int mxa_attention_bits(const mxa_attn_params* p, int32_t elem_bits, hipStream_t stream) {
-  if (elem_bits != 8 && elem_bits != 4) return MXA_ERR_ARG;
-  return attention_impl({.p = p, .stream = stream, .long_rows = true, .elem_bits = elem_bits});
+  return attention_impl({.p = p, .stream = stream, .reach = kReachLong, .elem_bits = elem_bits});
 }
 
 // mxa_attention_bits plus, on rows over 512 keys, the dense branch and k_top > 64
 // (MX_transformer_block.py:704-705, :700-702) on finish_qk_long_kernel
 extern "C" int64_t mxa_attention_full_workspace_bytes(const mxa_attn_params* p, int32_t elem_bits) {
-  if (elem_bits != 8 && elem_bits != 4) return -1;
-  return attn_shape_ok(p) ? attn_workspace_total(p, nullptr, nullptr, nullptr, true) : -1;
+  return mx_width_ok(elem_bits) && attn_shape_ok(p) ? attn_workspace_total({.p = p, .reach = kReachFull}) : -1;
 }
 
 extern "C" int mxa_attention_full(const mxa_attn_params* p, int32_t elem_bits, hipStream_t stream) {
-  if (elem_bits != 8 && elem_bits != 4) return MXA_ERR_ARG;
-  return attention_impl({.p = p, .stream = stream, .long_rows = true, .elem_bits = elem_bits, .full = true});
+  return attention_impl({.p = p, .stream = stream, .reach = kReachFull, .elem_bits = elem_bits});
 }
 
 extern "C" int mxa_attention_full_finish_kernel(const mxa_attn_params* p, int32_t elem_bits) {
-  if (elem_bits != 8 && elem_bits != 4) return MXA_ERR_ARG;
   int plan = -1, fin = -1;
-  const int rc = attention_impl({.p = p, .long_rows = true, .plan = &plan, .fin = &fin, .elem_bits = elem_bits, .full = true});
+  const int rc = attention_impl({.p = p, .reach = kReachFull, .plan = &plan, .fin = &fin, .elem_bits = elem_bits});
   return rc ? rc : fin;
 }
 
 extern "C" int mxa_approx_scores_bits(const mxa_attn_params* p, int32_t elem_bits, hipStream_t stream) {
-  if (elem_bits != 8 && elem_bits != 4) return MXA_ERR_ARG;
-  return attention_impl({.p = p, .stream = stream, .scores_only = true, .long_rows = true, .elem_bits = elem_bits});
+  return attention_impl({.p = p, .stream = stream, .scores_only = true, .reach = kReachLong, .elem_bits = elem_bits});
 }
 
 extern "C" int mxa_qkv_attention(const mxa_attn_params* p, const mxa_qkv_params* xq, hipStream_t stream) {
@@ -669,8 +671,7 @@ static int matmul_impl(const void* a, const void* b, bool bt_rows, void* c, int6
   if (!a || !b || !c || batch <= 0 || M <= 0 || K <= 0 || Nc <= 0) return MXA_ERR_ARG;
   for (int dt : {a_dtype, b_dtype, c_dtype})
     if (dt < MXA_DT_F32 || dt > MXA_DT_BF16) return MXA_ERR_ARG;
-  if ((elem_mbits_a != 8 && elem_mbits_a != 4) || (elem_mbits_b != 8 && elem_mbits_b != 4))
-    return MXA_ERR_UNSUPPORTED;
+  if (!mx_width_ok(elem_mbits_a) || !mx_width_ok(elem_mbits_b)) return MXA_ERR_UNSUPPORTED;
   if (!valid_bfloat(bfloat)) return MXA_ERR_ARG;
   Carver ws(workspace);
   const MatmulLayout L = matmul_layout(ws, batch, M, K, Nc);

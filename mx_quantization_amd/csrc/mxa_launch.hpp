@@ -13,6 +13,8 @@ namespace mxa {
 // what a launcher returns after its launches: did the runtime take them?
 inline int launch_status() { return hipGetLastError() == hipSuccess ? MXA_OK : MXA_ERR_LAUNCH; }
 inline bool aligned16(const void* ptr) { return (reinterpret_cast<uintptr_t>(ptr) & 15u) == 0; }
+// the element widths of include/mxa.h: MXINT8 or MXINT4
+inline bool mx_width_ok(int elem_bits) { return elem_bits == 8 || elem_bits == 4; }
 // the bfloat settings of include/mxa.h: 0 / 32 (no rounding) or bfloat10 .. bfloat31
 inline bool valid_bfloat(int bfloat) { return bfloat == 0 || bfloat == 32 || (bfloat >= 10 && bfloat <= 31); }
 // may rows at ptr + i0 * s0 + i1 * s1 + i2 * s2 (elements of dtype) be read in 16-B loads?
@@ -134,7 +136,7 @@ inline int launch_select_mode(const Rows2Args& ra, int mode, int BH, hipStream_t
 #endif
 // topk, k (0 on the dense branch), xo: the finishing kernel writes the proj Linear's MX input codes
 // (the call's `direct`, known before any pointer is bound); xdt: float16 / bfloat16 inputs or scores;
-// bits: 8 or 4, P's element width; full: mxa_attention_full
+// bits: 8 or 4, P's element width; full: the entry point reaches finish_qk_long_kernel (mxa_attention_full)
 struct FinFacts { bool topk; int k, T, nbd; bool xo, xdt; int bits; bool full; };
 // kind: MXA_FIN_* (include/mxa.h); reads_mask: the kernel reads the selection's prune-mask words (the
 // caller's mask_out, else a workspace copy), not the kept indices; status: MXA_ERR_UNSUPPORTED where the

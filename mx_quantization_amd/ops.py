@@ -350,9 +350,6 @@ def _bind_out(p, out: torch.Tensor) -> torch.Tensor:
     return out
 
 
-LONG_ROWS_T = 512  # longer rows (up to 1,024 keys) go to mxa_attention_long / mxa_approx_scores_long
-
-
 def _new_idx(p, B, H, Nq, k_top, top_k, dev):
     """The kept indices (B, H, N, k) int64 bound to p.idx_out; None without top-k."""
     idx = torch.empty((B, H, Nq, k_top), dtype=torch.int64, device=dev) if top_k else None
@@ -378,7 +375,7 @@ def mx_topk_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: 
                       return_scores: bool = False, out: Optional[torch.Tensor] = None,
                       return_mask: bool = False, elsa_proj: Optional[torch.Tensor] = None,
                       autocast: Optional[torch.dtype] = None, elem_bits: int = 8):
-    """The fused hot path (include/mxa.h mxa_attention): q (B,H,N,D), k/v (B,H,T,D)
+    """The fused hot path (include/mxa.h mxa_attention_full): q (B,H,N,D), k/v (B,H,T,D)
     float32, float16 or bfloat16 (strided views of a packed qkv are fine; the ops follow
     the tensors' dtype as the reference's do).  autocast: the torch.autocast dtype the
     reference's matmuls would return (scores, P and out in it).  Returns (out (B,H,N,D),
@@ -387,8 +384,8 @@ def mx_topk_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: 
     elem_bits: 8, or 4 -- Q, K, P and V as MXINT4 and every approximator from the MXINT4 codes
     (the reference at a_elem_format = w_elem_format = "int4"; include/mxa.h mxa_attention_bits:
     float32, no autocast, no ELSA -- the library refuses those).
-    Rows of 513 .. 1,024 keys (float32): top_k=False and k_top > 64 go to mxa_attention_full, at
-    either width; k_top <= 64 to mxa_attention_long / mxa_attention_bits."""
+    One route: mxa_attention_full takes every call its siblings (mxa_attention, _long, _bits) take,
+    on the same kernels; which kernel finishes a call is the library's decision."""
     bits = _elem_bits(elem_bits)
     p, dev, (B, H, Nq, T, D), keep = _attn_params(q, k, v, scale, k_top, pred_mode, top_k, approx and top_k, bias,
                                                   flush_subnormals, bfloat, elsa_proj, autocast)
@@ -412,19 +409,8 @@ def mx_topk_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: 
         true_s = torch.empty((B, H, Nq, T), dtype=torch.float32, device=dev)
         pred_s = torch.full((B, H, Nq, T), float("nan"), dtype=torch.float32, device=dev)
         p.true_out, p.pred_out = true_s.data_ptr(), pred_s.data_ptr()
-    if T > LONG_ROWS_T and (not top_k or k_top > 64):
-        # the dense branch and k > 64 on rows of 513 .. 1,024 keys (PixArt 512 x 512 with self_top_k=False,
-        # exclude_timesteps or exclude_blocks; a large self_k): finish_qk_long_kernel, either width
-        _call_with_workspace(lib().mxa_attention_full_workspace_bytes, lib().mxa_attention_full, "mxa_attention_full", p,
-                             bits, dev=dev)
-    elif bits == 4:
-        _call_with_workspace(lib().mxa_attention_bits_workspace_bytes, lib().mxa_attention_bits, "mxa_attention_bits", p,
-                             bits, dev=dev)
-    elif T > LONG_ROWS_T:  # rows of 513 .. 1,024 keys: the sibling entry points (include/mxa.h)
-        _call_with_workspace(lib().mxa_attention_long_workspace_bytes, lib().mxa_attention_long, "mxa_attention_long", p,
-                             dev=dev)
-    else:
-        _call_with_workspace(lib().mxa_attention_workspace_bytes, lib().mxa_attention, "mxa_attention", p, dev=dev)
+    _call_with_workspace(lib().mxa_attention_full_workspace_bytes, lib().mxa_attention_full, "mxa_attention_full", p, bits,
+                         dev=dev)
     return (out, idx) + ((true_s, pred_s) if return_scores else ()) + ((mask,) if return_mask else ())
 
 
@@ -433,22 +419,16 @@ def mx_approx_scores(q: torch.Tensor, k: torch.Tensor, pred_mode: str = "ex_pred
                      elsa_proj: Optional[torch.Tensor] = None, autocast: Optional[torch.dtype] = None,
                      elem_bits: int = 8) -> torch.Tensor:
     """pred = aQ @ aK^T (+ bias) of the approximator `pred_mode` (or ELSA's
-    approximation_scores), (B,H,N,T) in the score dtype -- include/mxa.h mxa_approx_scores.
-    elem_bits 4: the approximators of the MXINT4 Q and K (mxa_approx_scores_bits)."""
+    approximation_scores), (B,H,N,T) in the score dtype -- include/mxa.h mxa_approx_scores_bits,
+    which takes every call mxa_approx_scores and _long take.  elem_bits 4: the approximators of the
+    MXINT4 Q and K."""
     bits = _elem_bits(elem_bits)
     p, dev, (B, H, Nq, T, D), keep = _attn_params(q, k, None, 1.0, 0, pred_mode, False, True, bias,
                                                   flush_subnormals, bfloat, elsa_proj, autocast)
     pred = torch.empty((B, H, Nq, T), dtype=torch.float32, device=dev)
     p.pred_out = pred.data_ptr()
-    if bits == 4:
-        _call_with_workspace(lib().mxa_attention_bits_workspace_bytes, lib().mxa_approx_scores_bits,
-                             "mxa_approx_scores_bits", p, bits, dev=dev, bad=None)
-    elif T > LONG_ROWS_T:
-        _call_with_workspace(lib().mxa_attention_long_workspace_bytes, lib().mxa_approx_scores_long,
-                             "mxa_approx_scores_long", p, dev=dev, bad=None)
-    else:
-        _call_with_workspace(lib().mxa_attention_workspace_bytes, lib().mxa_approx_scores, "mxa_approx_scores", p, dev=dev,
-                             bad=None)
+    _call_with_workspace(lib().mxa_attention_bits_workspace_bytes, lib().mxa_approx_scores_bits, "mxa_approx_scores_bits",
+                         p, bits, dev=dev, bad=None)
     odt = _out_dtype(q, autocast)
     return pred if odt == torch.float32 else pred.to(odt)  # the values are exact in odt
 
@@ -462,9 +442,7 @@ class LinearWeightMX:
 
     def __init__(self, weight: torch.Tensor, group_width: int, flush_subnormals: bool = False, bfloat: int = 0,
                  elem_bits: int = 8):
-        if int(elem_bits) not in (8, 4):
-            raise ValueError(f"elem_bits must be 8 or 4 (got {elem_bits!r})")
-        self.elem_bits = int(elem_bits)
+        self.elem_bits = _elem_bits(elem_bits)
         dev = require_device(weight)
         w = _f32(weight.detach(), "weight").contiguous()
         self.out_features, self.in_features = w.shape
@@ -636,10 +614,6 @@ def mx_qkv_attention(x: torch.Tensor, weight, bias: Optional[torch.Tensor], num_
     D = out_f // (3 * num_heads)
     wq = _prepared(weight, D, flush_subnormals, bfloat)
     _check_fits(wq, "weight", C, D, out_f, f"x C={C}, heads={num_heads}")
-    if top_k and not (0 < k_top <= Ntok):
-        raise ValueError(f"k={k_top} out of range for {Ntok} keys")
-    if approx and top_k and pred_mode not in N.PRED_MODES:
-        raise ValueError(f"pred_mode {pred_mode!r} not supported")
     # q / k / v are produced inside the call
     p, keep = _attn_shape_params(dev, torch.float32, B, num_heads, Ntok, Ntok, D, scale, k_top, pred_mode, top_k,
                                  approx and top_k, None, flush_subnormals, bfloat, elsa_proj, autocast)
@@ -703,8 +677,6 @@ def mx_cross_attention(x: torch.Tensor, cond: torch.Tensor, q_weight, q_bias: Op
     wkv = _prepared(kv_weight, D, flush_subnormals, bfloat)
     _check_fits(wq, "q weight", C, D, HD, f"x C={C}, heads={num_heads}")
     _check_fits(wkv, "kv weight", Ckv, D, 2 * HD, f"cond C_kv={Ckv}, 2 * heads * head_dim = {2 * HD}")
-    if approx and top_k and pred_mode not in N.PRED_MODES:
-        raise ValueError(f"pred_mode {pred_mode!r} not supported")
     # q / k / v are produced inside the call
     p, keep = _attn_shape_params(dev, torch.float32, B, num_heads, Ntok, T, D, scale, k_top, pred_mode, top_k,
                                  approx and top_k, bias, flush_subnormals, bfloat, None)

@@ -1,5 +1,5 @@
 """What the MXINT4 attention tests share (test_attn4_cpu.py, test_gpu_attn4.py): the oracle's
-attention restated at elem="int4", the row-wise output bound at that width, the exact-result
+attention restated at elem="int4", the exact-result
 cases with a V that is its own MXINT4, and the GPU cases with their references (computed once,
 left unchanged).  Nothing here touches the device.
 
@@ -14,6 +14,7 @@ import numpy as np
 
 import exact_out_cases as EC
 import gpu_support as GS
+from gpu_support import r_kw, r_scale, rnd  # noqa: F401
 from oracle import mx_oracle as O
 
 F32 = np.float32
@@ -59,69 +60,15 @@ def attention4(q, k, v, scale, k_top=20, pred_mode="ex_pred", top_k=True, approx
     return res
 
 
-# ---- the row-wise bound at width 4 (gpu_support.out_row_bound restated) -------------------------
-def out_row_bound4(r, v, kernel=None):
-    """gpu_support.out_row_bound for MXINT4 P and V: one code step is 2^(eP - 2), the block
-    maximum's mantissa pmax / (4 step), and a rounding tie at y >= 7 (between the codes 7 and 8)
-    is no tie: both sides clip to 7.  n_add and chain are the same kernels'."""
-    attn, true = np.asarray(r["attn"], np.float64), np.asarray(r["true"], np.float64)
-    T, D = attn.shape[-1], v.shape[-1]
-    k = r["idx"].shape[-1] if "idx" in r else 0
-    kernel = kernel or GS.finish_kernel_of(T, D, k)
-    assert kernel in ("fin16", "qk", "dense_qk"), kernel  # the kernels with an MXINT4-P form
-    n_add, chain = GS.n_add_and_chain(kernel, T, k)
-    kept = O.prune_mask(r["idx"], T) if k else np.ones(attn.shape, bool)
-    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
-        pq, _, pe = O.quantize_mx(r["attn"], "int4", 32, -1)
-        vq = np.abs(O.quantize_mx(np.asarray(v, F32), "int4", 32, -2)[0].astype(np.float64))
-        S = np.matmul(np.abs(pq.astype(np.float64)), vq)
-        fin = np.isfinite(attn).all(-1) & np.isfinite(r["out"]).all(-1) & np.isfinite(S).all(-1)
-        gap = np.where(kept, np.abs(true - np.max(np.where(kept, true, -np.inf), -1, keepdims=True)), np.inf)
-        gap = np.where(fin[..., None], gap, np.inf)
-        loose = ((gap > 0) & (gap < GS.EXACT_GAP)).any(-1, keepdims=True)
-        tau = (GS.TAU_C0 + (chain + GS.ref_chain(k or T)) / 2 + 2.0 * gap) * 2.0 ** -23
-        pb = O.to_blocks(r["attn"], -1, 32)[0].astype(np.float64)
-        tb = O.to_blocks(np.where(np.isfinite(tau), tau, 0).astype(F32), -1, 32)[0].astype(np.float64)
-        live = O.to_blocks((kept & loose & fin[..., None] & (attn > 0)).astype(F32), -1, 32)[0] > 0
-        step = np.exp2(pe.astype(np.float64) - 2)  # (..., nb, 1): one code step of the block
-        y = pb / step
-        tie = (np.abs(y - np.floor(y) - 0.5) <= tb * y) & (np.floor(y) < 7)
-        pmax = pb.max(-1, keepdims=True)
-        tmax = np.take_along_axis(tb, pb.argmax(-1)[..., None], -1)
-        mant = pmax / (4 * step)  # in [1, 2)
-        edge = (mant * (1 - 2 * tmax) < 1) | (mant * (1 + 2 * tmax) >= 2)
-        elig = live & (tie | edge)
-        F = np.matmul(O.from_blocks(np.where(elig, step, 0.0), T, -1), np.where(np.isfinite(vq), vq, 0.0))
-    shares = (elig.sum() / max(1, (kept & fin[..., None]).sum()), elig.any((-1, -2))[fin].mean() if fin.any() else 0.0)
-    return (n_add + 1) * 2.0 ** -24 * S + F, fin, shares, kernel, O.from_blocks(elig, T, -1)
-
-
 def shares_within_caps(r, v):
-    se, sr = out_row_bound4(r, v)[2]
+    se, sr = GS.out_row_bound(r, v, bits=4)[2]
     return se <= GS.ELIGIBLE_ELEMS and sr <= GS.ELIGIBLE_ROWS, (se, sr)
-
-
-def out_rows_close4(got, r, v, what):
-    """gpu_support.out_rows_close against out_row_bound4"""
-    bound, fin, (se, sr), kernel, _ = out_row_bound4(r, v)
-    assert se <= GS.ELIGIBLE_ELEMS and sr <= GS.ELIGIBLE_ROWS, f"{what}: eligible elements {se:.4%}, rows {sr:.2%}"
-    ref = np.asarray(r["out"])
-    GS.same(np.isnan(got), np.isnan(ref), what + " NaN pattern")
-    err = np.abs(got[fin].astype(np.float64) - ref[fin].astype(np.float64))
-    b = bound[fin]
-    ratio = np.where(err == 0, 0.0, err / np.where(b > 0, b, 1e-300))
-    worst = float(ratio.max()) if ratio.size else 0.0
-    print(f"out_rows_close4 {what}: {kernel}, eligible elements {se:.4%} rows {sr:.2%}, worst |got - ref| / (A + F) {worst:.3f}")
-    if worst > 1:
-        i = np.unravel_index(np.argmax(ratio), ratio.shape)
-        raise AssertionError(f"{what}: |got - ref| / (A + F) = {worst:.3f} at row {np.argwhere(fin)[i[0]].tolist()} "
-                             f"column {i[1]}: got {got[fin][i]!r} want {ref[fin][i]!r} bound {b[i]:.3e}")
 
 
 def eligible_bf16(r, v, flush=False):
     """bfloat = 16: the P blocks whose MXINT4 codes or exponent may differ between two correct
     implementations.  P enters the output through its codes alone; the codes come from
-    bf16(p), and two float32 softmaxes within tau of each other (out_row_bound4's tau) round to
+    bf16(p), and two float32 softmaxes within tau of each other (gpu_support.out_row_bound's tau) round to
     different bfloat16 values only where p lies within tau of a bfloat16 rounding midpoint.
     Those elements are moved to their lower, then to their upper bfloat16 neighbour; a block whose
     codes or exponent change, or that holds two such elements, is eligible.  Returns the number of
@@ -181,10 +128,6 @@ def exact_reference(c):
 
 
 # ---- the random GPU cases -----------------------------------------------------------------------
-def rnd(shape, seed, mult=1.0):
-    return (np.random.default_rng(seed).standard_normal(shape, dtype=F32) * F32(mult)).astype(F32)
-
-
 def pixart_bias(B, N, T, valid):
     """(1 - mask) * -10000 over the text tokens, (B, 1, 1, T)"""
     b = np.zeros((B, 1, 1, T), F32)
@@ -245,19 +188,10 @@ def r_inputs(c):
     return q, k, v, bias
 
 
-def r_scale(c):
-    return float(F32(c.D ** -0.5))
-
-
 @functools.lru_cache(maxsize=None)
 def r_reference(c):
     q, k, v, bias = r_inputs(c)
-    kw = dict(k_top=c.k) if c.k else dict(top_k=False)
-    if c.mode is None:
-        kw["approx"] = False
-    else:
-        kw["pred_mode"] = c.mode
-    return attention4(q, k, v, r_scale(c), bias=bias, flush=c.flush, bfloat=c.bfloat, **kw)
+    return attention4(q, k, v, r_scale(c), bias=bias, flush=c.flush, bfloat=c.bfloat, **r_kw(c))
 
 
 # ---- special blocks: NaN, +-Inf, all-zero and 2^+-100 blocks in Q, K and V ------------------------

@@ -18,7 +18,7 @@ import numpy as np
 
 import gate_cases as GC
 from gate_cases import DIGIT4_SPREAD  # noqa: F401
-from gpu_support import same_bits  # noqa: F401
+from gpu_support import rnd, same_bits  # noqa: F401
 from mlp_cases import case as mlp_case  # noqa: F401
 from oracle import mx_oracle as O
 
@@ -31,10 +31,6 @@ SPECS = {  # the reference's workloads/PixArt/scripts/mx_inference.py:106-122
     'round_output': 'nearest', 'round_weight': 'nearest',
     'mx_flush_fp32_subnorms': False, 'custom_cuda': False, 'quantize_backprop': False,
 }
-
-
-def rnd(shape, seed, mult=1.0):
-    return (np.random.default_rng(seed).standard_normal(shape, dtype=F32) * F32(mult)).astype(F32)
 
 
 def golden_linear(P, i):

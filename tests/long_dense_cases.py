@@ -11,6 +11,7 @@ import numpy as np
 
 import attn4_cases as A
 import exact_out_cases as EC
+from gpu_support import out_row_bound, r_kw, r_scale  # noqa: F401
 from oracle import mx_oracle as O
 
 F32 = np.float32
@@ -91,19 +92,6 @@ def r_inputs(c):
     return q, k, v, bias
 
 
-def r_scale(c):
-    return float(F32(c.D ** -0.5))
-
-
-def r_kw(c):
-    kw = dict(k_top=c.k) if c.k else dict(top_k=False)
-    if c.k and c.mode is None:
-        kw["approx"] = False
-    elif c.k:
-        kw["pred_mode"] = c.mode
-    return kw
-
-
 @functools.lru_cache(maxsize=None)
 def r_reference(c):
     q, k, v, bias = r_inputs(c)
@@ -113,8 +101,7 @@ def r_reference(c):
 
 def r_shares(c):
     """the eligible shares (elements, rows) of the row-wise bound, from the oracle alone"""
-    bound = A.out_row_bound4 if c.bits == 4 else __import__("gpu_support").out_row_bound
-    return bound(r_reference(c), r_inputs(c)[2], kernel_name(c.k))[2]
+    return out_row_bound(r_reference(c), r_inputs(c)[2], kernel_name(c.k), c.bits)[2]
 
 
 # ---- the exact epilogue's branches -----------------------------------------------------------------

@@ -10,7 +10,7 @@ import pytest
 
 import attn4_cases as A
 import exact_out_cases as EC
-from gpu_support import ELIGIBLE_ELEMS, ELIGIBLE_ROWS, OUT_TOL, load, same, same_bits
+from gpu_support import ELIGIBLE_ELEMS, ELIGIBLE_ROWS, OUT_TOL, host_params, load, same, same_bits
 from oracle import mx_oracle as O
 
 ARG, UNSUPPORTED, WORKSPACE = -1, -2, -4
@@ -89,19 +89,10 @@ def test_exports_sigs_and_abi_version(nat):
     assert nat.ABI_VERSION == 6 and nat.lib().mxa_abi_version() == 6
 
 
-def _params(nat, B, H, Nq, T, D, k, mode="ex_pred", top_k=1):
-    p = nat.AttnParams()
-    p.q = p.k = p.v = p.out = 16  # non-null placeholders: nothing is launched
-    p.elsa_proj = 16
-    p.B, p.H, p.N, p.T, p.D, p.k_top = B, H, Nq, T, D, k
-    p.pred_mode, p.top_k, p.approx, p.scale = nat.PRED_MODES[mode], top_k, 1, 0.125
-    return p
-
-
 def test_bits_entry_points_refuse_before_any_launch(nat):
     lib = nat.lib()
     bits = lambda p, w=4: lib.mxa_attention_bits(ctypes.byref(p), w, None)
-    ok = _params(nat, 1, 1, 10, 70, 64, 5)
+    ok = host_params(nat, 1, 1, 10, 70, 64, 5)
     ok.pred_out = 16
     for w in (3, 0, 16, -4):
         assert bits(ok, w) == ARG, w
@@ -109,19 +100,19 @@ def test_bits_entry_points_refuse_before_any_launch(nat):
         assert lib.mxa_attention_bits_workspace_bytes(ctypes.byref(ok), w) == -1, w
         assert lib.mxa_approx_values_bits(16, 16, 4, 32, 32, 32, 0, 0, 0, 0, w, None) == ARG, w
     assert bits(ok) == WORKSPACE and lib.mxa_approx_scores_bits(ctypes.byref(ok), 4, None) == WORKSPACE
-    assert bits(_params(nat, 1, 1, 70, 70, 64, 5, "ELSA")) == UNSUPPORTED
+    assert bits(host_params(nat, 1, 1, 70, 70, 64, 5, "ELSA")) == UNSUPPORTED
     for field in ("dtype", "score_dtype"):
-        p = _params(nat, 1, 1, 10, 70, 64, 5)
+        p = host_params(nat, 1, 1, 10, 70, 64, 5)
         setattr(p, field, nat.DT_F16)
         assert bits(p) == UNSUPPORTED, field
-    assert bits(_params(nat, 1, 1, 10, 300, 64, 65)) == UNSUPPORTED            # finish_kernel
-    assert bits(_params(nat, 1, 1, 10, 300, 64, 0, top_k=0)) == UNSUPPORTED    # dense_rows_kernel
-    assert bits(_params(nat, 1, 1, 10, 1025, 64, 5)) == UNSUPPORTED            # T > 1,024
-    p = _params(nat, 1, 1, 10, 1025, 64, 5)
+    assert bits(host_params(nat, 1, 1, 10, 300, 64, 65)) == UNSUPPORTED            # finish_kernel
+    assert bits(host_params(nat, 1, 1, 10, 300, 64, 0, top_k=0)) == UNSUPPORTED    # dense_rows_kernel
+    assert bits(host_params(nat, 1, 1, 10, 1025, 64, 5)) == UNSUPPORTED            # T > 1,024
+    p = host_params(nat, 1, 1, 10, 1025, 64, 5)
     p.pred_out = 16
     assert lib.mxa_approx_scores_bits(ctypes.byref(p), 4, None) == UNSUPPORTED
     # the scores alone have no finishing kernel: any T <= 1,024
-    p = _params(nat, 1, 1, 10, 300, 64, 0, top_k=0)
+    p = host_params(nat, 1, 1, 10, 300, 64, 0, top_k=0)
     p.pred_out = 16
     assert lib.mxa_approx_scores_bits(ctypes.byref(p), 4, None) == WORKSPACE
     # approx_values_bits validates like approx_values
@@ -139,7 +130,7 @@ def test_every_supported_combination_has_a_plan(nat, mode):
         for T in (70, 256, 513, 1024):
             ks = (5, 20, 64) + ((65, 0) if T <= 256 else ())
             for k in ks:
-                p = _params(nat, 2, 16, T, T, D, k, mode, top_k=int(k > 0))
+                p = host_params(nat, 2, 16, T, T, D, k, mode, top_k=int(k > 0))
                 assert lib.mxa_attention_bits(ctypes.byref(p), 4, None) == WORKSPACE, (mode, D, T, k)
                 p.approx = 0
                 assert lib.mxa_attention_bits(ctypes.byref(p), 4, None) == WORKSPACE, (mode, D, T, k, "approx=0")
@@ -149,10 +140,10 @@ def test_every_supported_combination_has_a_plan(nat, mode):
 
 def test_width_8_is_the_long_entry_point(nat):
     lib = nat.lib()
-    cases = [_params(nat, 2, 3, 70, 70, 64, 20), _params(nat, 1, 1, 10, 600, 64, 5), _params(nat, 1, 1, 10, 600, 64, 65),
-             _params(nat, 1, 1, 10, 1025, 64, 5), _params(nat, 1, 2, 40, 300, 72, 0, top_k=0),
-             _params(nat, 1, 1, 70, 70, 64, 5, "ELSA"), _params(nat, 1, 1, 10, 70, 200, 5)]
-    f16 = _params(nat, 1, 1, 10, 70, 64, 5)
+    cases = [host_params(nat, 2, 3, 70, 70, 64, 20), host_params(nat, 1, 1, 10, 600, 64, 5), host_params(nat, 1, 1, 10, 600, 64, 65),
+             host_params(nat, 1, 1, 10, 1025, 64, 5), host_params(nat, 1, 2, 40, 300, 72, 0, top_k=0),
+             host_params(nat, 1, 1, 70, 70, 64, 5, "ELSA"), host_params(nat, 1, 1, 10, 70, 200, 5)]
+    f16 = host_params(nat, 1, 1, 10, 70, 64, 5)
     f16.dtype = nat.DT_F16
     for p in cases + [f16]:
         assert lib.mxa_attention_bits(ctypes.byref(p), 8, None) == lib.mxa_attention_long(ctypes.byref(p), None)

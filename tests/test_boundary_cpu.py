@@ -9,6 +9,8 @@ import re
 import pytest
 import torch
 
+from gpu_support import host_params
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -107,15 +109,6 @@ def test_product_refuses_cpu_tensors():
         m.mx_topk_attention(q, q, q, 0.125, k_top=4)
 
 
-def _params(B, H, Nq, T, D, k, mode="ex_pred", top_k=1):
-    from mx_quantization_amd import _native as nat
-    p = nat.AttnParams()
-    p.q = p.k = p.v = p.out = 16  # non-null placeholders: the path query launches nothing
-    p.B, p.H, p.N, p.T, p.D, p.k_top = B, H, Nq, T, D, k
-    p.pred_mode, p.top_k, p.approx, p.scale = nat.PRED_MODES[mode], top_k, 1, 0.125
-    return p
-
-
 def test_attention_path_selection_is_host_logic():
     """mxa_attention_path: selection + finishing kernels for top-k at every bench
     shape, the dense row kernel for top_k=False (no launch, no GPU)."""
@@ -123,6 +116,7 @@ def test_attention_path_selection_is_host_logic():
     from mx_quantization_amd import _native as N
     lib = N.lib()
     split, fused = 3, 2
+    _params = lambda *a, **kw: host_params(N, *a, **kw)
     for shape in [(256, 12, 197, 197, 64, 20), (64, 16, 256, 256, 72, 154), (1, 3, 197, 197, 64, 20)]:
         assert lib.mxa_attention_path(ctypes.byref(_params(*shape))) == split, shape
     assert lib.mxa_attention_path(ctypes.byref(_params(8, 16, 256, 120, 72, 20, "MXINT4"))) == split
@@ -137,7 +131,7 @@ def test_finishing_kernel_selection_is_host_logic():
     reports (no launch, no GPU)."""
     import ctypes
     from mx_quantization_amd import _native as N
-    fk = lambda *a, **kw: N.lib().mxa_attention_finish_kernel(ctypes.byref(_params(*a, **kw)))
+    fk = lambda *a, **kw: N.lib().mxa_attention_finish_kernel(ctypes.byref(host_params(N, *a, **kw)))
     assert fk(256, 12, 197, 197, 64, 20) == 1            # DeiT-base k = 20: finish16_kernel
     assert fk(64, 16, 256, 256, 72, 154) == 3            # DiT-XL/2 k = 154: finish_qk_kernel (MFMA QK^T)
     assert fk(8, 16, 256, 120, 72, 20, "MXINT4") == 1    # PixArt cross

@@ -6,13 +6,16 @@ the row-wise bound at width 4 elsewhere, by the norm on the bfloat = 16 rows tha
 test_attn4_cpu.py shows to have no eligible P block.  The references are computed once in
 attn4_cases.py and shared with the CPU file, which asserts the eligible-share caps from the oracle
 alone."""
+import collections
+
 import numpy as np
 import pytest
 import torch
 
 import attn4_cases as A
 import exact_out_cases as EC
-from gpu_support import M, OUT_TOL, dev, dev_opt, host, load, out_close, same, same_bits  # noqa: F401
+from gpu_support import M, OUT_TOL, attn_run, check_attn, check_exact_out, check_siblings, dev, host, load  # noqa: F401
+from gpu_support import out_close, out_rows_close, r_kw, r_scale, rnd, same, same_bits
 from oracle import mx_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -23,32 +26,14 @@ def gold():
     return load("attn_int4.npz")
 
 
-def _run(M, q, k, v, scale, c_k, mode, bias, flush, bfloat, scores, T):
-    """the op at elem_bits=4 -> (out, idx, mask as bools, true, pred) on the host (None where absent)"""
-    kw = dict(k_top=c_k) if c_k else dict(top_k=False)
-    if mode is None:
-        kw["approx"] = False
-    else:
-        kw["pred_mode"] = mode
-    res = M.mx_topk_attention(q, k, v, scale, bias=bias, flush_subnormals=flush, bfloat=0 if bfloat == 32 else bfloat,
-                              return_scores=scores, return_mask=c_k > 0, elem_bits=4, **kw)
-    torch.cuda.synchronize()
-    mask = host(M.unpack_mask(res[-1], T)) if c_k else None
-    return (host(res[0]), host(res[1]) if c_k else None, mask, host(res[2]) if scores else None,
-            host(res[3]) if scores else None)
+# what _run reads of an RCase, for the calls that are none: k = 0 dense; mode None: approx=False (r_kw)
+Call = collections.namedtuple("Call", "k mode flush bfloat", defaults=(False, 32))
 
 
-def _check_scores(got, r, what, approx):
-    out, idx, mask, true, pred = got
-    if "idx" in r:
-        same(idx, r["idx"], what + " idx")
-        same(mask, O.prune_mask(r["idx"], r["true"].shape[-1]), what + " mask")
-    else:
-        assert idx is None
-    if true is not None:
-        same_bits(true, r["true"], what + " true")
-        if approx and "pred" in r:
-            same_bits(pred, r["pred"], what + " pred")
+def _run(M, q, k, v, scale, c, bias=None, scores=True):
+    """attn_run at elem_bits=4 for an RCase or a Call"""
+    return attn_run(M, q, k, v, scale, 4, scores, bias=bias, flush_subnormals=c.flush, bfloat=0 if c.bfloat == 32 else c.bfloat,
+                    **r_kw(c))
 
 
 # ---- the reference's fixture --------------------------------------------------------------------
@@ -62,12 +47,12 @@ def test_fixture_self(M, gold, tag, k, mode):
     r = A.attention4(q, kk, v, sc, **kw)  # (test_attn4_cpu.py: equal to the fixture bit for bit)
     if k:
         same(r["idx"], gold[f"self/{tag}/idx"].astype(np.int64), "oracle idx vs fixture")
-    got = _run(M, dev(q), dev(kk), dev(v), sc, k, mode, None, False, 32, True, 70)
-    same_bits(got[3], gold["self/true"], tag + " true vs fixture")
+    got = _run(M, q, kk, v, sc, Call(k, mode))
+    same_bits(got["true"], gold["self/true"], tag + " true vs fixture")
     if k and mode is not None:
-        same_bits(got[4], gold[f"self/{tag}/pred"], tag + " pred vs fixture")
-    _check_scores(got, r, tag, mode is not None)
-    A.out_rows_close4(got[0], dict(r, out=gold[f"self/{tag}/out"]), v, tag)
+        same_bits(got["pred"], gold[f"self/{tag}/pred"], tag + " pred vs fixture")
+    check_attn(got, r, tag, same_bits)
+    out_rows_close(got["out"], dict(r, out=gold[f"self/{tag}/out"]), v, tag, bits=4)
 
 
 @pytest.mark.parametrize("tag,k,mode", [("ex_pred_k20", 20, "ex_pred"), ("MXINT4_k20", 20, "MXINT4"), ("dense", 0, "ex_pred")])
@@ -79,13 +64,13 @@ def test_fixture_cross_bf16(M, gold, tag, k, mode):
     kw = dict(k_top=k, pred_mode=mode) if k else dict(top_k=False)
     r = A.attention4(q, kk, v, sc, bias=bias, flush=True, bfloat=16, **kw)
     rows = ~A.eligible_bf16(r, v, True)[2]
-    got = _run(M, dev(q), dev(kk), dev(v), sc, k, mode, dev(bias), True, 16, True, 120)
-    same_bits(got[3], gold["cross/true"], tag + " true vs fixture")
+    got = _run(M, q, kk, v, sc, Call(k, mode, True, 16), bias)
+    same_bits(got["true"], gold["cross/true"], tag + " true vs fixture")
     if k:
-        same_bits(got[4], gold[f"cross/{tag}/pred"], tag + " pred vs fixture")
-        same(got[1], gold[f"cross/{tag}/idx"].astype(np.int64), tag + " idx vs fixture")
-    _check_scores(got, r, tag, True)
-    out_close(got[0][rows], gold[f"cross/{tag}/out"][rows], OUT_TOL, tag + " out")
+        same_bits(got["pred"], gold[f"cross/{tag}/pred"], tag + " pred vs fixture")
+        same(got["idx"], gold[f"cross/{tag}/idx"].astype(np.int64), tag + " idx vs fixture")
+    check_attn(got, r, tag, same_bits)
+    out_close(got["out"][rows], gold[f"cross/{tag}/out"][rows], OUT_TOL, tag + " out")
 
 
 # ---- the grid, the long rows and finish_qk_kernel against attention4 ---------------------------------
@@ -98,18 +83,18 @@ def test_rows_vs_attention4(M, c):
         qkv = torch.stack([tq.permute(0, 2, 1, 3), tk.permute(0, 2, 1, 3), tv.permute(0, 2, 1, 3)], 2).contiguous()
         tq, tk, tv = (qkv[:, :, j].permute(0, 2, 1, 3) for j in range(3))
         assert not tq.is_contiguous()
-    got = _run(M, tq, tk, tv, A.r_scale(c), c.k, c.mode, dev_opt(bias), c.flush, c.bfloat, c.scores, c.T)
-    _check_scores(got, r, A.rcase_id(c), c.mode is not None)
-    A.out_rows_close4(got[0], r, v, A.rcase_id(c))
+    got = _run(M, tq, tk, tv, r_scale(c), c, bias, c.scores)
+    check_attn(got, r, A.rcase_id(c), same_bits)
+    out_rows_close(got["out"], r, v, A.rcase_id(c), bits=4)
 
 
 def test_random_bf16_case_by_the_norm(M):
     c = A.BF16
     q, k, v, bias = A.r_inputs(c)
     r = A.r_reference(c)
-    got = _run(M, dev(q), dev(k), dev(v), A.r_scale(c), c.k, c.mode, dev_opt(bias), c.flush, c.bfloat, c.scores, c.T)
-    _check_scores(got, r, "bf16", True)
-    out_close(got[0], r["out"], OUT_TOL, "bf16 out")
+    got = _run(M, q, k, v, r_scale(c), c, bias, c.scores)
+    check_attn(got, r, "bf16", same_bits)
+    out_close(got["out"], r["out"], OUT_TOL, "bf16 out")
 
 
 def test_approx_scores_bits(M, gold):
@@ -125,19 +110,7 @@ def test_approx_scores_bits(M, gold):
 # ---- exact-result cases: out, idx and mask bit for bit ------------------------------------------------
 @pytest.mark.parametrize("c", A.EXACT, ids=EC.case_id)
 def test_exact_out4(M, c):
-    q, kk, v, bias = A.exact_inputs(c)
-    r = A.exact_reference(c)
-    kw = dict(c.kw)
-    for scores in (False, True):
-        got = _run(M, dev(q), dev(kk), dev(v), EC.SCALE, c.k, kw.get("pred_mode", "ex_pred") if kw.get("approx", True) else None,
-                   dev_opt(bias), False, kw.get("bfloat", 32), scores, c.T)
-        w = f"{EC.case_id(c)} scores={scores}"
-        if c.k:
-            same(got[1], r["idx"], w + " idx")
-            same(got[2], O.prune_mask(r["idx"], c.T), w + " mask")
-        if scores:
-            same(got[3], r["true"], w + " true")
-        same_bits(got[0], r["out"], w + " out")
+    check_exact_out(M, c, A.exact_inputs(c), A.exact_reference(c), EC.SCALE, 4, EC.case_id(c))
 
 
 # ---- special blocks ------------------------------------------------------------------------------
@@ -168,46 +141,23 @@ def test_special_blocks_fused(M, mode):
     nor the device; its operands on these blocks are pinned by test_special_blocks_operands)"""
     q, k, v = A.special_inputs()
     r = A.special_reference(mode)
-    got = _run(M, dev(q), dev(k), dev(v), A.SPECIAL_SCALE, A.SPECIAL_K, mode, None, False, 32, True, 70)
-    same_bits(got[3], r["true"], mode + " true")
-    same_bits(got[4], r["pred"], mode + " pred")
-    same(got[1], r["idx"], mode + " idx")  # (NaN scores rank first, in torch's order)
-    same(got[2], O.prune_mask(r["idx"], 70), mode + " mask")
-    A.out_rows_close4(got[0], r, v, mode)  # the NaN pattern (a NaN V block poisons its column) and the finite rows
+    got = _run(M, q, k, v, A.SPECIAL_SCALE, Call(A.SPECIAL_K, mode))
+    check_attn(got, r, mode, same_bits)  # (idx: NaN scores rank first, in torch's order)
+    out_rows_close(got["out"], r, v, mode, bits=4)  # the NaN pattern (a NaN V block poisons its column) and the finite rows
 
 
-# ---- width 8 through the new entry points ------------------------------------------------------------
+# ---- width 8 through the width-taking entry points ----------------------------------------------------
 @pytest.mark.parametrize("T", [70, 600])
 def test_width_8_is_byte_identical(M, T):
-    import ctypes
-    q, k, v = (dev(A.rnd((2, 2, T, 64), 500 + j)) for j in range(3))
-    ref = M.mx_topk_attention(q, k, v, 0.125, 20, return_scores=True, return_mask=True)
-    # the same call through mxa_attention_bits(p, 8)
-    p, dv, (B, H, Nq, T_, D), _ = M.ops._attn_params(q, k, v, 0.125, 20, "ex_pred", True, True, None, False, 0, None)
-    out = torch.empty_like(ref[0])
-    M.ops._bind_out(p, out)
-    idx = M.ops._new_idx(p, B, H, Nq, 20, True, dv)
-    mask = torch.empty_like(ref[4])
-    true_s, pred_s = torch.empty_like(ref[2]), torch.empty_like(ref[3])
-    p.mask_out, p.true_out, p.pred_out = mask.data_ptr(), true_s.data_ptr(), pred_s.data_ptr()
-    lib = M._native.lib()
-    M.ops._call_with_workspace(lib.mxa_attention_bits_workspace_bytes, lib.mxa_attention_bits, "mxa_attention_bits", p, 8,
-                               dev=dv)
-    torch.cuda.synchronize()
-    for a, b, what in zip((out, idx, true_s, pred_s, mask), ref, ("out", "idx", "true", "pred", "mask")):
-        assert torch.equal(a.view(torch.int32) if a.dtype == torch.float32 else a,
-                           b.view(torch.int32) if b.dtype == torch.float32 else b), what
-    pred8 = torch.empty_like(ref[3])
-    p.pred_out = pred8.data_ptr()
-    M.ops._call_with_workspace(lib.mxa_attention_bits_workspace_bytes, lib.mxa_approx_scores_bits, "mxa_approx_scores_bits",
-                               p, 8, dev=dv)
-    torch.cuda.synchronize()
-    assert torch.equal(pred8.view(torch.int32), ref[3].view(torch.int32))
+    """self-attention rows (N = T, two images) at width 8: mxa_attention_bits(p, 8), mxa_attention_full(p, 8),
+    mxa_attention_long and (T <= 512) mxa_attention, called directly, and their score entry points"""
+    q, k, v = (dev(rnd((2, 2, T, 64), 500 + j)) for j in range(3))
+    check_siblings(M, q, k, v, 0.125, (8,), k_top=20)
     assert torch.equal(M.ops.approx_values(q, "sign", elem_bits=8), M.ops.approx_values(q, "sign"))
 
 
 def test_library_refuses_at_width_4(M):
-    q = dev(A.rnd((1, 2, 70, 64), 510))
+    q = dev(rnd((1, 2, 70, 64), 510))
     with pytest.raises(M._native.NativeError):
         M.mx_topk_attention(q.half(), q.half(), q.half(), 0.125, 20, elem_bits=4)
     with pytest.raises(M._native.NativeError):

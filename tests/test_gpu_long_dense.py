@@ -5,7 +5,8 @@ the norm and by the row-wise bound of finish_qk_kernel's arithmetic (n_add = ntb
 on the peaked random inputs whose eligible shares test_long_dense_cpu.py asserts; the edges of the
 tiling (a 17th block of one key, the 256-key chunk boundary, ragged and full last blocks, partial
 query tiles, one to four D blocks); special values and both branches of the exact epilogue; the
-launch plan's grid.y split; and the delegation of every other call to the existing route.  The
+launch plan's grid.y split; and, for the calls the sibling entry points take too, every accepting
+entry point's outputs against mxa_attention_full's and the op's, bit for bit.  The
 references are computed once in long_dense_cases.py and shared with the CPU file."""
 import numpy as np
 import pytest
@@ -15,28 +16,12 @@ import attn4_cases as A
 import exact_out_cases as EC
 import long_dense_cases as LC
 import topk_cases as TC
-from gpu_support import M, OUT_TOL, dev, dev_opt, host, out_close, out_row_bound, same, same_bits  # noqa: F401
-from gpu_support import ELIGIBLE_ELEMS, ELIGIBLE_ROWS
+from gpu_support import M, OUT_TOL, attn_entry, attn_run as run, check_attn as check_scores, check_exact_out  # noqa: F401
+from gpu_support import check_siblings, dev, out_close, out_rows_close, r_kw, r_scale, rnd, same, same_bits
 from oracle import mx_oracle as O
 
 pytestmark = pytest.mark.gpu
 F32 = np.float32
-
-
-def run(M, q, k, v, scale, bits=8, scores=True, **kw):
-    """the op -> dict of host arrays (out; idx, mask on the top-k path; true, pred with scores)"""
-    topk = kw.get("top_k", True)
-    kw = {a: (dev(x) if isinstance(x, np.ndarray) else x) for a, x in kw.items()}
-    res = M.mx_topk_attention(dev(q), dev(k), dev(v), scale, return_scores=scores, return_mask=topk, elem_bits=bits, **kw)
-    torch.cuda.synchronize()
-    got = dict(out=host(res[0]))
-    if topk:
-        got.update(idx=host(res[1]), mask=host(M.unpack_mask(res[-1], k.shape[-2])))
-    else:
-        assert res[1] is None
-    if scores:
-        got.update(true=host(res[2]), pred=host(res[3]))
-    return got
 
 
 def oracle(q, k, v, scale, bits=8, **kw):
@@ -45,62 +30,15 @@ def oracle(q, k, v, scale, bits=8, **kw):
     return (A.attention4 if bits == 4 else O.attention)(q, k, v, scale, **kw)
 
 
-def check_scores(got, r, what):
-    """true, and on the top-k path pred (absent with approx off), idx and the mask: equal values, NaN
-    against NaN (gpu_support.same, as test_gpu_long_rows.py compares them)"""
-    if "true" in got:
-        same(got["true"], r["true"], what + " true")
-        if "pred" in r:
-            same(got["pred"], r["pred"], what + " pred")
-    if "idx" in r:
-        same(got["idx"], r["idx"], what + " idx")
-        same(got["mask"], O.prune_mask(r["idx"], r["true"].shape[-1]), what + " mask")
-    else:
-        assert "idx" not in got
-
-
-def rows_close(got, r, v, what, k, bits=8):
-    """gpu_support.out_rows_close with finish_qk_kernel's n_add and chain, at either width"""
-    bound, fin, (se, sr), kernel, _ = (A.out_row_bound4 if bits == 4 else out_row_bound)(r, v, LC.kernel_name(k))
-    assert se <= ELIGIBLE_ELEMS and sr <= ELIGIBLE_ROWS, f"{what}: eligible elements {se:.4%}, rows {sr:.2%}"
-    ref = np.asarray(r["out"])
-    same(np.isnan(got), np.isnan(ref), what + " NaN pattern")
-    err = np.abs(got[fin].astype(np.float64) - ref[fin].astype(np.float64))
-    b = bound[fin]
-    ratio = np.where(err == 0, 0.0, err / np.where(b > 0, b, 1e-300))
-    worst = float(ratio.max()) if ratio.size else 0.0
-    print(f"rows_close {what}: {kernel} w{bits}, eligible elements {se:.4%} rows {sr:.2%}, worst |got - ref| / (A + F) {worst:.3f}")
-    if worst > 1:
-        i = np.unravel_index(np.argmax(ratio), ratio.shape)
-        raise AssertionError(f"{what}: |got - ref| / (A + F) = {worst:.3f} at row {np.argwhere(fin)[i[0]].tolist()} "
-                             f"column {i[1]}: got {got[fin][i]!r} want {ref[fin][i]!r} bound {b[i]:.3e}")
-
-
 # ---- 1. the exact-result cases, bit for bit --------------------------------------------------------------
-def _exact(M, c, bits):
-    q, kk, v, bias = A.exact_inputs(c) if bits == 4 else EC.inputs(c)
-    r = A.exact_reference(c) if bits == 4 else EC.reference(c)
-    kw = dict(c.kw)
-    kw.update(dict(k_top=c.k) if c.k else dict(top_k=False))
-    for scores in (False, True):  # the plain and the EXTRA instantiations (a bias / bfloat: EXTRA both times)
-        got = run(M, q, kk, v, EC.SCALE, bits, scores, bias=dev_opt(bias), **kw)
-        w = f"{LC.case_id(c)} w{bits} scores={scores}"
-        if c.k:
-            same(got["idx"], r["idx"], w + " idx")
-            same(got["mask"], O.prune_mask(r["idx"], c.T), w + " mask")
-        if scores:
-            same(got["true"], r["true"], w + " true")
-        same_bits(got["out"], r["out"], w + " out")
-
-
 @pytest.mark.parametrize("c", LC.EXACT + LC.EXACT_BF16, ids=LC.case_id)
 def test_exact_out(M, c):
-    _exact(M, c, 8)
+    check_exact_out(M, c, EC.inputs(c), EC.reference(c), EC.SCALE, 8, LC.case_id(c))
 
 
 @pytest.mark.parametrize("c", LC.EXACT4, ids=LC.case_id)
 def test_exact_out4(M, c):
-    _exact(M, c, 4)
+    check_exact_out(M, c, A.exact_inputs(c), A.exact_reference(c), EC.SCALE, 4, LC.case_id(c))
 
 
 # ---- 2. against the oracle on the peaked random inputs ---------------------------------------------------
@@ -108,18 +46,14 @@ def test_exact_out4(M, c):
 def test_rows_vs_oracle(M, c):
     q, k, v, bias = LC.r_inputs(c)
     r = LC.r_reference(c)
-    got = run(M, q, k, v, LC.r_scale(c), c.bits, True, bias=dev_opt(bias), **LC.r_kw(c))
+    got = run(M, q, k, v, r_scale(c), c.bits, True, bias=bias, **r_kw(c))
     what = LC.rcase_id(c)
     check_scores(got, r, what)
     out_close(got["out"], r["out"], OUT_TOL, what + " out")
-    rows_close(got["out"], r, v, what, c.k, c.bits)
+    out_rows_close(got["out"], r, v, what, LC.kernel_name(c.k), c.bits)  # finish_qk_kernel's n_add and chain
 
 
 # ---- 3. the edges of the tiling ----------------------------------------------------------------------------
-def rnd(shape, seed):
-    return np.random.default_rng(seed).standard_normal(shape, dtype=F32)
-
-
 EDGES = [(513, 1, 8), (513, 33, 72), (768, 17, 32), (769, 33, 128), (1000, 17, 72), (1000, 1, 128), (1024, 33, 8),
          (1024, 17, 32)]
 
@@ -237,41 +171,16 @@ def test_64_heads_of_33_rows(M):
 
 
 # ---- 6. delegation -----------------------------------------------------------------------------------------
-def _full(M, q, k, v, scale, bits, **kw):
-    """mxa_attention_full called directly with every output -> (out, idx, true, pred, mask) tensors"""
-    kt, topk = kw.get("k_top", 20), kw.get("top_k", True)
-    p, dv, (B, H, Nq, T, D), _ = M.ops._attn_params(q, k, v, scale, kt, "ex_pred", topk, topk, None, False, 0, None)
-    out = torch.empty((B, H, Nq, D), dtype=torch.float32, device=dv)
-    M.ops._bind_out(p, out)
-    idx = M.ops._new_idx(p, B, H, Nq, kt, topk, dv)
-    mask = torch.empty((B, H, Nq, (T + 31) // 32), dtype=torch.int32, device=dv) if topk else None
-    true_s = torch.empty((B, H, Nq, T), dtype=torch.float32, device=dv)
-    pred_s = torch.full((B, H, Nq, T), float("nan"), dtype=torch.float32, device=dv)
-    p.true_out, p.pred_out = true_s.data_ptr(), pred_s.data_ptr()
-    if topk:
-        p.mask_out = mask.data_ptr()
-    lib = M._native.lib()
-    M.ops._call_with_workspace(lib.mxa_attention_full_workspace_bytes, lib.mxa_attention_full, "mxa_attention_full", p, bits,
-                               dev=dv)
-    torch.cuda.synchronize()
-    return out, idx, true_s, pred_s, mask
-
-
 @pytest.mark.parametrize("T,kw,widths", [(197, dict(k_top=20), (8, 4)), (256, dict(k_top=154), (8, 4)), (120, dict(top_k=False), (8, 4)),
                                          (300, dict(top_k=False), (8,)), (300, dict(k_top=100), (8,)), (600, dict(k_top=20), (8, 4)),
-                                         (1000, dict(k_top=64), (8, 4))])
+                                         (1000, dict(k_top=64), (8, 4)), (70, dict(k_top=20), (8, 4))])
 def test_other_calls_are_byte_identical(M, T, kw, widths):
-    """T <= 512, and k <= 64 on longer rows: the new entry point runs today's route"""
+    """T <= 512, and k <= 64 on longer rows: every entry point that accepts the call, called directly,
+    writes the bytes mxa_attention_full writes -- out, idx, true, pred and the mask words -- and so does
+    M.mx_topk_attention; the same for the scores alone (mxa_approx_scores, _long, _bits and
+    M.mx_approx_scores)"""
     q, k, v = (dev(rnd((1, 2, n, 64), 60 + j)) for j, n in enumerate((40, T, T)))
-    for bits in widths:
-        ref = M.mx_topk_attention(q, k, v, 0.125, return_scores=True, return_mask=kw.get("top_k", True), elem_bits=bits, **kw)
-        got = _full(M, q, k, v, 0.125, bits, **kw)
-        bits32 = lambda a: a.view(torch.int32) if a.dtype == torch.float32 else a
-        for a, b, what in zip(got, tuple(ref) + (None,), ("out", "idx", "true", "pred", "mask")):
-            if b is None:
-                assert a is None or what == "mask" and not kw.get("top_k", True), what
-            else:
-                assert torch.equal(bits32(a), bits32(b)), (what, bits)
+    check_siblings(M, q, k, v, 0.125, widths, **kw)
 
 
 def test_depth_limit_adversary_above_k_64(M):
@@ -294,11 +203,6 @@ def test_without_idx_and_mask_out(M):
     q, k, v = (dev(x) for x in (rnd((1, 2, 33, 72), 70), rnd((1, 2, 1000, 72), 71), rnd((1, 2, 1000, 72), 72)))
     scale = 72.0 ** -0.5
     want = M.mx_topk_attention(q, k, v, scale, k_top=129, return_mask=True)[0]
-    lib = M._native.lib()
-    p, d, _, keep = M.ops._attn_params(q, k, v, scale, 129, "ex_pred", True, True, None, False, 0, None)
-    out = torch.full_like(want, float("nan"))
-    M.ops._bind_out(p, out)
-    assert not p.idx_out and not p.mask_out
-    M.ops._call_with_workspace(lib.mxa_attention_full_workspace_bytes, lib.mxa_attention_full, "mxa_attention_full", p, 8, dev=d)
-    torch.cuda.synchronize()
-    assert torch.equal(out, want)
+    got = attn_entry(M, "mxa_attention_full", q, k, v, scale, 8, take=(), k_top=129)
+    assert set(got) == {"out"}
+    assert torch.equal(got["out"], want)

@@ -1,5 +1,5 @@
-"""The fused op on rows of 513 .. 1,024 keys (mxa_attention_long / mxa_approx_scores_long behind
-mx_topk_attention / mx_approx_scores): true and approximate scores, kept indices and prune-mask
+"""The fused op on rows of 513 .. 1,024 keys with k <= 64 (mx_topk_attention / mx_approx_scores on
+select_long_kernel and finish16_kernel's long variant; mxa_attention_long called directly): true and approximate scores, kept indices and prune-mask
 words bit-exact against the oracle (the reference itself for the fixture), the output within
 OUT_TOL with an equal NaN pattern.  Shapes: N = 20 is one full 16-row tile and a partial one;
 T = 513 / 1000 / 1024 one key past the short rows, a ragged last 32-block, the full mirror;
@@ -10,43 +10,22 @@ import pytest
 import torch
 
 import topk_cases as TC
-from gpu_support import OUT_TOL, M, dev, host, load, out_close, out_rows_close, same  # noqa: F401
+from gpu_support import OUT_TOL, M, attn_entry, attn_run as run, check_attn, dev, host, load, out_close  # noqa: F401
+from gpu_support import out_rows_close, rnd, same
 from oracle import mx_oracle as O
 
 pytestmark = pytest.mark.gpu
-
-
-def rnd(shape, seed):
-    return np.random.default_rng(seed).standard_normal(shape, dtype=np.float32)
 
 
 def qkv(B, H, N, T, D, seed):
     return rnd((B, H, N, D), seed), rnd((B, H, T, D), seed + 1), rnd((B, H, T, D), seed + 2)
 
 
-def run(M, q, kk, v, scale, **kw):
-    kw = {k_: (dev(x) if isinstance(x, np.ndarray) else x) for k_, x in kw.items()}
-    res = M.mx_topk_attention(dev(q), dev(kk), dev(v), scale, return_scores=True, return_mask=True, **kw)
-    torch.cuda.synchronize()
-    out, idx, true_s, pred_s, mask = res
-    return dict(out=host(out), idx=host(idx), true=host(true_s), pred=host(pred_s),
-                mask=host(M.unpack_mask(mask, kk.shape[-2])))
-
-
 def check(got, ref, what, v=None):
     """ref: the oracle's (or the reference's) true, pred (absent with approx off), idx, out; v: of
     a float32 call with bfloat 0 / 32 and no flush checked against the oracle -- the row-wise
     bound beside the norm"""
-    T = got["true"].shape[-1]
-    same(got["true"], ref["true"], what + " true")
-    if "pred" in ref:
-        same(got["pred"], ref["pred"], what + " pred")
-    idx = np.asarray(ref["idx"]).astype(np.int64)
-    if not np.array_equal(got["idx"], idx):
-        bad = np.argwhere(got["idx"] != idx)
-        print(f"{what}: idx mismatches at {bad[:8].tolist()}")
-    same(got["idx"], idx, what + " idx")
-    same(got["mask"], O.prune_mask(idx, T), what + " mask")
+    check_attn(got, ref, what)
     out_close(got["out"], ref["out"], OUT_TOL, what + " out")
     if v is not None:
         out_rows_close(got["out"], ref, v, what + " out")
@@ -176,14 +155,9 @@ def test_long_rows_without_idx_out(M):
     q, kk, v = (dev(x) for x in qkv(1, 2, 20, 1000, 72, 9))
     scale = 72.0 ** -0.5
     want, _, mask = M.mx_topk_attention(q, kk, v, scale, k_top=20, return_mask=True)
-    lib = M._native.lib()
-    p, d, _, keep = M.ops._attn_params(q, kk, v, scale, 20, "ex_pred", True, True, None, False, 0, None)
-    out = torch.full_like(want, float("nan"))
-    M.ops._bind_out(p, out)
-    assert not p.idx_out and not p.mask_out
-    M.ops._call_with_workspace(lib.mxa_attention_long_workspace_bytes, lib.mxa_attention_long, "mxa_attention_long", p, dev=d)
-    torch.cuda.synchronize()
-    assert torch.equal(out, want)
+    got = attn_entry(M, "mxa_attention_long", q, kk, v, scale, take=(), k_top=20)
+    assert set(got) == {"out"}
+    assert torch.equal(got["out"], want)
 
 
 # ---- 10. the scores alone ---------------------------------------------------------------------------

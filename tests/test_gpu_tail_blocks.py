@@ -18,7 +18,7 @@ import pytest
 import torch
 
 import topk_cases as TC
-from gpu_support import OUT_TOL, M, dev, host, out_rows_close, same, same_bits  # noqa: F401
+from gpu_support import OUT_TOL, M, attn_entry, dev, host, out_rows_close, same, same_bits  # noqa: F401
 from oracle import mx_oracle as O
 
 pytestmark = pytest.mark.gpu
@@ -46,20 +46,10 @@ def _attention(M, q, kk, v, k, idx="new", mask=True):
     """mxa_attention (ex_pred) through the C ABI: idx "new" (a fresh int64 tensor), None (no idx
     output: the kept indices stay in the workspace's 16-bit copy) or a caller's int64 tensor
     of H * N * k elements, written in place.  Returns out, idx, mask words on the host."""
-    from mx_quantization_amd import ops
-    tq, tk, tv = dev(q), dev(kk), dev(v)
-    p, d, (B, H, N, T, D), keep = ops._attn_params(tq, tk, tv, 0.125, k, "ex_pred", True, True, None, False, 0, None)
-    out = ops._bind_out(p, torch.empty((B, H, N, D), dtype=torch.float32, device=d))
-    if isinstance(idx, str):
-        idx = torch.empty(B * H * N * k, dtype=torch.int64, device=d)
-    p.idx_out = None if idx is None else idx.data_ptr()
-    words = None
-    if mask:
-        words = torch.empty((B * H * N, (T + 31) // 32), dtype=torch.int32, device=d)
-        p.mask_out = words.data_ptr()
-    ops._call_with_workspace(M.lib().mxa_attention_workspace_bytes, M.lib().mxa_attention, "mxa_attention", p, dev=d)
-    torch.cuda.synchronize()
-    return host(out), None if idx is None else host(idx).reshape(-1, k), None if words is None else host(words)
+    take = (() if idx is None else ("idx",)) + (("mask",) if mask else ())
+    r = attn_entry(M, "mxa_attention", dev(q), dev(kk), dev(v), 0.125, take=take, k_top=k, idx=None if isinstance(idx, str) else idx)
+    rows = lambda name: host(r[name]).reshape(-1, r[name].shape[-1] if r[name].dim() > 1 else k) if name in r else None
+    return host(r["out"]), rows("idx"), rows("mask")
 
 
 def _mask_bits(M, words, T):

@@ -15,7 +15,7 @@ import exact_out_cases as EC
 import long_dense_cases as LC
 import test_attn4_cpu as T4
 import test_exact_out_cpu as TE
-from gpu_support import ELIGIBLE_ELEMS, ELIGIBLE_ROWS
+from gpu_support import ELIGIBLE_ELEMS, ELIGIBLE_ROWS, host_params
 from oracle import mx_oracle as O
 
 MODES = ["ex_pred", "partial_Q", "partial_K", "MXINT4", "two_step_leading_ones", "true_ex", "ELSA"]
@@ -28,15 +28,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def nat():
     from mx_quantization_amd import _native
     return _native
-
-
-def _params(nat, B, H, Nq, T, D, k, mode="ex_pred", top_k=1):
-    p = nat.AttnParams()
-    p.q = p.k = p.v = p.out = 16  # non-null placeholders: nothing is launched
-    p.elsa_proj = 16
-    p.B, p.H, p.N, p.T, p.D, p.k_top = B, H, Nq, T, D, k
-    p.pred_mode, p.top_k, p.approx, p.scale = nat.PRED_MODES[mode], top_k, 1, 0.125
-    return p
 
 
 def _full(nat, p, bits=8):
@@ -59,35 +50,35 @@ def test_exports_sigs_and_abi_version(nat):
 def test_full_entry_point_refuses_before_any_launch(nat):
     lib = nat.lib()
     for bits in (8, 4):
-        assert _full(nat, _params(nat, 1, 1, 10, 1025, 64, 5), bits) == UNSUPPORTED           # T > 1,024
-        assert _full(nat, _params(nat, 1, 1, 10, 1025, 64, 0, top_k=0), bits) == UNSUPPORTED
+        assert _full(nat, host_params(nat, 1, 1, 10, 1025, 64, 5), bits) == UNSUPPORTED           # T > 1,024
+        assert _full(nat, host_params(nat, 1, 1, 10, 1025, 64, 0, top_k=0), bits) == UNSUPPORTED
         for k, top_k in ((5, 1), (65, 1), (0, 0)):
             for field in ("dtype", "score_dtype"):                                          # float16 tensors / autocast
-                p = _params(nat, 1, 1, 10, 600, 64, k, top_k=top_k)
+                p = host_params(nat, 1, 1, 10, 600, 64, k, top_k=top_k)
                 setattr(p, field, nat.DT_F16)
                 assert _full(nat, p, bits) == UNSUPPORTED, (bits, k, field)
     for k, top_k in ((5, 1), (65, 1)):                                                      # ELSA at width 4
-        assert _full(nat, _params(nat, 1, 1, 600, 600, 64, k, "ELSA", top_k), 4) == UNSUPPORTED
-        assert _full(nat, _params(nat, 1, 1, 600, 600, 64, k, "ELSA", top_k), 8) == WORKSPACE
+        assert _full(nat, host_params(nat, 1, 1, 600, 600, 64, k, "ELSA", top_k), 4) == UNSUPPORTED
+        assert _full(nat, host_params(nat, 1, 1, 600, 600, 64, k, "ELSA", top_k), 8) == WORKSPACE
     for bits in (0, 2, 16, -4):                                                             # other widths
-        p = _params(nat, 1, 1, 10, 600, 64, 65)
+        p = host_params(nat, 1, 1, 10, 600, 64, 65)
         assert _full(nat, p, bits) == ARG
         assert lib.mxa_attention_full_workspace_bytes(ctypes.byref(p), bits) == -1
         assert lib.mxa_attention_full_finish_kernel(ctypes.byref(p), bits) == ARG
     assert lib.mxa_attention_full_workspace_bytes(None, 8) == -1
     # what mxa_attention_bits refuses at T <= 512 stays refused: the 32-row and the dense row kernel at width 4
-    assert _full(nat, _params(nat, 1, 2, 100, 300, 64, 100), 4) == UNSUPPORTED
-    assert _full(nat, _params(nat, 1, 2, 100, 300, 64, 0, top_k=0), 4) == UNSUPPORTED
-    assert _full(nat, _params(nat, 1, 1, 10, 60, 160, 5), 8) == UNSUPPORTED                  # D > 128
+    assert _full(nat, host_params(nat, 1, 2, 100, 300, 64, 100), 4) == UNSUPPORTED
+    assert _full(nat, host_params(nat, 1, 2, 100, 300, 64, 0, top_k=0), 4) == UNSUPPORTED
+    assert _full(nat, host_params(nat, 1, 1, 10, 60, 160, 5), 8) == UNSUPPORTED                  # D > 128
     # mxa_attention_long still refuses the dense branch and k = 65 at T = 600; the new entry point takes
     # the same parameters as far as their (absent) workspace
     for k, top_k in ((5, 0), (65, 1)):
-        p = _params(nat, 1, 1, 10, 600, 64, k, top_k=top_k)
+        p = host_params(nat, 1, 1, 10, 600, 64, k, top_k=top_k)
         assert lib.mxa_attention_long(ctypes.byref(p), None) == UNSUPPORTED
         assert lib.mxa_attention_bits(ctypes.byref(p), 8, None) == UNSUPPORTED
         assert lib.mxa_attention_bits(ctypes.byref(p), 4, None) == UNSUPPORTED
         assert _full(nat, p, 8) == WORKSPACE and _full(nat, p, 4) == WORKSPACE
-    p = _params(nat, 1, 1, 10, 600, 64, 601)                                                # k > T
+    p = host_params(nat, 1, 1, 10, 600, 64, 601)                                                # k > T
     assert _full(nat, p, 8) == ARG
 
 
@@ -99,7 +90,7 @@ def test_every_supported_combination_has_a_plan(nat, mode):
         for D in (32, 64, 72, 128):
             for T in (513, 1000, 1024):
                 for k in (0, 65, 154, 512, T):
-                    p = _params(nat, 2, 16, T, T, D, k, mode, top_k=int(k > 0))
+                    p = host_params(nat, 2, 16, T, T, D, k, mode, top_k=int(k > 0))
                     assert _full(nat, p, bits) == WORKSPACE, (mode, bits, D, T, k)
                     p.approx = 0  # top-k on the true scores
                     assert _full(nat, p, bits) == WORKSPACE, (mode, bits, D, T, k, "approx=0")
@@ -111,19 +102,19 @@ def test_dispatch_report(nat):
     for bits in (8, 4):
         for T in (513, 1000, 1024):
             for k in (65, 154, T):
-                assert fk(_params(nat, 2, 16, T, T, 72, k), bits) == LC.MFMA_LONG == LC.kind_of(T, k)
-            assert fk(_params(nat, 2, 16, T, T, 72, 0, top_k=0), bits) == LC.DENSE_MFMA_LONG == LC.kind_of(T, 0)
+                assert fk(host_params(nat, 2, 16, T, T, 72, k), bits) == LC.MFMA_LONG == LC.kind_of(T, k)
+            assert fk(host_params(nat, 2, 16, T, T, 72, 0, top_k=0), bits) == LC.DENSE_MFMA_LONG == LC.kind_of(T, 0)
             for k in (1, 20, 64):
-                assert fk(_params(nat, 2, 16, T, T, 72, k), bits) == EC.GATHER16 == LC.kind_of(T, k)
+                assert fk(host_params(nat, 2, 16, T, T, 72, k), bits) == EC.GATHER16 == LC.kind_of(T, k)
     # rows of at most 512 keys: what mxa_attention_finish_kernel reports
     for a, kw in (((256, 12, 197, 197, 64, 20), {}), ((64, 16, 256, 256, 72, 154), {}), ((1, 2, 100, 300, 64, 100), {}),
                   ((256, 12, 197, 197, 64, 20), dict(top_k=0)), ((1, 2, 100, 300, 64, 20), dict(top_k=0)),
                   ((1, 2, 100, 512, 64, 65), {}), ((1, 2, 100, 512, 64, 0), dict(top_k=0))):
-        p = _params(nat, *a, **kw)
+        p = host_params(nat, *a, **kw)
         want = lib.mxa_attention_finish_kernel(ctypes.byref(p))
         assert want in (1, 2, 3, 4, 5) and fk(p) == want, (a, kw)
     for c in LC.EXACT + LC.EXACT_BF16 + LC.EXACT4:
-        p = _params(nat, c.B, c.H, c.N, c.T, c.D, c.k, top_k=int(c.k > 0))
+        p = host_params(nat, c.B, c.H, c.N, c.T, c.D, c.k, top_k=int(c.k > 0))
         assert fk(p) == LC.kind_of(c.T, c.k) and fk(p, 4) == LC.kind_of(c.T, c.k), LC.case_id(c)
 
 
@@ -136,14 +127,14 @@ def test_workspace_bytes(nat):
     for bits in (8, 4):
         for a, kw in (((256, 12, 197, 197, 64, 20), {}), ((64, 16, 256, 256, 72, 154), {}), ((2, 16, 1024, 1024, 72, 20), {}),
                       ((1, 2, 100, 300, 64, 100), {}), ((1, 2, 77, 120, 72, 0), dict(top_k=0)), ((2, 2, 33, 513, 32, 64), {})):
-            f, b = both(_params(nat, *a, **kw), bits)
+            f, b = both(host_params(nat, *a, **kw), bits)
             assert f == b > 0, (bits, a, kw)
-        p = _params(nat, 2, 16, 1024, 1024, 72, 154)
+        p = host_params(nat, 2, 16, 1024, 1024, 72, 154)
         f, b = both(p, bits)
         assert f == b + 32 * 1024 * 32 * 4  # (B H N) rows of ntb = 32 words, a multiple of 256 B
         p.mask_out = 16
         assert both(p, bits)[0] == f
-        f, b = both(_params(nat, 2, 16, 1024, 1024, 72, 0, top_k=0), bits)
+        f, b = both(host_params(nat, 2, 16, 1024, 1024, 72, 0, top_k=0), bits)
         assert f == b
 
 

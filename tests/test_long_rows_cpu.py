@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 import topk_cases as TC
-from gpu_support import OUT_TOL, load, same
+from gpu_support import OUT_TOL, host_params, load, same
 from oracle import mx_oracle as O
 
 MODES = ["ex_pred", "partial_Q", "partial_K", "MXINT4", "two_step_leading_ones", "true_ex", "ELSA"]
@@ -19,15 +19,6 @@ UNSUPPORTED, WORKSPACE = -2, -4
 def nat():
     from mx_quantization_amd import _native
     return _native
-
-
-def _params(nat, B, H, Nq, T, D, k, mode="ex_pred", top_k=1):
-    p = nat.AttnParams()
-    p.q = p.k = p.v = p.out = 16  # non-null placeholders: nothing is launched
-    p.elsa_proj = 16
-    p.B, p.H, p.N, p.T, p.D, p.k_top = B, H, Nq, T, D, k
-    p.pred_mode, p.top_k, p.approx, p.scale = nat.PRED_MODES[mode], top_k, 1, 0.125
-    return p
 
 
 @pytest.mark.parametrize("mode", ["ex_pred", "MXINT4"])
@@ -44,18 +35,18 @@ def test_oracle_vs_reference_long_rows(mode):
 def test_long_entry_points_refuse_before_any_launch(nat):
     lib = nat.lib()
     long_ = lambda p: lib.mxa_attention_long(ctypes.byref(p), None)
-    assert long_(_params(nat, 1, 1, 10, 1025, 64, 5)) == UNSUPPORTED            # T > 1,024
-    assert long_(_params(nat, 1, 1, 10, 600, 64, 5, top_k=0)) == UNSUPPORTED    # the dense branch
-    assert long_(_params(nat, 1, 1, 10, 600, 64, 65)) == UNSUPPORTED            # k > 64
+    assert long_(host_params(nat, 1, 1, 10, 1025, 64, 5)) == UNSUPPORTED            # T > 1,024
+    assert long_(host_params(nat, 1, 1, 10, 600, 64, 5, top_k=0)) == UNSUPPORTED    # the dense branch
+    assert long_(host_params(nat, 1, 1, 10, 600, 64, 65)) == UNSUPPORTED            # k > 64
     for field in ("dtype", "score_dtype"):                                      # float16 tensors / autocast
-        p = _params(nat, 1, 1, 10, 600, 64, 5)
+        p = host_params(nat, 1, 1, 10, 600, 64, 5)
         setattr(p, field, nat.DT_F16)
         assert long_(p) == UNSUPPORTED, field
-    p = _params(nat, 1, 1, 10, 1025, 64, 5)
+    p = host_params(nat, 1, 1, 10, 1025, 64, 5)
     p.pred_out = 16
     assert lib.mxa_approx_scores_long(ctypes.byref(p), None) == UNSUPPORTED
     # the short entry points keep their rule
-    p = _params(nat, 1, 1, 10, 600, 64, 5)
+    p = host_params(nat, 1, 1, 10, 600, 64, 5)
     p.pred_out = 16
     assert lib.mxa_attention(ctypes.byref(p), None) == UNSUPPORTED
     assert lib.mxa_approx_scores(ctypes.byref(p), None) == UNSUPPORTED
@@ -74,7 +65,7 @@ def test_every_supported_combination_has_a_plan(nat, mode):
     for D in (32, 64, 72, 128):
         for T in (513, 1000, 1024):
             for k in (5, 20, 64):
-                p = _params(nat, 2, 16, T, T, D, k, mode)
+                p = host_params(nat, 2, 16, T, T, D, k, mode)
                 assert lib.mxa_attention_long(ctypes.byref(p), None) == WORKSPACE, (mode, D, T, k)
                 p.approx = 0  # top-k on the true scores
                 assert lib.mxa_attention_long(ctypes.byref(p), None) == WORKSPACE, (mode, D, T, k, "approx=0")
@@ -82,14 +73,14 @@ def test_every_supported_combination_has_a_plan(nat, mode):
 
 def test_long_workspace_bytes(nat):
     lib = nat.lib()
-    p = _params(nat, 256, 12, 197, 197, 64, 20)
+    p = host_params(nat, 256, 12, 197, 197, 64, 20)
     assert lib.mxa_attention_long_workspace_bytes(ctypes.byref(p)) == lib.mxa_attention_workspace_bytes(ctypes.byref(p))
     # PixArt 512x512 self-attention, ex_pred.  Per head: Q, K codes + exponents (true and
     # approximate) + sign words (2 x 1024 x (96 + 6 + 6 + 12) B), V^T codes + exponents
     # (72 x 1024 + 32 x 72 x 2 B), the 16-bit kept indices (1024 x 20 x 2 B); no tail
     # records, flags or mask words (those belong to rows of <= 256 keys); 11 regions, each
     # rounded up to 256 B
-    p = _params(nat, 2, 16, 1024, 1024, 72, 20)
+    p = host_params(nat, 2, 16, 1024, 1024, 72, 20)
     per_head = 2 * 1024 * (96 + 6 + 6 + 12) + 72 * 1024 + 32 * 72 * 2 + 1024 * 20 * 2
     nbytes = lib.mxa_attention_long_workspace_bytes(ctypes.byref(p))
     assert 32 * per_head <= nbytes < 32 * per_head + 12 * 256

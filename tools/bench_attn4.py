@@ -1,4 +1,4 @@
-"""The MXINT4 attention core, M.mx_topk_attention(.., elem_bits=4) (mxa_attention_bits), against
+"""The MXINT4 attention core, M.mx_topk_attention(.., elem_bits=4), against
 the 8-bit fused call at the same shape and against what a W4A4 caller ran before it: the unchanged
 glue of the patched attention forward on the drop-in modules under the int4 spec -- mx.matmul
 (true QK^T), funcs.exponent_approximation and a torch matmul (pred), M.topk on the N x T matrix,
@@ -18,27 +18,13 @@ the chain and the normwise relative difference of their outputs.  One JSON line 
 --only: one fused call alone (for a kernel trace of it)."""
 import argparse
 import json
-import os
-import statistics
-import sys
 
 import torch
 
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import mx_quantization_amd as M  # noqa: E402
+from ab_routes import M, agreement, alternate, chain, ms_fields
 
 H, D, K_TOP, MODE = 16, 72, 20, "ex_pred"
 SHAPES = {"self_256": (8, 256, 256, False), "self_512": (2, 1024, 1024, False), "cross": (8, 256, 120, True)}
-
-
-def timed(fn, steps):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(steps):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / steps
 
 
 def main():
@@ -50,12 +36,6 @@ def main():
     ap.add_argument("--shapes", default=",".join(SHAPES))
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
-    M.install_dropin()
-    from funcs import exponent_approximation
-    from mx import matmul
-    from mx.specs import apply_mx_specs
-    specs = apply_mx_specs({"a_elem_format": "int4", "w_elem_format": "int4", "block_size": 32, "scale_bits": 8,
-                            "bfloat": 32, "shared_exp_method": "max", "round": "nearest"})
     scale = D ** -0.5
     for name in args.shapes.split(","):
         B, N, T, masked = SHAPES[name]
@@ -70,40 +50,15 @@ def main():
         def fused(bits):
             return M.mx_topk_attention(q, k, v, scale, k_top=K_TOP, pred_mode=MODE, bias=bias, elem_bits=bits)
 
-        def chain():
-            true_scores = matmul(q, k.transpose(-2, -1), mx_specs=specs, mode_config="aa") * scale
-            if bias is not None:
-                true_scores = true_scores + bias
-            aq, ak = exponent_approximation(Q=q, K=k, mx_specs=specs).exponent_based_sign()
-            pred_scores = aq @ ak.transpose(-2, -1)
-            if bias is not None:
-                pred_scores = pred_scores + bias
-            _, idx = M.topk(pred_scores, K_TOP)
-            vals = true_scores.gather(dim=-1, index=idx)
-            attn = torch.zeros_like(true_scores)
-            attn.scatter_(-1, idx, torch.softmax(vals, dim=-1).to(attn.dtype))
-            return matmul(attn, v, mx_specs=specs, mode_config="aa"), idx
-
-        routes = {"fused4": lambda: fused(4), "fused8": lambda: fused(8), "chain4": chain}
+        routes = {"fused4": lambda: fused(4), "fused8": lambda: fused(8),
+                  "chain4": lambda: chain(q, k, v, scale, K_TOP, MODE, 4, bias)}
         if args.only:
             routes = {args.only: routes[args.only]}
-        for _ in range(args.warmup):  # warm-up of every route before any timing
-            for fn in routes.values():
-                fn()
-        torch.cuda.synchronize()
-        times = {r: [] for r in routes}
-        for _ in range(args.reps):  # alternating
-            for r, fn in routes.items():
-                times[r].append(timed(fn, args.steps))
+        times, = alternate([routes], args.steps, args.warmup, args.reps)
         line = {"shape": name, "B_H_N_T_D_k": (B, H, N, T, D, K_TOP), "pred_mode": MODE, "steps": args.steps,
-                "reps": args.reps}
-        for r, ts in times.items():
-            line.update({f"{r}_ms_median": round(statistics.median(ts), 4), f"{r}_ms_spread": round(max(ts) - min(ts), 4),
-                         f"{r}_ms": [round(t, 4) for t in ts]})
+                "reps": args.reps, **ms_fields(times)}
         if not args.only:
-            (of, idf), (oc, idc) = fused(4), chain()
-            line.update({"idx_equal": bool(torch.equal(idf, idc)),
-                         "out_normwise_rel_diff": (torch.linalg.norm((of - oc).double()) / torch.linalg.norm(oc.double())).item()})
+            line.update(agreement(routes["fused4"](), routes["chain4"]()))
         print(json.dumps(line), flush=True)
         del q, k, v
 

@@ -20,19 +20,11 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import mx_quantization_amd as M  # noqa: E402
+from ab_routes import timed  # noqa: E402
 
 B, N, T, C, CKV, H, K_TOP = 8, 256, 120, 1152, 1152, 16, 20
 MODES = ("MXINT4", "ex_pred")
 
-
-def timed(fn, steps):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(steps):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / steps
 
 
 def main():

@@ -26,6 +26,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import mx_quantization_amd as M  # noqa: E402
+from ab_routes import timed  # noqa: E402
 from mx_quantization_amd import ops  # noqa: E402
 from mx_quantization_amd.mx.elemwise_ops import quantize_elemwise_op  # noqa: E402
 from mx_quantization_amd.mx.specs import apply_mx_specs  # noqa: E402
@@ -97,15 +98,6 @@ def mlp_bytes(rows, inf, hid, outf):
     old = lin(rows, inf, hid) + 2 * hidden + lin(rows, hid, outf)
     return fused4, old, fused8
 
-
-def timed(fn, steps):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(steps):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / steps
 
 
 def stats(ts):

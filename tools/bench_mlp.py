@@ -19,6 +19,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import mx_quantization_amd as M  # noqa: E402
+from ab_routes import timed  # noqa: E402
 
 SHAPES = (("deit_base", 50432, 768, 3072, 768), ("dit_xl2", 16384, 1152, 4608, 1152))
 
@@ -39,15 +40,6 @@ def algorithmic_bytes(rows, inf, hid, outf):
                + fc2 + w)
     return fused, unfused
 
-
-def timed(fn, steps):
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(steps):
-        fn()
-    b.record()
-    b.synchronize()
-    return a.elapsed_time(b) / steps
 
 
 def main():
