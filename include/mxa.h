@@ -260,8 +260,9 @@ int mxa_approx_scores_long(const mxa_attn_params* p, hipStream_t stream);
  *                bfloat16 tensors or a nonzero score_dtype, k_top > 64 or the dense branch with
  *                T > 256 (finish_kernel, dense_rows_kernel), T > 1,024.
  *   any other width: -1 / MXA_ERR_ARG before any HIP call.
- * The fused projections have no 4-bit form (they return MXA_ERR_ARG for a 4-bit weight): a W4A4
- * block is mxa_linear x 3, mxa_attention_bits(p, 4), mxa_linear.
+ * The fused projections at 4 bits (a W4A4 block in one call) are mxa_qkv_attention_bits,
+ * mxa_attention_proj_bits and mxa_cross_attention_bits below; their siblings without _bits return
+ * MXA_ERR_ARG for a 4-bit weight.
  */
 int64_t mxa_attention_bits_workspace_bytes(const mxa_attn_params* p, int32_t elem_bits);
 int mxa_attention_bits(const mxa_attn_params* p, int32_t elem_bits, hipStream_t stream);
@@ -382,7 +383,8 @@ int mxa_linear_weight_prep(const float* w, int32_t out_features, int32_t in_feat
  * a smaller buffer, its header marked 4 bits); any other width: -1 / MXA_ERR_ARG before any
  * HIP call.  mxa_linear and mxa_mlp take the width from the weight's header and quantize their
  * activations at the same width (W4A4); the attention entry points (mxa_qkv_attention,
- * mxa_attention_proj, mxa_cross_attention) return MXA_ERR_ARG for a 4-bit weight.
+ * mxa_attention_proj, mxa_cross_attention) return MXA_ERR_ARG for a 4-bit weight: a W4A4 block
+ * goes through their *_bits forms (below, after mxa_cross_attention).
  */
 int64_t mxa_linear_weight_bytes_bits(int32_t out_features, int32_t in_features, int32_t group_width,
                                      int32_t elem_bits);
@@ -515,6 +517,43 @@ int64_t mxa_cross_attention_workspace_bytes(const mxa_attn_params* p, const mxa_
                                             const mxa_proj_params* pj);
 int mxa_cross_attention(const mxa_attn_params* p, const mxa_cross_params* xc, const mxa_proj_params* pj,
                         hipStream_t stream);
+
+/*
+ * The three fused blocks with the element width as an argument: the W4A4 block in one call (the
+ * reference's PixArt inference runs every Linear and both attentions at w_elem_format =
+ * a_elem_format = "int4", workloads/PixArt/scripts/mx_inference.py:106-122).  The same parameter
+ * structs, outputs and workspace rules as mxa_qkv_attention, mxa_attention_proj and
+ * mxa_cross_attention.
+ *   elem_bits 8: exactly the sibling without _bits -- the same kernels, bytes, statuses and
+ *                workspace size, MXA_ERR_ARG for a 4-bit weight included.
+ *   elem_bits 4: every weight of the call (qkv, or q and kv, and proj) is an
+ *                mxa_linear_weight_prep_bits(.., 4) buffer with the header the sibling expects at
+ *                elem_bits 4; an 8-bit weight, or widths mixed within one call: MXA_ERR_ARG.  x
+ *                and cond are quantized at MXINT4 and every projection is mxa_linear's on the same
+ *                4-bit weight bit for bit (the exact product rounded once, then the Linear output
+ *                rule); the fp32 q, k, v never reach HBM: the projection kernel writes the
+ *                operands mxa_attention_bits(p, 4) would build from them, and the attention is
+ *                that call's on rows of at most 512 keys.  With pj the attention's fp32 output
+ *                goes through a workspace copy and the MXINT4 row quantizer for every D (at 8 bits
+ *                only for D % 32 != 0), then mxa_linear's kernel for the 4-bit proj weight.
+ *                Float32, no autocast.  MXA_ERR_UNSUPPORTED, before any HIP call: a nonzero
+ *                score_dtype or autocast_dtype, float16 / bfloat16 tensors, MXA_PRED_ELSA (with
+ *                approx), T > 512, k_top > 64, the dense branch with 256 < T <= 512.
+ *                The workspace: the 8-bit size without pj; with pj the 8-bit size plus, for
+ *                D % 32 == 0, the 256-byte-aligned fp32 copy (B*N*H*D floats).
+ *   any other width: -1 / MXA_ERR_ARG before any HIP call.
+ * There are no timed variants at 4 bits.
+ */
+int64_t mxa_qkv_attention_bits_workspace_bytes(const mxa_attn_params* p, const mxa_qkv_params* x, int32_t elem_bits);
+int mxa_qkv_attention_bits(const mxa_attn_params* p, const mxa_qkv_params* x, int32_t elem_bits, hipStream_t stream);
+int64_t mxa_attention_proj_bits_workspace_bytes(const mxa_attn_params* p, const mxa_qkv_params* xq,
+                                                const mxa_proj_params* pj, int32_t elem_bits);
+int mxa_attention_proj_bits(const mxa_attn_params* p, const mxa_qkv_params* xq, const mxa_proj_params* pj,
+                            int32_t elem_bits, hipStream_t stream);
+int64_t mxa_cross_attention_bits_workspace_bytes(const mxa_attn_params* p, const mxa_cross_params* xc,
+                                                 const mxa_proj_params* pj, int32_t elem_bits);
+int mxa_cross_attention_bits(const mxa_attn_params* p, const mxa_cross_params* xc, const mxa_proj_params* pj,
+                             int32_t elem_bits, hipStream_t stream);
 
 /*
  * mx.matmul forward (microxscaling/mx/matmul.py:31-100, :211-222): in1 (batch, M, K)

@@ -131,6 +131,13 @@ _SIGS = {
     # AttnParams, CrossParams, ProjParams (or None) by reference[, stream]
     "mxa_cross_attention_workspace_bytes": (c_i64, [c_vp, c_vp, c_vp]),
     "mxa_cross_attention": (c_i32, [c_vp, c_vp, c_vp, c_vp]),
+    # the three fused blocks at a stated width: the params by reference (or None), elem_bits[, stream]
+    "mxa_qkv_attention_bits_workspace_bytes": (c_i64, [c_vp, c_vp, c_i32]),
+    "mxa_qkv_attention_bits": (c_i32, [c_vp, c_vp, c_i32, c_vp]),
+    "mxa_attention_proj_bits_workspace_bytes": (c_i64, [c_vp, c_vp, c_vp, c_i32]),
+    "mxa_attention_proj_bits": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp]),
+    "mxa_cross_attention_bits_workspace_bytes": (c_i64, [c_vp, c_vp, c_vp, c_i32]),
+    "mxa_cross_attention_bits": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp]),
     "mxa_matmul": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32,
                            c_i32, c_i32, c_i32, c_vp, c_i64, c_vp]),
     "mxa_matmul_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i32]),

@@ -28,6 +28,7 @@ UNITS += [("mxa_fin16.hip", "_x0w4", ("MXA_F16_W4=1",)), ("mxa_fin16.hip", "_l0w
 # the long rows' selection kernel: the dispatcher and one score mode each (MXA_SELL_PART)
 UNITS += [("mxa_sel_long.hip", "", ("MXA_SELL_PART=0",))] + [("mxa_sel_long.hip", f"_p{i}", (f"MXA_SELL_PART={i}",)) for i in range(1, 7)]
 UNITS += [("mxa_proj.hip", "", ()), ("mxa_gemm.hip", "", ())]
+UNITS += [("mxa_proj4.hip", "", ())]  # the fused projections' MXINT4 kernels
 # the MLP's fc1 (the digit kernel's body with the GELU + quantizing epilogue) in a unit of its own
 UNITS += [("mxa_mlp.hip", "", ())]
 # the MFMA finishing kernel's float32 and float16 / bfloat16 instantiations (MXA_FQ_XDT)
@@ -36,7 +37,7 @@ UNITS += [("mxa_fin_qk.hip", "_x0w4", ("MXA_FQ_W4=1",))]  # ... and its MXINT4-P
 # its tiled sibling for rows of 513 .. 1,024 keys: MXINT8-P and MXINT4-P instantiations (MXA_FQL_W4)
 UNITS += [("mxa_fin_qkl.hip", f"_w{8 - 4 * i}", (f"MXA_FQL_W4={i}",)) for i in range(2)]
 SOURCES = sorted({u[0] for u in UNITS})
-HEADERS = ["mxa_common.hpp", "mxa_kernels.hpp", "mxa_prep.hpp", "mxa_proj.hpp", "mxa_proj_args.hpp", "mxa_gemm_parts.hpp", "mxa_finish.hpp",
+HEADERS = ["mxa_common.hpp", "mxa_kernels.hpp", "mxa_prep.hpp", "mxa_proj.hpp", "mxa_proj_launch.hpp", "mxa_proj_args.hpp", "mxa_gemm_parts.hpp", "mxa_finish.hpp",
            "mxa_order.hpp", "mxa_topk_grp.hpp", "mxa_topk_wave.hpp", "mxa_finish16.hpp", "mxa_finish_qk.hpp", "mxa_finish_qk_long.hpp", "mxa_tail.hpp", "mxa_gemm.hpp", "mxa_dot.hpp", "mxa_select.hpp", "mxa_select_long.hpp", "mxa_rows2.hpp", "mxa_modes.hpp", "mxa_launch.hpp", "mxa_act.hpp", "mxa_mlp.hpp",
            "../../include/mxa.h"]
 ARCH = os.environ.get("MXA_OFFLOAD_ARCH", "gfx950")

@@ -100,10 +100,13 @@ ModeNeeds mode_needs(int mode) {
   return n;
 }
 
-// the proj Linear's input comes MX-quantized out of the finishing kernel
-bool proj_codes_direct(const mxa_attn_params* p) {
-  return p->D % 32 == 0 && p->dtype == MXA_DT_F32 && p->score_dtype <= MXA_DT_F32;
+// the proj Linear's input comes MX-quantized out of the finishing kernel (MXINT8 only: at 4 bits the
+// fp32 rows go through the workspace and the row quantizer for every D)
+bool proj_codes_direct(const mxa_attn_params* p, int elem_bits) {
+  return elem_bits == 8 && p->D % 32 == 0 && p->dtype == MXA_DT_F32 && p->score_dtype <= MXA_DT_F32;
 }
+// a width as a prepared weight's header and flat_rows_prep state it: 0 MXINT8, 4 MXINT4
+int header_bits(int elem_bits) { return elem_bits == 4 ? 4 : 0; }
 
 // How far an entry point reaches, in order: each value takes every call the one before it takes, on the
 // same kernels.  kReachShort: rows of at most 512 keys; kReachLong (the *_long and *_bits entry points):
@@ -124,13 +127,14 @@ struct AttnCall {
   int *plan, *fin;   // plan: only report the kernel path (MXA_PATH_*), launch nothing; fin (with plan): the
                      // finishing kernel (MXA_FIN_*, 0 for the scores alone)
   int elem_bits = 8;  // 8 MXINT8; 4 (the *_bits / *_full entry points) MXINT4 for Q, K, P and V and for the
-                      // codes every approximator is derived from (include/mxa.h mxa_attention_bits)
+                      // codes every approximator is derived from (include/mxa.h mxa_attention_bits); with
+                      // xq / xc / pj (W4A4): for x, cond and the proj's input too, on 4-bit weights
 };
 
 // what finish_choice (mxa_launch.hpp) decides a call's finishing kernel from; p: the call's parameters
 // as the kernels see them (attention_impl's copy)
 FinFacts attn_fin_facts(const AttnCall& c, const mxa_attn_params* p) {
-  return {p->top_k != 0, p->top_k ? p->k_top : 0, p->T, (p->D + 31) / 32, c.pj && proj_codes_direct(p),
+  return {p->top_k != 0, p->top_k ? p->k_top : 0, p->T, (p->D + 31) / 32, c.pj && proj_codes_direct(p, c.elem_bits),
           p->dtype != MXA_DT_F32 || p->score_dtype > MXA_DT_F32, c.elem_bits, c.reach == kReachFull};
 }
 
@@ -199,7 +203,7 @@ AttnLayout attn_layout(const AttnCall& c, const mxa_attn_params* p, int mode, vo
   }
   if (pj) {
     L.y = carve_mx_rows(ws, qtok, p->H * p->D, true);
-    L.yf = ws.take<float>(proj_codes_direct(p) ? 0 : qtok * p->H * p->D);
+    L.yf = ws.take<float>(proj_codes_direct(p, c.elem_bits) ? 0 : qtok * p->H * p->D);
   }
   L.total = ws.off;
   return L;
@@ -239,6 +243,10 @@ int attn_validate(const AttnCall& c) {
   if (p->pred_mode < MXA_PRED_EX_PRED || p->pred_mode > MXA_PRED_ELSA) return MXA_ERR_ARG;
   if (p->dtype < MXA_DT_F32 || p->dtype > MXA_DT_BF16 || p->score_dtype < 0 || p->score_dtype > MXA_DT_BF16)
     return MXA_ERR_ARG;
+  // W4A4 (a fused projection or proj Linear at 4 bits): float32 tensors and scores, no autocast
+  if (elem_bits == 4 && (xq || xc || pj) &&
+      (p->dtype != MXA_DT_F32 || p->score_dtype != 0 || (xq && xq->autocast_dtype != 0)))
+    return MXA_ERR_UNSUPPORTED;
   if (xq && (p->dtype != MXA_DT_F32 || (xq->autocast_dtype != 0 && xq->autocast_dtype != p->score_dtype)))
     return MXA_ERR_ARG;  // the fused projection reads fp32 x; under autocast its scores follow autocast
   if (xc && p->dtype != MXA_DT_F32) return MXA_ERR_ARG;
@@ -250,21 +258,27 @@ int attn_validate(const AttnCall& c) {
     return MXA_ERR_UNSUPPORTED;
   if (!valid_bfloat(p->bfloat)) return MXA_ERR_ARG;
   if (p->T > (reach == kReachShort ? kShortRowsT : kLongRowsT) || p->D > 32 * kMaxNB) return MXA_ERR_UNSUPPORTED;
-  // rows over 512 keys, and MXINT4 (mxa_attention_bits at width 4): float32, no fused projection;
-  // MXINT4: the approximators of exponent_approximation (ELSA's hashes would need the width too)
-  if ((long_rows(p->T) || elem_bits == 4) && (xq || xc || pj || p->dtype != MXA_DT_F32 || p->score_dtype > MXA_DT_F32))
-    return MXA_ERR_UNSUPPORTED;
+  // rows over 512 keys: float32, no fused projection; MXINT4: float32, and the approximators of
+  // exponent_approximation (ELSA's hashes would need the width too)
+  const bool xdt = p->dtype != MXA_DT_F32 || p->score_dtype > MXA_DT_F32;
+  if ((long_rows(p->T) && (xq || xc || pj || xdt)) || (elem_bits == 4 && xdt)) return MXA_ERR_UNSUPPORTED;
   if (elem_bits == 4 && p->approx && p->pred_mode == MXA_PRED_ELSA) return MXA_ERR_UNSUPPORTED;
   // ... and a finishing kernel with an instantiation for them (finish_choice: the 16-row and the MFMA
   // kernels), or the scores alone
   if (!scores_only && finish_choice(attn_fin_facts(c, p)).status) return MXA_ERR_UNSUPPORTED;
   // the prepared weights must have been prepared for this geometry and these settings
-  const int HD = p->H * p->D, fl = p->flush_subnormals, bf = p->bfloat;
-  if (xq && !linear_weight_verify(xq->wq, linear_weight_header(3 * HD, xq->C, p->D, fl, bf), stream)) return MXA_ERR_ARG;
-  if (xc && !(linear_weight_verify(xc->wq_q, linear_weight_header(HD, xc->C, p->D, fl, bf), stream) &&
-              linear_weight_verify(xc->wq_kv, linear_weight_header(2 * HD, xc->C_kv, p->D, fl, bf), stream)))
+  // (every weight of the call at the call's width: an 8-bit call refuses a 4-bit weight and a 4-bit
+  // call an 8-bit one)
+  const int HD = p->H * p->D, fl = p->flush_subnormals, bf = p->bfloat, hb = header_bits(elem_bits);
+  if (xq && !linear_weight_verify(xq->wq, linear_weight_header(3 * HD, xq->C, p->D, fl, bf, hb), stream)) return MXA_ERR_ARG;
+  if (xc && !(linear_weight_verify(xc->wq_q, linear_weight_header(HD, xc->C, p->D, fl, bf, hb), stream) &&
+              linear_weight_verify(xc->wq_kv, linear_weight_header(2 * HD, xc->C_kv, p->D, fl, bf, hb), stream)))
     return MXA_ERR_ARG;
-  if (pj && !linear_weight_verify_any_group(pj->wq, pj->out_features, HD, fl, bf, stream)) return MXA_ERR_ARG;
+  if (pj) {
+    int wb = 0;
+    if (!linear_weight_verify_any_group(pj->wq, pj->out_features, HD, fl, bf, stream, hb ? &wb : nullptr) || wb != hb)
+      return MXA_ERR_ARG;
+  }
   return MXA_OK;
 }
 
@@ -295,18 +309,20 @@ struct ProjTokens {
 // One projection pass (part: ProjPart): x -> MX codes along C (rows_prep) into the workspace,
 // then the projection kernel on the prepared weight, writing the part's q / k operands (rq,
 // rk) and V's transposed codes (cv)
+// (elem_bits 4: the tokens quantized at MXINT4, the weight a 4-bit one -- one digit plane)
 int launch_proj_pass(const mxa_attn_params& pp, int part, const ProjTokens& t, const RowsPrepArgs& rq,
-                     const RowsPrepArgs& rk, const ColsPrepArgs& cv, hipStream_t stream) {
+                     const RowsPrepArgs& rk, const ColsPrepArgs& cv, hipStream_t stream, int elem_bits) {
   const int parts = part == kPartQKV ? 3 : part == kPartKV ? 2 : 1;
   const int nbk = (t.C + 31) / 32, Cpad = 32 * nbk;
   const int64_t tokens = (int64_t)pp.B * t.ntok;
-  const RowsPrepArgs rx = flat_rows_prep(t.x, tokens, t.C, t.row_stride, pp.flush_subnormals, pp.bfloat, t.rows.codes, t.rows.exps, 0);
+  const RowsPrepArgs rx = flat_rows_prep(t.x, tokens, t.C, t.row_stride, pp.flush_subnormals, pp.bfloat, t.rows.codes, t.rows.exps, 0,
+                                         header_bits(elem_bits));
   int rc = launch_rows_prep(rx, stream);
   if (rc) return rc;
-  const LinearLayout W = linear_layout(parts * pp.H * pp.D, t.C, pp.D);
+  const LinearLayout W = linear_layout(parts * pp.H * pp.D, t.C, pp.D, header_bits(elem_bits));
   const unsigned char* wb = static_cast<const unsigned char*>(t.wq);
   ProjArgs pa{};
-  pa.xc = rx.codes; pa.xs = rx.sT;
+  pa.xc = t.rows.codes; pa.xs = t.rows.exps;  // (rx's codes / sT, or at 4 bits its op / sA)
   pa.pk = reinterpret_cast<const int8_t*>(wb + W.pk);
   pa.pe = reinterpret_cast<const int16_t*>(wb + W.pe);
   pa.ps = reinterpret_cast<const int16_t*>(wb + W.ps);
@@ -323,7 +339,7 @@ int launch_proj_pass(const mxa_attn_params& pp, int part, const ProjTokens& t, c
   pa.B = pp.B; pa.N = t.ntok; pa.H = pp.H; pa.D = pp.D; pa.nbk = nbk; pa.Cpad = Cpad; pa.bfloat = pp.bfloat;
   pa.smax = gemm_smax(nbk);
   pa.rq = rq; pa.rk = rk; pa.cv = cv;
-  return launch_proj(pa, stream, part);
+  return elem_bits == 4 ? launch_proj4(pa, stream, part) : launch_proj(pa, stream, part);
 }
 
 // Q's and K's operands and V's transposed codes: from q, k, v in one launch (scores alone: Q
@@ -342,15 +358,15 @@ int attn_build_operands(const AttnCall& c, const mxa_attn_params& pp, const Attn
   if (c.xq) {
     const mxa_qkv_params& xq = *c.xq;
     return launch_proj_pass(pp, kPartQKV, {xq.x, xq.x_row_stride, xq.C, pp.N, xq.wq, xq.bias, xq.qkv_out, xq.autocast_dtype, L.x},
-                            rq, rk, cv, c.stream);
+                            rq, rk, cv, c.stream, bits);
   }
   if (c.xc) {
     const mxa_cross_params& xc = *c.xc;
     const int rc = launch_proj_pass(pp, kPartQ, {xc.x, xc.x_row_stride, xc.C, pp.N, xc.wq_q, xc.bias_q, xc.q_out, 0, L.x}, rq,
-                                    rk, cv, c.stream);
+                                    rk, cv, c.stream, bits);
     if (rc) return rc;
     return launch_proj_pass(pp, kPartKV, {xc.cond, xc.cond_row_stride, xc.C_kv, pp.T, xc.wq_kv, xc.bias_kv, xc.kv_out, 0, L.c},
-                            rq, rk, cv, c.stream);
+                            rq, rk, cv, c.stream, bits);
   }
   if (c.scores_only) {
     const int rc = launch_rows_prep(rq, c.stream);
@@ -408,12 +424,14 @@ int rows2_bind(Rows2Args& r2, const mxa_attn_params& pp, const AttnLayout& L, co
 // the proj Linear on the attention's output rows (quantized first unless the finishing
 // kernel wrote the codes)
 int attn_proj_linear(const mxa_attn_params& pp, const AttnLayout& L, const mxa_proj_params& pj, bool direct,
-                     hipStream_t stream) {
+                     hipStream_t stream, int elem_bits) {
   const int C = pp.H * pp.D;
   const int64_t tokens = (int64_t)pp.B * pp.N;
   if (!direct) {
     const int rc =
-        launch_rows_prep(flat_rows_prep(L.yf, tokens, C, C, pp.flush_subnormals, pp.bfloat, L.y.codes, L.y.exps, 1), stream);
+        launch_rows_prep(flat_rows_prep(L.yf, tokens, C, C, pp.flush_subnormals, pp.bfloat, L.y.codes, L.y.exps, 1,
+                                        header_bits(elem_bits)),
+                         stream);
     if (rc) return rc;
   }
   return launch_linear_codes(L.y.codes, L.y.exps, tokens, C, pj.wq, pj.out_features, pj.bias, pj.y, pj.y_row_stride,
@@ -481,7 +499,7 @@ int attention_impl(const AttnCall& c) {
   }
   mark(5);
   if (c.pj) {
-    rc = attn_proj_linear(pp, L, *c.pj, direct, c.stream);
+    rc = attn_proj_linear(pp, L, *c.pj, direct, c.stream, c.elem_bits);
     if (rc) return rc;
     mark(6);
   }
@@ -614,6 +632,46 @@ extern "C" int mxa_cross_attention(const mxa_attn_params* p, const mxa_cross_par
                                    hipStream_t stream) {
   if (!xc) return MXA_ERR_ARG;
   return attention_impl({.p = p, .stream = stream, .xc = xc, .pj = pj});
+}
+
+// The fused blocks at a stated width.  8: the siblings above, call for call.  4 (W4A4): every weight a
+// 4-bit one, x / cond and the proj's input quantized at MXINT4, the attention mxa_attention_bits(p, 4)'s
+// on rows of at most 512 keys
+extern "C" int64_t mxa_qkv_attention_bits_workspace_bytes(const mxa_attn_params* p, const mxa_qkv_params* xq,
+                                                          int32_t elem_bits) {
+  if (!mx_width_ok(elem_bits) || !attn_shape_ok(p) || !xq || xq->C <= 0) return -1;
+  return attn_workspace_total({.p = p, .xq = xq, .elem_bits = elem_bits});
+}
+
+extern "C" int mxa_qkv_attention_bits(const mxa_attn_params* p, const mxa_qkv_params* xq, int32_t elem_bits,
+                                      hipStream_t stream) {
+  if (!xq) return MXA_ERR_ARG;
+  return attention_impl({.p = p, .stream = stream, .xq = xq, .elem_bits = elem_bits});
+}
+
+extern "C" int64_t mxa_attention_proj_bits_workspace_bytes(const mxa_attn_params* p, const mxa_qkv_params* xq,
+                                                           const mxa_proj_params* pj, int32_t elem_bits) {
+  if (!mx_width_ok(elem_bits) || !attn_shape_ok(p) || !pj || pj->out_features <= 0 || (xq && xq->C <= 0)) return -1;
+  return attn_workspace_total({.p = p, .xq = xq, .pj = pj, .elem_bits = elem_bits});
+}
+
+extern "C" int mxa_attention_proj_bits(const mxa_attn_params* p, const mxa_qkv_params* xq, const mxa_proj_params* pj,
+                                       int32_t elem_bits, hipStream_t stream) {
+  if (!pj) return MXA_ERR_ARG;
+  return attention_impl({.p = p, .stream = stream, .xq = xq, .pj = pj, .elem_bits = elem_bits});
+}
+
+extern "C" int64_t mxa_cross_attention_bits_workspace_bytes(const mxa_attn_params* p, const mxa_cross_params* xc,
+                                                            const mxa_proj_params* pj, int32_t elem_bits) {
+  if (!mx_width_ok(elem_bits) || !attn_shape_ok(p) || !xc || xc->C <= 0 || xc->C_kv <= 0 || (pj && pj->out_features <= 0))
+    return -1;
+  return attn_workspace_total({.p = p, .xc = xc, .pj = pj, .elem_bits = elem_bits});
+}
+
+extern "C" int mxa_cross_attention_bits(const mxa_attn_params* p, const mxa_cross_params* xc, const mxa_proj_params* pj,
+                                        int32_t elem_bits, hipStream_t stream) {
+  if (!xc) return MXA_ERR_ARG;
+  return attention_impl({.p = p, .stream = stream, .xc = xc, .pj = pj, .elem_bits = elem_bits});
 }
 
 extern "C" int mxa_attention_path(const mxa_attn_params* p) {

@@ -272,6 +272,8 @@ int launch_rows(const Rows2Args& ra, const FinFacts& f, bool true_mode, int S, i
 // fused projection kernel (mxa_proj.hip): part 0 the self-attention q, k, v of one token
 // matrix, 1 / 2 cross-attention's q and k, v passes (mxa_proj.hpp ProjPart)
 int launch_proj(const ProjArgs& pa, hipStream_t stream, int part = 0);
+// ... at MXINT4 (mxa_proj4.hip): pa.xc / pa.xs MXINT4 rows, the weight a 4-bit one (pd one plane)
+int launch_proj4(const ProjArgs& pa, hipStream_t stream, int part);
 // does the prepared weight at wq carry this header?  Buffers prepared in this process
 // are looked up host-side; others have their header read once (not under stream capture)
 // (elem_bits: the header's field -- 0 an MXINT8 weight, 4 an MXINT4 one; the attention entry

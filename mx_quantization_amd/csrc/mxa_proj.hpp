@@ -38,7 +38,8 @@ struct ProjLds {
 // parts = 3) at columns 0, 32 NBD, 64 NBD (padding columns beyond D take the padded MFMA
 // columns, so every lane stores unpredicated; the odd stride keeps V's column reads
 // conflict-free; compile-time, so the epilogue's 16 stores take immediate offsets)
-__host__ __device__ inline ProjLds proj_lds(int Cpad, int nbk, int D, int parts = 3) {
+// (bits 4, the MXINT4 kernels: a folded code is one digit, so there is no second tile)
+__host__ __device__ inline ProjLds proj_lds(int Cpad, int nbk, int D, int parts = 3, int bits = 8) {
   ProjLds L;
   auto al = [](size_t x) { return (x + 15) & ~(size_t)15; };
   size_t o = 0;
@@ -46,7 +47,7 @@ __host__ __device__ inline ProjLds proj_lds(int Cpad, int nbk, int D, int parts 
   L.xt = o;
   o += (size_t)32 * L.xst;
   L.xh = o;
-  o += (size_t)32 * L.xst;
+  if (bits != 4) o += (size_t)32 * L.xst;
   L.xe = o;
   o += al((size_t)nbk * 32 * 2);
   L.rlo = o;
@@ -83,15 +84,24 @@ struct ProjParts {
 // rounding code (a third of the code and registers of the general instantiation).
 // Per head: the exponent-folded digits, the shifted int32 block sums, or (wide spreads, a
 // subnormal result) fp64 block sums, all in this workgroup.
-template <int NBD, bool PLAIN, int PART = kPartQKV>
+// MB: the element width of x, the weight and the operands written.  4 (qkv_proj4_kernel,
+// cross_proj4_kernel; general rounding only): MXINT4 codes in [-7, 7], exponents of a code unit
+// es - 2.  A code times 2^s is one signed int8 for s <= kDigit4Spread (fold_digit16), so the digit
+// path has one x tile, the weight's one digit plane, one MFMA per K-block into one accumulator
+// (digit4_k_loop) and the sum scaled by 2^(lo + wlo) rounded once -- mx_gemm_dig4_kernel's rule;
+// the shifted int32 and fp64 sums work on the codes as at 8 bits; the operands are those of
+// attn_prep4_kernel (rows_prep_block_plain4 / rows_prep_block<4>, cols_prep_column at mbits 4).
+template <int NBD, bool PLAIN, int PART = kPartQKV, int MB = 8>
 __device__ __forceinline__ void proj_block(const ProjArgs& a, int tb, int b, int h_begin, int h_end,
                                            unsigned char* smem) {
   constexpr int kParts = ProjParts<PART>::kParts;
   constexpr int kThreads = 64 * kParts * NBD;
   constexpr int kOst = 32 * kParts * NBD + 1;  // == proj_lds(...).ost
+  static_assert(MB == 8 || (MB == 4 && !PLAIN), "MXINT8, or MXINT4 with the general rounding");
+  constexpr int kSpread = MB == 4 ? kDigit4Spread : kDigitSpread;  // the digit gate's
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int D = a.D, HD = a.H * D, nbk = a.nbk;
-  const ProjLds L = proj_lds(a.Cpad, nbk, D, kParts);
+  const ProjLds L = proj_lds(a.Cpad, nbk, D, kParts, MB);
   int8_t* xt = reinterpret_cast<int8_t*>(smem + L.xt);
   int16_t* xe = reinterpret_cast<int16_t*>(smem + L.xe);
   int* rlo = reinterpret_cast<int*>(smem + L.rlo);
@@ -179,15 +189,17 @@ __device__ __forceinline__ void proj_block(const ProjArgs& a, int tb, int b, int
     if (lane == 0) {
       st[0] = (int)smx;
       st[1] = (int)bmn - (1 << 20);
-      st[2] = smx <= kDigitSpread && gmx <= kDigitSpread;
+      st[2] = smx <= kSpread && gmx <= kSpread;
     }
   }
   __syncthreads();
   const bool dig = st[2];  // uniform over the workgroup
-  int8_t* xh = reinterpret_cast<int8_t*>(smem + L.xh);
+  int8_t* xh = reinterpret_cast<int8_t*>(smem + L.xh);  // (MB 4: no such tile, never touched)
   auto put_code = [&](int i, const uint4& v) {
     const int m = i / cpr, c = i - m * cpr;
-    if (dig) {
+    if constexpr (MB == 4) {
+      *reinterpret_cast<uint4*>(xt + m * L.xst + 16 * c) = dig ? fold_digit16(v, xe[(c >> 1) * 32 + m]) : v;
+    } else if (dig) {
       uint4 d0, d1;
       fold_digits16(v, xe[(c >> 1) * 32 + m], d0, d1);
       *reinterpret_cast<uint4*>(xt + m * L.xst + 16 * c) = d0;
@@ -369,13 +381,24 @@ __device__ __forceinline__ void proj_block(const ProjArgs& a, int tb, int b, int
     // weight's (pd), sum = c0 + 2^8 c1 + 2^16 c2 rounded once (digits_to_f32)
     auto run_dig = [&]() {
       const auto drs = __builtin_amdgcn_make_buffer_rsrc(const_cast<int8_t*>(a.pd), 0, a.pd_bytes, 0x00020000);
-      const int dsoff = __builtin_amdgcn_readfirstlane((int)(blkc * nbk) * 2048);
-      const DigitSums d = digit_k_loop(
-          [&](int kb, int p) {
-            return __builtin_bit_cast(v4i_, __builtin_amdgcn_raw_buffer_load_b128(drs, woff, dsoff + kb * 2048 + p * 1024, 0));
-          },
-          xa, xh + ln * L.xst + kh, 32, nbk);
-      store_tile([&](int i, int lo) { return digits_to_f32(d.c0[i], d.c1[i], d.c2[i], lo + wlo); }, a.pn[pc] != 0);
+      if constexpr (MB == 4) {  // one plane [blkc][kb][lane][16 B], one accumulator, one rounding
+        const int dsoff = __builtin_amdgcn_readfirstlane((int)(blkc * nbk) * 1024);
+        const v16i c = digit4_k_loop(
+            [&](int kb) {
+              return __builtin_bit_cast(v4i_, __builtin_amdgcn_raw_buffer_load_b128(drs, woff, dsoff + kb * 1024, 0));
+            },
+            xa, 32, nbk);
+        store_tile([&](int i, int lo) { return (float)ldexp((double)c[i], lo + wlo); }, a.pn[pc] != 0);
+      } else {
+        const int dsoff = __builtin_amdgcn_readfirstlane((int)(blkc * nbk) * 2048);
+        const DigitSums d = digit_k_loop(
+            [&](int kb, int p) {
+              return __builtin_bit_cast(v4i_,
+                                        __builtin_amdgcn_raw_buffer_load_b128(drs, woff, dsoff + kb * 2048 + p * 1024, 0));
+            },
+            xa, xh + ln * L.xst + kh, 32, nbk);
+        store_tile([&](int i, int lo) { return digits_to_f32(d.c0[i], d.c1[i], d.c2[i], lo + wlo); }, a.pn[pc] != 0);
+      }
     };
     // the fp64 block sums for a head whose spreads allow neither the digits nor the shifted
     // int32 sums (rare): one K-block at a time, ascending (exact while the scaled blocks span
@@ -386,12 +409,13 @@ __device__ __forceinline__ void proj_block(const ProjArgs& a, int tb, int b, int
       for (int i = 0; i < 16; ++i) acc[i] = 0.0;
       const v16i zero = {};
       // (a digit tile -- its subnormal test failed -- holds code * 2^xe as two base-256 digits:
-      // the block's sum c0 + 256 c1 is then the shifted sum, scaled by the row's base exponent)
+      // the block's sum c0 + 256 c1 is then the shifted sum, scaled by the row's base exponent;
+      // MB 4: the one folded plane's sum already is)
       const int8_t* xha = reinterpret_cast<int8_t*>(smem + L.xh) + ln * L.xst + kh;
       for (int kb = 0; kb < nbk; ++kb) {
         const v4i_ w = __builtin_bit_cast(v4i_, __builtin_amdgcn_raw_buffer_load_b128(wrs, woff, wsoff + kb * 1024, 0));
         v16i c = __builtin_amdgcn_mfma_i32_32x32x32_i8(*reinterpret_cast<const v4i_*>(xa + 32 * kb), w, zero, 0, 0, 0);
-        if (dig) {
+        if (MB == 8 && dig) {
           const v16i ch = __builtin_amdgcn_mfma_i32_32x32x32_i8(*reinterpret_cast<const v4i_*>(xha + 32 * kb), w, zero, 0, 0, 0);
 #pragma unroll
           for (int i = 0; i < 16; ++i) c[i] += ch[i] << 8;
@@ -444,6 +468,9 @@ __device__ __forceinline__ void proj_block(const ProjArgs& a, int tb, int b, int
       const RowsPrepArgs& ra = (PART == kPartKV || sk) ? a.rk : a.rq;
       if constexpr (PLAIN) {
         rows_prep_block_plain<kF32>(ra, hrow0 + m, blk, sub, c0, xv, m < rows);
+      } else if constexpr (MB == 4) {
+        if (rows_prep_plain4(ra)) rows_prep_block_plain4(ra, hrow0 + m, blk, sub, c0, xv, m < rows);
+        else rows_prep_block<4>(ra, hrow0 + m, blk, sub, c0, xv, m < rows);
       } else {
         if (rows_prep_plain(ra)) rows_prep_block_plain(ra, hrow0 + m, blk, sub, c0, xv, m < rows);
         else rows_prep_block(ra, hrow0 + m, blk, sub, c0, xv, m < rows);
@@ -482,6 +509,22 @@ cross_proj_kernel(ProjArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   proj_block<NBD, PLAIN, PART>(a, blockIdx.x, blockIdx.y, (int)blockIdx.z * a.hpg,
                                min(a.H, ((int)blockIdx.z + 1) * a.hpg), smem);
+}
+
+// MXINT4 (W4A4): x, the weight and the operands at 4 bits, the general rounding (proj_block's MB 4)
+template <int NBD>
+__global__ __launch_bounds__(64 * 3 * NBD) __attribute__((amdgpu_waves_per_eu(4, 8))) void qkv_proj4_kernel(ProjArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  proj_block<NBD, false, kPartQKV, 4>(a, blockIdx.x, blockIdx.y, (int)blockIdx.z * a.hpg,
+                                      min(a.H, ((int)blockIdx.z + 1) * a.hpg), smem);
+}
+
+template <int NBD, int PART>
+__global__ __launch_bounds__(64 * ProjParts<PART>::kParts * NBD) __attribute__((amdgpu_waves_per_eu(4, 8))) void
+cross_proj4_kernel(ProjArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  proj_block<NBD, false, PART, 4>(a, blockIdx.x, blockIdx.y, (int)blockIdx.z * a.hpg,
+                                  min(a.H, ((int)blockIdx.z + 1) * a.hpg), smem);
 }
 
 }  // namespace mxa

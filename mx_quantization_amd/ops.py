@@ -555,9 +555,18 @@ def mx_mlp(x: torch.Tensor, w1, b1: Optional[torch.Tensor], w2, b2: Optional[tor
     return y
 
 
-def _proj_params(proj_weight, proj_bias, C: int, rows: int, flush_subnormals: bool, bfloat: int, dev):
+def _fused_entry(name: str, bits: int):
+    """(size function, entry point, its name, trailing arguments) of the fused block `name` at a width:
+    8 the entry point itself (today's call), 4 its *_bits form with the width behind the structs."""
+    if bits == 8:
+        return getattr(lib(), name + "_workspace_bytes"), getattr(lib(), name), name, ()
+    return getattr(lib(), name + "_bits_workspace_bytes"), getattr(lib(), name + "_bits"), name + "_bits", (bits,)
+
+
+def _proj_params(proj_weight, proj_bias, C: int, rows: int, flush_subnormals: bool, bfloat: int, dev,
+                 elem_bits: int = 8):
     """(ProjParams, y (rows, out_features), keep) for the proj Linear behind the attention."""
-    wp = _prepared(proj_weight, None, flush_subnormals, bfloat)
+    wp = _prepared(proj_weight, None, flush_subnormals, bfloat, elem_bits)
     if wp.in_features != C:
         raise ValueError(f"proj weight takes {wp.in_features} features, the attention gives H*D = {C}")
     pj = N.ProjParams()
@@ -573,18 +582,21 @@ def _proj_params(proj_weight, proj_bias, C: int, rows: int, flush_subnormals: bo
 def mx_topk_attention_proj(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: float, proj_weight,
                            proj_bias: Optional[torch.Tensor] = None, k_top: int = 20, pred_mode: str = "ex_pred",
                            approx: bool = True, bias: Optional[torch.Tensor] = None, flush_subnormals: bool = False,
-                           bfloat: int = 0, elsa_proj: Optional[torch.Tensor] = None):
+                           bfloat: int = 0, elsa_proj: Optional[torch.Tensor] = None, elem_bits: int = 8):
     """The top-k attention core with the proj mx.Linear fused behind it (include/mxa.h
     mxa_attention_proj): y = proj(out.transpose(1, 2).reshape(B, N, H*D)) as (B, N, out)
-    float32, plus idx (B,H,N,k).  float32 q, k, v (views fine)."""
+    float32, plus idx (B,H,N,k).  float32 q, k, v (views fine).
+    elem_bits 4 (W4A4, mxa_attention_proj_bits): the attention of mx_topk_attention(elem_bits=4) and
+    the proj at MXINT4 -- a weight tensor is prepared at 4 bits, a LinearWeightMX must be a 4-bit one."""
+    bits = _elem_bits(elem_bits)
     p, dev, (B, H, Nq, T, D), keep = _attn_params(q, k, v, scale, k_top, pred_mode, True, approx, bias,
                                                   flush_subnormals, bfloat, elsa_proj)
     if p.dtype != N.DT_F32:
         raise TypeError("the fused proj takes float32 q, k, v")
     idx = _new_idx(p, B, H, Nq, k_top, True, dev)
-    pj, y, keep2 = _proj_params(proj_weight, proj_bias, H * D, B * Nq, flush_subnormals, bfloat, dev)
-    _call_with_workspace(lib().mxa_attention_proj_workspace_bytes, lib().mxa_attention_proj, "mxa_attention_proj", p,
-                         None, ctypes.byref(pj), dev=dev)
+    pj, y, keep2 = _proj_params(proj_weight, proj_bias, H * D, B * Nq, flush_subnormals, bfloat, dev, bits)
+    size_fn, fn, name, tail = _fused_entry("mxa_attention_proj", bits)
+    _call_with_workspace(size_fn, fn, name, p, None, ctypes.byref(pj), *tail, dev=dev)
     return y.reshape(B, Nq, -1), idx
 
 
@@ -598,13 +610,19 @@ def mx_qkv_attention(x: torch.Tensor, weight, bias: Optional[torch.Tensor], num_
                      k_top: int = 20, pred_mode: str = "ex_pred", top_k: bool = True, approx: bool = True,
                      flush_subnormals: bool = False, bfloat: int = 0, return_qkv: bool = False,
                      elsa_proj: Optional[torch.Tensor] = None, autocast: Optional[torch.dtype] = None,
-                     proj_weight=None, proj_bias: Optional[torch.Tensor] = None):
+                     proj_weight=None, proj_bias: Optional[torch.Tensor] = None, elem_bits: int = 8):
     """The qkv mx.Linear fused into the attention core (include/mxa.h mxa_qkv_attention):
     x (B, N, C) float32 tokens; weight a (3C', C) tensor or a LinearWeightMX; returns
     (out (B,H,N,D), idx (B,H,N,k) or None[, qkv (B,N,3C') fp32 projection]).
     autocast (float16 / bfloat16): torch.autocast around the module -- the projection's
     product is rounded to it before the fp32 bias add, and the attention's matmuls return
-    it (the output is of that dtype)."""
+    it (the output is of that dtype).
+    elem_bits 4 (W4A4, mxa_qkv_attention_bits / mxa_attention_proj_bits): x, the weights, Q, K, P, V
+    and the proj's input at MXINT4 -- weight tensors are prepared at 4 bits, a LinearWeightMX must be a
+    4-bit one; float32, no autocast."""
+    bits = _elem_bits(elem_bits)
+    if bits == 4 and autocast not in (None, torch.float32):
+        raise ValueError("elem_bits=4 runs in float32: no autocast")
     dev = require_device(x, bias, elsa_proj)
     xs = _token_rows(x, "x", "N")
     B, Ntok, C = x.shape
@@ -612,7 +630,7 @@ def mx_qkv_attention(x: torch.Tensor, weight, bias: Optional[torch.Tensor], num_
     if out_f % (3 * num_heads):
         raise ValueError(f"weight rows {out_f} are not 3 * heads * head_dim")
     D = out_f // (3 * num_heads)
-    wq = _prepared(weight, D, flush_subnormals, bfloat)
+    wq = _prepared(weight, D, flush_subnormals, bfloat, bits)
     _check_fits(wq, "weight", C, D, out_f, f"x C={C}, heads={num_heads}")
     # q / k / v are produced inside the call
     p, keep = _attn_shape_params(dev, torch.float32, B, num_heads, Ntok, Ntok, D, scale, k_top, pred_mode, top_k,
@@ -629,14 +647,14 @@ def mx_qkv_attention(x: torch.Tensor, weight, bias: Optional[torch.Tensor], num_
         # ... then the proj mx.Linear on the attention output (mxa_attention_proj): (y, idx[, qkv])
         if not top_k or autocast not in (None, torch.float32):
             raise ValueError("the fused proj runs on the float32 top-k path")
-        pj, y, keep2 = _proj_params(proj_weight, proj_bias, num_heads * D, B * Ntok, flush_subnormals, bfloat, dev)
+        pj, y, keep2 = _proj_params(proj_weight, proj_bias, num_heads * D, B * Ntok, flush_subnormals, bfloat, dev, bits)
         p.out = None
-        _call_with_workspace(lib().mxa_attention_proj_workspace_bytes, lib().mxa_attention_proj, "mxa_attention_proj", p,
-                             ctypes.byref(xp), ctypes.byref(pj), dev=dev, bad="bad shape")
+        size_fn, fn, name, tail = _fused_entry("mxa_attention_proj", bits)
+        _call_with_workspace(size_fn, fn, name, p, ctypes.byref(xp), ctypes.byref(pj), *tail, dev=dev, bad="bad shape")
         y = y.reshape(B, Ntok, -1)
         return (y, idx, qkv) if return_qkv else (y, idx)
-    _call_with_workspace(lib().mxa_qkv_attention_workspace_bytes, lib().mxa_qkv_attention, "mxa_qkv_attention", p,
-                         ctypes.byref(xp), dev=dev, bad="bad shape")
+    size_fn, fn, name, tail = _fused_entry("mxa_qkv_attention", bits)
+    _call_with_workspace(size_fn, fn, name, p, ctypes.byref(xp), *tail, dev=dev, bad="bad shape")
     return (out, idx, qkv) if return_qkv else (out, idx)
 
 
@@ -654,7 +672,8 @@ def mx_cross_attention(x: torch.Tensor, cond: torch.Tensor, q_weight, q_bias: Op
                        kv_bias: Optional[torch.Tensor], num_heads: int, scale: float, k_top: int = 20,
                        pred_mode: str = "ex_pred", top_k: bool = True, approx: bool = True,
                        bias: Optional[torch.Tensor] = None, flush_subnormals: bool = False, bfloat: int = 0,
-                       return_proj: bool = False, proj_weight=None, proj_bias: Optional[torch.Tensor] = None):
+                       return_proj: bool = False, proj_weight=None, proj_bias: Optional[torch.Tensor] = None,
+                       elem_bits: int = 8):
     """Cross-attention with its q and kv mx.Linears fused in front (include/mxa.h
     mxa_cross_attention; PixArt's MXCrossAttention.forward): x (B, N, C) float32 query tokens,
     cond (B, T, C_kv) float32 key / value tokens; q_weight (H*D, C) and kv_weight
@@ -662,7 +681,10 @@ def mx_cross_attention(x: torch.Tensor, cond: torch.Tensor, q_weight, q_bias: Op
     additive mask, broadcast to (B, H, N, T).  Returns (out (B,H,N,D), idx (B,H,N,k) or None);
     with proj_weight the proj mx.Linear runs behind the attention and y (B, N, out_features)
     takes out's place (top-k only); return_proj appends the fp32 projections q (B, N, H*D) and
-    kv (B, T, 2*H*D).  Float32, no autocast."""
+    kv (B, T, 2*H*D).  Float32, no autocast.
+    elem_bits 4 (W4A4, mxa_cross_attention_bits): x, cond, the weights, Q, K, P, V and the proj's input
+    at MXINT4 -- weight tensors are prepared at 4 bits, a LinearWeightMX must be a 4-bit one."""
+    bits = _elem_bits(elem_bits)
     dev = require_device(x, cond, q_bias, kv_bias, bias)
     xs, cs = _token_rows(x, "x"), _token_rows(cond, "cond")
     B, Ntok, C = x.shape
@@ -673,8 +695,8 @@ def mx_cross_attention(x: torch.Tensor, cond: torch.Tensor, q_weight, q_bias: Op
     if HD % num_heads:
         raise ValueError(f"q weight rows {HD} are not heads * head_dim")
     D = HD // num_heads
-    wq = _prepared(q_weight, D, flush_subnormals, bfloat)
-    wkv = _prepared(kv_weight, D, flush_subnormals, bfloat)
+    wq = _prepared(q_weight, D, flush_subnormals, bfloat, bits)
+    wkv = _prepared(kv_weight, D, flush_subnormals, bfloat, bits)
     _check_fits(wq, "q weight", C, D, HD, f"x C={C}, heads={num_heads}")
     _check_fits(wkv, "kv weight", Ckv, D, 2 * HD, f"cond C_kv={Ckv}, 2 * heads * head_dim = {2 * HD}")
     # q / k / v are produced inside the call
@@ -696,12 +718,13 @@ def mx_cross_attention(x: torch.Tensor, cond: torch.Tensor, q_weight, q_bias: Op
     if proj_weight is not None:
         if not top_k:
             raise ValueError("the fused proj runs on the top-k path")
-        pj, y, keep2 = _proj_params(proj_weight, proj_bias, HD, B * Ntok, flush_subnormals, bfloat, dev)
+        pj, y, keep2 = _proj_params(proj_weight, proj_bias, HD, B * Ntok, flush_subnormals, bfloat, dev, bits)
         res = y.reshape(B, Ntok, -1)
     else:
         res = _bind_out(p, torch.empty((B, num_heads, Ntok, D), dtype=torch.float32, device=dev))
-    _call_with_workspace(lib().mxa_cross_attention_workspace_bytes, lib().mxa_cross_attention, "mxa_cross_attention", p,
-                         ctypes.byref(xc), ctypes.byref(pj) if pj is not None else None, dev=dev, bad="bad shape")
+    size_fn, fn, name, tail = _fused_entry("mxa_cross_attention", bits)
+    _call_with_workspace(size_fn, fn, name, p, ctypes.byref(xc), ctypes.byref(pj) if pj is not None else None, *tail,
+                         dev=dev, bad="bad shape")
     return (res, idx, qo, kvo) if return_proj else (res, idx)
 
 

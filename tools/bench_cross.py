@@ -1,15 +1,21 @@
-"""M.mx_cross_attention (with the proj Linear behind it) against the unfused chain of public
-ops -- M.mx_linear (q), M.mx_linear (kv), M.mx_topk_attention, M.mx_linear (to_out[0]) -- at the
-PixArt-alpha cross-attention block: B = 8, N = 256 image tokens, T = 120 text tokens,
-C = C_kv = 1152, H = 16 (D = 72), k = 20, MXINT4 and ex_pred, flush_subnormals and the mask bias,
-weights prepared once.
+"""A fused PixArt-alpha attention block against the unfused chain of public ops, weights prepared once.
 
-    python tools/bench_cross.py [--steps 20] [--warmup 3] [--reps 3]
+  --block cross (default): M.mx_cross_attention (with the proj Linear behind it) against M.mx_linear
+      (q), M.mx_linear (kv), M.mx_topk_attention, M.mx_linear (to_out[0]) at B = 8, N = 256 image
+      tokens, T = 120 text tokens, C = C_kv = 1152, H = 16 (D = 72), k = 20, the mask bias;
+  --block self: M.mx_qkv_attention (with the proj Linear) against M.mx_linear (qkv),
+      M.mx_topk_attention, M.mx_linear (proj) at the 256 x 256 image: B = 8, N = 256, C = 1152, H = 16,
+      k = 20, no bias.
+MXINT4 and ex_pred approximators, flush_subnormals.  --elem-bits 4: every Linear and the attention at
+MXINT4 (W4A4, the reference's PixArt script; the fused call is the *_bits entry point).  --bfloat: the
+bfloat setting of every op (the script runs 16).  The defaults reproduce the MXINT8 cross run.
+
+    python tools/bench_cross.py [--block cross|self] [--elem-bits 8|4] [--bfloat 0] [--steps 20] [--warmup 3] [--reps 3]
 
 Both chains and both modes are warmed up first; then per mode `reps` repetitions alternate the
 two chains, each timed with device events around `steps` calls.  Prints per mode the median
-and the spread (max - min over the repetitions) of both chains in ms per call, whether idx
-agrees and the normwise relative difference of the two y.  One JSON line per mode."""
+and the spread (max - min over the repetitions) of both chains in ms per call, whether idx and y
+agree bit for bit and the normwise relative difference of the two y.  One JSON line per mode."""
 import argparse
 import json
 import os
@@ -26,12 +32,14 @@ B, N, T, C, CKV, H, K_TOP = 8, 256, 120, 1152, 1152, 16, 20
 MODES = ("MXINT4", "ex_pred")
 
 
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reps", type=int, default=3)
+    ap.add_argument("--block", choices=("cross", "self"), default="cross")
+    ap.add_argument("--elem-bits", type=int, choices=(8, 4), default=8)
+    ap.add_argument("--bfloat", type=int, default=0)
     args = ap.parse_args()
     if args.steps < 20:
         ap.error("--steps must be at least 20")
@@ -43,21 +51,38 @@ def main():
     lin = lambda o, i: ((torch.randn(o, i, generator=g) * i ** -0.5).to(dev), (torch.randn(o, generator=g) * 0.1).to(dev))  # noqa: E731
     (Wq, bq), (Wkv, bkv), (Wo, bo) = lin(C, C), lin(2 * C, CKV), lin(C, C)
     bias = torch.where(torch.arange(T) < T // 2, 0.0, -10000.0).reshape(1, 1, 1, T).repeat(B, 1, 1, 1).to(dev)
-    kw = dict(flush_subnormals=True)
+    kw = dict(flush_subnormals=True, bfloat=args.bfloat)
+    bits = dict(elem_bits=args.elem_bits)
+    prep = lambda W, gw: M.LinearWeightMX(W, gw, **kw, **bits)  # noqa: E731
     # the fused call takes the weights in head groups; mx_linear takes any grouping: one group each
-    wq_f, wkv_f = M.LinearWeightMX(Wq, D, **kw), M.LinearWeightMX(Wkv, D, **kw)
-    wq_u, wkv_u, wo = M.LinearWeightMX(Wq, C, **kw), M.LinearWeightMX(Wkv, 2 * C, **kw), M.LinearWeightMX(Wo, C, **kw)
+    wo = prep(Wo, C)
+    if args.block == "cross":
+        wq_f, wkv_f = prep(Wq, D), prep(Wkv, D)
+        wq_u, wkv_u = prep(Wq, C), prep(Wkv, 2 * C)
 
-    def fused(mode):
-        return M.mx_cross_attention(x, cond, wq_f, bq, wkv_f, bkv, H, scale, k_top=K_TOP, pred_mode=mode, bias=bias,
-                                    proj_weight=wo, proj_bias=bo, **kw)
+        def fused(mode):
+            return M.mx_cross_attention(x, cond, wq_f, bq, wkv_f, bkv, H, scale, k_top=K_TOP, pred_mode=mode, bias=bias,
+                                        proj_weight=wo, proj_bias=bo, **kw, **bits)
 
-    def unfused(mode):
-        q = M.mx_linear(x, wq_u, bq, **kw).view(B, N, H, D).transpose(1, 2)
-        kv = M.mx_linear(cond, wkv_u, bkv, **kw).view(B, T, 2, H, D)
-        k, v = kv[:, :, 0].transpose(1, 2), kv[:, :, 1].transpose(1, 2)
-        out, idx = M.mx_topk_attention(q, k, v, scale, k_top=K_TOP, pred_mode=mode, bias=bias, **kw)
-        return M.mx_linear(out.transpose(1, 2).reshape(B, N, C), wo, bo, **kw), idx
+        def unfused(mode):
+            q = M.mx_linear(x, wq_u, bq, **kw).view(B, N, H, D).transpose(1, 2)
+            kv = M.mx_linear(cond, wkv_u, bkv, **kw).view(B, T, 2, H, D)
+            k, v = kv[:, :, 0].transpose(1, 2), kv[:, :, 1].transpose(1, 2)
+            out, idx = M.mx_topk_attention(q, k, v, scale, k_top=K_TOP, pred_mode=mode, bias=bias, **kw, **bits)
+            return M.mx_linear(out.transpose(1, 2).reshape(B, N, C), wo, bo, **kw), idx
+    else:
+        (Wqkv, bqkv) = lin(3 * C, C)
+        wqkv_f, wqkv_u = prep(Wqkv, D), prep(Wqkv, 3 * C)
+
+        def fused(mode):
+            return M.mx_qkv_attention(x, wqkv_f, bqkv, H, scale, k_top=K_TOP, pred_mode=mode, proj_weight=wo, proj_bias=bo,
+                                      **kw, **bits)
+
+        def unfused(mode):
+            qkv = M.mx_linear(x, wqkv_u, bqkv, **kw).view(B, N, 3, H, D)
+            q, k, v = (qkv[:, :, j].transpose(1, 2) for j in range(3))
+            out, idx = M.mx_topk_attention(q, k, v, scale, k_top=K_TOP, pred_mode=mode, **kw, **bits)
+            return M.mx_linear(out.transpose(1, 2).reshape(B, N, C), wo, bo, **kw), idx
 
     for mode in MODES:  # warm-up of both chains before any timing
         for _ in range(args.warmup):
@@ -71,13 +96,15 @@ def main():
             tu.append(timed(lambda: unfused(mode), args.steps))
         (yf, idf), (yu, idu) = fused(mode), unfused(mode)
         diff = (torch.linalg.norm((yf - yu).double()) / torch.linalg.norm(yu.double())).item()
+        shape = (B, N, T, C, H, K_TOP) if args.block == "cross" else (B, N, N, C, H, K_TOP)
         print(json.dumps({
-            "shape": "pixart_cross", "B_N_T_C_H_k": (B, N, T, C, H, K_TOP), "pred_mode": mode, "steps": args.steps,
-            "reps": args.reps,
+            "shape": f"pixart_{args.block}", "B_N_T_C_H_k": shape, "pred_mode": mode, "elem_bits": args.elem_bits,
+            "bfloat": args.bfloat, "steps": args.steps, "reps": args.reps,
             "fused_ms_median": round(statistics.median(tf), 4), "fused_ms_spread": round(max(tf) - min(tf), 4),
             "unfused_ms_median": round(statistics.median(tu), 4), "unfused_ms_spread": round(max(tu) - min(tu), 4),
             "fused_ms": [round(t, 4) for t in tf], "unfused_ms": [round(t, 4) for t in tu],
-            "idx_equal": bool(torch.equal(idf, idu)), "y_normwise_rel_diff": diff}), flush=True)
+            "idx_equal": bool(torch.equal(idf, idu)), "y_equal": bool(torch.equal(yf, yu)),
+            "y_normwise_rel_diff": diff}), flush=True)
 
 
 if __name__ == "__main__":
