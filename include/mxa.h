@@ -183,9 +183,17 @@ typedef struct mxa_attn_params {
   int32_t flush_subnormals;/* mx_specs["mx_flush_fp32_subnorms"]                           */
   int32_t bfloat;          /* mx_specs["bfloat"]: 0/32 none, 16 bfloat16                   */
   const void* bias;        /* additive score bias (PixArt mask), dtype `dtype`, nullable   */
-  int64_t bias_strides[4]; /* (b,h,n,t) element strides, 0 = broadcast                     */
+  int64_t bias_strides[4]; /* (b,h,n,t) strides in elements of `dtype`, 0 = broadcast: any
+                              non-negative values (the t stride too: a transposed or
+                              every-second-element view is read in place); no alignment
+                              beyond the element's is required                             */
   void* out;               /* (B,H,N,D) output, dtype: score_dtype ? score_dtype : dtype   */
-  int64_t out_strides[3];
+  int64_t out_strides[3];  /* (b,h,n) strides in elements of out's dtype, the D axis
+                              contiguous: any non-negative values that keep the B*H*N rows
+                              apart ((B,N,H*D): {N*H*D, D, H*D}); no alignment beyond the
+                              element's.  The kernels store exactly the D elements of each
+                              row and nothing else; that out holds them is the caller's to
+                              check (M.mx_topk_attention checks shape, dtype and device)   */
   int64_t* idx_out;        /* (B,H,N,k_top) contiguous int64, nullable                     */
   float* true_out;         /* optional (B,H,N,T) contiguous true scores (tests)            */
   float* pred_out;         /* optional (B,H,N,T) contiguous approximate scores            */
@@ -204,7 +212,14 @@ typedef struct mxa_attn_params {
                               torch.autocast -- the fp32 q, k, v operands' matmuls return that
                               dtype, P = zeros_like(true scores) is of it and is quantized by its
                               rules (deit main.py:101, :118, :147; engine.py:97).  true_out /
-                              pred_out hold those dtype values as float32.                  */
+                              pred_out hold those dtype values as float32.
+                              With a bias (float32, as q is): `true_scores += bias` is in
+                              place, true = score_dtype(true + bias); `pred = pred + bias` is
+                              out of place and torch promotes it, pred = fl32(score_dtype(aQ
+                              aK^T) + bias) with no second rounding: the ranking, and
+                              pred_out, are of float32 values (MX_transformer_block.py:
+                              821-822).  With 16-bit q, k, v and bias both sums stay in
+                              `dtype`.                                                      */
 } mxa_attn_params;
 
 int64_t mxa_attention_workspace_bytes(const mxa_attn_params* p);
@@ -358,7 +373,8 @@ int mxa_attention_timed(const mxa_attn_params* p, hipStream_t stream, int32_t it
  * inside a stream capture: call once before capturing.
  *
  * mxa_qkv_attention: mxa_attention with q, k, v produced from x (p->q, p->k, p->v are
- * ignored; self-attention, p->N == p->T).  The projection is exact-then-rounded (the
+ * ignored; self-attention, p->N == p->T; p->bias is the additive score bias, float32, as in
+ * mxa_attention -- M.mx_qkv_attention's attn_bias).  The projection is exact-then-rounded (the
  * reference's fp32 GEMM order is unpinned: equal within fp32 rounding).
  */
 typedef struct mxa_qkv_params {

@@ -273,10 +273,14 @@ __device__ __forceinline__ void sel_scores(const Rows2Args& a, const SelTabs& t,
   const int64_t grow = (int64_t)bh * a.N + r;
   const int64_t brow = a.bias ? b_ * a.bs0 + h_ * a.bs1 + (int64_t)r * a.bs2 : -1;
   // scores in the score dtype: the approximator GEMM's (or the true matmul's) output
-  // rounded to it, then + bias (MX_transformer_block.py:821-822), rounded again
+  // rounded to it, then + bias (MX_transformer_block.py:821-822): `true_scores += bias` in place,
+  // rounded again to the score dtype; `pred = pred + bias` out of place, which torch promotes to
+  // float32 for a float32 bias (a 16-bit autocast pred: no second rounding, the ranking is of
+  // float32 values; a float32 score dtype rounds to itself either way)
+  const int sum_dt = MODE != kModeTrue && a.in_dt == kF32 ? (int)kF32 : a.s_dt;
   auto emit = [&](int j, float v) {
     v = round_dt(v, a.s_dt);
-    if (brow >= 0) v = round_dt(v + load_dt(a.bias, brow + (int64_t)j * a.bs3, a.in_dt), a.s_dt);
+    if (brow >= 0) v = round_dt(v + load_dt(a.bias, brow + (int64_t)j * a.bs3, a.in_dt), sum_dt);
     if (MODE == kModeTrue) {
       if (a.true_out) a.true_out[grow * T + j] = v;
     } else if (a.pred_out) {

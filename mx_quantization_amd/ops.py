@@ -380,7 +380,10 @@ def mx_topk_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: 
     the tensors' dtype as the reference's do).  autocast: the torch.autocast dtype the
     reference's matmuls would return (scores, P and out in it).  Returns (out (B,H,N,D),
     idx (B,H,N,k_top) int64 or None[, true, pred][, mask words (B,H,N,ceil(T/32))]);
-    true / pred are float32 tensors holding the score-dtype values.
+    true / pred are float32 tensors holding the score-dtype values (pred under autocast with a bias:
+    the float32 sums, include/mxa.h score_dtype).  bias: q's dtype, anything that broadcasts to
+    (B,H,N,T), read through its strides.  out: the caller's (B,H,N,D) tensor or view of the output
+    dtype on q's device, last axis contiguous (a view of a (B,N,H*D) buffer is fine); it is returned.
     elem_bits: 8, or 4 -- Q, K, P and V as MXINT4 and every approximator from the MXINT4 codes
     (the reference at a_elem_format = w_elem_format = "int4"; include/mxa.h mxa_attention_bits:
     float32, no autocast, no ELSA -- the library refuses those).
@@ -392,11 +395,15 @@ def mx_topk_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: 
     odt = _out_dtype(q, autocast)
     if out is None:
         out = torch.empty((B, H, Nq, D), dtype=odt, device=dev)
-    elif out.dtype != odt:
-        raise TypeError(f"out must be {odt} (got {out.dtype})")
+    else:  # the caller's buffer: the kernels store (B, H, N, D) elements through its strides, unchecked
+        require_device(q, out)
+        if tuple(out.shape) != (B, H, Nq, D):
+            raise ValueError(f"out must be {(B, H, Nq, D)} (got {tuple(out.shape)})")
+        if out.dtype != odt:
+            raise TypeError(f"out must be {odt} (got {out.dtype})")
+        if out.stride(3) != 1:
+            raise ValueError("out must be contiguous in its last axis")
     _bind_out(p, out)
-    if out.stride(3) != 1:
-        raise ValueError("out must be contiguous in its last axis")
     idx = _new_idx(p, B, H, Nq, k_top, top_k, dev)
     mask = None
     if return_mask:
@@ -421,7 +428,8 @@ def mx_approx_scores(q: torch.Tensor, k: torch.Tensor, pred_mode: str = "ex_pred
     """pred = aQ @ aK^T (+ bias) of the approximator `pred_mode` (or ELSA's
     approximation_scores), (B,H,N,T) in the score dtype -- include/mxa.h mxa_approx_scores_bits,
     which takes every call mxa_approx_scores and _long take.  elem_bits 4: the approximators of the
-    MXINT4 Q and K."""
+    MXINT4 Q and K.  Float32 q, k under a 16-bit autocast with a bias: float32, as torch promotes the
+    reference's `pred + bias`."""
     bits = _elem_bits(elem_bits)
     p, dev, (B, H, Nq, T, D), keep = _attn_params(q, k, None, 1.0, 0, pred_mode, False, True, bias,
                                                   flush_subnormals, bfloat, elsa_proj, autocast)
@@ -430,7 +438,9 @@ def mx_approx_scores(q: torch.Tensor, k: torch.Tensor, pred_mode: str = "ex_pred
     _call_with_workspace(lib().mxa_attention_bits_workspace_bytes, lib().mxa_approx_scores_bits, "mxa_approx_scores_bits",
                          p, bits, dev=dev, bad=None)
     odt = _out_dtype(q, autocast)
-    return pred if odt == torch.float32 else pred.to(odt)  # the values are exact in odt
+    if odt == torch.float32 or (bias is not None and q.dtype == torch.float32):
+        return pred  # (a 16-bit autocast pred + the float32 bias: torch's promotion, include/mxa.h score_dtype)
+    return pred.to(odt)  # the values are exact in odt
 
 
 class LinearWeightMX:
@@ -610,10 +620,13 @@ def mx_qkv_attention(x: torch.Tensor, weight, bias: Optional[torch.Tensor], num_
                      k_top: int = 20, pred_mode: str = "ex_pred", top_k: bool = True, approx: bool = True,
                      flush_subnormals: bool = False, bfloat: int = 0, return_qkv: bool = False,
                      elsa_proj: Optional[torch.Tensor] = None, autocast: Optional[torch.dtype] = None,
-                     proj_weight=None, proj_bias: Optional[torch.Tensor] = None, elem_bits: int = 8):
+                     proj_weight=None, proj_bias: Optional[torch.Tensor] = None, elem_bits: int = 8,
+                     attn_bias: Optional[torch.Tensor] = None):
     """The qkv mx.Linear fused into the attention core (include/mxa.h mxa_qkv_attention):
     x (B, N, C) float32 tokens; weight a (3C', C) tensor or a LinearWeightMX; returns
     (out (B,H,N,D), idx (B,H,N,k) or None[, qkv (B,N,3C') fp32 projection]).
+    bias is the Linear's; attn_bias the additive score bias, float32, broadcast to (B, H, N, N) as
+    mx_topk_attention's.
     autocast (float16 / bfloat16): torch.autocast around the module -- the projection's
     product is rounded to it before the fp32 bias add, and the attention's matmuls return
     it (the output is of that dtype).
@@ -623,7 +636,7 @@ def mx_qkv_attention(x: torch.Tensor, weight, bias: Optional[torch.Tensor], num_
     bits = _elem_bits(elem_bits)
     if bits == 4 and autocast not in (None, torch.float32):
         raise ValueError("elem_bits=4 runs in float32: no autocast")
-    dev = require_device(x, bias, elsa_proj)
+    dev = require_device(x, bias, elsa_proj, attn_bias)
     xs = _token_rows(x, "x", "N")
     B, Ntok, C = x.shape
     out_f = weight.out_features if isinstance(weight, LinearWeightMX) else weight.shape[0]
@@ -634,7 +647,7 @@ def mx_qkv_attention(x: torch.Tensor, weight, bias: Optional[torch.Tensor], num_
     _check_fits(wq, "weight", C, D, out_f, f"x C={C}, heads={num_heads}")
     # q / k / v are produced inside the call
     p, keep = _attn_shape_params(dev, torch.float32, B, num_heads, Ntok, Ntok, D, scale, k_top, pred_mode, top_k,
-                                 approx and top_k, None, flush_subnormals, bfloat, elsa_proj, autocast)
+                                 approx and top_k, attn_bias, flush_subnormals, bfloat, elsa_proj, autocast)
     out = _bind_out(p, torch.empty((B, num_heads, Ntok, D), dtype=_out_dtype(x, autocast), device=dev))
     idx = _new_idx(p, B, num_heads, Ntok, k_top, top_k, dev)
     xp = N.QkvParams()

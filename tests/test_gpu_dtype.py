@@ -1,5 +1,6 @@
 """GPU parity of the float16 / bfloat16 inputs and of torch.autocast, against vectors the
-reference itself produced (tests/golden/gen_golden.py gen_dtype -> attn_dtype.npz).
+reference itself produced (tests/golden/gen_golden.py gen_dtype -> attn_dtype.npz; with a score
+bias tests/golden/gen_dtype_bias_golden.py -> attn_dtype_bias*.npz, at the end of the file).
 
 The reference's ops follow their input's dtype (microxscaling/mx/mx_ops.py:85, :283;
 elemwise_ops.py:146): shared exponents are floor(log2) computed in the dtype, a float16
@@ -18,8 +19,9 @@ import numpy as np
 import pytest
 import torch
 
+import bias_cases as BC
 import gpu_support
-from gpu_support import TDT, G, M, from_bits, out_close, same, same_bits, to_f32  # noqa: F401
+from gpu_support import TDT, G, M, from_bits, out_close, same, same_bits, to_bits, to_f32  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 TOL = {"f16": 1e-3, "bf16": 8e-3}
@@ -156,3 +158,78 @@ def test_elsa_rejects_bias(M):
     with pytest.raises(ValueError, match="ELSA"):
         M.mx_approx_scores(q, q, "ELSA", bias=torch.zeros(64, 64, device="cuda"),
                            elsa_proj=torch.eye(64, device="cuda"))
+
+
+# ---- a score bias on 16-bit tensors and under autocast (gen_dtype_bias_golden.py) ---------------------------
+# The reference's glue has `true_scores += bias` (in place: the sum stays in the scores' dtype) and
+# `pred = pred + bias` (out of place: torch promotes a 16-bit autocast pred plus a float32 bias to float32).
+# Inputs are stored once as float16 patterns; the bfloat16 tensors are their .to(bfloat16), the autocast
+# case's float32 q, k, v their .float().
+BIAS_SHAPES = {"g16": BC.G16, "mfma": BC.MFMA, "g32": BC.G32}
+
+
+@pytest.fixture(scope="module")
+def DB():
+    files = [np.load(os.path.join(G, f"attn_dtype_bias{s}.npz")) for s in ("", "_g32", "_ac")]
+    return {name: f[name] for f in files for name in f.files}
+
+
+def _bias_inputs(DB, tag, dt):
+    return tuple(from_bits(DB[f"{tag}/{n}"], "f16").to(TDT[dt]) for n in ("q", "k", "v", "bias"))
+
+
+@pytest.mark.parametrize("dt,tag,mode", [(dt, tag, mode) for dt in ("f16", "bf16")
+                                         for tag, mode in (("g16", "ex_pred"), ("g16", "MXINT4"), ("mfma", "ex_pred"), ("g32", "ex_pred"))
+                                         if (dt, tag) != ("bf16", "g32")])
+def test_attention_dtype_bias(M, DB, dt, tag, mode):
+    """float16 / bfloat16 q, k, v and a real-valued (H, N, T) bias of the same dtype: the bias loads of the
+    selection kernel and of the 16-bit (XDT) finishing kernels -- GATHER16, MFMA, GATHER32"""
+    c = BIAS_SHAPES[tag]
+    q, k, v, bias = _bias_inputs(DB, tag, dt)
+    assert bias.shape == (c.H, c.N, c.T) and bias.dtype == TDT[dt]
+    out, idx, true_s, pred_s = M.mx_topk_attention(q, k, v, c.D ** -0.5, k_top=c.k, pred_mode=mode, bias=bias, return_scores=True)
+    assert out.dtype == TDT[dt]
+    pre = f"{dt}/{tag}/{mode}"
+    if tag == "g16":
+        same_bits(host(true_s), to_f32(DB[f"{dt}/g16/true"], dt), pre + " true")
+        same_bits(host(pred_s), to_f32(DB[f"{pre}/pred"], dt), pre + " pred")
+        pred = M.mx_approx_scores(q, k, mode, bias=bias)
+        assert pred.dtype == TDT[dt]
+        same_bits(to_bits(pred), DB[f"{pre}/pred"], pre + " mx_approx_scores", dt=dt, patterns=True)
+    same(host(idx), DB[f"{pre}/idx"].astype(np.int64), pre + " idx")
+    out_close(host(out), to_f32(DB[f"{pre}/out"], dt), TOL[dt], pre + " out")
+
+
+@pytest.mark.parametrize("dt", ["f16", "bf16"])
+@pytest.mark.parametrize("kind", ["dense_mfma", "dense_rows"])
+def test_attention_dtype_bias_dense(M, DB, dt, kind):
+    """the dense branch: DENSE_MFMA on the first two heads of the GATHER16 tensors, DENSE_ROWS on GATHER32's"""
+    q, k, v, bias = _bias_inputs(DB, "g16" if kind == "dense_mfma" else "g32", dt)
+    if kind == "dense_mfma":
+        q, k, v, bias = q[:, :2], k[:, :2], v[:, :2], bias[:2]
+    out, _ = M.mx_topk_attention(q, k, v, q.shape[-1] ** -0.5, top_k=False, bias=bias)
+    out_close(host(out), to_f32(DB[f"{dt}/{kind}/out"], dt), TOL[dt], f"{dt} {kind}")
+
+
+@pytest.mark.parametrize("dt", ["f16", "bf16"])
+@pytest.mark.parametrize("btag", ["real", "mask"])
+def test_attention_autocast_bias(M, DB, dt, btag):
+    """fp32 q / k / v and a float32 bias under torch.autocast: true = dtype(true + bias), pred the float32
+    sum of the dtype's pred and the bias (tests/test_bias_cases_cpu.py: re-rounded, it ranks differently)"""
+    c = BC.G16
+    q, k, v = (t.float() for t in _bias_inputs(DB, "g16", "f16")[:3])
+    bias = torch.from_numpy(DB[f"{btag}/bias"]).cuda()
+    assert bias.dtype == torch.float32 and bias.shape == ((c.B, c.H, c.N, c.T) if btag == "real" else (c.B, 1, 1, c.T))
+    pre = f"{dt}/{btag}"
+    kw = dict(bias=bias, autocast=TDT[dt])
+    out, idx, true_s, pred_s = M.mx_topk_attention(q, k, v, c.D ** -0.5, k_top=c.k, pred_mode="ex_pred", return_scores=True, **kw)
+    assert out.dtype == TDT[dt] and DB[f"{pre}/pred"].dtype == np.float32
+    same_bits(host(true_s), to_f32(DB[f"{pre}/true"], dt), pre + " true")
+    same_bits(host(pred_s), DB[f"{pre}/pred"], pre + " pred")
+    same(host(idx), DB[f"{pre}/idx"].astype(np.int64), pre + " idx")
+    out_close(host(out), to_f32(DB[f"{pre}/out"], dt), TOL[dt], pre + " out")
+    pred = M.mx_approx_scores(q, k, "ex_pred", **kw)
+    assert pred.dtype == torch.float32
+    same_bits(host(pred), DB[f"{pre}/pred"], pre + " mx_approx_scores")
+    dense, _ = M.mx_topk_attention(q, k, v, c.D ** -0.5, top_k=False, **kw)
+    out_close(host(dense), to_f32(DB[f"{pre}/dense/out"], dt), TOL[dt], pre + " dense out")
