@@ -346,10 +346,23 @@ int mxa_attention_finish_kernel(const mxa_attn_params* p);
  * Measurement entry point (bench.py): runs mxa_attention `iters` times on `stream`
  * recording HIP events between the kernels, synchronizes the stream, and writes
  * the mean milliseconds of each stage to stage_ms[MXA_ATTN_STAGES]:
- *   0 the operand builders (Q, K rows and V columns, one launch; for mxa_qkv_attention_timed
- *   the x quantization + projection)  1, 2 empty  3 scores+top-k (on MXA_PATH_ROWS_FUSED: 0)
+ *   0 the operand builders (for mxa_qkv_attention_timed the x quantization + projection).  A
+ *   call that forks (below): slot 0 then covers the critical builder only -- Q's and K's rows --
+ *   and V's columns are built on the library's stream during slot 3
+ *   1, 2 empty  3 scores+top-k, to the join (on MXA_PATH_ROWS_FUSED: 0)
  *   4 gather+softmax+P+P.V (on MXA_PATH_ROWS_FUSED: the dense row kernel)
  * Host-synchronizing: not for use inside graph capture.
+ *
+ * Streams.  Every entry point enqueues on `stream` and the caller sees one ordered stream: what
+ * was enqueued on it before the call happens before the call's first read or write, and what is
+ * enqueued after the call sees all of its results.  Inside, a top-k call of mxa_attention and its
+ * _long / _bits / _full siblings on q, k, v whose selection runs the one-lane tail (T <= 256, no
+ * bias, an approximator whose scores pack, k_top + 2 <= 48) builds V's table, which only its
+ * finishing kernel reads, on one stream of the library's own per device, created on the first
+ * such call and kept: forked behind the selection kernel, beside the tail, and joined before the
+ * finishing kernel, both with events.  It therefore reads v and writes the workspace from that
+ * stream too, between those two points.  While `stream` is capturing a graph
+ * (hipStreamIsCapturing) the call keeps everything on `stream`.
  */
 #define MXA_ATTN_STAGES 5
 #define MXA_ATTN_STAGES_PLUS1 6

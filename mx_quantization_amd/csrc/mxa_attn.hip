@@ -27,6 +27,7 @@
 
 #include <algorithm>
 #include <cstdlib>
+#include <mutex>
 #include <vector>
 
 namespace mxa {
@@ -342,11 +343,93 @@ int launch_proj_pass(const mxa_attn_params& pp, int part, const ProjTokens& t, c
   return elem_bits == 4 ? launch_proj4(pa, stream, part) : launch_proj(pa, stream, part);
 }
 
+// ---- the fork: finish-only operands beside the tail ("The side lane") ----
+// A call on q, k, v whose packed selection hands its rows to the one-lane tail is five dependent
+// kernels, and the tail (LDS-bound at three waves per SIMD) leaves registers, wave slots and the whole
+// memory system idle.  What only the finishing kernel reads is therefore built on a stream of the
+// library's own, behind the packed selection pass and beside the tail, and joined before the finishing
+// kernel; the caller still sees one ordered stream.  Beside select_kernel itself the same launch only
+// takes its issue slots (measured), so a call without a tail does not fork.
+// What moves: V's columns.  Measured and left where they were (§8): the codes and sT of Q and K (a
+// second pass over Q and K, longer than the tail) and the 64-bit selection pass (launch_select_packed).
+constexpr int kSideDevices = 64;
+
+// One device's lane: created on the first forked call there and kept for the process
+struct SideState {
+  int state;  // 0 untried, 1 usable, -1 the runtime gave none (calls keep the single-stream order)
+  hipStream_t stream;
+  hipEvent_t packed, join;
+};
+
+// One call's use of the lane.  The lane and its events are one per device, so forked calls hold a
+// process-wide lock from their fork to their join's enqueue (host time only); the streams order the rest.
+//   lane():    what launch_select forks with: it records `packed` behind the packed pass on the caller's
+//              stream and makes the lane wait for it -- so the lane is also behind the call's critical
+//              builder and behind the previous call's finishing kernel, which still reads the tables
+//              the side launches overwrite
+//   forked():  launch_select did; the lane now holds work to join
+//   join():    the caller's stream waits for the lane (the destructor does, on an error path too)
+class SideFork {
+ public:
+  SideFork(hipStream_t caller, bool wanted) : caller_(caller) {
+    if (!wanted) return;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(caller, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) {
+      (void)hipGetLastError();
+      return;  // under capture: today's single-stream order
+    }
+    static std::mutex mu;
+    lock_ = std::unique_lock<std::mutex>(mu);
+    s_ = lane(caller);
+    if (!s_) lock_.unlock();
+  }
+  ~SideFork() { (void)join(); }
+  SideFork(const SideFork&) = delete;
+  SideFork& operator=(const SideFork&) = delete;
+  bool on() const { return s_ != nullptr; }
+  hipStream_t stream() const { return s_->stream; }
+  SideLane lane() const { return {s_->stream, s_->packed}; }
+  void forked() { forked_ = true; }
+  int join() {
+    if (!forked_) return MXA_OK;
+    forked_ = false;
+    const bool ok = hipEventRecord(s_->join, s_->stream) == hipSuccess && hipStreamWaitEvent(caller_, s_->join, 0) == hipSuccess;
+    return ok ? MXA_OK : MXA_ERR_LAUNCH;
+  }
+
+ private:
+  // the lane of the caller's device, which must be the current one (the lane is created on it)
+  static SideState* lane(hipStream_t caller) {
+    static SideState lanes[kSideDevices] = {};
+    int dev = -1;
+    hipDevice_t sdev = -1;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kSideDevices ||
+        (caller && (hipStreamGetDevice(caller, &sdev) != hipSuccess || (int)sdev != dev))) {
+      (void)hipGetLastError();
+      return nullptr;
+    }
+    SideState& s = lanes[dev];
+    if (s.state == 0) {
+      const bool ok = hipStreamCreateWithFlags(&s.stream, hipStreamNonBlocking) == hipSuccess &&
+                      hipEventCreateWithFlags(&s.packed, hipEventDisableTiming) == hipSuccess &&
+                      hipEventCreateWithFlags(&s.join, hipEventDisableTiming) == hipSuccess;
+      s.state = ok ? 1 : -1;
+      if (!ok) (void)hipGetLastError();
+    }
+    return s.state == 1 ? &s : nullptr;
+  }
+  hipStream_t caller_;
+  SideState* s_ = nullptr;
+  bool forked_ = false;
+  std::unique_lock<std::mutex> lock_;
+};
+
 // Q's and K's operands and V's transposed codes: from q, k, v in one launch (scores alone: Q
 // and K), or out of the fused projections -- qkv in one pass; cross-attention's query tokens
 // -> the q operands, then its key / value tokens -> the k operands and V (two launches of
-// the projection kernel by parts)
-int attn_build_operands(const AttnCall& c, const mxa_attn_params& pp, const AttnLayout& L, int opq, int opk) {
+// the projection kernel by parts).  side (a forked call on q, k, v): Q's and K's rows are launched
+// here and V's builder is left in *side for the lane (launch_cols_prep)
+int attn_build_operands(const AttnCall& c, const mxa_attn_params& pp, const AttnLayout& L, int opq, int opk, ColsPrepArgs* side) {
   const int bits = c.elem_bits;
   const RowsPrepArgs rq = attn_rows_prep(pp, L, L.q, pp.q, pp.q_strides, pp.N, opq, bits);
   const RowsPrepArgs rk = attn_rows_prep(pp, L, L.k, pp.k, pp.k_strides, pp.T, opk, bits);
@@ -372,7 +455,11 @@ int attn_build_operands(const AttnCall& c, const mxa_attn_params& pp, const Attn
     const int rc = launch_rows_prep(rq, c.stream);
     return rc ? rc : launch_rows_prep(rk, c.stream);
   }
-  return launch_attn_prep(rq, rk, cv, c.stream);  // Q, K and V in one launch
+  if (!side) return launch_attn_prep(rq, rk, cv, c.stream);  // Q, K and V in one launch
+  *side = cv;
+  ColsPrepArgs none = cv;
+  none.mats = 0;
+  return launch_attn_prep(rq, rk, none, c.stream);
 }
 
 // ELSA: hashes of MX(Q), MX(K); norms of MX(K) rows
@@ -469,8 +556,8 @@ int attention_impl(const AttnCall& c) {
   Rows2Args r2 = rows2_shape(pp, L);
   // feasibility of the path's kernels (LDS budgets), before any pointer is bound
   // (rows over 512 keys: the one-wave-per-row selection kernel, mxa_select_long.hpp)
-  auto select = [&](bool plan) {
-    return long_rows(pp.T) ? launch_select_long(r2, mode, BH, c.stream, plan) : launch_select(r2, mode, BH, c.stream, plan);
+  auto select = [&](bool plan, const SideLane* side = nullptr) {
+    return long_rows(pp.T) ? launch_select_long(r2, mode, BH, c.stream, plan) : launch_select(r2, mode, BH, c.stream, plan, side);
   };
   rc = c.scores_only ? MXA_OK : launch_rows(r2, ff, mode == kModeTrue, S, BH, c.stream, true);
   if (!rc && ranked) rc = select(true);
@@ -485,12 +572,26 @@ int attention_impl(const AttnCall& c) {
 
   auto mark = [&c](int slot) { if (c.ev) (void)hipEventRecord(c.ev[slot], c.stream); };  // a stage's start
   mark(0);
-  rc = attn_build_operands(c, pp, L, opq, opk);
+  // forked: q, k, v given and the packed selection with its tail to run beside (launch_select_packed's
+  // tail branch, which forks the lane it is given)
+  SideFork fork(c.stream, topk && !c.xq && !c.xc && !long_rows(pp.T) && L.fbf &&
+                              sel_tail_width(mode, pp.T, pp.k_top, pp.bias != nullptr) == kTailPref);
+  ColsPrepArgs side{};
+  rc = attn_build_operands(c, pp, L, opq, opk, fork.on() ? &side : nullptr);
   if (!rc && mode == kModeElsa) rc = attn_elsa_prep(pp, L, c.stream);
   if (rc) return rc;
   mark(1), mark(2), mark(3);  // stages 1 and 2 are empty: the operand builders run as stage 0
   rc = rows2_bind(r2, pp, L, c.pj, direct);
-  if (!rc && ranked) rc = select(false);
+  if (!rc && ranked) {
+    const SideLane lane = fork.on() ? fork.lane() : SideLane{};
+    rc = select(false, fork.on() ? &lane : nullptr);
+  }
+  if (fork.on()) {
+    fork.forked();  // (joined after an error too)
+    if (!rc) rc = launch_cols_prep(side, fork.stream());
+    const int rj = fork.join();  // the finishing kernel reads what the lane built
+    if (!rc) rc = rj;
+  }
   if (rc) return rc;
   mark(4);
   if (!c.scores_only) {

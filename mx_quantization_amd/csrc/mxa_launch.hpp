@@ -77,8 +77,15 @@ inline RowsPrepArgs flat_rows_prep(const void* x, int64_t rows, int cols, int64_
 // from the workspace instead of staging the head's K table (mxa_finish16.hpp)
 constexpr int kShortRowsT = 512, kLongRowsT = 1024;
 inline bool long_rows(int T) { return T > kShortRowsT; }
+// The side lane of a forked attention call (mxa_attn.hip, SideFork): the library's own stream beside the
+// caller's, joined before the finishing kernel.  `packed`: the event launch_select records behind the
+// packed pass
+struct SideLane { hipStream_t stream; hipEvent_t packed; };
 // selection kernel (mxa_sel.hip); plan: only check the LDS budget, launch nothing
-int launch_select(const Rows2Args& ra, int mode, int BH, hipStream_t stream, bool plan);
+// side (nullable; given only where the packed pass runs with its tail, sel_tail_width == kTailPref): the
+// lane is forked behind the packed pass -- it waits for `packed` -- so that the caller's launches on
+// it run beside the tail
+int launch_select(const Rows2Args& ra, int mode, int BH, hipStream_t stream, bool plan, const SideLane* side = nullptr);
 // ... for long rows (mxa_sel_long.hip)
 int launch_select_long(const Rows2Args& ra, int mode, int BH, hipStream_t stream, bool plan);
 // the one-lane tail's prefix (measured, DeiT-base: 48 positions 0.575-0.583 ms against 0.585-0.599
@@ -111,20 +118,20 @@ inline int tail_width_for(int n, int k) {
 inline int sel_tail_width(int mode, int T, int k, bool bias) { return sel_packs(mode, T, bias) ? tail_width_for(T, k) : 0; }
 
 // one score mode per translation unit of mxa_sel.hip (MXA_SEL_PART 1..6)
-int launch_select_p1(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);  // ex_pred
-int launch_select_p2(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);  // EXION
-int launch_select_p3(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);  // MXINT4 / partial
-int launch_select_p4(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);  // true_ex
-int launch_select_p5(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);  // ELSA
-int launch_select_p6(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);  // the true scores
-inline int launch_select_mode(const Rows2Args& ra, int mode, int BH, hipStream_t stream, bool plan) {
+int launch_select_p1(const Rows2Args& ra, int BH, hipStream_t stream, bool plan, const SideLane* side);  // ex_pred
+int launch_select_p2(const Rows2Args& ra, int BH, hipStream_t stream, bool plan, const SideLane* side);  // EXION
+int launch_select_p3(const Rows2Args& ra, int BH, hipStream_t stream, bool plan, const SideLane* side);  // MXINT4 / partial
+int launch_select_p4(const Rows2Args& ra, int BH, hipStream_t stream, bool plan, const SideLane* side);  // true_ex
+int launch_select_p5(const Rows2Args& ra, int BH, hipStream_t stream, bool plan, const SideLane* side);  // ELSA
+int launch_select_p6(const Rows2Args& ra, int BH, hipStream_t stream, bool plan, const SideLane* side);  // the true scores
+inline int launch_select_mode(const Rows2Args& ra, int mode, int BH, hipStream_t stream, bool plan, const SideLane* side) {
   switch (mode) {
-    case kModeExSign: return launch_select_p1(ra, BH, stream, plan);
-    case kModeOpMul: return launch_select_p2(ra, BH, stream, plan);
-    case kModeOpExp: return launch_select_p3(ra, BH, stream, plan);
-    case kModeTrueEx: return launch_select_p4(ra, BH, stream, plan);
-    case kModeElsa: return launch_select_p5(ra, BH, stream, plan);
-    default: return launch_select_p6(ra, BH, stream, plan);
+    case kModeExSign: return launch_select_p1(ra, BH, stream, plan, side);
+    case kModeOpMul: return launch_select_p2(ra, BH, stream, plan, side);
+    case kModeOpExp: return launch_select_p3(ra, BH, stream, plan, side);
+    case kModeTrueEx: return launch_select_p4(ra, BH, stream, plan, side);
+    case kModeElsa: return launch_select_p5(ra, BH, stream, plan, side);
+    default: return launch_select_p6(ra, BH, stream, plan, side);
   }
 }
 // ---- the finishing kernel of a call: the one decision -------------------------------------

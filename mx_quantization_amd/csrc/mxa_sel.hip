@@ -55,14 +55,36 @@ static int launch_tail(const TailArgs& ta0, hipStream_t stream) {
   hipLaunchKernelGGL(topk_tail_kernel<TW>, dim3((unsigned)((ta.rows + per - 1) / per)), dim3(64 * kTailWaves), lds, stream, ta);
   return launch_status();
 }
+// The packed pass (rows of <= 256 keys) for the approximators whose scores are sums of small
+// integers times powers of two, the one-lane tail behind it for small k, and the 64-bit kernel on
+// the rows whose scores do not pack (fb_only: its workgroups without such rows return at once).
+// side (the tail branch): the caller's side lane is forked here, behind the packed pass -- `packed`
+// recorded on the stream, the lane made to wait for it -- so that what the caller launches there runs
+// beside the tail.  The 64-bit pass itself stays behind the tail: it is independent of it (a row is
+// the tail's, first kept index 0 and a pending record, or the 64-bit pass's, first kept index -1),
+// but on the lane beside the tail its few workgroups wait for the LDS the tail's hold (traced: 105 us
+// instead of 6, in front of everything else on the lane).
 template <int NP, int MODE, int W>
-static int launch_select_packed(const Rows2Args& ra, int BH, hipStream_t stream, bool plan) {
+static int launch_select_packed(const Rows2Args& ra, int BH, hipStream_t stream, bool plan, const SideLane* side) {
+  const auto left_pass = [&](hipStream_t s) {
+    Rows2Args fb = ra;
+    fb.fb_only = 1;
+    return launch_select_w<NP, MODE, W>(fb, BH, s, plan);
+  };
   const int tw = sel_tail_width(MODE, ra.T, ra.k_top, ra.bias != nullptr);
-  if (tw != kTailPref) return launch_select_w<NP, MODE, W, uint32_t, 0, 0>(ra, BH, stream, plan);
-  const int rc = launch_select_w<NP, MODE, W, uint32_t, 1, kTailPref>(ra, BH, stream, plan);
-  if (rc != MXA_OK || plan) return rc;
-  return launch_tail<kTailPref>(
-      TailArgs{ra.tail_rec, (int64_t)BH * ra.N, ra.k_top, (ra.T + 31) / 32, ra.idx_out, ra.idx16, ra.mask_out}, stream);
+  if (tw != kTailPref) {
+    const int rc = launch_select_w<NP, MODE, W, uint32_t, 0, 0>(ra, BH, stream, plan);
+    return rc ? rc : left_pass(stream);
+  }
+  int rc = launch_select_w<NP, MODE, W, uint32_t, 1, kTailPref>(ra, BH, stream, plan);
+  if (rc != MXA_OK) return rc;
+  if (plan) return left_pass(stream);
+  const TailArgs ta{ra.tail_rec, (int64_t)BH * ra.N, ra.k_top, (ra.T + 31) / 32, ra.idx_out, ra.idx16, ra.mask_out};
+  if (side && (hipEventRecord(side->packed, stream) != hipSuccess ||
+               hipStreamWaitEvent(side->stream, side->packed, 0) != hipSuccess))
+    return MXA_ERR_LAUNCH;
+  rc = launch_tail<kTailPref>(ta, stream);
+  return rc ? rc : left_pass(stream);
 }
 // f(integral_constant<int, W>) for the workgroup's wave count W = sel_waves_for(...)
 template <typename F>
@@ -70,30 +92,23 @@ static int with_sel_waves(int wsel, F&& f) {
   return wsel == 2 ? f(std::integral_constant<int, 2>{}) : f(std::integral_constant<int, 4>{});
 }
 template <int NP, int MODE>
-static int launch_select_np(const Rows2Args& ra, int BH, hipStream_t stream, bool plan) {
+static int launch_select_np(const Rows2Args& ra, int BH, hipStream_t stream, bool plan, const SideLane* side) {
   return with_sel_waves(sel_waves_for(ra.T, BH, ra.N), [&](auto w_c) {
     constexpr int W = decltype(w_c)::value;
-    // packed elements (rows of <= 256 keys) for the approximators whose scores are sums of
-    // small integers times powers of two (the one-lane tail behind it for small k); then the
-    // 64-bit kernel on the rows whose scores do not pack (fb_only: its workgroups without
-    // such rows return at once).  The true scores, ELSA and longer rows: the 64-bit kernel.
+    // the packed pass and what follows it (launch_select_packed); the true scores, ELSA and
+    // longer rows: the 64-bit kernel
     if constexpr (NP <= 256) {
-      if (sel_packs(MODE, ra.T, ra.bias != nullptr) && ra.k_top > 0 && ra.fb_flags) {
-        const int rc = launch_select_packed<NP, MODE, W>(ra, BH, stream, plan);
-        if (rc != MXA_OK) return rc;
-        Rows2Args fb = ra;
-        fb.fb_only = 1;
-        return launch_select_w<NP, MODE, W>(fb, BH, stream, plan);
-      }
+      if (sel_packs(MODE, ra.T, ra.bias != nullptr) && ra.k_top > 0 && ra.fb_flags)
+        return launch_select_packed<NP, MODE, W>(ra, BH, stream, plan, side);
     }
     return launch_select_w<NP, MODE, W>(ra, BH, stream, plan);
   });
 }
 template <int MODE>
-static int launch_select_m(const Rows2Args& ra, int BH, hipStream_t stream, bool plan) {
-  if (ra.T <= 128) return launch_select_np<128, MODE>(ra, BH, stream, plan);
-  if (ra.T <= 256) return launch_select_np<256, MODE>(ra, BH, stream, plan);
-  return launch_select_np<512, MODE>(ra, BH, stream, plan);
+static int launch_select_m(const Rows2Args& ra, int BH, hipStream_t stream, bool plan, const SideLane* side) {
+  if (ra.T <= 128) return launch_select_np<128, MODE>(ra, BH, stream, plan, side);
+  if (ra.T <= 256) return launch_select_np<256, MODE>(ra, BH, stream, plan, side);
+  return launch_select_np<512, MODE>(ra, BH, stream, plan, side);
 }
 // The selection kernel's instantiations are split over one compilation of this file per
 // score mode (MXA_SEL_PART 1..6; part 0 holds the dispatcher and the standalone top-k:
@@ -102,15 +117,15 @@ static int launch_select_m(const Rows2Args& ra, int BH, hipStream_t stream, bool
 #define MXA_SEL_PART 0
 #endif
 #if MXA_SEL_PART == 0
-int launch_select(const Rows2Args& ra, int mode, int BH, hipStream_t stream, bool plan) {
-  return launch_select_mode(ra, mode, BH, stream, plan);
+int launch_select(const Rows2Args& ra, int mode, int BH, hipStream_t stream, bool plan, const SideLane* side) {
+  return launch_select_mode(ra, mode, BH, stream, plan, side);
 }
 #else
 constexpr int kPartMode[7] = {0, kModeExSign, kModeOpMul, kModeOpExp, kModeTrueEx, kModeElsa, kModeTrue};
 #define MXA_SEL_FN2(i) launch_select_p##i
 #define MXA_SEL_FN(i) MXA_SEL_FN2(i)
-int MXA_SEL_FN(MXA_SEL_PART)(const Rows2Args& ra, int BH, hipStream_t stream, bool plan) {
-  return launch_select_m<kPartMode[MXA_SEL_PART]>(ra, BH, stream, plan);
+int MXA_SEL_FN(MXA_SEL_PART)(const Rows2Args& ra, int BH, hipStream_t stream, bool plan, const SideLane* side) {
+  return launch_select_m<kPartMode[MXA_SEL_PART]>(ra, BH, stream, plan, side);
 }
 #endif
 
