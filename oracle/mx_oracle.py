@@ -322,8 +322,8 @@ def elsa_scores(Q, K, proj, block_size=32, flush=False, bfloat=32):
     return (knorm[..., :, None] * elsa_cos_table(d)[ham]).astype(F32)
 
 
-def approx_operands(Q, K, mode, block_size=32, flush=False, bfloat=32):
-    ea = ExponentApproximation(Q, K, block_size, flush=flush, bfloat=bfloat)
+def approx_operands(Q, K, mode, block_size=32, flush=False, bfloat=32, elem="int8"):
+    ea = ExponentApproximation(Q, K, block_size, elem=elem, flush=flush, bfloat=bfloat)
     fn = {
         "ex_pred": ea.exponent_based_sign,
         "partial_Q": ea.partial_Q,
@@ -447,16 +447,18 @@ def softmax_f32(x, axis=-1):
 # the attention core (caller glue restated)
 # ---------------------------------------------------------------------------
 def attention(q, k, v, scale, k_top=20, pred_mode="ex_pred", top_k=True, approx=True,
-              bias=None, block_size=32, flush=False, bfloat=32, elsa_proj=None):
+              bias=None, block_size=32, flush=False, bfloat=32, elsa_proj=None, elem="int8"):
     """The mx_quant branch of QuantizedAttention.forward (deit main.py:100-152) /
     DiT Attention.forward (models.py:168-225) / MXCrossAttention.forward
     (MX_transformer_block.py:792-859), from q,k,v (…,N,d),(…,T,d) to the
-    pre-projection output (…,N,d).  `bias` broadcasts to (…,N,T) (PixArt mask)."""
+    pre-projection output (…,N,d).  `bias` broadcasts to (…,N,T) (PixArt mask).
+    `elem` is a_elem_format = w_elem_format: both matmuls quantize their operands to it
+    and exponent_approximation builds every approximator from MX_Q / MX_K at it."""
     q = np.asarray(q, F32)
     k = np.asarray(k, F32)
     v = np.asarray(v, F32)
     res = {}
-    true = mx_matmul(q, np.swapaxes(k, -1, -2), block_size=block_size, flush=flush, bfloat=bfloat)
+    true = mx_matmul(q, np.swapaxes(k, -1, -2), elem, block_size, flush=flush, bfloat=bfloat)
     true = (true * F32(scale)).astype(F32)
     if bias is not None:
         bias = np.broadcast_to(np.asarray(bias, F32), true.shape)
@@ -464,12 +466,14 @@ def attention(q, k, v, scale, k_top=20, pred_mode="ex_pred", top_k=True, approx=
     res["true"] = true
     if top_k:
         if approx and pred_mode == "ELSA":
+            if elem != "int8":
+                raise ValueError("ELSA is 8-bit only (the library refuses it at any other width)")
             pred = elsa_scores(q, k, elsa_proj, block_size, flush=flush, bfloat=bfloat)
             res["pred"] = pred
             _, idx = topk(pred, k_top)
             vals = np.take_along_axis(true, idx, axis=-1)
         elif approx:
-            aq, ak = approx_operands(q, k, pred_mode, block_size, flush=flush, bfloat=bfloat)
+            aq, ak = approx_operands(q, k, pred_mode, block_size, flush=flush, bfloat=bfloat, elem=elem)
             pred = exact_matmul_f32(aq, np.swapaxes(ak, -1, -2))
             if bias is not None:
                 pred = (pred + bias).astype(F32)
@@ -485,7 +489,7 @@ def attention(q, k, v, scale, k_top=20, pred_mode="ex_pred", top_k=True, approx=
     else:
         attn = softmax_f32(true)
     res["attn"] = attn
-    res["out"] = mx_matmul(attn, v, block_size=block_size, flush=flush, bfloat=bfloat)
+    res["out"] = mx_matmul(attn, v, elem, block_size, flush=flush, bfloat=bfloat)
     return res
 
 

@@ -1,12 +1,11 @@
-"""What the MXINT4 attention tests share (test_attn4_cpu.py, test_gpu_attn4.py): the oracle's
-attention restated at elem="int4", the exact-result
+"""What the MXINT4 attention tests share (test_attn4_cpu.py, test_gpu_attn4.py): the exact-result
 cases with a V that is its own MXINT4, and the GPU cases with their references (computed once,
 left unchanged).  Nothing here touches the device.
 
 The reference is the caller glue of the PixArt modules (MX_transformer_block.py:648-717,
 :792-859) at a_elem_format = w_elem_format = "int4": matmul(q, k^T) and matmul(attn, v) quantize
 their operands to MXINT4 and exponent_approximation builds every approximator from the MXINT4
-MX_Q / MX_K.  attention4 assembles it from the oracle's pieces, which take the width already."""
+MX_Q / MX_K: O.attention(elem="int4")."""
 import collections
 import functools
 
@@ -19,45 +18,6 @@ from oracle import mx_oracle as O
 
 F32 = np.float32
 MODES = ("ex_pred", "partial_Q", "partial_K", "MXINT4", "two_step_leading_ones", "true_ex")
-
-
-def operands4(q, k, mode, flush=False, bfloat=32):
-    ea = O.ExponentApproximation(q, k, 32, elem="int4", flush=flush, bfloat=bfloat)
-    return {"ex_pred": ea.exponent_based_sign, "partial_Q": ea.partial_Q, "partial_K": ea.partial_K,
-            "MXINT4": ea.MXINT4, "two_step_leading_ones": ea.two_step_leading_ones,
-            "true_ex": ea.exponent_based_sign_leading_ones}[mode]()
-
-
-def attention4(q, k, v, scale, k_top=20, pred_mode="ex_pred", top_k=True, approx=True, bias=None, flush=False,
-               bfloat=32):
-    """O.attention with every MX operand at int4 (same keys in the result)"""
-    q, k, v = (np.asarray(x, F32) for x in (q, k, v))
-    res = {}
-    true = O.mx_matmul(q, np.swapaxes(k, -1, -2), elem="int4", flush=flush, bfloat=bfloat)
-    true = (true * F32(scale)).astype(F32)
-    if bias is not None:
-        bias = np.broadcast_to(np.asarray(bias, F32), true.shape)
-        true = (true + bias).astype(F32)
-    res["true"] = true
-    if top_k:
-        if approx:
-            aq, ak = operands4(q, k, pred_mode, flush, bfloat)
-            pred = O.exact_matmul_f32(aq, np.swapaxes(ak, -1, -2))
-            if bias is not None:
-                pred = (pred + bias).astype(F32)
-            res["aq"], res["ak"], res["pred"] = aq, ak, pred
-            _, idx = O.topk(pred, k_top)
-            vals = np.take_along_axis(true, idx, axis=-1)
-        else:
-            vals, idx = O.topk(true, k_top)
-        res["idx"], res["vals"] = idx, vals
-        attn = np.zeros_like(true)
-        np.put_along_axis(attn, idx, O.softmax_f32(vals), axis=-1)
-    else:
-        attn = O.softmax_f32(true)
-    res["attn"] = attn
-    res["out"] = O.mx_matmul(attn, v, elem="int4", flush=flush, bfloat=bfloat)
-    return res
 
 
 def shares_within_caps(r, v):
@@ -124,7 +84,7 @@ def exact_inputs(c):
 @functools.lru_cache(maxsize=None)
 def exact_reference(c):
     q, k, v, bias = exact_inputs(c)
-    return attention4(q, k, v, EC.SCALE, bias=bias, **EC.oracle_kw(c))
+    return O.attention(q, k, v, EC.SCALE, bias=bias, elem="int4", **EC.oracle_kw(c))
 
 
 # ---- the random GPU cases -----------------------------------------------------------------------
@@ -191,7 +151,7 @@ def r_inputs(c):
 @functools.lru_cache(maxsize=None)
 def r_reference(c):
     q, k, v, bias = r_inputs(c)
-    return attention4(q, k, v, r_scale(c), bias=bias, flush=c.flush, bfloat=c.bfloat, **r_kw(c))
+    return O.attention(q, k, v, r_scale(c), bias=bias, flush=c.flush, bfloat=c.bfloat, elem="int4", **r_kw(c))
 
 
 # ---- special blocks: NaN, +-Inf, all-zero and 2^+-100 blocks in Q, K and V ------------------------
@@ -223,5 +183,5 @@ def special_inputs():
 @functools.lru_cache(maxsize=None)
 def special_reference(mode):
     q, k, v = special_inputs()
-    return attention4(q, k, v, SPECIAL_SCALE, SPECIAL_K, mode)
+    return O.attention(q, k, v, SPECIAL_SCALE, SPECIAL_K, mode, elem="int4")
 

@@ -15,12 +15,10 @@ import functools
 
 import numpy as np
 
-import attn4_cases as A
 import cross_cases as CC
 import exact_out_cases as EC
 import long_dense_cases as LC
-import proj4_cases as P4
-from gpu_support import out_row_bound, r_kw, r_scale  # noqa: F401
+from gpu_support import ELEM, out_row_bound, r_kw, r_scale  # noqa: F401
 from oracle import mx_oracle as O
 
 F32 = np.float32
@@ -91,8 +89,7 @@ def bias_values(c, vs):
 @functools.lru_cache(maxsize=None)
 def reference(c, vs="full"):
     q, k, v, _ = inputs(c)
-    fn = A.attention4 if c.bits == 4 else O.attention
-    return fn(q, k, v, r_scale(c), bias=bias_values(c, vs), **r_kw(c))
+    return O.attention(q, k, v, r_scale(c), bias=bias_values(c, vs), elem=ELEM[c.bits], **r_kw(c))
 
 
 def shares(c, vs):
@@ -108,24 +105,22 @@ def fused_bias(B, H, N, T, vs, seed=3):
 
 @functools.lru_cache(maxsize=None)
 def cross_reference(bits, vs):
-    """mx_cross_attention on cross_cases / proj4_cases "d48": the chain's qh, kh, vh (the oracle's Linears and the
+    """mx_cross_attention on cross_cases "d48": the chain's qh, kh, vh (the oracle's Linears and the
     module's head split) through the oracle's attention at the width, with the bias of a value set.
     Returns (the chain, bias, r)."""
     (B, N, T, C, _, H), k_top = CC.SHAPES["d48"]
-    ch = (P4.chain if bits == 4 else CC.chain)("d48", "ex_pred")
+    ch = CC.chain("d48", "ex_pred", elem=ELEM[bits])
     bias = fused_bias(B, H, N, T, vs)
-    fn = A.attention4 if bits == 4 else O.attention
-    return ch, bias, fn(ch["qh"], ch["kh"], ch["vh"], (C // H) ** -0.5, k_top=k_top, pred_mode="ex_pred", bias=bias)
+    return ch, bias, O.attention(ch["qh"], ch["kh"], ch["vh"], (C // H) ** -0.5, k_top=k_top, pred_mode="ex_pred", bias=bias,
+                                 elem=ELEM[bits])
 
 
 @functools.lru_cache(maxsize=None)
 def self_reference(bits, vs):
-    """mx_qkv_attention on proj4_cases.SELF_SHAPES["d48"]: at 4 bits proj4_cases.self_chain's projections, at 8 the
-    same chain with the oracle's MXINT8 Linear.  Returns (qkv, (qh, kh, vh), bias, r)."""
-    (B, N, C, H), k = P4.SELF_SHAPES["d48"]
-    x, W, b, _, _ = P4.self_case("d48")
-    qkv = P4.lin4(x, W, b) if bits == 4 else O.mx_linear(x, W, b)
-    heads = tuple(np.ascontiguousarray(t) for t in O.qkv_split(qkv, H))
+    """mx_qkv_attention on cross_cases.SELF_SHAPES["d48"]: cross_cases.self_chain's projections at the width.
+    Returns (qkv, (qh, kh, vh), bias, r)."""
+    (B, N, C, H), k = CC.SELF_SHAPES["d48"]
+    ch = CC.self_chain("d48", elem=ELEM[bits])
+    heads = ch["qh"], ch["kh"], ch["vh"]
     bias = fused_bias(B, H, N, N, vs)
-    fn = A.attention4 if bits == 4 else O.attention
-    return qkv, heads, bias, fn(*heads, (C // H) ** -0.5, k_top=k, pred_mode="ex_pred", bias=bias)
+    return ch["qkv"], heads, bias, O.attention(*heads, (C // H) ** -0.5, k_top=k, pred_mode="ex_pred", bias=bias, elem=ELEM[bits])

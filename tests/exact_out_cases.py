@@ -21,6 +21,7 @@ import functools
 
 import numpy as np
 
+from gpu_support import same, same_bits
 from oracle import mx_oracle as O
 
 SCALE = 0.125
@@ -144,3 +145,110 @@ def tied(c, r):
     with np.errstate(invalid="ignore"):
         m = (a == a.max(-1, keepdims=True)).sum(-1)
     return np.where(np.isnan(a).any(-1), 0, m), (c.k or c.T)
+
+
+# ---- the five conditions under which out is the only float32 result ----------
+# Each takes the case, its inputs (q, k, v, bias), the oracle's reference at the width and the width as
+# the oracle's elem; test_exact_out_cpu.py, test_attn4_cpu.py and test_long_dense_cpu.py call them.
+WIDTH = {"int8": (6, 15 * 8), "int4": (2, 7 * 8)}  # es - (a code unit's exponent); the bound on |v|
+
+
+def _bf(c):
+    return dict(c.kw).get("bfloat", 32)
+
+
+def _finite_rows(r):
+    return ~np.isnan(r["attn"]).any(-1)
+
+
+def _mx(a, c, elem, axis):
+    return O.quantize_mx(O.quantize_bfloat(a, _bf(c)), elem, 32, axis)
+
+
+def score_gaps_are_zero_or_wide(c, inputs, r, elem):
+    """1. within every query row two true scores are equal or at least 150 apart: exp of the
+    lower one is exactly 0 in float32, by np.exp and by exp2((v - mx) log2 e), subnormals flushed
+    or not (e^-150 < 2^-216)"""
+    t = np.sort(r["true"].astype(np.float64), axis=-1)
+    fin = np.isfinite(t).all(-1)
+    assert fin.sum() >= fin.size - (c.H if c.bias else 0) and fin.any()
+    gap = np.diff(t[fin], axis=-1)
+    assert ((gap == 0) | (gap >= 150)).all(), gap[(gap != 0) & (gap < 150)][:4]
+    assert (gap >= 150).any(-1).all()  # (no row whose scores all tie)
+    x = np.float32(-150.0)
+    assert np.exp(x) == 0 and np.exp2(np.float32(x * np.float32(1.4426950408889634))) == 0
+
+
+def operands_are_their_own_mx(c, inputs, r, elem):
+    """2. q and k are their own MX along D, v along the tokens, and v holds integers"""
+    q, k, v, _ = inputs
+    same_bits(_mx(q, c, elem, -1)[0], q, "MX(q)")
+    same_bits(_mx(k, c, elem, -1)[0], k, "MX(k)")
+    same_bits(_mx(v, c, elem, -2)[0], v, "MX(v)")
+    assert (v == np.round(v)).all() and np.abs(v).max() <= WIDTH[elem][1]
+
+
+def out_is_the_exact_product(c, inputs, r, elem):
+    """3. out equals the float64 product of the quantized operands, that product is a float32,
+    and the per-element sum of |Pq| |Vq| is below 2^24 granules (a row's granule: the code step
+    2^(e - 6), at int4 2^(e - 2), of its lowest non-zero P block, V being integers): every partial
+    sum in every order is an integer below 2^24 times the granule, so exact in float32"""
+    fin = _finite_rows(r)
+    pq, _, pe = _mx(r["attn"], c, elem, -1)
+    vq = _mx(inputs[2], c, elem, -2)[0]
+    with np.errstate(invalid="ignore"):
+        prod = np.matmul(pq.astype(np.float64), vq.astype(np.float64))
+        S = np.matmul(np.abs(pq).astype(np.float64), np.abs(vq).astype(np.float64))
+    assert (prod[fin] == prod[fin].astype(np.float32)).all()
+    same_bits(r["out"][fin], O.quantize_bfloat(prod[fin].astype(np.float32), _bf(c)), "out vs the exact product")
+    assert np.isnan(r["out"][~fin]).all()
+    blk, _ = O.to_blocks(pq, -1, 32)
+    e = np.where((blk != 0).any(-1), pe[..., 0], np.inf)  # the exponents of the non-zero blocks
+    gran = np.exp2(e.min(-1) - WIDTH[elem][0])[fin]
+    assert np.isfinite(gran).all()
+    assert (pq[fin] / gran[:, None] == np.round(pq[fin] / gran[:, None])).all()
+    worst = (S[fin] / gran[:, None]).max()
+    print(f"{case_id(c)} {elem}: sum |Pq||Vq| reaches 2^{np.log2(max(worst, 1)):.1f} granules")
+    assert worst < 2 ** 24
+
+
+def p_codes_survive_four_ulp(c, inputs, r, elem):
+    """4. every non-zero p moved by 4 ulp either way keeps the MX codes of P (at int4: p = 1/m lies
+    4 ulp inside a cell of the 4-bit grid, floor(p 2^(2 - e) + 1/2) with the clip at 7 -- m = 65,
+    129: y = 7.9 clips from either side).  Rows whose m is a power of two are exempt: p = 1/m is
+    exact there in any implementation, and below it lies the next binade."""
+    m, _ = tied(c, r)
+    rows = (m > 0) & ((m & (m - 1)) != 0)
+    assert rows.any() or c.k == 1
+    a = r["attn"][rows]
+    codes = _mx(a, c, elem, -1)[1]
+    for d in (-4, 4):
+        b = a.copy().view(np.int32)
+        b[a != 0] += d
+        same(_mx(b.view(np.float32), c, elem, -1)[1], codes, f"P codes at {d} ulp")
+
+
+def tie_counts_vary(c, inputs, r, elem):
+    """5. rows with m < k (kept slots of zero weight, P blocks whose codes are all zero) and
+    rows with m >= k; on the dense branch m takes several values; k = 1 has m = 1"""
+    m_all, kept = tied(c, r)
+    m = m_all[m_all > 0]
+    if c.k == 1:
+        assert (m == 1).all()
+    elif c.k:
+        assert (m < kept).any() and (m >= kept).any(), np.unique(m)
+        fin = _finite_rows(r)
+        assert (np.take_along_axis(r["attn"], r["idx"], -1)[fin] == 0).any()  # a kept slot of zero weight
+        if c.T >= 197:  # (a row of three key blocks can have a hot key in each)
+            pq = O.quantize_mx(r["attn"], elem, 32, -1)[0]
+            idx_blocks = np.take_along_axis(O.to_blocks(pq, -1, 32)[0].any(-1), r["idx"] >> 5, -1)
+            assert (~idx_blocks)[fin].any()  # a kept key in a P block whose codes are all zero
+    else:
+        assert len(np.unique(m)) >= 3, np.unique(m)
+    if c.T > 512 and not c.bias:  # the rows won by a hot class: weights on both sides of key 512
+        hot = (r["attn"] > 0) & ((m_all > 0) & (m_all < kept))[..., None]
+        assert hot[..., :512].any() and hot[..., 512:].any()
+
+
+CONDITIONS = (score_gaps_are_zero_or_wide, operands_are_their_own_mx, out_is_the_exact_product, p_codes_survive_four_ulp,
+              tie_counts_vary)

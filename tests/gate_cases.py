@@ -30,7 +30,7 @@ DIGIT_SPREAD = 8     # mxa_proj_args.hpp kDigitSpread
 DIGIT4_SPREAD = 4    # mxa_proj_args.hpp kDigit4Spread
 F32_MIN_NORMAL = np.float32(2.0 ** -126)
 _UNIT = {"int8": 6.0, "int4": 2.0}                       # es - e per format
-_SPREAD = {"int8": DIGIT_SPREAD, "int4": DIGIT4_SPREAD}  # the digit operands' spread limit
+SPREAD = {"int8": DIGIT_SPREAD, "int4": DIGIT4_SPREAD}  # the digit operands' spread limit
 
 
 def unit_exps(A, elem="int8", bfloat=32, flush=False):
@@ -77,7 +77,7 @@ def gemm_gate(x, W, bfloat=32, elem="int8"):
 def on_digits(x, W, bfloat=32, elem="int8"):
     """per 32-row block: does the digit K loop take it?"""
     q, smx, wsp = gemm_gate(x, W, bfloat, elem)
-    return (smx <= _SPREAD[elem]) & (wsp <= _SPREAD[elem]) & ~(q < GATE)
+    return (smx <= SPREAD[elem]) & (wsp <= SPREAD[elem]) & ~(q < GATE)
 
 
 def assert_side(x, W, want, bfloat=32, what="", elem="int8"):

@@ -20,6 +20,7 @@ from oracle import mx_oracle as O
 G = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 OUT_TOL = 1e-3  # the attention output, normwise relative error
 TDT = {"f16": torch.float16, "bf16": torch.bfloat16}
+ELEM = {8: "int8", 4: "int4"}  # the ops' elem_bits -> the oracle's elem
 
 
 @pytest.fixture(scope="module")
@@ -193,7 +194,7 @@ def out_row_bound(r, v, kernel=None, bits=8):
     equal the maximum or lie EXACT_GAP below it has no eligible element: its p are 1/m,
     correctly rounded, on both sides.  At 4 bits a rounding tie at y >= 7 (between the codes 7
     and 8) is no tie: both sides clip to 7."""
-    elem, unit, top = ("int4", 2, 4) if bits == 4 else ("int8", 6, 64)  # the code unit's exponent, the top binade's first code
+    elem, (unit, top) = ELEM[bits], (2, 4) if bits == 4 else (6, 64)  # the code unit's exponent, the top binade's first code
     attn, true = np.asarray(r["attn"], np.float64), np.asarray(r["true"], np.float64)
     T, D = attn.shape[-1], v.shape[-1]
     k = r["idx"].shape[-1] if "idx" in r else 0
@@ -230,8 +231,8 @@ def out_row_bound(r, v, kernel=None, bits=8):
 
 
 def out_rows_close(got, r, v, what, kernel=None, bits=8):
-    """The attention output of a float32 call with bfloat 0 / 32 against the oracle's (bits = 4:
-    attn4_cases.attention4's), row by row: |got - ref| <= A + F elementwise on the finite rows (out_row_bound), the NaN pattern
+    """The attention output of a float32 call with bfloat 0 / 32 against the oracle's at that width
+    (O.attention(elem=ELEM[bits])), row by row: |got - ref| <= A + F elementwise on the finite rows (out_row_bound), the NaN pattern
     equal everywhere.  The eligible shares are asserted first, from the oracle alone.  Prints
     the kernel, the shares and the worst ratio; on failure its row and column."""
     bound, fin, (se, sr), kernel, _ = out_row_bound(r, v, kernel, bits)
@@ -404,7 +405,7 @@ def check_mlp_chain(M, x, W1, b1, W2, b2, act, *, elem_bits=8, cmp, bfloat=0, w1
     the device produced; y without the hidden copies.  w1: fc1's weight as prepared by the
     caller.  Returns y, pre, act on the host."""
     kw = dict(flush_subnormals=flush, bfloat=bfloat, elem_bits=elem_bits)
-    ok = dict(elem=f"int{elem_bits}", flush=flush, bfloat=bfloat or 32)
+    ok = dict(elem=ELEM[elem_bits], flush=flush, bfloat=bfloat or 32)
     y, pre, a = M.mx_mlp(dev(x), dev(W1) if w1 is None else w1, dev_opt(b1), dev(W2), dev_opt(b2), act=act,
                          return_hidden=True, **kw)
     torch.cuda.synchronize()

@@ -11,7 +11,7 @@ import numpy as np
 
 import attn4_cases as A
 import exact_out_cases as EC
-from gpu_support import out_row_bound, r_kw, r_scale  # noqa: F401
+from gpu_support import ELEM, out_row_bound, r_kw, r_scale  # noqa: F401
 from oracle import mx_oracle as O
 
 F32 = np.float32
@@ -95,8 +95,7 @@ def r_inputs(c):
 @functools.lru_cache(maxsize=None)
 def r_reference(c):
     q, k, v, bias = r_inputs(c)
-    fn = A.attention4 if c.bits == 4 else O.attention
-    return fn(q, k, v, r_scale(c), bias=bias, **r_kw(c))
+    return O.attention(q, k, v, r_scale(c), bias=bias, elem=ELEM[c.bits], **r_kw(c))
 
 
 def r_shares(c):

@@ -1,5 +1,5 @@
 """The MXINT4 attention core (mxa_attention_bits and its siblings), the part that needs no GPU:
-attention4 (tests/attn4_cases.py) against the reference's fixture at a_elem_format = "int4", the
+the oracle's attention at elem="int4" against the reference's fixture at a_elem_format = "int4", the
 new entry points' bindings and refusals (host logic that returns before any HIP call), the
 conditions of the exact-result cases at this width, and the eligible-share caps of every case
 test_gpu_attn4.py bounds row by row."""
@@ -46,13 +46,13 @@ def _check(r, g, tag, true_key):
 @pytest.mark.parametrize("mode", A.MODES)
 def test_attention4_vs_reference_self(gold, mode):
     q, k, v, sc = gold["self/q"], gold["self/k"], gold["self/v"], float(gold["self/scale"])
-    _check(A.attention4(q, k, v, sc, 20, mode), gold, f"self/{mode}_k20", "self/true")
+    _check(O.attention(q, k, v, sc, 20, mode, elem="int4"), gold, f"self/{mode}_k20", "self/true")
 
 
 def test_attention4_vs_reference_true_topk_and_dense(gold):
     q, k, v, sc = gold["self/q"], gold["self/k"], gold["self/v"], float(gold["self/scale"])
-    _check(A.attention4(q, k, v, sc, 30, approx=False), gold, "self/trueK_k30", "self/true")
-    _check(A.attention4(q, k, v, sc, top_k=False), gold, "self/dense", "self/true")
+    _check(O.attention(q, k, v, sc, 30, approx=False, elem="int4"), gold, "self/trueK_k30", "self/true")
+    _check(O.attention(q, k, v, sc, top_k=False, elem="int4"), gold, "self/dense", "self/true")
 
 
 @pytest.mark.parametrize("mode", ["ex_pred", "MXINT4"])
@@ -61,9 +61,9 @@ def test_attention4_vs_reference_cross(gold, mode):
     q, k, v, sc = gold["cross/q"], gold["cross/k"], gold["cross/v"], float(gold["cross/scale"])
     bias = gold["cross/bias"][:, None]  # (B, 1, 1, T)
     kw = dict(bias=bias, flush=True, bfloat=16)
-    _check(A.attention4(q, k, v, sc, 20, mode, **kw), gold, f"cross/{mode}_k20", "cross/true")
+    _check(O.attention(q, k, v, sc, 20, mode, elem="int4", **kw), gold, f"cross/{mode}_k20", "cross/true")
     if mode == "ex_pred":
-        _check(A.attention4(q, k, v, sc, top_k=False, **kw), gold, "cross/dense", "cross/true")
+        _check(O.attention(q, k, v, sc, top_k=False, elem="int4", **kw), gold, "cross/dense", "cross/true")
 
 
 def test_int4_operands_differ_from_int8_ones(gold):
@@ -169,88 +169,34 @@ def test_ops_refuse_other_widths():
             M.ops.approx_values(x, "sign", elem_bits=w)
 
 
-# ---- the exact-result cases at 4 bits (the five conditions of test_exact_out_cpu.py) --------------
-def _bf(c):
-    return dict(c.kw).get("bfloat", 32)
-
-
-def _finite_rows(r):
-    return ~np.isnan(r["attn"]).any(-1)
+# ---- the exact-result cases at 4 bits (exact_out_cases.CONDITIONS) --------------
+def _exact4(c):
+    return c, A.exact_inputs(c), A.exact_reference(c), "int4"
 
 
 @pytest.mark.parametrize("c", A.EXACT, ids=EC.case_id)
 def test_exact4_operands_are_their_own_mxint4(c):
-    """q and k are their own MXINT4 along D, v along the tokens (integers |n| <= 7 times 2^e)"""
-    q, k, v, _ = A.exact_inputs(c)
-    same_bits(O.quantize_mx(O.quantize_bfloat(q, _bf(c)), "int4", 32, -1)[0], q, "MX4(q)")
-    same_bits(O.quantize_mx(O.quantize_bfloat(k, _bf(c)), "int4", 32, -1)[0], k, "MX4(k)")
-    same_bits(O.quantize_mx(O.quantize_bfloat(v, _bf(c)), "int4", 32, -2)[0], v, "MX4(v)")
-    assert (v == np.round(v)).all() and np.abs(v).max() <= 7 * 8
+    EC.operands_are_their_own_mx(*_exact4(c))
 
 
 @pytest.mark.parametrize("c", A.EXACT, ids=EC.case_id)
 def test_exact4_score_gaps_are_zero_or_wide(c):
-    r = A.exact_reference(c)
-    t = np.sort(r["true"].astype(np.float64), axis=-1)
-    fin = np.isfinite(t).all(-1)
-    assert fin.sum() >= fin.size - (c.H if c.bias else 0) and fin.any()
-    gap = np.diff(t[fin], axis=-1)
-    assert ((gap == 0) | (gap >= 150)).all(), gap[(gap != 0) & (gap < 150)][:4]
-    assert (gap >= 150).any(-1).all()
+    EC.score_gaps_are_zero_or_wide(*_exact4(c))
 
 
 @pytest.mark.parametrize("c", A.EXACT, ids=EC.case_id)
 def test_exact4_out_is_the_exact_product(c):
-    """out equals the float64 product of the MXINT4 operands, that product is a float32, and the
-    per-element sum of |Pq| |Vq| is below 2^24 granules (the code step 2^(e - 2) of the row's
-    lowest non-zero P block): every partial sum in every order is exact in float32"""
-    (_, _, v, _), r = A.exact_inputs(c), A.exact_reference(c)
-    fin = _finite_rows(r)
-    pq, _, pe = O.quantize_mx(O.quantize_bfloat(r["attn"], _bf(c)), "int4", 32, -1)
-    vq = O.quantize_mx(O.quantize_bfloat(v, _bf(c)), "int4", 32, -2)[0]
-    with np.errstate(invalid="ignore"):
-        prod = np.matmul(pq.astype(np.float64), vq.astype(np.float64))
-        S = np.matmul(np.abs(pq).astype(np.float64), np.abs(vq).astype(np.float64))
-    assert (prod[fin] == prod[fin].astype(np.float32)).all()
-    same_bits(r["out"][fin], O.quantize_bfloat(prod[fin].astype(np.float32), _bf(c)), "out vs the exact product")
-    assert np.isnan(r["out"][~fin]).all()
-    blk, _ = O.to_blocks(pq, -1, 32)
-    e = np.where((blk != 0).any(-1), pe[..., 0], np.inf)
-    gran = np.exp2(e.min(-1) - 2)[fin]
-    assert np.isfinite(gran).all()
-    assert (pq[fin] / gran[:, None] == np.round(pq[fin] / gran[:, None])).all()
-    assert (S[fin] / gran[:, None]).max() < 2 ** 24
+    EC.out_is_the_exact_product(*_exact4(c))
 
 
 @pytest.mark.parametrize("c", A.EXACT, ids=EC.case_id)
 def test_exact4_p_codes_survive_four_ulp(c):
-    """every non-zero p moved by 4 ulp either way keeps the MXINT4 codes of P: p = 1/m lies
-    4 ulp inside a cell of the 4-bit grid, floor(p 2^(2 - e) + 1/2) with the clip at 7 (m = 65,
-    129: y = 7.9 clips from either side).  Rows whose m is a power of two are exempt, as at 8 bits."""
-    r = A.exact_reference(c)
-    m, _ = EC.tied(c, r)
-    rows = (m > 0) & ((m & (m - 1)) != 0)
-    assert rows.any() or c.k == 1
-    a = r["attn"][rows]
-    codes = O.quantize_mx(O.quantize_bfloat(a, _bf(c)), "int4", 32, -1)[1]
-    for d in (-4, 4):
-        b = a.copy().view(np.int32)
-        b[a != 0] += d
-        same(O.quantize_mx(O.quantize_bfloat(b.view(np.float32), _bf(c)), "int4", 32, -1)[1], codes, f"P codes at {d} ulp")
+    EC.p_codes_survive_four_ulp(*_exact4(c))
 
 
 @pytest.mark.parametrize("c", A.EXACT, ids=EC.case_id)
 def test_exact4_tie_counts_vary(c):
-    r = A.exact_reference(c)
-    m_all, kept = EC.tied(c, r)
-    m = m_all[m_all > 0]
-    if c.k == 1:
-        assert (m == 1).all()
-    elif c.k:
-        assert (m < kept).any() and (m >= kept).any(), np.unique(m)
-        assert (np.take_along_axis(r["attn"], r["idx"], -1)[_finite_rows(r)] == 0).any()  # a kept slot of zero weight
-    else:
-        assert len(np.unique(m)) >= 3, np.unique(m)
+    EC.tie_counts_vary(*_exact4(c))
 
 
 def test_exact4_cases_cover_the_kernels():
@@ -282,7 +228,7 @@ def test_fixture_cases_eligible_shares(gold, tag, k):
     q, kk, v, sc = gold["self/q"], gold["self/k"], gold["self/v"], float(gold["self/scale"])
     mode = tag.split("/")[1].rsplit("_k", 1)[0]
     kw = dict(top_k=False) if not k else (dict(k_top=k, approx=False) if mode == "trueK" else dict(k_top=k, pred_mode=mode))
-    assert A.shares_within_caps(A.attention4(q, kk, v, sc, **kw), v)[0]
+    assert A.shares_within_caps(O.attention(q, kk, v, sc, elem="int4", **kw), v)[0]
 
 
 def test_bf16_cases_have_no_eligible_block(gold):
@@ -293,7 +239,7 @@ def test_bf16_cases_have_no_eligible_block(gold):
     assert A.eligible_bf16(A.r_reference(c), A.r_inputs(c)[2], c.flush)[0] == 0
     q, k, v, sc = gold["cross/q"], gold["cross/k"], gold["cross/v"], float(gold["cross/scale"])
     for kw in (dict(k_top=20, pred_mode="ex_pred"), dict(k_top=20, pred_mode="MXINT4"), dict(top_k=False)):
-        r = A.attention4(q, k, v, sc, bias=gold["cross/bias"][:, None], flush=True, bfloat=16, **kw)
+        r = O.attention(q, k, v, sc, bias=gold["cross/bias"][:, None], flush=True, bfloat=16, elem="int4", **kw)
         rows = A.eligible_bf16(r, v, True)[2]
         print(kw, "rows with an eligible block:", int(rows.sum()), "of", rows.size)
         assert rows.mean() <= 0.02, kw

@@ -2,7 +2,11 @@
 M.mx_cross_attention): the symbols, the argument validation that returns before any HIP call,
 the workspace formula, the refusal of CPU tensors -- and, with the oracle alone, that the
 inputs of tests/test_gpu_cross.py sit in the regimes those tests are about
-(tests/cross_cases.py)."""
+(tests/cross_cases.py): the NaN rows at width 8, and at both widths every accumulation path in
+every pass of the spread case and the digit tile behind its subnormal gate.  What exists at
+width 4 only (the *_bits entry points' host logic, the eligible-share caps) is in
+tests/test_proj4_cpu.py."""
+import collections
 import ctypes
 
 import numpy as np
@@ -11,7 +15,10 @@ import torch
 
 import cross_cases as CC
 import gate_cases as GC
+import gpu_support as GS
 from oracle import mx_oracle as O
+
+BITS = pytest.mark.parametrize("bits", [8, 4])
 
 
 @pytest.fixture(scope="module")
@@ -130,56 +137,78 @@ def test_nan_cond_in_the_oracle():
     """A NaN in one cond row of image 1: its key and value rows are NaN in every head, every
     output row of that image is NaN (the NaN score is the largest, torch.topk keeps it) and
     the other images are finite."""
-    H, x, cond, Wq, Wkv, q, kv, r = CC.nan_cond_case()
+    H, x, cond, Wq, Wkv, q, kv, _, r = CC.nan_cond_case()
     assert np.isnan(kv).any(-1).sum() == 1 and np.isnan(kv[1, 9]).all() and not np.isnan(q).any()
     bad = np.isnan(r["out"]).any(-1)
     assert bad[1].all() and not bad[0].any() and not bad[2].any()
     assert (r["idx"][1] == 9).any(-1).all()
 
 
+# per width: the digit limit, the tiles' largest row spreads, one head's k column spread, the path counts
+# (digit, int32, fp64) of the q, kv and qkv passes at H = 4 and 2 (asserted at width 4 only)
+SPREADS = {8: (8, [8, 20, 9], 8, None),
+           4: (4, [4, 20, 5], 4, {4: {"q": (6, 6, 12), "kv": (8, 8, 8), "qkv": (6, 6, 12)},
+                                  2: {"q": (2, 2, 8), "kv": (4, 4, 4), "qkv": (2, 2, 8)}})}
+
+
+@BITS
 @pytest.mark.parametrize("H", [4, 2])
-def test_spread_case_paths(H):
-    """Each pass of the spread case takes the digit, the shifted-int32 and the fp64 accumulation:
-    tile 0 (row spreads 8) digits for the heads whose columns spread <= 8 and fp64 for the head
-    spreading 10; tile 1 (row spreads 20) fp64; tile 2 (row spreads 9) shifted int32 sums for the
-    heads whose columns spread 0 (9 + 0 <= smax = 9), fp64 for the others."""
-    x, cond, Wq, bq, Wkv, bkv = CC.spread_case(H)
+def test_spread_case_paths(H, bits):
+    """Every pass of the spread case takes the digit, the shifted-int32 and the fp64 accumulation:
+    tile 0 (row spreads at the digit limit, 8 / 4) digits for the heads whose columns spread within
+    the limit and fp64 for the head spreading 10; tile 1 (row spreads 20) fp64; tile 2 (row spreads
+    one above the limit, 9 / 5) shifted int32 sums where that + the column spread <= smax = 9 (at
+    width 8: column spread 0), fp64 for the others."""
+    elem, (limit, rows, kcol, want_counts) = GS.ELEM[bits], SPREADS[bits]
+    x, cond, Wq, bq, Wkv, bkv = CC.spread_case(H, elem)
     assert CC.proj_smax(8) == 9
-    for tokens, W, parts, wide in ((x, Wq, 1, {0: 10}), (cond, Wkv, 2, {min(1, H - 1): 8})):
+    hk = min(1, H - 1)
+    passes = [("q", x, Wq, 1, {0: 10}), ("kv", cond, Wkv, 2, {hk: kcol})]
+    if bits == 4:  # the QKV pass has a spread case at this width only
+        xs, W3, _ = CC.spread_case_qkv(H, elem)
+        passes.append(("qkv", xs, W3, 3, {0: 10, hk: 10 if hk == 0 else kcol}))
+    counts = {}
+    for what, tokens, W, parts, wide in passes:
         for b in range(tokens.shape[0]):
-            _, smx, _ = GC.gemm_gate(tokens[b], W[:32])
-            assert smx.tolist() == [8, 20, 9], smx
+            _, smx, _ = GC.gemm_gate(tokens[b], W[:32], elem=elem)
+            assert smx.tolist() == rows, smx
         for h in range(H):
-            D = W.shape[0] // (parts * H)
-            Wh = np.concatenate([W[(s * H + h) * D: (s * H + h + 1) * D] for s in range(parts)])
-            assert GC.row_stats(Wh, False)[1].max() == wide.get(h, 0)
-        paths = CC.spread_paths(tokens, W, H, parts)
+            assert GC.row_stats(CC.head_rows(W, H, parts, h), False, elem=elem)[1].max() == wide.get(h, 0)
+        paths = CC.spread_paths(tokens, W, H, parts, elem)  # (asserts the gate quantity >= -126 everywhere)
         for (b, tb, h), path in paths.items():
             sp = wide.get(h, 0)
-            want = {0: "digit" if sp <= 8 else "fp64", 1: "fp64", 2: "int32" if sp == 0 else "fp64"}[tb]
-            assert path == want, (b, tb, h, path)
+            want = {0: "digit" if sp <= limit else "fp64", 1: "fp64", 2: "int32" if rows[2] + sp <= 9 else "fp64"}[tb]
+            assert path == want, (what, b, tb, h, path)
         assert set(paths.values()) == {"digit", "int32", "fp64"}
-    # the widest span of scaled block exponents stays within what the fp64 sums hold exactly
-    assert 20 + 10 <= 34
+        c = collections.Counter(paths.values())
+        counts[what] = (c["digit"], c["int32"], c["fp64"])
+    assert want_counts is None or counts == want_counts[H]
+    assert 20 + 10 <= 34  # the widest span of scaled block exponents: exact in the fp64 sums
 
 
+@BITS
 @pytest.mark.parametrize("which", ["q", "kv"])
-def test_subnormal_case_gate(which):
-    """The scaled pass's first tile: row spreads <= 8 and column spreads <= 8 (the digit
+def test_subnormal_case_gate(which, bits):
+    """The scaled pass's first tile: row and column spreads within the digit limit (the digit
     operands), the gate quantity at least 20 below -126 for every head, and more than 0.9 of the
     tile's results subnormal."""
-    H, x, cond, Wq, bq, Wkv, bkv = CC.subnormal_case(which)
+    elem, limit = GS.ELEM[bits], SPREADS[bits][0]
+    H, x, cond, Wq, bq, Wkv, bkv = CC.subnormal_case(which, elem)
     tokens, W, parts = (x, Wq, 1) if which == "q" else (cond, Wkv, 2)
-    D = W.shape[0] // (parts * H)
     for h in range(H):
-        Wh = np.concatenate([W[(s * H + h) * D: (s * H + h + 1) * D] for s in range(parts)])
+        Wh = CC.head_rows(W, H, parts, h)
         for b in range(tokens.shape[0]):
-            q, smx, wsp = GC.gemm_gate(tokens[b, :32], Wh)
-            assert smx[0] <= GC.DIGIT_SPREAD and wsp <= GC.DIGIT_SPREAD, (smx, wsp)
+            q, smx, wsp = GC.gemm_gate(tokens[b, :32], Wh, elem=elem)
+            assert smx[0] <= limit and wsp <= limit, (smx, wsp)
             assert q[0] <= GC.GATE - 20, q
-    want = O.mx_linear(tokens, W)
+    want = O.mx_linear(tokens, W, elem=elem)
     sub = np.isfinite(want) & (want != 0) & (np.abs(want) < GC.F32_MIN_NORMAL)
     assert sub[:, :32].mean() > 0.9
-    # the other pass is unscaled: its results are normal
-    other = O.mx_linear(cond, Wkv) if which == "q" else O.mx_linear(x, Wq)
-    assert not (np.isfinite(other) & (other != 0) & (np.abs(other) < GC.F32_MIN_NORMAL)).any()
+    if bits == 8:  # the other pass is unscaled: its results are normal
+        other = O.mx_linear(cond, Wkv) if which == "q" else O.mx_linear(x, Wq)
+        assert not (np.isfinite(other) & (other != 0) & (np.abs(other) < GC.F32_MIN_NORMAL)).any()
+    else:  # the same gate in the QKV pass the GPU test builds from these operands
+        W3 = np.concatenate([Wq, Wq, Wq]) if which == "q" else np.concatenate([Wkv[: Wkv.shape[0] // 2], Wkv])
+        for h in range(H):
+            q, smx, wsp = GC.gemm_gate(tokens[0, :32], CC.head_rows(W3, H, 3, h), elem=elem)
+            assert smx[0] <= limit and wsp <= limit and q[0] <= GC.GATE - 20

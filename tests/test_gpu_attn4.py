@@ -1,6 +1,6 @@
 """The MXINT4 attention core on the device (mx_topk_attention / mx_approx_scores / approx_values
 with elem_bits=4: mxa_attention_bits and its siblings) against the reference's fixture at
-a_elem_format = "int4" and against attention4 (tests/attn4_cases.py): true and approximate
+a_elem_format = "int4" and against the oracle's attention at elem="int4": true and approximate
 scores, kept indices and mask words bit for bit; out bit for bit on the exact-result cases, by
 the row-wise bound at width 4 elsewhere, by the norm on the bfloat = 16 rows that
 test_attn4_cpu.py shows to have no eligible P block.  The references are computed once in
@@ -44,7 +44,7 @@ FIXTURE = [(f"{m}_k20", 20, m) for m in A.MODES] + [("trueK_k30", 30, None), ("d
 def test_fixture_self(M, gold, tag, k, mode):
     q, kk, v, sc = gold["self/q"], gold["self/k"], gold["self/v"], float(gold["self/scale"])
     kw = dict(top_k=False) if not k else (dict(k_top=k, approx=False) if mode is None else dict(k_top=k, pred_mode=mode))
-    r = A.attention4(q, kk, v, sc, **kw)  # (test_attn4_cpu.py: equal to the fixture bit for bit)
+    r = O.attention(q, kk, v, sc, elem="int4", **kw)  # (test_attn4_cpu.py: equal to the fixture bit for bit)
     if k:
         same(r["idx"], gold[f"self/{tag}/idx"].astype(np.int64), "oracle idx vs fixture")
     got = _run(M, q, kk, v, sc, Call(k, mode))
@@ -62,7 +62,7 @@ def test_fixture_cross_bf16(M, gold, tag, k, mode):
     q, kk, v, sc = gold["cross/q"], gold["cross/k"], gold["cross/v"], float(gold["cross/scale"])
     bias = gold["cross/bias"][:, None]
     kw = dict(k_top=k, pred_mode=mode) if k else dict(top_k=False)
-    r = A.attention4(q, kk, v, sc, bias=bias, flush=True, bfloat=16, **kw)
+    r = O.attention(q, kk, v, sc, bias=bias, flush=True, bfloat=16, elem="int4", **kw)
     rows = ~A.eligible_bf16(r, v, True)[2]
     got = _run(M, q, kk, v, sc, Call(k, mode, True, 16), bias)
     same_bits(got["true"], gold["cross/true"], tag + " true vs fixture")
@@ -73,7 +73,7 @@ def test_fixture_cross_bf16(M, gold, tag, k, mode):
     out_close(got["out"][rows], gold[f"cross/{tag}/out"][rows], OUT_TOL, tag + " out")
 
 
-# ---- the grid, the long rows and finish_qk_kernel against attention4 ---------------------------------
+# ---- the grid, the long rows and finish_qk_kernel against the oracle at int4 ---------------------------------
 @pytest.mark.parametrize("c", A.ROWS_CASES, ids=A.rcase_id)
 def test_rows_vs_attention4(M, c):
     q, k, v, bias = A.r_inputs(c)

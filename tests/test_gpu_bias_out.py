@@ -4,7 +4,7 @@ from the oracle alone that each case runs on the kernel it names, that a wrong b
 every row's kept indices, and that the eligible shares of the row-wise bound stay within the caps).
 
 The bias is real-valued on all of (B, H, N, T).  Its contiguous layout (a) is compared with the oracle
-(tests/attn4_cases.attention4 at width 4): true, pred, idx and the mask bit for bit, out by the row-wise
+(the oracle's attention at the width): true, pred, idx and the mask bit for bit, out by the row-wise
 bound.  The same values in other storage -- (b) every second element of a wider buffer, 4 bytes off 16-byte
 alignment; (c) transposed storage; (d) rows padded by three elements -- must give the bytes of (a).  The
 broadcast layouts (e) (H, N, T), (f) (1, H, 1, T), (g) (N, T) and the mask (h) are compared with the oracle on
@@ -23,7 +23,6 @@ import torch
 
 import bias_cases as BC
 import cross_cases as CC
-import proj4_cases as P4
 from gpu_support import M, attn_run, check_attn, check_siblings, dev, host, out_rows_close, r_kw, r_scale, same, same_bits  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -131,7 +130,7 @@ def _fused_checks(M, out, idx, r, heads, bias, scale, k_top, bits, what):
 @pytest.mark.parametrize("bits", [8, 4])
 def test_cross_attention_bias(M, bits, vs):
     (B, N, T, C, Ckv, H), k_top = CC.SHAPES["d48"]
-    x, cond, Wq, bq, Wkv, bkv, _, _ = P4.case("d48")
+    x, cond, Wq, bq, Wkv, bkv, _, _ = CC.case("d48")
     ch, bias, r = BC.cross_reference(bits, vs)
     bias, scale = dev(bias), (C // H) ** -0.5
     out, idx = M.mx_cross_attention(dev(x), dev(cond), dev(Wq), dev(bq), dev(Wkv), dev(bkv), H, scale, k_top=k_top,
@@ -143,8 +142,8 @@ def test_cross_attention_bias(M, bits, vs):
 @pytest.mark.parametrize("vs", ["full", "hnt"], ids=["a", "e"])
 @pytest.mark.parametrize("bits", [8, 4])
 def test_qkv_attention_bias(M, bits, vs):
-    (B, N, C, H), k_top = P4.SELF_SHAPES["d48"]
-    x, W, b, _, _ = P4.self_case("d48")
+    (B, N, C, H), k_top = CC.SELF_SHAPES["d48"]
+    x, W, b, _, _ = CC.self_case("d48")
     qkv, heads, bias, r = BC.self_reference(bits, vs)
     bias, scale = dev(bias), (C // H) ** -0.5
     out, idx, got_qkv = M.mx_qkv_attention(dev(x), dev(W), dev(b), H, scale, k_top=k_top, pred_mode="ex_pred", attn_bias=bias,

@@ -16,7 +16,7 @@ import attn4_cases as A
 import exact_out_cases as EC
 import long_dense_cases as LC
 import topk_cases as TC
-from gpu_support import M, OUT_TOL, attn_entry, attn_run as run, check_attn as check_scores, check_exact_out  # noqa: F401
+from gpu_support import ELEM, M, OUT_TOL, attn_entry, attn_run as run, check_attn as check_scores, check_exact_out  # noqa: F401
 from gpu_support import check_siblings, dev, out_close, out_rows_close, r_kw, r_scale, rnd, same, same_bits
 from oracle import mx_oracle as O
 
@@ -27,7 +27,7 @@ F32 = np.float32
 def oracle(q, k, v, scale, bits=8, **kw):
     if "flush_subnormals" in kw:
         kw["flush"] = kw.pop("flush_subnormals")
-    return (A.attention4 if bits == 4 else O.attention)(q, k, v, scale, **kw)
+    return O.attention(q, k, v, scale, elem=ELEM[bits], **kw)
 
 
 # ---- 1. the exact-result cases, bit for bit --------------------------------------------------------------

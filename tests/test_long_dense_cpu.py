@@ -13,8 +13,6 @@ import pytest
 import attn4_cases as A
 import exact_out_cases as EC
 import long_dense_cases as LC
-import test_attn4_cpu as T4
-import test_exact_out_cpu as TE
 from gpu_support import ELIGIBLE_ELEMS, ELIGIBLE_ROWS, host_params
 from oracle import mx_oracle as O
 
@@ -138,23 +136,17 @@ def test_workspace_bytes(nat):
         assert f == b
 
 
-# ---- the exact-result cases: the five conditions of test_exact_out_cpu.py ---------------------------------
+# ---- the exact-result cases: the five conditions (exact_out_cases.CONDITIONS) ---------------------------------
 @pytest.mark.parametrize("c", LC.EXACT + LC.EXACT_BF16, ids=LC.case_id)
 def test_exact_cases_meet_the_five_conditions(c):
-    TE.test_score_gaps_are_zero_or_wide(c)
-    TE.test_v_is_its_own_mx_along_the_tokens(c)
-    TE.test_out_is_the_exact_product(c)
-    TE.test_p_codes_survive_four_ulp(c)
-    TE.test_tie_counts_vary(c)
+    for condition in EC.CONDITIONS:
+        condition(c, EC.inputs(c), EC.reference(c), "int8")
 
 
 @pytest.mark.parametrize("c", LC.EXACT4, ids=LC.case_id)
 def test_exact4_cases_meet_the_five_conditions(c):
-    T4.test_exact4_operands_are_their_own_mxint4(c)
-    T4.test_exact4_score_gaps_are_zero_or_wide(c)
-    T4.test_exact4_out_is_the_exact_product(c)
-    T4.test_exact4_p_codes_survive_four_ulp(c)
-    T4.test_exact4_tie_counts_vary(c)
+    for condition in EC.CONDITIONS:
+        condition(c, A.exact_inputs(c), A.exact_reference(c), "int4")
 
 
 # ---- the peaked random inputs: the eligible shares, from the oracle alone ---------------------------------

@@ -1,10 +1,9 @@
 """CPU checks of the W4A4 fused blocks (include/mxa.h mxa_qkv_attention_bits, mxa_attention_proj_bits,
 mxa_cross_attention_bits): the symbols, the validation that returns before any HIP call, the
-workspace sizes -- and, with the oracle alone, that the inputs of tests/test_gpu_proj4.py sit in the
-regimes those tests are about (tests/proj4_cases.py): every accumulation path in every pass of the
-spread case, the one-digit tile behind its subnormal gate, the NaN rows, and the eligible-share caps
-of every output that is compared with the oracle row by row."""
-import collections
+workspace sizes -- and, with the oracle alone (tests/cross_cases.py at elem="int4"), the NaN rows and
+the eligible-share caps of every width-4 output that tests/test_gpu_cross.py compares with the oracle
+row by row.  The accumulation paths of the spread case and the subnormal gate are asserted at both
+widths in tests/test_cross_cpu.py."""
 import ctypes
 import json
 import os
@@ -15,12 +14,11 @@ import torch
 
 import attn4_cases as A4
 import cross_cases as CC
-import gate_cases as GC
 import gpu_support as GS
-import proj4_cases as P
 
 UNSUPPORTED, ARG = -2, -1
 NAMES = ("mxa_qkv_attention", "mxa_attention_proj", "mxa_cross_attention")
+MODES = ("ex_pred", "MXINT4", "two_step_leading_ones")
 
 
 @pytest.fixture(scope="module")
@@ -160,61 +158,8 @@ def test_python_refusals_without_gpu():
         M.mx_cross_attention(x, x, torch.zeros(64, 64), None, torch.zeros(128, 64), None, 2, 0.125, k_top=4, elem_bits=4)
 
 
-# ---------------------------------------------------------------- the regimes of the GPU tests' inputs
-@pytest.mark.parametrize("H", [4, 2])
-def test_spread_case_paths(H):
-    """Every pass of the width-4 spread case takes the digit, the shifted-int32 and the fp64 accumulation:
-    tile 0 (row spreads 4) digits for the heads whose columns spread <= 4, fp64 for the head spreading 10;
-    tile 1 (row spreads 20) fp64; tile 2 (row spreads 5) shifted int32 sums where 5 + the column spread <=
-    smax = 9, fp64 for the head spreading 10."""
-    x, cond, Wq, bq, Wkv, bkv = P.spread_case(H)
-    xs, W3, _ = P.spread_case_qkv(H)
-    assert CC.proj_smax(8) == 9
-    hk = min(1, H - 1)
-    counts = {}
-    for what, tokens, W, parts, wide in (("q", x, Wq, 1, {0: 10}), ("kv", cond, Wkv, 2, {hk: 4}),
-                                         ("qkv", xs, W3, 3, {0: 10, hk: 10 if hk == 0 else 4})):
-        for b in range(tokens.shape[0]):
-            _, smx, _ = GC.gemm_gate(tokens[b], W[:32], elem="int4")
-            assert smx.tolist() == [4, 20, 5], smx
-        for h in range(H):
-            assert GC.row_stats(P.head_rows(W, H, parts, h), False, elem="int4")[1].max() == wide.get(h, 0)
-        paths = P.spread_paths(tokens, W, H, parts)  # (asserts the gate quantity >= -126 everywhere)
-        for (b, tb, h), path in paths.items():
-            sp = wide.get(h, 0)
-            want = {0: "digit" if sp <= 4 else "fp64", 1: "fp64", 2: "int32" if 5 + sp <= 9 else "fp64"}[tb]
-            assert path == want, (what, b, tb, h, path)
-        assert set(paths.values()) == {"digit", "int32", "fp64"}
-        c = collections.Counter(paths.values())
-        counts[what] = (c["digit"], c["int32"], c["fp64"])
-    assert counts == ({"q": (6, 6, 12), "kv": (8, 8, 8), "qkv": (6, 6, 12)} if H == 4 else
-                      {"q": (2, 2, 8), "kv": (4, 4, 4), "qkv": (2, 2, 8)})
-    assert 20 + 10 <= 34  # the widest span of scaled block exponents: exact in the fp64 sums
-
-
-@pytest.mark.parametrize("which", ["q", "kv"])
-def test_subnormal_case_gate(which):
-    """The scaled pass's first tile: row and column spreads <= 4 (the one-digit operands), the gate
-    quantity at least 20 below -126 for every head, more than 0.9 of the tile's results subnormal"""
-    H, x, cond, Wq, bq, Wkv, bkv = P.subnormal_case(which)
-    tokens, W, parts = (x, Wq, 1) if which == "q" else (cond, Wkv, 2)
-    for h in range(H):
-        Wh = P.head_rows(W, H, parts, h)
-        for b in range(tokens.shape[0]):
-            q, smx, wsp = GC.gemm_gate(tokens[b, :32], Wh, elem="int4")
-            assert smx[0] <= GC.DIGIT4_SPREAD and wsp <= GC.DIGIT4_SPREAD, (smx, wsp)
-            assert q[0] <= GC.GATE - 20, q
-    want = P.lin4(tokens, W)
-    sub = np.isfinite(want) & (want != 0) & (np.abs(want) < GC.F32_MIN_NORMAL)
-    assert sub[:, :32].mean() > 0.9
-    # the same gate in the QKV pass the GPU test builds from these operands
-    W3 = np.concatenate([Wq, Wq, Wq]) if which == "q" else np.concatenate([Wkv[: Wkv.shape[0] // 2], Wkv])
-    for h in range(H):
-        q, smx, wsp = GC.gemm_gate(tokens[0, :32], P.head_rows(W3, H, 3, h), elem="int4")
-        assert smx[0] <= GC.DIGIT4_SPREAD and wsp <= GC.DIGIT4_SPREAD and q[0] <= GC.GATE - 20
-
-
-CAPS = [(n, m, f) for n in ("d48", "d32", "d72") for m in P.MODES for f in (False, True)] + [("d32w", "ex_pred", False),
+# ---------------------------------------------------------------- the eligible-share caps
+CAPS = [(n, m, f) for n in ("d48", "d32", "d72") for m in MODES for f in (False, True)] + [("d32w", "ex_pred", False),
                                                                                               ("pixart", "MXINT4", True)]
 
 
@@ -222,8 +167,8 @@ CAPS = [(n, m, f) for n in ("d48", "d32", "d72") for m in P.MODES for f in (Fals
 def test_output_caps_cross(name, mode, flush):
     """the eligible shares of every cross case compared by out_rows_close, from the oracle alone; exactly
     H NaN rows -- the NaN token's"""
-    H = P.SHAPES[name][0][5]
-    c = P.chain(name, mode, flush)
+    H = CC.SHAPES[name][0][5]
+    c = CC.chain(name, mode, flush, elem="int4")
     ok, (se, sr) = A4.shares_within_caps(c["r"], c["vh"])
     assert ok and se == 0 and sr == 0, (se, sr)
     bad = np.isnan(c["r"]["out"]).any(-1)
@@ -232,15 +177,15 @@ def test_output_caps_cross(name, mode, flush):
 
 
 def test_output_caps_other_cases():
-    c = P.chain("d48", "MXINT4", False, 0, True, False)  # dense
+    c = CC.chain("d48", "MXINT4", False, 0, True, False, elem="int4")  # dense
     assert A4.shares_within_caps(c["r"], c["vh"])[1] == (0, 0)
     assert np.isnan(c["r"]["out"]).any(-1).sum() == 2
-    c = P.chain("d48", "MXINT4", False, 0, False)  # without the mask bias
+    c = CC.chain("d48", "MXINT4", False, 0, False, elem="int4")  # without the mask bias
     assert A4.shares_within_caps(c["r"], c["vh"])[1] == (0, 0)
     for name in ("d48", "d32", "d64k65", "d72dense"):
-        c = P.self_chain(name)
+        c = CC.self_chain(name, elem="int4")
         assert A4.shares_within_caps(c["r"], c["vh"])[0], name
-    H, x, cond, Wq, Wkv, q, kv, vh, r = P.nan_cond_case()
+    H, x, cond, Wq, Wkv, q, kv, vh, r = CC.nan_cond_case("int4")
     assert A4.shares_within_caps(r, vh)[0]
     bad = np.isnan(r["out"]).any(-1)
     assert bad[1].all() and not bad[0].any() and not bad[2].any()
