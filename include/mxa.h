@@ -585,6 +585,37 @@ int mxa_cross_attention_bits(const mxa_attn_params* p, const mxa_cross_params* x
                              int32_t elem_bits, hipStream_t stream);
 
 /*
+ * The self-attention block at 512 x 512: the fused qkv projection and the proj Linear on rows of
+ * 513 .. 1,024 keys (PixArt's MXSelfAttention.forward, workloads/PixArt/models/MX_transformer_block.py:624-717,
+ * at N = T = 1,024; DiT at 512 x 512; DeiT at 384 x 384, 577 tokens).  The parameter structs, outputs
+ * and workspace rules of mxa_qkv_attention_bits and mxa_attention_proj_bits (xq may be NULL in the proj
+ * form: q, k, v given).
+ *   T <= 512: exactly the _bits sibling at the same elem_bits -- the same kernels, bytes, statuses
+ *             and workspace size (at 4 bits the 32-row and dense-row kernel shapes stay refused).
+ *   513 <= T <= 1,024, float32: the projection kernel of the sibling writes the operands
+ *             mxa_attention_full(p, elem_bits) would build from q, k, v, and the attention is that
+ *             call's: every k_top <= T, every pred_mode (MXA_PRED_ELSA at 8 bits only), approx == 0,
+ *             bias, bfloat, flush_subnormals, the optional outputs, and (qkv form only) the dense
+ *             branch.  The proj's input: at 8 bits with D % 32 == 0 and k_top <= 32 the 16-row
+ *             finishing kernel writes the MX codes itself; every other call (D % 32 != 0,
+ *             k_top > 32, 4 bits) goes through the fp32 workspace copy and the row quantizer -- the
+ *             same y bit for bit.  The workspace holds that 256-byte-aligned copy (B*N*H*D floats)
+ *             exactly when the codes are not written directly.
+ *   Unchanged answers: pj with top_k == 0 and xq with N != T are MXA_ERR_ARG.  MXA_ERR_UNSUPPORTED,
+ *             before any HIP call: T > 1,024, D > 128, float16 / bfloat16 tensors, a nonzero
+ *             score_dtype or autocast_dtype on rows over 512 keys, MXA_PRED_ELSA (with approx) at
+ *             4 bits.
+ * mxa_qkv_attention, mxa_attention_proj, mxa_cross_attention and their _bits forms keep T <= 512;
+ * cross-attention is not extended (its T is the condition length).
+ */
+int64_t mxa_qkv_attention_full_workspace_bytes(const mxa_attn_params* p, const mxa_qkv_params* x, int32_t elem_bits);
+int mxa_qkv_attention_full(const mxa_attn_params* p, const mxa_qkv_params* x, int32_t elem_bits, hipStream_t stream);
+int64_t mxa_attention_proj_full_workspace_bytes(const mxa_attn_params* p, const mxa_qkv_params* xq,
+                                                const mxa_proj_params* pj, int32_t elem_bits);
+int mxa_attention_proj_full(const mxa_attn_params* p, const mxa_qkv_params* xq, const mxa_proj_params* pj,
+                            int32_t elem_bits, hipStream_t stream);
+
+/*
  * mx.matmul forward (microxscaling/mx/matmul.py:31-100, :211-222): in1 (batch, M, K)
  * quantized along K, in2 (batch, K, Nc) quantized along K, fp32 result (batch, M, Nc)
  * contiguous.  Integer formats, block size 32.  a_dtype / b_dtype (MXA_DT_*): each operand's

@@ -138,6 +138,11 @@ _SIGS = {
     "mxa_attention_proj_bits": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp]),
     "mxa_cross_attention_bits_workspace_bytes": (c_i64, [c_vp, c_vp, c_vp, c_i32]),
     "mxa_cross_attention_bits": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp]),
+    # the self-attention blocks at their full reach (rows of up to 1,024 keys): as the _bits forms
+    "mxa_qkv_attention_full_workspace_bytes": (c_i64, [c_vp, c_vp, c_i32]),
+    "mxa_qkv_attention_full": (c_i32, [c_vp, c_vp, c_i32, c_vp]),
+    "mxa_attention_proj_full_workspace_bytes": (c_i64, [c_vp, c_vp, c_vp, c_i32]),
+    "mxa_attention_proj_full": (c_i32, [c_vp, c_vp, c_vp, c_i32, c_vp]),
     "mxa_matmul": (c_i32, [c_vp, c_vp, c_vp, c_i64, c_i32, c_i32, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32,
                            c_i32, c_i32, c_i32, c_vp, c_i64, c_vp]),
     "mxa_matmul_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32, c_i32]),

@@ -25,6 +25,8 @@ UNITS += [("mxa_fin16.hip", f"_x{i}", (f"MXA_F16_XDT={i}",)) for i in range(2)]
 UNITS += [("mxa_fin16.hip", "_l0", ("MXA_F16_LONG=1",))]
 # ... and its MXINT4-P instantiations (mxa_attention_bits at width 4), short and long rows
 UNITS += [("mxa_fin16.hip", "_x0w4", ("MXA_F16_W4=1",)), ("mxa_fin16.hip", "_l0w4", ("MXA_F16_LONG=1", "MXA_F16_W4=1"))]
+# ... and the long rows' instantiations that write the proj Linear's MX input codes (mxa_attention_proj_full)
+UNITS += [("mxa_fin16.hip", "_l0xo", ("MXA_F16_LXO=1",))]
 # the long rows' selection kernel: the dispatcher and one score mode each (MXA_SELL_PART)
 UNITS += [("mxa_sel_long.hip", "", ("MXA_SELL_PART=0",))] + [("mxa_sel_long.hip", f"_p{i}", (f"MXA_SELL_PART={i}",)) for i in range(1, 7)]
 UNITS += [("mxa_proj.hip", "", ()), ("mxa_gemm.hip", "", ())]

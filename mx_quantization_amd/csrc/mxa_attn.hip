@@ -16,6 +16,10 @@
 //                               dense_rows_kernel (mxa_rows2.hpp)
 //   finish_qk_long_kernel       mxa_attention_full on rows of 513 .. 1,024 keys: the dense branch and
 //                               k > 64, three passes over the key blocks (mxa_finish_qk_long.hpp)
+//   mxa_qkv_attention_full / mxa_attention_proj_full
+//                               those rows with the fused qkv projection in front and the proj Linear
+//                               behind: qkv_proj_kernel as it is; the proj's codes from finish16_kernel's
+//                               LONG + XO instantiations (MXINT8, D % 32 == 0, k <= 32), else the fp32 copy
 // Which of these finishes a call is finish_choice's answer (mxa_launch.hpp) to the call's facts
 // (attn_fin_facts): attn_validate takes its refusal, attn_layout whether to hold mask words,
 // launch_rows (mxa_fin.hip) the kernel, the *_finish_kernel entry points the kind they report.
@@ -101,19 +105,22 @@ ModeNeeds mode_needs(int mode) {
   return n;
 }
 
+// How far an entry point reaches, in order: each value takes every call the one before it takes, on the
+// same kernels.  kReachShort: rows of at most 512 keys; kReachLong (the *_long and *_bits entry points):
+// rows of at most kLongRowsT keys on the kernels that existed before finish_qk_long_kernel; kReachFull
+// (mxa_attention_full): those rows' dense branch and k_top > 64 too; kReachBlock (mxa_qkv_attention_full,
+// mxa_attention_proj_full): on those rows the fused qkv projection and the proj Linear as well
+enum Reach { kReachShort, kReachLong, kReachFull, kReachBlock };
+
 // the proj Linear's input comes MX-quantized out of the finishing kernel (MXINT8 only: at 4 bits the
-// fp32 rows go through the workspace and the row quantizer for every D)
-bool proj_codes_direct(const mxa_attn_params* p, int elem_bits) {
+// fp32 rows go through the workspace and the row quantizer for every D; rows over 512 keys: from the LONG
+// 16-row kernel alone, k <= 32 -- there is no 32-row kernel behind it, and finish_qk_long_kernel writes fp32)
+bool proj_codes_direct(const mxa_attn_params* p, int elem_bits, Reach reach) {
+  if (reach == kReachBlock && long_rows(p->T) && !(p->top_k && p->k_top <= 32)) return false;
   return elem_bits == 8 && p->D % 32 == 0 && p->dtype == MXA_DT_F32 && p->score_dtype <= MXA_DT_F32;
 }
 // a width as a prepared weight's header and flat_rows_prep state it: 0 MXINT8, 4 MXINT4
 int header_bits(int elem_bits) { return elem_bits == 4 ? 4 : 0; }
-
-// How far an entry point reaches, in order: each value takes every call the one before it takes, on the
-// same kernels.  kReachShort: rows of at most 512 keys; kReachLong (the *_long and *_bits entry points):
-// rows of at most kLongRowsT keys on the kernels that existed before finish_qk_long_kernel; kReachFull
-// (mxa_attention_full): those rows' dense branch and k_top > 64 too
-enum Reach { kReachShort, kReachLong, kReachFull };
 
 // One attention call
 struct AttnCall {
@@ -135,8 +142,8 @@ struct AttnCall {
 // what finish_choice (mxa_launch.hpp) decides a call's finishing kernel from; p: the call's parameters
 // as the kernels see them (attention_impl's copy)
 FinFacts attn_fin_facts(const AttnCall& c, const mxa_attn_params* p) {
-  return {p->top_k != 0, p->top_k ? p->k_top : 0, p->T, (p->D + 31) / 32, c.pj && proj_codes_direct(p, c.elem_bits),
-          p->dtype != MXA_DT_F32 || p->score_dtype > MXA_DT_F32, c.elem_bits, c.reach == kReachFull};
+  return {p->top_k != 0, p->top_k ? p->k_top : 0, p->T, (p->D + 31) / 32, c.pj && proj_codes_direct(p, c.elem_bits, c.reach),
+          p->dtype != MXA_DT_F32 || p->score_dtype > MXA_DT_F32, c.elem_bits, c.reach >= kReachFull, c.reach == kReachBlock};
 }
 
 // one side's (Q's or K's) row operands; null: the score mode does not read it
@@ -204,7 +211,7 @@ AttnLayout attn_layout(const AttnCall& c, const mxa_attn_params* p, int mode, vo
   }
   if (pj) {
     L.y = carve_mx_rows(ws, qtok, p->H * p->D, true);
-    L.yf = ws.take<float>(proj_codes_direct(p, c.elem_bits) ? 0 : qtok * p->H * p->D);
+    L.yf = ws.take<float>(proj_codes_direct(p, c.elem_bits, c.reach) ? 0 : qtok * p->H * p->D);
   }
   L.total = ws.off;
   return L;
@@ -248,6 +255,11 @@ int attn_validate(const AttnCall& c) {
   if (elem_bits == 4 && (xq || xc || pj) &&
       (p->dtype != MXA_DT_F32 || p->score_dtype != 0 || (xq && xq->autocast_dtype != 0)))
     return MXA_ERR_UNSUPPORTED;
+  // the fused qkv projection on rows over 512 keys: unsupported, not a bad argument, for float16 / bfloat16
+  // tensors and under autocast (the rule below would answer MXA_ERR_ARG first; the score dtype and the
+  // form without xq are the long rows' refusal further down)
+  if (reach == kReachBlock && long_rows(p->T) && xq && (p->dtype != MXA_DT_F32 || xq->autocast_dtype != 0))
+    return MXA_ERR_UNSUPPORTED;
   if (xq && (p->dtype != MXA_DT_F32 || (xq->autocast_dtype != 0 && xq->autocast_dtype != p->score_dtype)))
     return MXA_ERR_ARG;  // the fused projection reads fp32 x; under autocast its scores follow autocast
   if (xc && p->dtype != MXA_DT_F32) return MXA_ERR_ARG;
@@ -259,10 +271,10 @@ int attn_validate(const AttnCall& c) {
     return MXA_ERR_UNSUPPORTED;
   if (!valid_bfloat(p->bfloat)) return MXA_ERR_ARG;
   if (p->T > (reach == kReachShort ? kShortRowsT : kLongRowsT) || p->D > 32 * kMaxNB) return MXA_ERR_UNSUPPORTED;
-  // rows over 512 keys: float32, no fused projection; MXINT4: float32, and the approximators of
-  // exponent_approximation (ELSA's hashes would need the width too)
+  // rows over 512 keys: float32, no fused projection but kReachBlock's qkv and proj Linears; MXINT4:
+  // float32, and the approximators of exponent_approximation (ELSA's hashes would need the width too)
   const bool xdt = p->dtype != MXA_DT_F32 || p->score_dtype > MXA_DT_F32;
-  if ((long_rows(p->T) && (xq || xc || pj || xdt)) || (elem_bits == 4 && xdt)) return MXA_ERR_UNSUPPORTED;
+  if ((long_rows(p->T) && (xc || ((xq || pj) && reach != kReachBlock) || xdt)) || (elem_bits == 4 && xdt)) return MXA_ERR_UNSUPPORTED;
   if (elem_bits == 4 && p->approx && p->pred_mode == MXA_PRED_ELSA) return MXA_ERR_UNSUPPORTED;
   // ... and a finishing kernel with an instantiation for them (finish_choice: the 16-row and the MFMA
   // kernels), or the scores alone
@@ -773,6 +785,33 @@ extern "C" int mxa_cross_attention_bits(const mxa_attn_params* p, const mxa_cros
                                         int32_t elem_bits, hipStream_t stream) {
   if (!xc) return MXA_ERR_ARG;
   return attention_impl({.p = p, .stream = stream, .xc = xc, .pj = pj, .elem_bits = elem_bits});
+}
+
+// The self-attention blocks at their full reach: the *_bits siblings call for call on rows of at most 512
+// keys; on rows of 513 .. 1,024 keys the fused qkv projection in front of, and the proj Linear behind,
+// what mxa_attention_full runs there (MX_transformer_block.py:624-717 at 512 x 512)
+extern "C" int64_t mxa_qkv_attention_full_workspace_bytes(const mxa_attn_params* p, const mxa_qkv_params* xq,
+                                                          int32_t elem_bits) {
+  if (!mx_width_ok(elem_bits) || !attn_shape_ok(p) || !xq || xq->C <= 0) return -1;
+  return attn_workspace_total({.p = p, .xq = xq, .reach = kReachBlock, .elem_bits = elem_bits});
+}
+
+extern "C" int mxa_qkv_attention_full(const mxa_attn_params* p, const mxa_qkv_params* xq, int32_t elem_bits,
+                                      hipStream_t stream) {
+  if (!xq) return MXA_ERR_ARG;
+  return attention_impl({.p = p, .stream = stream, .xq = xq, .reach = kReachBlock, .elem_bits = elem_bits});
+}
+
+extern "C" int64_t mxa_attention_proj_full_workspace_bytes(const mxa_attn_params* p, const mxa_qkv_params* xq,
+                                                           const mxa_proj_params* pj, int32_t elem_bits) {
+  if (!mx_width_ok(elem_bits) || !attn_shape_ok(p) || !pj || pj->out_features <= 0 || (xq && xq->C <= 0)) return -1;
+  return attn_workspace_total({.p = p, .xq = xq, .pj = pj, .reach = kReachBlock, .elem_bits = elem_bits});
+}
+
+extern "C" int mxa_attention_proj_full(const mxa_attn_params* p, const mxa_qkv_params* xq, const mxa_proj_params* pj,
+                                       int32_t elem_bits, hipStream_t stream) {
+  if (!pj) return MXA_ERR_ARG;
+  return attention_impl({.p = p, .stream = stream, .xq = xq, .pj = pj, .reach = kReachBlock, .elem_bits = elem_bits});
 }
 
 extern "C" int mxa_attention_path(const mxa_attn_params* p) {

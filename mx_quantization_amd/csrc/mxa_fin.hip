@@ -126,6 +126,7 @@ int launch_rows(const Rows2Args& ra0, const FinFacts& f, bool true_mode, int S, 
       if (w4) return launch_finish_qk_x0w4(ra, BH, stream, plan);
       return f.xdt ? launch_finish_qk_x1(ra, BH, stream, plan) : launch_finish_qk_x0(ra, BH, stream, plan);
     case MXA_FIN_GATHER16:  // (rows over 512 keys: the LONG instantiations, which stage no K table)
+      if (long_rows(ra.T) && f.xo) return launch_finish16_l0xo(ra, BH, stream, plan);  // (finish_choice: MXINT8, k <= 32)
       if (long_rows(ra.T)) return w4 ? launch_finish16_l0w4(ra, BH, stream, plan) : launch_finish16_l0(ra, BH, stream, plan);
       if (w4) return launch_finish16_x0w4(ra, BH, stream, plan);
       return f.xdt ? launch_finish16_x1(ra, BH, stream, plan) : launch_finish16_x0(ra, BH, stream, plan);

@@ -5,6 +5,9 @@
 // only), holds the LONG instantiations for rows of 513 .. 1,024 keys (launch_finish16_l0).
 // MXA_F16_W4=1 (float32 only, with or without MXA_F16_LONG): the MXINT4-P instantiations of
 // mxa_attention_bits at width 4 (launch_finish16_x0w4, launch_finish16_l0w4).
+// MXA_F16_LXO=1 (float32, MXINT8 P): the LONG instantiations that write the proj Linear's MX input codes
+// (launch_finish16_l0xo: the fused blocks on rows of 513 .. 1,024 keys), and nothing else -- a unit of
+// its own, so that every other unit keeps the code it had.
 #include "mxa_finish16.hpp"
 #include "mxa_launch.hpp"
 
@@ -17,7 +20,14 @@
 #ifndef MXA_F16_W4
 #define MXA_F16_W4 0
 #endif
-#if MXA_F16_W4 && MXA_F16_LONG
+#ifndef MXA_F16_LXO
+#define MXA_F16_LXO 0
+#endif
+#if MXA_F16_LXO
+#undef MXA_F16_LONG
+#define MXA_F16_LONG 1
+#define MXA_F16_FN launch_finish16_l0xo
+#elif MXA_F16_W4 && MXA_F16_LONG
 #define MXA_F16_FN launch_finish16_l0w4
 #elif MXA_F16_W4
 #define MXA_F16_FN launch_finish16_x0w4
@@ -34,7 +44,9 @@ namespace mxa {
 constexpr bool kF16Xdt = MXA_F16_XDT != 0;
 constexpr bool kF16Long = MXA_F16_LONG != 0;
 constexpr bool kF16W4 = MXA_F16_W4 != 0;
+constexpr bool kF16Lxo = MXA_F16_LXO != 0;
 static_assert(!(kF16Xdt && (kF16Long || kF16W4)), "long rows, MXINT4 P: float32 only");
+static_assert(!(kF16Lxo && (kF16Xdt || kF16W4)), "the proj's codes on long rows: float32, MXINT8 P");
 
 // waves per workgroup by finish_tile_plan (mxa_launch.hpp) from the waves per SIMD the
 // kernel's registers allow
@@ -57,14 +69,16 @@ static int launch_finish16_ks(const Rows2Args& ra, int BH, hipStream_t stream) {
   // EXTRA: a bias, the debug true scores or bfloatX rounding (float16 / bfloat16 always round)
   const bool extra = kF16Xdt || ra.bias || ra.true_out || (ra.bfloat != 0 && ra.bfloat != 32);
   if (ra.xo_codes) {  // the proj Linear's MX input codes: float32, D % 32 == 0, k <= 32
-    if constexpr (!kF16Xdt && !kF16Long && !kF16W4 && KS <= 8) {
+    if constexpr (!kF16Xdt && kF16Long == kF16Lxo && !kF16W4 && KS <= 8) {
       if (ra.D % 32) return MXA_ERR_UNSUPPORTED;
       return extra ? launch_finish16_x<NB, KS, true, true>(ra, BH, stream) : launch_finish16_x<NB, KS, false, true>(ra, BH, stream);
     }
     return MXA_ERR_UNSUPPORTED;
   }
-  if (extra) return launch_finish16_x<NB, KS, true>(ra, BH, stream);
-  if constexpr (!kF16Xdt) return launch_finish16_x<NB, KS, false>(ra, BH, stream);
+  if constexpr (!kF16Lxo) {
+    if (extra) return launch_finish16_x<NB, KS, true>(ra, BH, stream);
+    if constexpr (!kF16Xdt) return launch_finish16_x<NB, KS, false>(ra, BH, stream);
+  }
   return MXA_ERR_UNSUPPORTED;
 }
 template <int NB>
@@ -79,7 +93,8 @@ static int launch_finish16_nb(const Rows2Args& ra, int BH, hipStream_t stream) {
 }
 
 int MXA_F16_FN(const Rows2Args& ra, int BH, hipStream_t stream, bool plan) {
-  if (ra.xo_codes && (kF16Xdt || kF16Long || kF16W4 || ra.k_top > 32 || ra.D % 32)) return MXA_ERR_UNSUPPORTED;
+  if (ra.xo_codes && (kF16Xdt || kF16Long != kF16Lxo || kF16W4 || ra.k_top > 32 || ra.D % 32)) return MXA_ERR_UNSUPPORTED;
+  if (kF16Lxo && !ra.xo_codes) return MXA_ERR_UNSUPPORTED;
   if (kF16W4 && (ra.s_dt != kF32 || ra.in_dt != kF32)) return MXA_ERR_UNSUPPORTED;
   if (kF16Long != long_rows(ra.T)) return MXA_ERR_UNSUPPORTED;
   if (plan) {

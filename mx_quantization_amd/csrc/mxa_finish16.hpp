@@ -87,12 +87,15 @@ __host__ __device__ inline Fin16Lds fin16_lds(int T, int D, int kst, int nbd, in
 // W4: P is MXINT4 (mxa_attention_bits at width 4: codes floor(p 2^(2 - es) + 1/2) <= 7, block
 // scale 2^(es - 2); the int8 MFMA and its epilogue as they are) -- it travels in the slot count
 // too, KSL = KS (+ kFin16LongKS) + kFin16Bits4KS; float32, no proj codes
+// LONG with XO (the fused blocks of mxa_attention_proj_full, MXINT8 P): the XO epilogue works on the tile's
+// 16 x D output wherever the K rows came from; the per-wave area of a LONG call (16 x (tpad + 16) code
+// bytes alone, >= 8,960 B at T = 513) holds the 16 x (D + 1) fp32 tile (8,256 B at D = 128)
 template <int NB, int KSL, bool XDT, bool EXTRA, bool XO = false>
 __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NB <= 2 && KSL % kFin16LongKS <= 12 ? kFin16Occ : (NB * (KSL % kFin16LongKS) <= 64 ? 3 : 2), 8))) void finish16_kernel(Rows2Args a) {
   constexpr int KS = KSL % kFin16LongKS;
   constexpr bool LONG = KSL % kFin16Bits4KS >= kFin16LongKS;
   constexpr bool W4 = KSL >= kFin16Bits4KS;
-  static_assert(!((LONG || W4) && (XDT || XO)), "long rows, MXINT4 P: float32, no proj codes");
+  static_assert(!((LONG || W4) && XDT) && !(W4 && XO), "long rows, MXINT4 P: float32; MXINT4 P: no proj codes");
   constexpr bool kRound = XDT || EXTRA;
   const int sdt = XDT ? a.s_dt : (int)kF32, idt = XDT ? a.in_dt : (int)kF32;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];

@@ -143,8 +143,10 @@ inline int launch_select_mode(const Rows2Args& ra, int mode, int BH, hipStream_t
 #endif
 // topk, k (0 on the dense branch), xo: the finishing kernel writes the proj Linear's MX input codes
 // (the call's `direct`, known before any pointer is bound); xdt: float16 / bfloat16 inputs or scores;
-// bits: 8 or 4, P's element width; full: the entry point reaches finish_qk_long_kernel (mxa_attention_full)
-struct FinFacts { bool topk; int k, T, nbd; bool xo, xdt; int bits; bool full; };
+// bits: 8 or 4, P's element width; full: the entry point reaches finish_qk_long_kernel (mxa_attention_full);
+// block: it reaches the fused projections on rows over 512 keys too (the *_full fused blocks), where xo is
+// the LONG 16-row kernel's: MXINT8, k <= 32
+struct FinFacts { bool topk; int k, T, nbd; bool xo, xdt; int bits; bool full; bool block = false; };
 // kind: MXA_FIN_* (include/mxa.h); reads_mask: the kernel reads the selection's prune-mask words (the
 // caller's mask_out, else a workspace copy), not the kept indices; status: MXA_ERR_UNSUPPORTED where the
 // kind has no instantiation for the facts
@@ -161,9 +163,10 @@ inline FinChoice finish_choice(const FinFacts& f) {
   else  // k <= 64 (DeiT's 20 / 30, PixArt's 20; with the proj's codes: k <= 32): 16-row tiles, else 32-row
     c.kind = f.k <= (f.xo ? 32 : 64) ? MXA_FIN_GATHER16 : MXA_FIN_GATHER32;
   c.reads_mask = c.kind == MXA_FIN_MFMA || c.kind == MXA_FIN_MFMA_LONG;
-  // long rows and MXINT4 P: float32 without the proj's codes, and not on the 32-row or the dense row
-  // kernel (a K table of <= 512 keys, MXINT8 P only)
-  if ((lng || w4) && (f.xdt || f.xo || c.kind == MXA_FIN_GATHER32 || c.kind == MXA_FIN_DENSE_ROWS))
+  // long rows and MXINT4 P: float32 without the proj's codes (but the fused blocks' on the LONG 16-row
+  // kernel at MXINT8), and not on the 32-row or the dense row kernel (a K table of <= 512 keys, MXINT8 P only)
+  const bool lxo = f.block && lng && !w4 && c.kind == MXA_FIN_GATHER16;
+  if ((lng || w4) && (f.xdt || (f.xo && !lxo) || c.kind == MXA_FIN_GATHER32 || c.kind == MXA_FIN_DENSE_ROWS))
     c.status = MXA_ERR_UNSUPPORTED;
   return c;
 }
@@ -268,6 +271,7 @@ int launch_finish16_x1(const Rows2Args& ra, int BH, hipStream_t stream, bool pla
 int launch_finish16_l0(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);  // long rows, float32
 int launch_finish16_x0w4(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);  // float32, MXINT4 P
 int launch_finish16_l0w4(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);  // ... on long rows
+int launch_finish16_l0xo(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);  // long rows, the proj's codes
 // the 32-row finishing kernel for NB blocks per head dim (mxa_fin.hip parts 1..4)
 int launch_finish32_p1(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 int launch_finish32_p2(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);

@@ -573,6 +573,14 @@ def _fused_entry(name: str, bits: int):
     return getattr(lib(), name + "_bits_workspace_bytes"), getattr(lib(), name + "_bits"), name + "_bits", (bits,)
 
 
+def _self_block_entry(name: str, bits: int, keys: int):
+    """_fused_entry of a self-attention block on rows of `keys` keys: up to 512 today's call; over 512 the
+    *_full form at either width (include/mxa.h mxa_qkv_attention_full: rows of 513 .. 1,024 keys)."""
+    if keys <= 512:
+        return _fused_entry(name, bits)
+    return getattr(lib(), name + "_full_workspace_bytes"), getattr(lib(), name + "_full"), name + "_full", (bits,)
+
+
 def _proj_params(proj_weight, proj_bias, C: int, rows: int, flush_subnormals: bool, bfloat: int, dev,
                  elem_bits: int = 8):
     """(ProjParams, y (rows, out_features), keep) for the proj Linear behind the attention."""
@@ -597,7 +605,8 @@ def mx_topk_attention_proj(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, sc
     mxa_attention_proj): y = proj(out.transpose(1, 2).reshape(B, N, H*D)) as (B, N, out)
     float32, plus idx (B,H,N,k).  float32 q, k, v (views fine).
     elem_bits 4 (W4A4, mxa_attention_proj_bits): the attention of mx_topk_attention(elem_bits=4) and
-    the proj at MXINT4 -- a weight tensor is prepared at 4 bits, a LinearWeightMX must be a 4-bit one."""
+    the proj at MXINT4 -- a weight tensor is prepared at 4 bits, a LinearWeightMX must be a 4-bit one.
+    Rows of 513 .. 1,024 keys: mxa_attention_proj_full at either width, every k_top <= T."""
     bits = _elem_bits(elem_bits)
     p, dev, (B, H, Nq, T, D), keep = _attn_params(q, k, v, scale, k_top, pred_mode, True, approx, bias,
                                                   flush_subnormals, bfloat, elsa_proj)
@@ -605,7 +614,7 @@ def mx_topk_attention_proj(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, sc
         raise TypeError("the fused proj takes float32 q, k, v")
     idx = _new_idx(p, B, H, Nq, k_top, True, dev)
     pj, y, keep2 = _proj_params(proj_weight, proj_bias, H * D, B * Nq, flush_subnormals, bfloat, dev, bits)
-    size_fn, fn, name, tail = _fused_entry("mxa_attention_proj", bits)
+    size_fn, fn, name, tail = _self_block_entry("mxa_attention_proj", bits, T)
     _call_with_workspace(size_fn, fn, name, p, None, ctypes.byref(pj), *tail, dev=dev)
     return y.reshape(B, Nq, -1), idx
 
@@ -632,7 +641,10 @@ def mx_qkv_attention(x: torch.Tensor, weight, bias: Optional[torch.Tensor], num_
     it (the output is of that dtype).
     elem_bits 4 (W4A4, mxa_qkv_attention_bits / mxa_attention_proj_bits): x, the weights, Q, K, P, V
     and the proj's input at MXINT4 -- weight tensors are prepared at 4 bits, a LinearWeightMX must be a
-    4-bit one; float32, no autocast."""
+    4-bit one; float32, no autocast.
+    More than 512 tokens (up to 1,024: PixArt / DiT at 512 x 512, DeiT at 384 x 384): mxa_qkv_attention_full /
+    mxa_attention_proj_full at either width -- everything mx_topk_attention serves on such rows, the dense
+    branch without the proj; autocast there raises NativeError (status -2)."""
     bits = _elem_bits(elem_bits)
     if bits == 4 and autocast not in (None, torch.float32):
         raise ValueError("elem_bits=4 runs in float32: no autocast")
@@ -662,11 +674,11 @@ def mx_qkv_attention(x: torch.Tensor, weight, bias: Optional[torch.Tensor], num_
             raise ValueError("the fused proj runs on the float32 top-k path")
         pj, y, keep2 = _proj_params(proj_weight, proj_bias, num_heads * D, B * Ntok, flush_subnormals, bfloat, dev, bits)
         p.out = None
-        size_fn, fn, name, tail = _fused_entry("mxa_attention_proj", bits)
+        size_fn, fn, name, tail = _self_block_entry("mxa_attention_proj", bits, Ntok)
         _call_with_workspace(size_fn, fn, name, p, ctypes.byref(xp), ctypes.byref(pj), *tail, dev=dev, bad="bad shape")
         y = y.reshape(B, Ntok, -1)
         return (y, idx, qkv) if return_qkv else (y, idx)
-    size_fn, fn, name, tail = _fused_entry("mxa_qkv_attention", bits)
+    size_fn, fn, name, tail = _self_block_entry("mxa_qkv_attention", bits, Ntok)
     _call_with_workspace(size_fn, fn, name, p, ctypes.byref(xp), *tail, dev=dev, bad="bad shape")
     return (out, idx, qkv) if return_qkv else (out, idx)
 

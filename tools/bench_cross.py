@@ -5,12 +5,16 @@
       tokens, T = 120 text tokens, C = C_kv = 1152, H = 16 (D = 72), k = 20, the mask bias;
   --block self: M.mx_qkv_attention (with the proj Linear) against M.mx_linear (qkv),
       M.mx_topk_attention, M.mx_linear (proj) at the 256 x 256 image: B = 8, N = 256, C = 1152, H = 16,
-      k = 20, no bias.
+      k = 20, no bias.  --tokens / --batch / --channels / --heads give another self-attention shape: over
+      512 tokens the fused call is the *_full entry point (rows of 513 .. 1,024 keys) -- the 512 x 512
+      image is --tokens 1024 --batch 2; DeiT-base at 384 x 384 (D = 64: the proj's codes straight from the
+      finishing kernel) --tokens 577 --batch 8 --channels 768 --heads 12.
 MXINT4 and ex_pred approximators, flush_subnormals.  --elem-bits 4: every Linear and the attention at
 MXINT4 (W4A4, the reference's PixArt script; the fused call is the *_bits entry point).  --bfloat: the
 bfloat setting of every op (the script runs 16).  The defaults reproduce the MXINT8 cross run.
 
     python tools/bench_cross.py [--block cross|self] [--elem-bits 8|4] [--bfloat 0] [--steps 20] [--warmup 3] [--reps 3]
+                                [--tokens N] [--batch B] [--channels C] [--heads H]      (--block self only)
 
 Both chains and both modes are warmed up first; then per mode `reps` repetitions alternate the
 two chains, each timed with device events around `steps` calls.  Prints per mode the median
@@ -28,7 +32,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import mx_quantization_amd as M  # noqa: E402
 from ab_routes import timed  # noqa: E402
 
-B, N, T, C, CKV, H, K_TOP = 8, 256, 120, 1152, 1152, 16, 20
+B_IMG, N_IMG, T_TXT, C_IMG, H_IMG, K_TOP = 8, 256, 120, 1152, 16, 20  # the PixArt-alpha block at 256 x 256
 MODES = ("MXINT4", "ex_pred")
 
 
@@ -40,9 +44,23 @@ def main():
     ap.add_argument("--block", choices=("cross", "self"), default="cross")
     ap.add_argument("--elem-bits", type=int, choices=(8, 4), default=8)
     ap.add_argument("--bfloat", type=int, default=0)
+    ap.add_argument("--tokens", type=int, default=None)
+    ap.add_argument("--batch", type=int, default=None)
+    ap.add_argument("--channels", type=int, default=None)
+    ap.add_argument("--heads", type=int, default=None)
     args = ap.parse_args()
     if args.steps < 20:
         ap.error("--steps must be at least 20")
+    shape_args = (args.tokens, args.batch, args.channels, args.heads)
+    if args.block != "self" and any(a is not None for a in shape_args):
+        ap.error("--tokens / --batch / --channels / --heads go with --block self")
+    # the run's shape: the PixArt block's unless --block self names another
+    N, B, C, H = (d if a is None else a for a, d in zip(shape_args, (N_IMG, B_IMG, C_IMG, H_IMG)))
+    T, CKV = T_TXT, C_IMG
+    if C % H:
+        ap.error("--channels must be a multiple of --heads")
+    pixart = (B, N, C, H) == (B_IMG, N_IMG, C_IMG, H_IMG)
+    label = f"pixart_{args.block}" if pixart else f"self_B{B}_N{N}_C{C}_H{H}"
     dev = torch.device("cuda", 0)
     g = torch.Generator(device="cpu").manual_seed(0)
     D = C // H
@@ -98,7 +116,7 @@ def main():
         diff = (torch.linalg.norm((yf - yu).double()) / torch.linalg.norm(yu.double())).item()
         shape = (B, N, T, C, H, K_TOP) if args.block == "cross" else (B, N, N, C, H, K_TOP)
         print(json.dumps({
-            "shape": f"pixart_{args.block}", "B_N_T_C_H_k": shape, "pred_mode": mode, "elem_bits": args.elem_bits,
+            "shape": label, "B_N_T_C_H_k": shape, "pred_mode": mode, "elem_bits": args.elem_bits,
             "bfloat": args.bfloat, "steps": args.steps, "reps": args.reps,
             "fused_ms_median": round(statistics.median(tf), 4), "fused_ms_spread": round(max(tf) - min(tf), 4),
             "unfused_ms_median": round(statistics.median(tu), 4), "unfused_ms_spread": round(max(tu) - min(tu), 4),
