@@ -137,7 +137,8 @@ int mxa_approx_values_bits(const void* x, void* out, int64_t rows, int32_t d, in
  * as called at workloads/deit/scripts/main.py:123, workloads/DiT/models.py:194,
  * workloads/PixArt/models/MX_transformer_block.py:678, :825.
  * rows x n with leading dim ld; n <= 1024 (PixArt 512x512 self-attention rows:
- * MX_transformer_block.py:648-717, 1,024 tokens).  out_vals nullable.
+ * MX_transformer_block.py:648-717, 1,024 tokens).  out_vals nullable.  k == 0 keeps nothing:
+ * out_idx may be null, and out_mask (if given) is cleared by a kernel.
  * out_mask (nullable): the prune mask zeros.scatter_(-1, idx, 1) of the callers
  * (deit main.py:147-148; examples/deit/top_k.py:16-42) as rows x ceil(n/32)
  * words, bit j%32 of word j/32 set iff j is kept.  vals / out_vals: dtype (MXA_DT_*).

@@ -135,6 +135,11 @@ int MXA_SEL_FN(MXA_SEL_PART)(const Rows2Args& ra, int BH, hipStream_t stream, bo
 using namespace mxa;
 
 // ---- standalone top-k: one DPP row per row (mxa_topk_grp.hpp) -----------------------
+// words zero words at p, a grid-stride loop
+__global__ __launch_bounds__(256) void clear_words_kernel(uint32_t* p, int64_t words) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < words; i += (int64_t)gridDim.x * 256) p[i] = 0u;
+}
+
 template <int NP>
 static int launch_topk_wave(const GrpTopkArgs& ga, hipStream_t stream) {
   const size_t lds = (size_t)4 * wrow_bytes(ga.n);
@@ -182,7 +187,8 @@ static int launch_topk_packed(const GrpTopkArgs& ga, const TopkWs& w, unsigned g
 }
 
 static int topk_check(const void* vals, int64_t rows, int32_t n, int64_t ld, int32_t k, int64_t* out_idx, int32_t dtype) {
-  if (!vals || !out_idx || rows < 0 || n <= 0 || ld < n || k < 0 || k > n) return MXA_ERR_ARG;
+  // (k == 0 keeps nothing: no index is written, and an empty buffer's pointer may be null)
+  if (!vals || (!out_idx && k > 0) || rows < 0 || n <= 0 || ld < n || k < 0 || k > n) return MXA_ERR_ARG;
   if (dtype != kF32 && dtype != kF16 && dtype != kBF16) return MXA_ERR_ARG;
   if (n > kWMaxN) return MXA_ERR_UNSUPPORTED;
   return MXA_OK;
@@ -198,10 +204,12 @@ extern "C" int mxa_topk(const void* vals, int64_t rows, int32_t n, int64_t ld, i
   int rc = topk_check(vals, rows, n, ld, k, out_idx, dtype);
   if (rc) return rc;
   if (rows == 0) return MXA_OK;
-  if (k == 0) {
-    if (out_mask) return hipMemsetAsync(out_mask, 0, (size_t)rows * ((n + 31) / 32) * 4, stream) == hipSuccess
-                             ? MXA_OK : MXA_ERR_LAUNCH;
-    return MXA_OK;
+  if (k == 0) {  // nothing kept: an all-zero mask, cleared by a kernel (a captured graph replays a kernel node)
+    if (!out_mask) return MXA_OK;
+    const int64_t words = rows * (int64_t)((n + 31) / 32);
+    hipLaunchKernelGGL(clear_words_kernel, dim3((unsigned)std::min<int64_t>((words + 255) / 256, 4096)), dim3(256), 0, stream,
+                       out_mask, words);
+    return launch_status();
   }
   const GrpTopkArgs ga{vals, rows, ld, n, k, out_idx, out_vals, out_mask, dtype};
   // rows of 513..1024 (PixArt 512x512 self-attention): one wave per row (mxa_topk_wave.hpp);

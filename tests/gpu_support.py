@@ -2,13 +2,15 @@
 the GPU, the two equalities, the tolerance checks, the golden directory, the package fixture,
 and the attention op's harness: attn_run (the op to host arrays), check_attn (its scores,
 indices and mask against a reference), attn_entry (one C entry point called directly),
-check_siblings (every entry point that accepts a call against mxa_attention_full and the op), rnd,
+check_siblings (every entry point that accepts a call against mxa_attention_full and the op), bind / workspace /
+launch (mxa_attention_full on a workspace and a stream of the test's own) and same_bytes, rnd,
 host_params and the RCase tables' r_scale / r_kw.  Imported like the *_cases.py modules (`from gpu_support import M  # noqa: F401`
 brings the fixture into a test file); it imports without a GPU -- torch.cuda is touched only
 inside dev / from_bits -- so the CPU tests use same, same_bits and load from here too.
 
 same is value equality (-0.0 equals +0.0), same_bits compares bit patterns (it does not): a
 call site keeps the one it has."""
+import ctypes
 import os
 
 import numpy as np
@@ -383,6 +385,36 @@ def check_siblings(M, q, k, v, scale, widths, **kw):
         for name, width in names[1:]:
             name = name.replace("attention", "approx_scores")
             _equal_bits(attn_entry(M, name, q, k, None, 1.0, width), pred, f"{name} w{bits}")
+
+
+# ---- mxa_attention_full on a workspace and a stream of the test's own ----------------------------
+def bind(M, q, k, v, scale, k_top):
+    """AttnParams of the ex_pred top-k call on device tensors with fresh out, idx and mask bound"""
+    p, dv, (B, H, n, t, D), keep = M.ops._attn_params(q, k, v, scale, k_top, "ex_pred", True, True, None, False, 0, None)
+    res = dict(out=M.ops._bind_out(p, torch.full((B, H, n, D), float("nan"), device=dv)),
+               idx=M.ops._new_idx(p, B, H, n, k_top, True, dv),
+               mask=torch.zeros((B, H, n, (t + 31) // 32), dtype=torch.int32, device=dv))
+    p.mask_out = res["mask"].data_ptr()
+    return p, res, keep
+
+
+def workspace(M, p):
+    nbytes = M._native.lib().mxa_attention_full_workspace_bytes(ctypes.byref(p), 8)
+    assert nbytes > 0
+    return torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
+
+
+def launch(M, p, ws, stream):
+    p.workspace, p.workspace_bytes = ws.data_ptr(), ws.numel()
+    M._native.check(M._native.lib().mxa_attention_full(ctypes.byref(p), 8, stream), "mxa_attention_full")
+
+
+def same_bytes(got, want, what):
+    """dicts of host arrays: every array of want, its dtype and its bytes"""
+    for name in want:
+        g, w = got[name], want[name]
+        assert g.dtype == w.dtype and g.shape == w.shape, (what, name, g.dtype, w.dtype, g.shape, w.shape)
+        assert np.array_equal(np.ascontiguousarray(g).reshape(-1).view(np.uint8), np.ascontiguousarray(w).reshape(-1).view(np.uint8)), (what, name)
 
 
 def quantize_bfloat_in_dtype(A, bfloat):

@@ -41,6 +41,8 @@ def test_status_strings_and_arg_errors():
     assert lib.mxa_quantize_mx(1, 1, None, None, 1, 1, 1, 32, 8, 8, 0, 0, 0, 7, None) == -1  # bad dtype
     assert lib.mxa_topk(1, 1, 1100, 1100, 3, 1, None, None, 0, None) == -2  # n > 1024
     assert lib.mxa_topk(1, 1, 10, 10, 11, 1, None, None, 0, None) == -1  # k > n
+    assert lib.mxa_topk(1, 1, 10, 10, 0, None, None, None, 0, None) == 0  # k = 0 keeps nothing: no index buffer (no launch)
+    assert lib.mxa_topk(1, 1, 10, 10, 3, None, None, None, 0, None) == -1  # ... which k > 0 needs
     assert lib.mxa_topk(1, 1, 10, 10, 3, 1, None, None, 5, None) == -1  # bad dtype
     p = N.AttnParams()
     assert lib.mxa_attention_workspace_bytes(p) == -1

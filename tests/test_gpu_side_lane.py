@@ -5,18 +5,21 @@ one-lane tail.
 What the caller must not notice: two calls back to back on one shared workspace (call n + 1's builders
 against call n's finishing kernel), the same on a non-default stream behind a long kernel, a call
 whose rows split between the tail and the 64-bit pass, and the tables themselves -- byte for byte
-what the one-pass builder writes.
+what the one-pass builder writes.  Two callers of the one lane: two streams that alternate, and two host
+threads, each with a workspace of its own.
 
 Shapes: B 2, H 2, N = T = 70 and 197, D 64, k 20, ex_pred: the packed pass, the one-lane tail and
 finish16_kernel all run (mxa_launch.hpp tail_width_for, finish_choice)."""
 import ctypes
 import functools
+import threading
 
 import numpy as np
 import pytest
 import torch
 
-from gpu_support import M, OUT_TOL, check_attn, dev, host, out_close, rnd  # noqa: F401
+import gpu_support
+from gpu_support import M, OUT_TOL, check_attn, dev, host, launch, out_close, rnd, same_bytes, workspace  # noqa: F401
 from oracle import mx_oracle as O
 
 B, H, D, K = 2, 2, 64, 20
@@ -70,26 +73,9 @@ def test_mixed_case_has_both_kinds_of_row(n):
     assert np.array_equal(r["pred"], pred)
 
 
-# ---- the entry point on a workspace and a stream of the test's own -------------------------------
+# ---- the entry point on a workspace and a stream of the test's own (gpu_support.bind / workspace / launch) ----
 def bind(M, q, k, v):
-    """AttnParams of the ex_pred top-k call on device tensors with fresh out, idx and mask bound"""
-    p, dv, (_, _, n, t, _), keep = M.ops._attn_params(q, k, v, SCALE, K, "ex_pred", True, True, None, False, 0, None)
-    res = dict(out=M.ops._bind_out(p, torch.full((B, H, n, D), float("nan"), device=dv)),
-               idx=M.ops._new_idx(p, B, H, n, K, True, dv),
-               mask=torch.zeros((B, H, n, (t + 31) // 32), dtype=torch.int32, device=dv))
-    p.mask_out = res["mask"].data_ptr()
-    return p, res, keep
-
-
-def workspace(M, p):
-    nbytes = M._native.lib().mxa_attention_full_workspace_bytes(ctypes.byref(p), 8)
-    assert nbytes > 0
-    return torch.zeros(nbytes, dtype=torch.uint8, device="cuda")
-
-
-def launch(M, p, ws, stream):
-    p.workspace, p.workspace_bytes = ws.data_ptr(), ws.numel()
-    M._native.check(M._native.lib().mxa_attention_full(ctypes.byref(p), 8, stream), "mxa_attention_full")
+    return gpu_support.bind(M, q, k, v, SCALE, K)
 
 
 def alone(M, qkv):
@@ -114,12 +100,6 @@ def pair_alone(M, n):
     if n not in _ALONE:
         _ALONE[n] = tuple(alone(M, x) for x in pair(n))
     return _ALONE[n]
-
-
-def same_bytes(got, want, what):
-    for name in want:
-        g, w = got[name], want[name]
-        assert g.dtype == w.dtype and np.array_equal(g.view(np.uint8), w.view(np.uint8)), (what, name)
 
 
 def back_to_back(M, n, stream, ahead=None):
@@ -189,6 +169,91 @@ def test_tail_rows_and_left_rows_in_a_forked_call(M, n):
     got = dict(out=host(res[0]), idx=host(res[1]), true=host(res[2]), pred=host(res[3]), mask=host(M.unpack_mask(res[4], n)))
     check_attn(got, r, f"N{n}")
     out_close(got["out"], r["out"], OUT_TOL, f"N{n} out")
+
+
+# ---- two callers of the one lane (one per device, with its two events and the process-wide lock) ----
+CALLS = 4  # forked calls per caller
+
+
+@functools.lru_cache(maxsize=None)
+def three(n):
+    """pair(n) plus a third seed: the inputs the two callers' calls cycle through"""
+    return pair(n) + (inputs(n, 5),)
+
+
+_THREE = {}
+
+
+def three_alone(M, n):
+    if n not in _THREE:
+        _THREE[n] = pair_alone(M, n) + (alone(M, three(n)[2]),)
+    return _THREE[n]
+
+
+class Caller:
+    """a stream, a workspace and CALLS bound calls of its own; call j of caller c takes input set (c + j) % 3"""
+
+    def __init__(self, M, n, c):
+        self.sets = [(c + j) % 3 for j in range(CALLS)]
+        self.keep = [[dev(x) for x in three(n)[i]] for i in self.sets]
+        self.calls = [bind(M, *t) for t in self.keep]
+        self.ws = workspace(M, self.calls[0][0])
+        self.stream = torch.cuda.Stream()
+
+    def issue(self, M, j):
+        launch(M, self.calls[j][0], self.ws, self.stream.cuda_stream)
+
+    def check(self, M, n, what):
+        want = three_alone(M, n)
+        for j, (_, res, _) in enumerate(self.calls):
+            same_bytes({a: host(x) for a, x in res.items()}, want[self.sets[j]], f"N{n} {what} call {j}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", SIZES)
+def test_two_caller_streams_alternate_on_the_lane(M, n):
+    """forked calls issued S1, S2, S1, S2, ... on two streams, each with a workspace and inputs of its own, no host
+    synchronisation in between: the lane's `packed` and `join` events are recorded again by the other stream's call
+    while a call's kernels are still queued, and every call's out, idx and mask words are the bytes it writes alone"""
+    callers = [Caller(M, n, c) for c in range(2)]
+    three_alone(M, n)
+    torch.cuda.synchronize()  # the inputs, outputs and workspaces exist before the callers' streams use them
+    for j in range(CALLS):
+        for c in callers:
+            c.issue(M, j)
+    torch.cuda.synchronize()
+    for i, c in enumerate(callers):
+        c.check(M, n, f"stream {i}")
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("n", SIZES)
+def test_two_host_threads_share_the_lane(M, n):
+    """two threads, each with a stream, a workspace and inputs of its own, make their forked calls through the C entry
+    point at once (ctypes releases the GIL): forked calls are serialised for the moment of their enqueue
+    (INTEGRATION.md), so each call's bytes are those it writes alone; an exception in a thread fails the test"""
+    callers = [Caller(M, n, c) for c in range(2)]
+    three_alone(M, n)
+    torch.cuda.synchronize()
+    errors = []
+
+    def run(c):
+        try:
+            for j in range(CALLS):
+                c.issue(M, j)
+        except BaseException as e:  # noqa: BLE001 (handed to the test's thread)
+            errors.append(e)
+
+    threads = [threading.Thread(target=run, args=(c,)) for c in callers]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join()
+    torch.cuda.synchronize()
+    if errors:
+        raise errors[0]
+    for i, c in enumerate(callers):
+        c.check(M, n, f"thread {i}")
 
 
 # ---- the tables of a forked call (the rows launch without V's blocks in its grid) ---------------
