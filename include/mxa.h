@@ -147,6 +147,16 @@ int mxa_topk(const void* vals, int64_t rows, int32_t n, int64_t ld, int32_t k,
              int64_t* out_idx, void* out_vals, uint32_t* out_mask, int32_t dtype, hipStream_t stream);
 
 /*
+ * mxa_topk for rows of 1,025 .. 4,096 values with 1 <= k <= 64 and k * 64 <= n, where torch
+ * takes std::partial_sort: libstdc++'s __heap_select + __sort_heap replayed on a heap held one
+ * element per lane (the selection body of mxa_attention_xl).  The same arguments, dtypes and
+ * outputs.  n <= 1,024: mxa_topk itself.  MXA_ERR_UNSUPPORTED: n > 4,096, and with n > 1,024
+ * k == 0, k > 64 or k * 64 > n (the nth_element regime).
+ */
+int mxa_topk_xl(const void* vals, int64_t rows, int32_t n, int64_t ld, int32_t k,
+                int64_t* out_idx, void* out_vals, uint32_t* out_mask, int32_t dtype, hipStream_t stream);
+
+/*
  * mxa_topk with a device workspace (the same results): rows of <= 256 values go through
  * the packed 32-bit selection pass and the one-lane tail (the fused op's selection
  * engine), which stage per-row state in the workspace.  mxa_topk_workspace_bytes:
@@ -309,6 +319,27 @@ int mxa_attention_full(const mxa_attn_params* p, int32_t elem_bits, hipStream_t 
 int mxa_attention_full_finish_kernel(const mxa_attn_params* p, int32_t elem_bits);
 
 /*
+ * mxa_attention_full plus rows of 1,025 .. 4,096 keys: PixArt-Sigma at 1024 x 1024 runs its
+ * self-attention (workloads/PixArt/models/MX_transformer_block.py:648-717) on 3,840 .. 4,096
+ * latent tokens with self_k = 20.  The same parameter struct, strides, outputs and workspace rules.
+ *   - every call mxa_attention_full(p, elem_bits) accepts runs exactly what that runs: the same
+ *     kernels, bytes, statuses and workspace size;
+ *   - with 1,024 < T <= 4,096 also the top-k branch with 1 <= k_top <= 64 and k_top * 64 <= T --
+ *     where torch.topk on CPU takes std::partial_sort (TopKImpl.h:45-86) -- at elem_bits 8 and 4,
+ *     float32: select_xl_kernel (the scores' order keys in a per-wave LDS strip, libstdc++'s
+ *     __heap_select + __sort_heap on a heap held one element per lane), then finish16_xl_kernel
+ *     (finish16_kernel's arithmetic with the keys walked in chunks of 1,024).
+ * MXA_ERR_UNSUPPORTED, before any HIP call, for every other call with T > 1,024: top_k == 0,
+ * k_top > 64, k_top * 64 > T (the nth_element regime), T > 4,096, float16 / bfloat16 tensors or a
+ * nonzero score_dtype, MXA_PRED_ELSA (with approx).  There is no scores-only or fused-projection
+ * form on such rows.  mxa_attention_xl_finish_kernel: the MXA_FIN_* kind of the call (no launch;
+ * the workspace may be null) -- MXA_FIN_GATHER16_XL on those rows.
+ */
+int64_t mxa_attention_xl_workspace_bytes(const mxa_attn_params* p, int32_t elem_bits);
+int mxa_attention_xl(const mxa_attn_params* p, int32_t elem_bits, hipStream_t stream);
+int mxa_attention_xl_finish_kernel(const mxa_attn_params* p, int32_t elem_bits);
+
+/*
  * Which kernels mxa_attention(p) runs (no launch; the workspace may be null):
  *   MXA_PATH_ROWS_SPLIT  selection kernel (scores + top-k) then finishing kernel
  *                        (gather, softmax, MX(P), P.V on int8 MFMA) -- top_k != 0
@@ -332,8 +363,11 @@ int mxa_attention_path(const mxa_attn_params* p);
  * and, reported by mxa_attention_full_finish_kernel for mxa_attention_full alone:
  *   MXA_FIN_MFMA_LONG        finish_qk_long_kernel: top-k with k >= 65 on rows over 512 keys
  *   MXA_FIN_DENSE_MFMA_LONG  finish_qk_long_kernel: top_k == 0 on rows over 512 keys
+ * and by mxa_attention_xl_finish_kernel for mxa_attention_xl alone:
+ *   MXA_FIN_GATHER16_XL      finish16_xl_kernel: top-k with k <= 64 on rows over 1,024 keys
  * or a negative MXA_ERR_* for invalid parameters.
  */
+#define MXA_FIN_GATHER16_XL 8
 #define MXA_FIN_GATHER16 1
 #define MXA_FIN_GATHER32 2
 #define MXA_FIN_MFMA 3

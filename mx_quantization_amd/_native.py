@@ -36,6 +36,8 @@ FIN_KERNELS = {1: ("finish16_kernel", "v_dot4 (kept keys)", "v_mfma_i32_16x16x32
 FIN_KERNELS_FULL = {6: ("finish_qk_long_kernel", "v_mfma_i32_16x16x32_i8 (every key, prune mask in the softmax)",
                    "v_mfma_i32_16x16x32_i8"),
                     7: ("finish_qk_long_kernel (dense: every key kept)", "v_mfma_i32_16x16x32_i8", "v_mfma_i32_16x16x32_i8")}
+# mxa_attention_xl_finish_kernel reports this one besides: rows of 1,025 .. 4,096 keys
+FIN_KERNELS_XL = {8: ("finish16_xl_kernel", "v_dot4 (kept keys)", "v_mfma_i32_16x16x32_i8")}
 PRED_MODES = {"ex_pred": 0, "partial_Q": 1, "partial_K": 2, "MXINT4": 3, "two_step_leading_ones": 4,
               "true_ex": 5, "ELSA": 6}
 ROUND_MODES = {"nearest": 0, "floor": 1, "even": 2}
@@ -90,6 +92,7 @@ _SIGS = {
     "mxa_approx_values": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "mxa_approx_values_bits": (c_i32, [c_vp, c_vp, c_i64, c_i32, c_i64, c_i64, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "mxa_topk": (c_i32, [c_vp, c_i64, c_i32, c_i64, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp]),
+    "mxa_topk_xl": (c_i32, [c_vp, c_i64, c_i32, c_i64, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp]),
     "mxa_topk_workspace_bytes": (c_i64, [c_i64, c_i32, c_i32]),
     "mxa_topk_ws": (c_i32, [c_vp, c_i64, c_i32, c_i64, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp, c_i64, c_vp]),
     "mxa_attention_workspace_bytes": (c_i64, [ctypes.POINTER(AttnParams)]),
@@ -105,6 +108,9 @@ _SIGS = {
     "mxa_attention_full_workspace_bytes": (c_i64, [c_vp, c_i32]),
     "mxa_attention_full": (c_i32, [c_vp, c_i32, c_vp]),
     "mxa_attention_full_finish_kernel": (c_i32, [c_vp, c_i32]),
+    "mxa_attention_xl_workspace_bytes": (c_i64, [c_vp, c_i32]),
+    "mxa_attention_xl": (c_i32, [c_vp, c_i32, c_vp]),
+    "mxa_attention_xl_finish_kernel": (c_i32, [c_vp, c_i32]),
     "mxa_attention_path": (c_i32, [ctypes.POINTER(AttnParams)]),
     "mxa_attention_finish_kernel": (c_i32, [ctypes.POINTER(AttnParams)]),
     "mxa_attention_timed": (c_i32, [ctypes.POINTER(AttnParams), c_vp, c_i32, ctypes.POINTER(c_f32)]),

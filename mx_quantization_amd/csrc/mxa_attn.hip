@@ -6,6 +6,10 @@
 //   select_kernel               approximate scores + torch-CPU-order top-k, four query
 //                               rows per wave (mxa_select.hpp, mxa_topk_grp.hpp), the
 //                               one-lane tail (mxa_tail.hpp)
+//   select_xl_kernel / finish16_xl_kernel
+//                               mxa_attention_xl on rows of 1,025 .. 4,096 keys (top-k, k * 64 <= T): the
+//                               streaming heap selection (mxa_select_xl.hpp), then the keys in chunks of 1,024
+//                               (mxa_finish16_xl.hpp)
 //   select_long_kernel          rows of 513 .. 1,024 keys (mxa_attention_long): one wave per query
 //                               row, the scores into the wave top-k's mirror (mxa_select_long.hpp);
 //                               finish16_kernel then reads the kept keys from the workspace
@@ -109,8 +113,10 @@ ModeNeeds mode_needs(int mode) {
 // same kernels.  kReachShort: rows of at most 512 keys; kReachLong (the *_long and *_bits entry points):
 // rows of at most kLongRowsT keys on the kernels that existed before finish_qk_long_kernel; kReachFull
 // (mxa_attention_full): those rows' dense branch and k_top > 64 too; kReachBlock (mxa_qkv_attention_full,
-// mxa_attention_proj_full): on those rows the fused qkv projection and the proj Linear as well
-enum Reach { kReachShort, kReachLong, kReachFull, kReachBlock };
+// mxa_attention_proj_full): on those rows the fused qkv projection and the proj Linear as well.
+// kReachXl (mxa_attention_xl) stands beside kReachBlock, not above it: kReachFull's calls plus the top-k
+// branch on rows of 1,025 .. kXlRowsT keys (xl_rows_ok), none of the fused projections there or on long rows
+enum Reach { kReachShort, kReachLong, kReachFull, kReachBlock, kReachXl };
 
 // the proj Linear's input comes MX-quantized out of the finishing kernel (MXINT8 only: at 4 bits the
 // fp32 rows go through the workspace and the row quantizer for every D; rows over 512 keys: from the LONG
@@ -143,7 +149,8 @@ struct AttnCall {
 // as the kernels see them (attention_impl's copy)
 FinFacts attn_fin_facts(const AttnCall& c, const mxa_attn_params* p) {
   return {p->top_k != 0, p->top_k ? p->k_top : 0, p->T, (p->D + 31) / 32, c.pj && proj_codes_direct(p, c.elem_bits, c.reach),
-          p->dtype != MXA_DT_F32 || p->score_dtype > MXA_DT_F32, c.elem_bits, c.reach >= kReachFull, c.reach == kReachBlock};
+          p->dtype != MXA_DT_F32 || p->score_dtype > MXA_DT_F32, c.elem_bits, c.reach >= kReachFull, c.reach == kReachBlock,
+          c.reach == kReachXl};
 }
 
 // one side's (Q's or K's) row operands; null: the score mode does not read it
@@ -270,7 +277,12 @@ int attn_validate(const AttnCall& c) {
       (p->pred_mode == MXA_PRED_EXION || p->pred_mode == MXA_PRED_TRUE_EX || p->pred_mode == MXA_PRED_ELSA))
     return MXA_ERR_UNSUPPORTED;
   if (!valid_bfloat(p->bfloat)) return MXA_ERR_ARG;
-  if (p->T > (reach == kReachShort ? kShortRowsT : kLongRowsT) || p->D > 32 * kMaxNB) return MXA_ERR_UNSUPPORTED;
+  if (p->T > (reach == kReachShort ? kShortRowsT : reach == kReachXl ? kXlRowsT : kLongRowsT) || p->D > 32 * kMaxNB)
+    return MXA_ERR_UNSUPPORTED;
+  // rows over 1,024 keys: the top-k branch in partial_sort's regime alone (the rest of their refusals --
+  // 16-bit dtypes, the fused projections -- are the long rows', below, and finish_choice's)
+  if (xl_rows(p->T) && (scores_only || !p->top_k || !xl_rows_ok(p->T, p->k_top) || (p->approx && p->pred_mode == MXA_PRED_ELSA)))
+    return MXA_ERR_UNSUPPORTED;
   // rows over 512 keys: float32, no fused projection but kReachBlock's qkv and proj Linears; MXINT4:
   // float32, and the approximators of exponent_approximation (ELSA's hashes would need the width too)
   const bool xdt = p->dtype != MXA_DT_F32 || p->score_dtype > MXA_DT_F32;
@@ -569,6 +581,7 @@ int attention_impl(const AttnCall& c) {
   // feasibility of the path's kernels (LDS budgets), before any pointer is bound
   // (rows over 512 keys: the one-wave-per-row selection kernel, mxa_select_long.hpp)
   auto select = [&](bool plan, const SideLane* side = nullptr) {
+    if (xl_rows(pp.T)) return launch_select_xl(r2, mode, BH, c.stream, plan);  // (mxa_select_xl.hpp)
     return long_rows(pp.T) ? launch_select_long(r2, mode, BH, c.stream, plan) : launch_select(r2, mode, BH, c.stream, plan, side);
   };
   rc = c.scores_only ? MXA_OK : launch_rows(r2, ff, mode == kModeTrue, S, BH, c.stream, true);
@@ -723,6 +736,22 @@ extern "C" int mxa_attention_full(const mxa_attn_params* p, int32_t elem_bits, h
 extern "C" int mxa_attention_full_finish_kernel(const mxa_attn_params* p, int32_t elem_bits) {
   int plan = -1, fin = -1;
   const int rc = attention_impl({.p = p, .reach = kReachFull, .plan = &plan, .fin = &fin, .elem_bits = elem_bits});
+  return rc ? rc : fin;
+}
+
+// mxa_attention_full plus the top-k branch on rows of 1,025 .. 4,096 keys with k_top <= 64 and
+// k_top * 64 <= T (MX_transformer_block.py:648-717 at 1024 x 1024): select_xl_kernel, finish16_xl_kernel
+extern "C" int64_t mxa_attention_xl_workspace_bytes(const mxa_attn_params* p, int32_t elem_bits) {
+  return mx_width_ok(elem_bits) && attn_shape_ok(p) ? attn_workspace_total({.p = p, .reach = kReachXl}) : -1;
+}
+
+extern "C" int mxa_attention_xl(const mxa_attn_params* p, int32_t elem_bits, hipStream_t stream) {
+  return attention_impl({.p = p, .stream = stream, .reach = kReachXl, .elem_bits = elem_bits});
+}
+
+extern "C" int mxa_attention_xl_finish_kernel(const mxa_attn_params* p, int32_t elem_bits) {
+  int plan = -1, fin = -1;
+  const int rc = attention_impl({.p = p, .reach = kReachXl, .plan = &plan, .fin = &fin, .elem_bits = elem_bits});
   return rc ? rc : fin;
 }
 

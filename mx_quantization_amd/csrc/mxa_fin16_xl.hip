@@ -1,0 +1,59 @@
+// Launches of the chunked 16-row finishing kernel (mxa_finish16_xl.hpp: rows of 1,025 .. 4,096
+// keys, k <= 64, float32).  Compiled twice (build_native.py): MXA_F16XL_W4=0 the MXINT8-P
+// instantiations (launch_finish16_xl_w8), MXA_F16XL_W4=1 the MXINT4-P ones (launch_finish16_xl_w4).
+#include "mxa_finish16_xl.hpp"
+#include "mxa_launch.hpp"
+
+#ifndef MXA_F16XL_W4
+#define MXA_F16XL_W4 0
+#endif
+#if MXA_F16XL_W4
+#define MXA_F16XL_FN launch_finish16_xl_w4
+#else
+#define MXA_F16XL_FN launch_finish16_xl_w8
+#endif
+
+namespace mxa {
+
+constexpr bool kF16XlW4 = MXA_F16XL_W4 != 0;
+
+// waves per workgroup by finish_tile_plan (mxa_launch.hpp) from the waves per SIMD the kernel's
+// registers allow
+static int finish16_xl_plan(const Rows2Args& ra, int BH, int regs_waves_per_simd, int* waves, int* rows_per_wg) {
+  auto lds = [&](int w) { return fin16_xl_lds(ra.D, ra.ntb, w).total; };
+  return finish_tile_plan(kFin16, ra.N, BH, lds, finish_wave_cap(regs_waves_per_simd), waves, rows_per_wg);
+}
+template <int NB, int KS, bool EXTRA>
+static int launch_finish16_xl_x(const Rows2Args& ra0, int BH, hipStream_t stream) {
+  Rows2Args ra = ra0;
+  constexpr auto kernel = &finish16_xl_kernel<NB, KS, EXTRA, kF16XlW4>;
+  const int rc = finish16_xl_plan(ra, BH, kernel_waves_per_simd<kernel>(), &ra.waves, &ra.rows_per_wg);
+  if (rc) return rc;
+  return launch_finish_tiles<kernel>(ra, BH, fin16_xl_lds(ra.D, ra.ntb, ra.waves).total, stream);
+}
+template <int NB>
+static int launch_finish16_xl_nb(const Rows2Args& ra, int BH, hipStream_t stream) {
+  // EXTRA: a bias, the debug true scores or bfloatX rounding
+  const bool extra = ra.bias || ra.true_out || (ra.bfloat != 0 && ra.bfloat != 32);
+  auto ks = [&](auto ks_c) {
+    constexpr int KS = decltype(ks_c)::value;
+    return extra ? launch_finish16_xl_x<NB, KS, true>(ra, BH, stream) : launch_finish16_xl_x<NB, KS, false>(ra, BH, stream);
+  };
+  // four lanes per row: slots ceil(k / 4), the sizes of finish16_kernel
+  const int n = (ra.k_top + 3) / 4;
+  if (n <= 5) return ks(std::integral_constant<int, 5>{});
+  if (n <= 8) return ks(std::integral_constant<int, 8>{});
+  if (n <= 12) return ks(std::integral_constant<int, 12>{});
+  return ks(std::integral_constant<int, 16>{});
+}
+
+int MXA_F16XL_FN(const Rows2Args& ra, int BH, hipStream_t stream, bool plan) {
+  if (!xl_rows_ok(ra.T, ra.k_top) || ra.xo_codes || ra.s_dt != kF32 || ra.in_dt != kF32) return MXA_ERR_UNSUPPORTED;
+  if (plan) {
+    int w, r;
+    return finish16_xl_plan(ra, BH, 2, &w, &r);
+  }
+  return dispatch_nbd(ra.nbd, [&](auto nb) { return launch_finish16_xl_nb<decltype(nb)::value>(ra, BH, stream); });
+}
+
+}  // namespace mxa

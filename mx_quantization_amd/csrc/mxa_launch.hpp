@@ -77,6 +77,12 @@ inline RowsPrepArgs flat_rows_prep(const void* x, int64_t rows, int cols, int64_
 // from the workspace instead of staging the head's K table (mxa_finish16.hpp)
 constexpr int kShortRowsT = 512, kLongRowsT = 1024;
 inline bool long_rows(int T) { return T > kShortRowsT; }
+// rows of 1,025 .. 4,096 keys (mxa_attention_xl, mxa_topk_xl): the top-k branch where torch takes
+// std::partial_sort (k * 64 <= T), k <= 64 -- the streaming selection (mxa_select_xl.hpp) and the
+// finishing kernel that walks the keys in chunks of 1,024 (mxa_finish16_xl.hpp)
+constexpr int kXlRowsT = 4096;
+inline bool xl_rows(int T) { return T > kLongRowsT; }
+inline bool xl_rows_ok(int T, int k) { return xl_rows(T) && T <= kXlRowsT && k >= 1 && k <= 64 && (int64_t)k * 64 <= T; }
 // The side lane of a forked attention call (mxa_attn.hip, SideFork): the library's own stream beside the
 // caller's, joined before the finishing kernel.  `packed`: the event launch_select records behind the
 // packed pass
@@ -88,6 +94,8 @@ struct SideLane { hipStream_t stream; hipEvent_t packed; };
 int launch_select(const Rows2Args& ra, int mode, int BH, hipStream_t stream, bool plan, const SideLane* side = nullptr);
 // ... for long rows (mxa_sel_long.hip)
 int launch_select_long(const Rows2Args& ra, int mode, int BH, hipStream_t stream, bool plan);
+// ... for rows of 1,025 .. 4,096 keys (mxa_sel_xl.hip)
+int launch_select_xl(const Rows2Args& ra, int mode, int BH, hipStream_t stream, bool plan);
 // the one-lane tail's prefix (measured, DeiT-base: 48 positions 0.575-0.583 ms against 0.585-0.599
 // for 64 -- 12 KB of LDS per wave, 3 waves per SIMD instead of 2, outweighs the selection kernel's
 // extra step -- and 0.573-0.584 for 56; a 32-position prefix is slower: the selection kernel then
@@ -145,8 +153,8 @@ inline int launch_select_mode(const Rows2Args& ra, int mode, int BH, hipStream_t
 // (the call's `direct`, known before any pointer is bound); xdt: float16 / bfloat16 inputs or scores;
 // bits: 8 or 4, P's element width; full: the entry point reaches finish_qk_long_kernel (mxa_attention_full);
 // block: it reaches the fused projections on rows over 512 keys too (the *_full fused blocks), where xo is
-// the LONG 16-row kernel's: MXINT8, k <= 32
-struct FinFacts { bool topk; int k, T, nbd; bool xo, xdt; int bits; bool full; bool block = false; };
+// the LONG 16-row kernel's: MXINT8, k <= 32; xl: it reaches rows of 1,025 .. 4,096 keys (mxa_attention_xl)
+struct FinFacts { bool topk; int k, T, nbd; bool xo, xdt; int bits; bool full; bool block = false; bool xl = false; };
 // kind: MXA_FIN_* (include/mxa.h); reads_mask: the kernel reads the selection's prune-mask words (the
 // caller's mask_out, else a workspace copy), not the kept indices; status: MXA_ERR_UNSUPPORTED where the
 // kind has no instantiation for the facts
@@ -154,6 +162,11 @@ struct FinChoice { int kind; bool reads_mask; int status; };
 inline FinChoice finish_choice(const FinFacts& f) {
   const bool lng = long_rows(f.T), w4 = f.bits == 4, regs = f.T <= 256 && f.nbd <= 4;  // regs: a row's scores in registers
   FinChoice c{};
+  if (f.xl && xl_rows(f.T) && f.topk && f.k <= 64) {  // the chunked 16-row kernel (mxa_finish16_xl.hpp):
+    c.kind = MXA_FIN_GATHER16_XL;                      // float32, top-k in partial_sort's regime
+    c.status = xl_rows_ok(f.T, f.k) && !f.xdt && !f.xo ? MXA_OK : MXA_ERR_UNSUPPORTED;
+    return c;
+  }
   if (f.full && lng && (!f.topk || f.k > 64))  // the tiled MFMA kernel (mxa_finish_qk_long.hpp)
     c.kind = f.topk ? MXA_FIN_MFMA_LONG : MXA_FIN_DENSE_MFMA_LONG;
   else if (!f.topk)  // the dense branch: finish_qk_kernel with every key kept, else the v_dot4 row kernel
@@ -168,6 +181,7 @@ inline FinChoice finish_choice(const FinFacts& f) {
   const bool lxo = f.block && lng && !w4 && c.kind == MXA_FIN_GATHER16;
   if ((lng || w4) && (f.xdt || (f.xo && !lxo) || c.kind == MXA_FIN_GATHER32 || c.kind == MXA_FIN_DENSE_ROWS))
     c.status = MXA_ERR_UNSUPPORTED;
+  if (xl_rows(f.T)) c.status = MXA_ERR_UNSUPPORTED;  // (no other kernel serves rows over 1,024 keys)
   return c;
 }
 
@@ -272,6 +286,9 @@ int launch_finish16_l0(const Rows2Args& ra, int BH, hipStream_t stream, bool pla
 int launch_finish16_x0w4(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);  // float32, MXINT4 P
 int launch_finish16_l0w4(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);  // ... on long rows
 int launch_finish16_l0xo(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);  // long rows, the proj's codes
+// its chunked sibling for rows of 1,025 .. 4,096 keys (mxa_fin16_xl.hip): float32, MXINT8 / MXINT4 P
+int launch_finish16_xl_w8(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
+int launch_finish16_xl_w4(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 // the 32-row finishing kernel for NB blocks per head dim (mxa_fin.hip parts 1..4)
 int launch_finish32_p1(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 int launch_finish32_p2(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
