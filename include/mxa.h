@@ -340,6 +340,28 @@ int mxa_attention_xl(const mxa_attn_params* p, int32_t elem_bits, hipStream_t st
 int mxa_attention_xl_finish_kernel(const mxa_attn_params* p, int32_t elem_bits);
 
 /*
+ * mxa_attention_xl plus the dense branch on rows of 1,025 .. 4,096 keys: at 1024 x 1024 the
+ * reference takes attn = softmax(true scores) (workloads/PixArt/models/MX_transformer_block.py:
+ * 704-705) on those rows when the model runs with self_top_k=False, in the exclude_timesteps (:656)
+ * and in the exclude_blocks (MX_pixart_transformer_2d.py:214).  The same parameter struct, strides,
+ * outputs and workspace rules.
+ *   - every call mxa_attention_xl(p, elem_bits) accepts runs exactly what that runs: the same
+ *     kernels, bytes, statuses and workspace size;
+ *   - with 1,024 < T <= 4,096 also top_k == 0, at elem_bits 8 and 4, float32, on finish_qk_xl_kernel:
+ *     finish_qk_long_kernel's three passes and arithmetic, addition for addition, with the keys
+ *     walked in chunks of 1,024 by the waves of a workgroup in lockstep (the per-key terms of one
+ *     chunk in LDS at a time).  No mask words and no selection state are reserved for it.
+ * MXA_ERR_UNSUPPORTED, before any HIP call, for every other call with T > 1,024 that
+ * mxa_attention_xl refuses: k_top > 64, k_top * 64 > T, T > 4,096, float16 / bfloat16 tensors or
+ * a nonzero score_dtype, MXA_PRED_ELSA (with approx); no scores-only or fused-projection form.
+ * mxa_attention_xl_full_finish_kernel: the MXA_FIN_* kind of the call (no launch; the workspace
+ * may be null) -- MXA_FIN_DENSE_MFMA_XL for the dense branch on those rows.
+ */
+int64_t mxa_attention_xl_full_workspace_bytes(const mxa_attn_params* p, int32_t elem_bits);
+int mxa_attention_xl_full(const mxa_attn_params* p, int32_t elem_bits, hipStream_t stream);
+int mxa_attention_xl_full_finish_kernel(const mxa_attn_params* p, int32_t elem_bits);
+
+/*
  * Which kernels mxa_attention(p) runs (no launch; the workspace may be null):
  *   MXA_PATH_ROWS_SPLIT  selection kernel (scores + top-k) then finishing kernel
  *                        (gather, softmax, MX(P), P.V on int8 MFMA) -- top_k != 0
@@ -365,8 +387,11 @@ int mxa_attention_path(const mxa_attn_params* p);
  *   MXA_FIN_DENSE_MFMA_LONG  finish_qk_long_kernel: top_k == 0 on rows over 512 keys
  * and by mxa_attention_xl_finish_kernel for mxa_attention_xl alone:
  *   MXA_FIN_GATHER16_XL      finish16_xl_kernel: top-k with k <= 64 on rows over 1,024 keys
+ * and by mxa_attention_xl_full_finish_kernel for mxa_attention_xl_full alone:
+ *   MXA_FIN_DENSE_MFMA_XL    finish_qk_xl_kernel: top_k == 0 on rows over 1,024 keys
  * or a negative MXA_ERR_* for invalid parameters.
  */
+#define MXA_FIN_DENSE_MFMA_XL 9
 #define MXA_FIN_GATHER16_XL 8
 #define MXA_FIN_GATHER16 1
 #define MXA_FIN_GATHER32 2

@@ -38,6 +38,8 @@ FIN_KERNELS_FULL = {6: ("finish_qk_long_kernel", "v_mfma_i32_16x16x32_i8 (every 
                     7: ("finish_qk_long_kernel (dense: every key kept)", "v_mfma_i32_16x16x32_i8", "v_mfma_i32_16x16x32_i8")}
 # mxa_attention_xl_finish_kernel reports this one besides: rows of 1,025 .. 4,096 keys
 FIN_KERNELS_XL = {8: ("finish16_xl_kernel", "v_dot4 (kept keys)", "v_mfma_i32_16x16x32_i8")}
+# mxa_attention_xl_full_finish_kernel reports this one besides: the dense branch on those rows
+FIN_KERNELS_XL_FULL = {9: ("finish_qk_xl_kernel (dense: every key kept)", "v_mfma_i32_16x16x32_i8", "v_mfma_i32_16x16x32_i8")}
 PRED_MODES = {"ex_pred": 0, "partial_Q": 1, "partial_K": 2, "MXINT4": 3, "two_step_leading_ones": 4,
               "true_ex": 5, "ELSA": 6}
 ROUND_MODES = {"nearest": 0, "floor": 1, "even": 2}
@@ -111,6 +113,9 @@ _SIGS = {
     "mxa_attention_xl_workspace_bytes": (c_i64, [c_vp, c_i32]),
     "mxa_attention_xl": (c_i32, [c_vp, c_i32, c_vp]),
     "mxa_attention_xl_finish_kernel": (c_i32, [c_vp, c_i32]),
+    "mxa_attention_xl_full_workspace_bytes": (c_i64, [c_vp, c_i32]),
+    "mxa_attention_xl_full": (c_i32, [c_vp, c_i32, c_vp]),
+    "mxa_attention_xl_full_finish_kernel": (c_i32, [c_vp, c_i32]),
     "mxa_attention_path": (c_i32, [ctypes.POINTER(AttnParams)]),
     "mxa_attention_finish_kernel": (c_i32, [ctypes.POINTER(AttnParams)]),
     "mxa_attention_timed": (c_i32, [ctypes.POINTER(AttnParams), c_vp, c_i32, ctypes.POINTER(c_f32)]),

@@ -42,9 +42,15 @@ UNITS += [("mxa_fin_qk.hip", f"_x{i}", (f"MXA_FQ_XDT={i}",)) for i in range(2)]
 UNITS += [("mxa_fin_qk.hip", "_x0w4", ("MXA_FQ_W4=1",))]  # ... and its MXINT4-P ones
 # its tiled sibling for rows of 513 .. 1,024 keys: MXINT8-P and MXINT4-P instantiations (MXA_FQL_W4)
 UNITS += [("mxa_fin_qkl.hip", f"_w{8 - 4 * i}", (f"MXA_FQL_W4={i}",)) for i in range(2)]
+# ... and that sibling's chunked form for dense rows of 1,025 .. 4,096 keys (MXA_FQXL_W4)
+UNITS += [("mxa_fin_qkxl.hip", f"_w{8 - 4 * i}", (f"MXA_FQXL_W4={i}",)) for i in range(2)]
+# per-source compiler flags: the newest kernels are compiled without the packed fp32 instructions
+# (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32); the older units keep the command lines their
+# measured code objects were built with
+UNIT_FLAGS = {"mxa_fin_qkxl.hip": ("-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops")}
 SOURCES = sorted({u[0] for u in UNITS})
 HEADERS = ["mxa_common.hpp", "mxa_kernels.hpp", "mxa_prep.hpp", "mxa_proj.hpp", "mxa_proj_launch.hpp", "mxa_proj_args.hpp", "mxa_gemm_parts.hpp", "mxa_finish.hpp",
-           "mxa_order.hpp", "mxa_topk_grp.hpp", "mxa_topk_wave.hpp", "mxa_finish16.hpp", "mxa_finish_qk.hpp", "mxa_finish_qk_long.hpp", "mxa_tail.hpp", "mxa_gemm.hpp", "mxa_dot.hpp", "mxa_select.hpp", "mxa_select_long.hpp", "mxa_select_xl.hpp", "mxa_finish16_xl.hpp", "mxa_rows2.hpp", "mxa_modes.hpp", "mxa_launch.hpp", "mxa_act.hpp", "mxa_mlp.hpp",
+           "mxa_order.hpp", "mxa_topk_grp.hpp", "mxa_topk_wave.hpp", "mxa_finish16.hpp", "mxa_finish_qk.hpp", "mxa_finish_qk_long.hpp", "mxa_finish_qk_xl.hpp", "mxa_tail.hpp", "mxa_gemm.hpp", "mxa_dot.hpp", "mxa_select.hpp", "mxa_select_long.hpp", "mxa_select_xl.hpp", "mxa_finish16_xl.hpp", "mxa_rows2.hpp", "mxa_modes.hpp", "mxa_launch.hpp", "mxa_act.hpp", "mxa_mlp.hpp",
            "../../include/mxa.h"]
 ARCH = os.environ.get("MXA_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -100,6 +106,7 @@ def build(force=False, verbose=True, defines=(), tag="", only=()):
         cmd = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
                "-Wall", "-Wno-unused-function", "-I", os.path.join(HERE, "..", "include"),
                "-c", os.path.join(CSRC, src), "-o", obj] + [f"-D{d}" for d in tuple(unit_defs) + tuple(defines)]
+        cmd += UNIT_FLAGS.get(src, ())
         objs.append(obj)
         cmd_file = obj + ".cmd"
         if not force and not _obj_stale(obj, dep, cmd_file, cmd):

@@ -20,6 +20,8 @@
 //                               dense_rows_kernel (mxa_rows2.hpp)
 //   finish_qk_long_kernel       mxa_attention_full on rows of 513 .. 1,024 keys: the dense branch and
 //                               k > 64, three passes over the key blocks (mxa_finish_qk_long.hpp)
+//   finish_qk_xl_kernel         mxa_attention_xl_full on rows of 1,025 .. 4,096 keys: the dense branch, those three
+//                               passes with the keys walked in chunks of 1,024 (mxa_finish_qk_xl.hpp)
 //   mxa_qkv_attention_full / mxa_attention_proj_full
 //                               those rows with the fused qkv projection in front and the proj Linear
 //                               behind: qkv_proj_kernel as it is; the proj's codes from finish16_kernel's
@@ -115,8 +117,9 @@ ModeNeeds mode_needs(int mode) {
 // (mxa_attention_full): those rows' dense branch and k_top > 64 too; kReachBlock (mxa_qkv_attention_full,
 // mxa_attention_proj_full): on those rows the fused qkv projection and the proj Linear as well.
 // kReachXl (mxa_attention_xl) stands beside kReachBlock, not above it: kReachFull's calls plus the top-k
-// branch on rows of 1,025 .. kXlRowsT keys (xl_rows_ok), none of the fused projections there or on long rows
-enum Reach { kReachShort, kReachLong, kReachFull, kReachBlock, kReachXl };
+// branch on rows of 1,025 .. kXlRowsT keys (xl_rows_ok), none of the fused projections there or on long rows.
+// kReachXlFull (mxa_attention_xl_full): kReachXl's calls plus the dense branch on those rows
+enum Reach { kReachShort, kReachLong, kReachFull, kReachBlock, kReachXl, kReachXlFull };
 
 // the proj Linear's input comes MX-quantized out of the finishing kernel (MXINT8 only: at 4 bits the
 // fp32 rows go through the workspace and the row quantizer for every D; rows over 512 keys: from the LONG
@@ -150,7 +153,7 @@ struct AttnCall {
 FinFacts attn_fin_facts(const AttnCall& c, const mxa_attn_params* p) {
   return {p->top_k != 0, p->top_k ? p->k_top : 0, p->T, (p->D + 31) / 32, c.pj && proj_codes_direct(p, c.elem_bits, c.reach),
           p->dtype != MXA_DT_F32 || p->score_dtype > MXA_DT_F32, c.elem_bits, c.reach >= kReachFull, c.reach == kReachBlock,
-          c.reach == kReachXl};
+          c.reach >= kReachXl, c.reach == kReachXlFull};
 }
 
 // one side's (Q's or K's) row operands; null: the score mode does not read it
@@ -277,11 +280,13 @@ int attn_validate(const AttnCall& c) {
       (p->pred_mode == MXA_PRED_EXION || p->pred_mode == MXA_PRED_TRUE_EX || p->pred_mode == MXA_PRED_ELSA))
     return MXA_ERR_UNSUPPORTED;
   if (!valid_bfloat(p->bfloat)) return MXA_ERR_ARG;
-  if (p->T > (reach == kReachShort ? kShortRowsT : reach == kReachXl ? kXlRowsT : kLongRowsT) || p->D > 32 * kMaxNB)
+  if (p->T > (reach == kReachShort ? kShortRowsT : reach >= kReachXl ? kXlRowsT : kLongRowsT) || p->D > 32 * kMaxNB)
     return MXA_ERR_UNSUPPORTED;
-  // rows over 1,024 keys: the top-k branch in partial_sort's regime alone (the rest of their refusals --
-  // 16-bit dtypes, the fused projections -- are the long rows', below, and finish_choice's)
-  if (xl_rows(p->T) && (scores_only || !p->top_k || !xl_rows_ok(p->T, p->k_top) || (p->approx && p->pred_mode == MXA_PRED_ELSA)))
+  // rows over 1,024 keys: the top-k branch in partial_sort's regime alone, and for kReachXlFull the dense
+  // branch (the rest of their refusals -- 16-bit dtypes, the fused projections -- are the long rows', below,
+  // and finish_choice's)
+  if (xl_rows(p->T) && (scores_only || (p->top_k ? !xl_rows_ok(p->T, p->k_top) : reach != kReachXlFull) ||
+                        (p->approx && p->pred_mode == MXA_PRED_ELSA)))
     return MXA_ERR_UNSUPPORTED;
   // rows over 512 keys: float32, no fused projection but kReachBlock's qkv and proj Linears; MXINT4:
   // float32, and the approximators of exponent_approximation (ELSA's hashes would need the width too)
@@ -752,6 +757,22 @@ extern "C" int mxa_attention_xl(const mxa_attn_params* p, int32_t elem_bits, hip
 extern "C" int mxa_attention_xl_finish_kernel(const mxa_attn_params* p, int32_t elem_bits) {
   int plan = -1, fin = -1;
   const int rc = attention_impl({.p = p, .reach = kReachXl, .plan = &plan, .fin = &fin, .elem_bits = elem_bits});
+  return rc ? rc : fin;
+}
+
+// mxa_attention_xl plus the dense branch on rows of 1,025 .. 4,096 keys (MX_transformer_block.py:704-705 at
+// 1024 x 1024): finish_qk_xl_kernel
+extern "C" int64_t mxa_attention_xl_full_workspace_bytes(const mxa_attn_params* p, int32_t elem_bits) {
+  return mx_width_ok(elem_bits) && attn_shape_ok(p) ? attn_workspace_total({.p = p, .reach = kReachXlFull}) : -1;
+}
+
+extern "C" int mxa_attention_xl_full(const mxa_attn_params* p, int32_t elem_bits, hipStream_t stream) {
+  return attention_impl({.p = p, .stream = stream, .reach = kReachXlFull, .elem_bits = elem_bits});
+}
+
+extern "C" int mxa_attention_xl_full_finish_kernel(const mxa_attn_params* p, int32_t elem_bits) {
+  int plan = -1, fin = -1;
+  const int rc = attention_impl({.p = p, .reach = kReachXlFull, .plan = &plan, .fin = &fin, .elem_bits = elem_bits});
   return rc ? rc : fin;
 }
 

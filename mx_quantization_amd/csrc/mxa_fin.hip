@@ -1,6 +1,6 @@
 // Row-kernel launches.  launch_rows switches once on the kind finish_choice (mxa_launch.hpp)
 // gives for the call and hands over to that kernel's launcher: the MFMA finishing kernels
-// (mxa_fin_qk.hip, mxa_fin_qkl.hip), the 16-row gather kernels (mxa_fin16.hip, mxa_fin16_xl.hip), and the two
+// (mxa_fin_qk.hip, mxa_fin_qkl.hip, mxa_fin_qkxl.hip), the 16-row gather kernels (mxa_fin16.hip, mxa_fin16_xl.hip), and the two
 // launched from this file: the 32-row gather kernel (mxa_finish.hpp) and the dense branch's
 // v_dot4 row kernel (mxa_rows2.hpp).
 #include "mxa_finish.hpp"
@@ -108,7 +108,7 @@ int launch_rows(const Rows2Args& ra0, const FinFacts& f, bool true_mode, int S, 
   if (c.status) return c.status;
   Rows2Args ra = ra0;
   if (f.topk && true_mode) ra.true_out = nullptr;  // the selection kernel already wrote the true scores
-  if (c.kind == MXA_FIN_DENSE_MFMA || c.kind == MXA_FIN_DENSE_MFMA_LONG) {  // every key kept: no mask words
+  if (c.kind == MXA_FIN_DENSE_MFMA || c.kind == MXA_FIN_DENSE_MFMA_LONG || c.kind == MXA_FIN_DENSE_MFMA_XL) {  // every key kept: no mask words
     ra.dense = 1;
     ra.mask_out = nullptr;
   }
@@ -121,6 +121,8 @@ int launch_rows(const Rows2Args& ra0, const FinFacts& f, bool true_mode, int S, 
     case MXA_FIN_MFMA_LONG:
     case MXA_FIN_DENSE_MFMA_LONG:
       return w4 ? launch_finish_qk_long_w4(ra, BH, stream, plan) : launch_finish_qk_long_w8(ra, BH, stream, plan);
+    case MXA_FIN_DENSE_MFMA_XL:
+      return w4 ? launch_finish_qk_xl_w4(ra, BH, stream, plan) : launch_finish_qk_xl_w8(ra, BH, stream, plan);
     case MXA_FIN_GATHER16_XL:
       return w4 ? launch_finish16_xl_w4(ra, BH, stream, plan) : launch_finish16_xl_w8(ra, BH, stream, plan);
     case MXA_FIN_MFMA:

@@ -1,0 +1,55 @@
+// Launches of the chunked tiled MFMA finishing kernel for dense rows of 1,025 .. 4,096 keys
+// (mxa_finish_qk_xl.hpp).  Compiled twice (build_native.py): MXA_FQXL_W4=0 the MXINT8-P
+// instantiations (launch_finish_qk_xl_w8), MXA_FQXL_W4=1 the MXINT4-P ones
+// (launch_finish_qk_xl_w4), so that the two build in parallel.
+#include "mxa_finish_qk_xl.hpp"
+#include "mxa_launch.hpp"
+
+#ifndef MXA_FQXL_W4
+#define MXA_FQXL_W4 0
+#endif
+#if MXA_FQXL_W4
+#define MXA_FQXL_FN launch_finish_qk_xl_w4
+#else
+#define MXA_FQXL_FN launch_finish_qk_xl_w8
+#endif
+
+namespace mxa {
+
+constexpr bool kFqxlW4 = MXA_FQXL_W4 != 0;
+
+// the LDS of a workgroup is one chunk's tables whatever T and the number of waves are; the waves per
+// workgroup come from finish_tile_plan by the waves per SIMD the instantiation's registers allow
+static int finish_qk_xl_plan(const Rows2Args& ra, int BH, int regs_waves_per_simd, int* waves, int* rows_per_wg) {
+  const size_t lds = fql_lds(ra.nbd, ra.D).total;
+  return finish_tile_plan(kFqRows, ra.N, BH, [lds](int) { return lds; }, finish_wave_cap(regs_waves_per_simd), waves, rows_per_wg);
+}
+template <int NB, bool EXTRA>
+static int launch_finish_qk_xl_x(const Rows2Args& ra0, int BH, hipStream_t stream) {
+  Rows2Args ra = ra0;
+  constexpr auto kernel = &finish_qk_xl_kernel<NB, kFqxlW4, EXTRA>;
+  const int rc = finish_qk_xl_plan(ra, BH, kernel_waves_per_simd<kernel>(), &ra.waves, &ra.rows_per_wg);
+  if (rc) return rc;
+  // the kernel's barriers need whole tiles of whole waves: 1 .. 8 waves, a workgroup's rows a multiple of the tile
+  if (ra.waves < 1 || ra.waves > 8 || ra.rows_per_wg <= 0 || ra.rows_per_wg % kFqRows) return MXA_ERR_LAUNCH;
+  return launch_finish_tiles<kernel>(ra, BH, fql_lds(NB, ra.D).total, stream);
+}
+template <int NB>
+static int launch_finish_qk_xl_nb(const Rows2Args& ra, int BH, hipStream_t stream) {
+  if (ra.dpad != 32 * NB) return MXA_ERR_ARG;
+  return finish_mfma_extra(ra) ? launch_finish_qk_xl_x<NB, true>(ra, BH, stream) : launch_finish_qk_xl_x<NB, false>(ra, BH, stream);
+}
+
+int MXA_FQXL_FN(const Rows2Args& ra, int BH, hipStream_t stream, bool plan) {
+  if (ra.s_dt != kF32 || ra.in_dt != kF32 || ra.xo_codes || !ra.dense) return MXA_ERR_UNSUPPORTED;
+  if (!xl_rows(ra.T) || ra.T > kXlRowsT || ra.ntb != (ra.T + 31) / 32 || ra.tpad != 32 * ra.ntb || ra.nbd < 1 || ra.nbd > 4 ||
+      ra.D > 32 * ra.nbd)
+    return MXA_ERR_UNSUPPORTED;
+  if (plan) {
+    int w, r;
+    return finish_qk_xl_plan(ra, BH, 2, &w, &r);
+  }
+  return dispatch_nbd(ra.nbd, [&](auto nb) { return launch_finish_qk_xl_nb<decltype(nb)::value>(ra, BH, stream); });
+}
+
+}  // namespace mxa

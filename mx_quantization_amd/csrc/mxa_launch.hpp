@@ -153,8 +153,9 @@ inline int launch_select_mode(const Rows2Args& ra, int mode, int BH, hipStream_t
 // (the call's `direct`, known before any pointer is bound); xdt: float16 / bfloat16 inputs or scores;
 // bits: 8 or 4, P's element width; full: the entry point reaches finish_qk_long_kernel (mxa_attention_full);
 // block: it reaches the fused projections on rows over 512 keys too (the *_full fused blocks), where xo is
-// the LONG 16-row kernel's: MXINT8, k <= 32; xl: it reaches rows of 1,025 .. 4,096 keys (mxa_attention_xl)
-struct FinFacts { bool topk; int k, T, nbd; bool xo, xdt; int bits; bool full; bool block = false; bool xl = false; };
+// the LONG 16-row kernel's: MXINT8, k <= 32; xl: it reaches rows of 1,025 .. 4,096 keys (mxa_attention_xl);
+// xl_dense: on those rows the dense branch too (mxa_attention_xl_full)
+struct FinFacts { bool topk; int k, T, nbd; bool xo, xdt; int bits; bool full; bool block = false; bool xl = false; bool xl_dense = false; };
 // kind: MXA_FIN_* (include/mxa.h); reads_mask: the kernel reads the selection's prune-mask words (the
 // caller's mask_out, else a workspace copy), not the kept indices; status: MXA_ERR_UNSUPPORTED where the
 // kind has no instantiation for the facts
@@ -165,6 +166,11 @@ inline FinChoice finish_choice(const FinFacts& f) {
   if (f.xl && xl_rows(f.T) && f.topk && f.k <= 64) {  // the chunked 16-row kernel (mxa_finish16_xl.hpp):
     c.kind = MXA_FIN_GATHER16_XL;                      // float32, top-k in partial_sort's regime
     c.status = xl_rows_ok(f.T, f.k) && !f.xdt && !f.xo ? MXA_OK : MXA_ERR_UNSUPPORTED;
+    return c;
+  }
+  if (f.xl_dense && xl_rows(f.T) && !f.topk) {  // the chunked tiled MFMA kernel (mxa_finish_qk_xl.hpp): float32
+    c.kind = MXA_FIN_DENSE_MFMA_XL;
+    c.status = f.T <= kXlRowsT && f.nbd <= 4 && !f.xdt && !f.xo ? MXA_OK : MXA_ERR_UNSUPPORTED;
     return c;
   }
   if (f.full && lng && (!f.topk || f.k > 64))  // the tiled MFMA kernel (mxa_finish_qk_long.hpp)
@@ -279,6 +285,9 @@ int launch_finish_qk_x0w4(const Rows2Args& ra, int BH, hipStream_t stream, bool 
 // its tiled sibling for rows of 513 .. 1,024 keys (mxa_fin_qkl.hip): float32, MXINT8 / MXINT4 P
 int launch_finish_qk_long_w8(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 int launch_finish_qk_long_w4(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
+// ... and that sibling's chunked form for dense rows of 1,025 .. 4,096 keys (mxa_fin_qkxl.hip)
+int launch_finish_qk_xl_w8(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
+int launch_finish_qk_xl_w4(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 // the 16-row finishing kernel (mxa_fin16.hip): float32 (x0), float16 / bfloat16 (x1)
 int launch_finish16_x0(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 int launch_finish16_x1(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);

@@ -8,6 +8,10 @@ MX_transformer_block.py:648-717): B = 2, H = 16, N = T = 1,024, D = 72, ex_pred;
 (self_top_k=False, exclude_timesteps, exclude_blocks) and k = 154, at widths 8 and 4.
 
     python tools/bench_long_dense.py [--steps 20] [--warmup 3] [--reps 3] [--cases dense,k154] [--widths 8,4] [--fused-only]
+                                     [--tokens 1024] [--batch 2]
+
+--tokens 4096 --batch 1: PixArt-Sigma at 1024x1024, whose dense rows run on finish_qk_xl_kernel
+(mxa_attention_xl_full); the library has no k = 154 on such rows, so the case list is `dense` there.
 
 Both routes of every case are warmed up first; then per case `reps` repetitions alternate the two
 routes, each timed with device events around `steps` calls.  Prints per case the median and the
@@ -21,7 +25,7 @@ import torch
 
 from ab_routes import M, agreement, alternate, chain, ms_fields
 
-B, H, N, D, MODE = 2, 16, 1024, 72, "ex_pred"
+H, D, MODE = 16, 72, "ex_pred"
 CASES = {"dense": 0, "k154": 154}
 
 
@@ -30,10 +34,14 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reps", type=int, default=3)
-    ap.add_argument("--cases", default=",".join(CASES))
+    ap.add_argument("--cases", default=None)
     ap.add_argument("--widths", default="8,4")
     ap.add_argument("--fused-only", action="store_true")
+    ap.add_argument("--tokens", type=int, default=1024)
+    ap.add_argument("--batch", type=int, default=2)
     args = ap.parse_args()
+    B, N = args.batch, args.tokens
+    cases = args.cases or (",".join(CASES) if N <= 1024 else "dense")
     dev = torch.device("cuda", 0)
     g = torch.Generator(device="cpu").manual_seed(0)
     q, k, v = (torch.randn(B, H, N, D, generator=g).to(dev) for _ in range(3))
@@ -50,10 +58,10 @@ def main():
             r["chain"] = lambda: chain(q, k, v, scale, kt, MODE, bits)
         return r
 
-    runs = [(name, CASES[name], int(w)) for name in args.cases.split(",") for w in args.widths.split(",")]
+    runs = [(name, CASES[name], int(w)) for name in cases.split(",") for w in args.widths.split(",")]
     for run, times in zip(runs, alternate(map(routes, runs), args.steps, args.warmup, args.reps)):
         name, kt, bits = run
-        line = {"shape": "pixart_self_512", "case": name, "elem_bits": bits, "B_H_N_T_D_k": (B, H, N, N, D, kt), "pred_mode": MODE,
+        line = {"shape": "pixart_self_512" if N == 1024 else f"pixart_self_{N}_tokens", "case": name, "elem_bits": bits, "B_H_N_T_D_k": (B, H, N, N, D, kt), "pred_mode": MODE,
                 "steps": args.steps, "reps": args.reps, **ms_fields(times)}
         if not args.fused_only:
             line.update(agreement(*(fn() for fn in routes(run).values())))
