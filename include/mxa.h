@@ -362,6 +362,30 @@ int mxa_attention_xl_full(const mxa_attn_params* p, int32_t elem_bits, hipStream
 int mxa_attention_xl_full_finish_kernel(const mxa_attn_params* p, int32_t elem_bits);
 
 /*
+ * mxa_attention_xl_full plus float16 / bfloat16 tensors and a nonzero score_dtype on rows of
+ * 513 .. 4,096 keys: the reference runs PixArt-Sigma with torch_dtype=torch.float16
+ * (workloads/PixArt/scripts/mx_inference.py:149-152) and DeiT under torch.cuda.amp.autocast
+ * (workloads/deit/engine.py:97; 577 keys at 384 x 384).  The same parameter struct, strides,
+ * outputs and workspace rules.
+ *   - every call mxa_attention_xl_full(p, elem_bits) accepts runs exactly what that runs: the same
+ *     kernels, bytes, statuses and workspace size;
+ *   - with 512 < T <= 4,096 and elem_bits 8 also dtype MXA_DT_F16 / MXA_DT_BF16 and score_dtype
+ *     MXA_DT_F16 / MXA_DT_BF16, at every call shape the float32 core takes there, on the
+ *     float16 / bfloat16 forms of the same four finishing kernels (the same MXA_FIN_* kinds) with
+ *     the rules of rows of at most 512 keys: P's shared exponents taken in the dtype, the true
+ *     scores rounded to the score dtype before and after the scale, p rounded once, P's codes by
+ *     the dtype's rule, the output rounded and stored in the score dtype, a float16 all-zero
+ *     block NaN.  The selection kernels are those of the float32 calls.
+ * MXA_ERR_UNSUPPORTED, before any HIP call: elem_bits 4 with such tensors or scores at any T;
+ * with T > 1,024 MXA_PRED_ELSA, k_top > 64, k_top * 64 > T; T > 4,096.  No scores-only or
+ * fused-projection form.  mxa_attention_dt_finish_kernel: the MXA_FIN_* kind of the call (no
+ * launch; the workspace may be null).
+ */
+int64_t mxa_attention_dt_workspace_bytes(const mxa_attn_params* p, int32_t elem_bits);
+int mxa_attention_dt(const mxa_attn_params* p, int32_t elem_bits, hipStream_t stream);
+int mxa_attention_dt_finish_kernel(const mxa_attn_params* p, int32_t elem_bits);
+
+/*
  * Which kernels mxa_attention(p) runs (no launch; the workspace may be null):
  *   MXA_PATH_ROWS_SPLIT  selection kernel (scores + top-k) then finishing kernel
  *                        (gather, softmax, MX(P), P.V on int8 MFMA) -- top_k != 0

@@ -116,6 +116,9 @@ _SIGS = {
     "mxa_attention_xl_full_workspace_bytes": (c_i64, [c_vp, c_i32]),
     "mxa_attention_xl_full": (c_i32, [c_vp, c_i32, c_vp]),
     "mxa_attention_xl_full_finish_kernel": (c_i32, [c_vp, c_i32]),
+    "mxa_attention_dt_workspace_bytes": (c_i64, [c_vp, c_i32]),
+    "mxa_attention_dt": (c_i32, [c_vp, c_i32, c_vp]),
+    "mxa_attention_dt_finish_kernel": (c_i32, [c_vp, c_i32]),
     "mxa_attention_path": (c_i32, [ctypes.POINTER(AttnParams)]),
     "mxa_attention_finish_kernel": (c_i32, [ctypes.POINTER(AttnParams)]),
     "mxa_attention_timed": (c_i32, [ctypes.POINTER(AttnParams), c_vp, c_i32, ctypes.POINTER(c_f32)]),

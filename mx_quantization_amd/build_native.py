@@ -33,6 +33,11 @@ UNITS += [("mxa_sel_long.hip", "", ("MXA_SELL_PART=0",))] + [("mxa_sel_long.hip"
 # MXA_SELX_PART) and the chunked 16-row finishing kernel at either P width (MXA_F16XL_W4)
 UNITS += [("mxa_sel_xl.hip", "", ("MXA_SELX_PART=0",))] + [("mxa_sel_xl.hip", f"_p{i}", (f"MXA_SELX_PART={i}",)) for i in range(1, 6)]
 UNITS += [("mxa_fin16_xl.hip", f"_w{8 - 4 * i}", (f"MXA_F16XL_W4={i}",)) for i in range(2)]
+# the float16 / bfloat16 forms of the four finishing kernels of rows over 512 keys (mxa_attention_dt), a unit
+# each beside the float32 ones: the LONG 16-row kernel, its chunked sibling, the tiled MFMA kernel and its
+# chunked form (which keeps its source's UNIT_FLAGS)
+UNITS += [("mxa_fin16.hip", "_l1", ("MXA_F16_LONG=1", "MXA_F16_XDT=1")), ("mxa_fin16_xl.hip", "_x1", ("MXA_F16XL_XDT=1",)),
+          ("mxa_fin_qkl.hip", "_x1", ("MXA_FQL_XDT=1",)), ("mxa_fin_qkxl.hip", "_x1", ("MXA_FQXL_XDT=1",))]
 UNITS += [("mxa_proj.hip", "", ()), ("mxa_gemm.hip", "", ())]
 UNITS += [("mxa_proj4.hip", "", ())]  # the fused projections' MXINT4 kernels
 # the MLP's fc1 (the digit kernel's body with the GELU + quantizing epilogue) in a unit of its own
@@ -47,7 +52,11 @@ UNITS += [("mxa_fin_qkxl.hip", f"_w{8 - 4 * i}", (f"MXA_FQXL_W4={i}",)) for i in
 # per-source compiler flags: the newest kernels are compiled without the packed fp32 instructions
 # (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32); the older units keep the command lines their
 # measured code objects were built with
-UNIT_FLAGS = {"mxa_fin_qkxl.hip": ("-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops")}
+NO_PK_F32 = ("-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops")
+UNIT_FLAGS = {"mxa_fin_qkxl.hip": NO_PK_F32}
+# ... and so are the float16 / bfloat16 units of the other three long-row kernels (by source and suffix: the
+# float32 units of those sources are older)
+UNIT_FLAGS.update({(src, "_" + sfx): NO_PK_F32 for src, sfx in (("mxa_fin16.hip", "l1"), ("mxa_fin16_xl.hip", "x1"), ("mxa_fin_qkl.hip", "x1"))})
 SOURCES = sorted({u[0] for u in UNITS})
 HEADERS = ["mxa_common.hpp", "mxa_kernels.hpp", "mxa_prep.hpp", "mxa_proj.hpp", "mxa_proj_launch.hpp", "mxa_proj_args.hpp", "mxa_gemm_parts.hpp", "mxa_finish.hpp",
            "mxa_order.hpp", "mxa_topk_grp.hpp", "mxa_topk_wave.hpp", "mxa_finish16.hpp", "mxa_finish_qk.hpp", "mxa_finish_qk_long.hpp", "mxa_finish_qk_xl.hpp", "mxa_tail.hpp", "mxa_gemm.hpp", "mxa_dot.hpp", "mxa_select.hpp", "mxa_select_long.hpp", "mxa_select_xl.hpp", "mxa_finish16_xl.hpp", "mxa_rows2.hpp", "mxa_modes.hpp", "mxa_launch.hpp", "mxa_act.hpp", "mxa_mlp.hpp",
@@ -106,7 +115,7 @@ def build(force=False, verbose=True, defines=(), tag="", only=()):
         cmd = [HIPCC, f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off",
                "-Wall", "-Wno-unused-function", "-I", os.path.join(HERE, "..", "include"),
                "-c", os.path.join(CSRC, src), "-o", obj] + [f"-D{d}" for d in tuple(unit_defs) + tuple(defines)]
-        cmd += UNIT_FLAGS.get(src, ())
+        cmd += UNIT_FLAGS.get((src, suffix), UNIT_FLAGS.get(src, ()))
         objs.append(obj)
         cmd_file = obj + ".cmd"
         if not force and not _obj_stale(obj, dep, cmd_file, cmd):

@@ -118,8 +118,9 @@ ModeNeeds mode_needs(int mode) {
 // mxa_attention_proj_full): on those rows the fused qkv projection and the proj Linear as well.
 // kReachXl (mxa_attention_xl) stands beside kReachBlock, not above it: kReachFull's calls plus the top-k
 // branch on rows of 1,025 .. kXlRowsT keys (xl_rows_ok), none of the fused projections there or on long rows.
-// kReachXlFull (mxa_attention_xl_full): kReachXl's calls plus the dense branch on those rows
-enum Reach { kReachShort, kReachLong, kReachFull, kReachBlock, kReachXl, kReachXlFull };
+// kReachXlFull (mxa_attention_xl_full): kReachXl's calls plus the dense branch on those rows; kReachDt
+// (mxa_attention_dt): kReachXlFull's calls plus, on rows over 512 keys, float16 / bfloat16 tensors and scores
+enum Reach { kReachShort, kReachLong, kReachFull, kReachBlock, kReachXl, kReachXlFull, kReachDt };
 
 // the proj Linear's input comes MX-quantized out of the finishing kernel (MXINT8 only: at 4 bits the
 // fp32 rows go through the workspace and the row quantizer for every D; rows over 512 keys: from the LONG
@@ -153,7 +154,7 @@ struct AttnCall {
 FinFacts attn_fin_facts(const AttnCall& c, const mxa_attn_params* p) {
   return {p->top_k != 0, p->top_k ? p->k_top : 0, p->T, (p->D + 31) / 32, c.pj && proj_codes_direct(p, c.elem_bits, c.reach),
           p->dtype != MXA_DT_F32 || p->score_dtype > MXA_DT_F32, c.elem_bits, c.reach >= kReachFull, c.reach == kReachBlock,
-          c.reach >= kReachXl, c.reach == kReachXlFull};
+          c.reach >= kReachXl, c.reach >= kReachXlFull, c.reach >= kReachDt};
 }
 
 // one side's (Q's or K's) row operands; null: the score mode does not read it
@@ -285,13 +286,14 @@ int attn_validate(const AttnCall& c) {
   // rows over 1,024 keys: the top-k branch in partial_sort's regime alone, and for kReachXlFull the dense
   // branch (the rest of their refusals -- 16-bit dtypes, the fused projections -- are the long rows', below,
   // and finish_choice's)
-  if (xl_rows(p->T) && (scores_only || (p->top_k ? !xl_rows_ok(p->T, p->k_top) : reach != kReachXlFull) ||
+  if (xl_rows(p->T) && (scores_only || (p->top_k ? !xl_rows_ok(p->T, p->k_top) : reach < kReachXlFull) ||
                         (p->approx && p->pred_mode == MXA_PRED_ELSA)))
     return MXA_ERR_UNSUPPORTED;
-  // rows over 512 keys: float32, no fused projection but kReachBlock's qkv and proj Linears; MXINT4:
-  // float32, and the approximators of exponent_approximation (ELSA's hashes would need the width too)
+  // rows over 512 keys: float32 (but for kReachDt), no fused projection but kReachBlock's qkv and proj Linears;
+  // MXINT4: float32, and the approximators of exponent_approximation (ELSA's hashes would need the width too)
   const bool xdt = p->dtype != MXA_DT_F32 || p->score_dtype > MXA_DT_F32;
-  if ((long_rows(p->T) && (xc || ((xq || pj) && reach != kReachBlock) || xdt)) || (elem_bits == 4 && xdt)) return MXA_ERR_UNSUPPORTED;
+  if ((long_rows(p->T) && (xc || ((xq || pj) && reach != kReachBlock) || (xdt && reach < kReachDt))) || (elem_bits == 4 && xdt))
+    return MXA_ERR_UNSUPPORTED;
   if (elem_bits == 4 && p->approx && p->pred_mode == MXA_PRED_ELSA) return MXA_ERR_UNSUPPORTED;
   // ... and a finishing kernel with an instantiation for them (finish_choice: the 16-row and the MFMA
   // kernels), or the scores alone
@@ -773,6 +775,23 @@ extern "C" int mxa_attention_xl_full(const mxa_attn_params* p, int32_t elem_bits
 extern "C" int mxa_attention_xl_full_finish_kernel(const mxa_attn_params* p, int32_t elem_bits) {
   int plan = -1, fin = -1;
   const int rc = attention_impl({.p = p, .reach = kReachXlFull, .plan = &plan, .fin = &fin, .elem_bits = elem_bits});
+  return rc ? rc : fin;
+}
+
+// mxa_attention_xl_full plus float16 / bfloat16 tensors and autocast score dtypes on rows of 513 .. 4,096 keys
+// (PixArt's torch_dtype=torch.float16, DeiT-384 under autocast): the XDT forms of finish16_kernel LONG,
+// finish_qk_long_kernel, finish16_xl_kernel and finish_qk_xl_kernel behind the same selection kernels
+extern "C" int64_t mxa_attention_dt_workspace_bytes(const mxa_attn_params* p, int32_t elem_bits) {
+  return mx_width_ok(elem_bits) && attn_shape_ok(p) ? attn_workspace_total({.p = p, .reach = kReachDt}) : -1;
+}
+
+extern "C" int mxa_attention_dt(const mxa_attn_params* p, int32_t elem_bits, hipStream_t stream) {
+  return attention_impl({.p = p, .stream = stream, .reach = kReachDt, .elem_bits = elem_bits});
+}
+
+extern "C" int mxa_attention_dt_finish_kernel(const mxa_attn_params* p, int32_t elem_bits) {
+  int plan = -1, fin = -1;
+  const int rc = attention_impl({.p = p, .reach = kReachDt, .plan = &plan, .fin = &fin, .elem_bits = elem_bits});
   return rc ? rc : fin;
 }
 

@@ -117,13 +117,18 @@ int launch_rows(const Rows2Args& ra0, const FinFacts& f, bool true_mode, int S, 
   static int8_t plan_xo;
   if (plan && f.xo) ra.xo_codes = &plan_xo;
   const bool w4 = f.bits == 4;  // (finish_choice: float32 then)
+  // rows over 512 keys: the float16 / bfloat16 units where a tensor or the scores are not float32
+  // (finish_choice: mxa_attention_dt alone, MXINT8, no proj codes)
   switch (c.kind) {
     case MXA_FIN_MFMA_LONG:
     case MXA_FIN_DENSE_MFMA_LONG:
+      if (f.xdt) return launch_finish_qk_long_x1(ra, BH, stream, plan);
       return w4 ? launch_finish_qk_long_w4(ra, BH, stream, plan) : launch_finish_qk_long_w8(ra, BH, stream, plan);
     case MXA_FIN_DENSE_MFMA_XL:
+      if (f.xdt) return launch_finish_qk_xl_x1(ra, BH, stream, plan);
       return w4 ? launch_finish_qk_xl_w4(ra, BH, stream, plan) : launch_finish_qk_xl_w8(ra, BH, stream, plan);
     case MXA_FIN_GATHER16_XL:
+      if (f.xdt) return launch_finish16_xl_x1(ra, BH, stream, plan);
       return w4 ? launch_finish16_xl_w4(ra, BH, stream, plan) : launch_finish16_xl_w8(ra, BH, stream, plan);
     case MXA_FIN_MFMA:
     case MXA_FIN_DENSE_MFMA:
@@ -131,6 +136,7 @@ int launch_rows(const Rows2Args& ra0, const FinFacts& f, bool true_mode, int S, 
       return f.xdt ? launch_finish_qk_x1(ra, BH, stream, plan) : launch_finish_qk_x0(ra, BH, stream, plan);
     case MXA_FIN_GATHER16:  // (rows over 512 keys: the LONG instantiations, which stage no K table)
       if (long_rows(ra.T) && f.xo) return launch_finish16_l0xo(ra, BH, stream, plan);  // (finish_choice: MXINT8, k <= 32)
+      if (long_rows(ra.T) && f.xdt) return launch_finish16_l1(ra, BH, stream, plan);
       if (long_rows(ra.T)) return w4 ? launch_finish16_l0w4(ra, BH, stream, plan) : launch_finish16_l0(ra, BH, stream, plan);
       if (w4) return launch_finish16_x0w4(ra, BH, stream, plan);
       return f.xdt ? launch_finish16_x1(ra, BH, stream, plan) : launch_finish16_x0(ra, BH, stream, plan);

@@ -8,6 +8,8 @@
 // MXA_F16_LXO=1 (float32, MXINT8 P): the LONG instantiations that write the proj Linear's MX input codes
 // (launch_finish16_l0xo: the fused blocks on rows of 513 .. 1,024 keys), and nothing else -- a unit of
 // its own, so that every other unit keeps the code it had.
+// MXA_F16_LONG=1 with MXA_F16_XDT=1 (MXINT8 P): the LONG instantiations for float16 / bfloat16 tensors or
+// scores (launch_finish16_l1: mxa_attention_dt on rows of 513 .. 1,024 keys), a unit of its own as well.
 #include "mxa_finish16.hpp"
 #include "mxa_launch.hpp"
 
@@ -31,6 +33,8 @@
 #define MXA_F16_FN launch_finish16_l0w4
 #elif MXA_F16_W4
 #define MXA_F16_FN launch_finish16_x0w4
+#elif MXA_F16_LONG && MXA_F16_XDT
+#define MXA_F16_FN launch_finish16_l1
 #elif MXA_F16_LONG
 #define MXA_F16_FN launch_finish16_l0
 #elif MXA_F16_XDT
@@ -45,7 +49,7 @@ constexpr bool kF16Xdt = MXA_F16_XDT != 0;
 constexpr bool kF16Long = MXA_F16_LONG != 0;
 constexpr bool kF16W4 = MXA_F16_W4 != 0;
 constexpr bool kF16Lxo = MXA_F16_LXO != 0;
-static_assert(!(kF16Xdt && (kF16Long || kF16W4)), "long rows, MXINT4 P: float32 only");
+static_assert(!(kF16Xdt && kF16W4), "MXINT4 P: float32 only");
 static_assert(!(kF16Lxo && (kF16Xdt || kF16W4)), "the proj's codes on long rows: float32, MXINT8 P");
 
 // waves per workgroup by finish_tile_plan (mxa_launch.hpp) from the waves per SIMD the

@@ -1,13 +1,20 @@
 // Launches of the chunked 16-row finishing kernel (mxa_finish16_xl.hpp: rows of 1,025 .. 4,096
 // keys, k <= 64, float32).  Compiled twice (build_native.py): MXA_F16XL_W4=0 the MXINT8-P
 // instantiations (launch_finish16_xl_w8), MXA_F16XL_W4=1 the MXINT4-P ones (launch_finish16_xl_w4).
+// A third compilation, MXA_F16XL_XDT=1 (MXINT8 P), holds the float16 / bfloat16 instantiations
+// (launch_finish16_xl_x1: mxa_attention_dt).
 #include "mxa_finish16_xl.hpp"
 #include "mxa_launch.hpp"
 
 #ifndef MXA_F16XL_W4
 #define MXA_F16XL_W4 0
 #endif
-#if MXA_F16XL_W4
+#ifndef MXA_F16XL_XDT
+#define MXA_F16XL_XDT 0
+#endif
+#if MXA_F16XL_XDT
+#define MXA_F16XL_FN launch_finish16_xl_x1
+#elif MXA_F16XL_W4
 #define MXA_F16XL_FN launch_finish16_xl_w4
 #else
 #define MXA_F16XL_FN launch_finish16_xl_w8
@@ -16,6 +23,8 @@
 namespace mxa {
 
 constexpr bool kF16XlW4 = MXA_F16XL_W4 != 0;
+constexpr bool kF16XlXdt = MXA_F16XL_XDT != 0;
+static_assert(!(kF16XlW4 && kF16XlXdt), "MXINT4 P: float32 only");
 
 // waves per workgroup by finish_tile_plan (mxa_launch.hpp) from the waves per SIMD the kernel's
 // registers allow
@@ -26,18 +35,20 @@ static int finish16_xl_plan(const Rows2Args& ra, int BH, int regs_waves_per_simd
 template <int NB, int KS, bool EXTRA>
 static int launch_finish16_xl_x(const Rows2Args& ra0, int BH, hipStream_t stream) {
   Rows2Args ra = ra0;
-  constexpr auto kernel = &finish16_xl_kernel<NB, KS, EXTRA, kF16XlW4>;
+  constexpr auto kernel = &finish16_xl_kernel<NB, KS + (kF16XlXdt ? kFin16XlDtKS : 0), EXTRA, kF16XlW4>;
   const int rc = finish16_xl_plan(ra, BH, kernel_waves_per_simd<kernel>(), &ra.waves, &ra.rows_per_wg);
   if (rc) return rc;
   return launch_finish_tiles<kernel>(ra, BH, fin16_xl_lds(ra.D, ra.ntb, ra.waves).total, stream);
 }
 template <int NB>
 static int launch_finish16_xl_nb(const Rows2Args& ra, int BH, hipStream_t stream) {
-  // EXTRA: a bias, the debug true scores or bfloatX rounding
-  const bool extra = ra.bias || ra.true_out || (ra.bfloat != 0 && ra.bfloat != 32);
+  // EXTRA: a bias, the debug true scores or bfloatX rounding (float16 / bfloat16 always round)
+  const bool extra = kF16XlXdt || ra.bias || ra.true_out || (ra.bfloat != 0 && ra.bfloat != 32);
   auto ks = [&](auto ks_c) {
     constexpr int KS = decltype(ks_c)::value;
-    return extra ? launch_finish16_xl_x<NB, KS, true>(ra, BH, stream) : launch_finish16_xl_x<NB, KS, false>(ra, BH, stream);
+    if (extra) return launch_finish16_xl_x<NB, KS, true>(ra, BH, stream);
+    if constexpr (!kF16XlXdt) return launch_finish16_xl_x<NB, KS, false>(ra, BH, stream);
+    return (int)MXA_ERR_UNSUPPORTED;
   };
   // four lanes per row: slots ceil(k / 4), the sizes of finish16_kernel
   const int n = (ra.k_top + 3) / 4;
@@ -48,7 +59,8 @@ static int launch_finish16_xl_nb(const Rows2Args& ra, int BH, hipStream_t stream
 }
 
 int MXA_F16XL_FN(const Rows2Args& ra, int BH, hipStream_t stream, bool plan) {
-  if (!xl_rows_ok(ra.T, ra.k_top) || ra.xo_codes || ra.s_dt != kF32 || ra.in_dt != kF32) return MXA_ERR_UNSUPPORTED;
+  // (launch_rows chooses the unit by the call's dtypes; the plan pass runs before they are bound)
+  if (!xl_rows_ok(ra.T, ra.k_top) || ra.xo_codes || (!kF16XlXdt && (ra.s_dt != kF32 || ra.in_dt != kF32))) return MXA_ERR_UNSUPPORTED;
   if (plan) {
     int w, r;
     return finish16_xl_plan(ra, BH, 2, &w, &r);

@@ -1,14 +1,20 @@
 // Launches of the tiled MFMA finishing kernel for rows of 513 .. 1,024 keys
 // (mxa_finish_qk_long.hpp).  Compiled twice (build_native.py): MXA_FQL_W4=0 the MXINT8-P
 // instantiations (launch_finish_qk_long_w8), MXA_FQL_W4=1 the MXINT4-P ones
-// (launch_finish_qk_long_w4), so that the two build in parallel.
+// (launch_finish_qk_long_w4), so that the two build in parallel.  A third compilation, MXA_FQL_XDT=1
+// (MXINT8 P), holds the float16 / bfloat16 instantiations (launch_finish_qk_long_x1: mxa_attention_dt).
 #include "mxa_finish_qk_long.hpp"
 #include "mxa_launch.hpp"
 
 #ifndef MXA_FQL_W4
 #define MXA_FQL_W4 0
 #endif
-#if MXA_FQL_W4
+#ifndef MXA_FQL_XDT
+#define MXA_FQL_XDT 0
+#endif
+#if MXA_FQL_XDT
+#define MXA_FQL_FN launch_finish_qk_long_x1
+#elif MXA_FQL_W4
 #define MXA_FQL_FN launch_finish_qk_long_w4
 #else
 #define MXA_FQL_FN launch_finish_qk_long_w8
@@ -17,17 +23,21 @@
 namespace mxa {
 
 constexpr bool kW4 = MXA_FQL_W4 != 0;
+constexpr bool kXdt = MXA_FQL_XDT != 0;
+static_assert(!(kW4 && kXdt), "MXINT4 P: float32 only");
 
 template <int NB>
 static int launch_finish_qk_long_nb(const Rows2Args& ra, int BH, hipStream_t stream) {
   if ((!ra.mask_out && !ra.dense) || ra.dpad != 32 * NB) return MXA_ERR_ARG;
   const size_t lds = fql_lds(NB, ra.D).total;
-  if (finish_mfma_extra(ra)) return launch_finish_mfma<&finish_qk_long_kernel<NB, kW4, true>>(ra, kFqRows, lds, BH, stream);
-  return launch_finish_mfma<&finish_qk_long_kernel<NB, kW4, false>>(ra, kFqRows, lds, BH, stream);
+  constexpr int NBX = NB + (kXdt ? kFqDtNB : 0);
+  if (finish_mfma_extra(ra)) return launch_finish_mfma<&finish_qk_long_kernel<NBX, kW4, true>>(ra, kFqRows, lds, BH, stream);
+  return launch_finish_mfma<&finish_qk_long_kernel<NBX, kW4, false>>(ra, kFqRows, lds, BH, stream);
 }
 
 int MXA_FQL_FN(const Rows2Args& ra, int BH, hipStream_t stream, bool plan) {
-  if (ra.s_dt != kF32 || ra.in_dt != kF32 || ra.xo_codes) return MXA_ERR_UNSUPPORTED;
+  // (launch_rows chooses the unit by the call's dtypes; the plan pass runs before they are bound)
+  if ((!kXdt && (ra.s_dt != kF32 || ra.in_dt != kF32)) || ra.xo_codes) return MXA_ERR_UNSUPPORTED;
   if (ra.T > kFqlT || ra.ntb > kFqlNTB || ra.nbd < 1 || ra.nbd > 4 || ra.D > 32 * ra.nbd) return MXA_ERR_UNSUPPORTED;
   if (plan) {
     int w, r;

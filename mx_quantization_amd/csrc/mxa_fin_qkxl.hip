@@ -1,14 +1,20 @@
 // Launches of the chunked tiled MFMA finishing kernel for dense rows of 1,025 .. 4,096 keys
 // (mxa_finish_qk_xl.hpp).  Compiled twice (build_native.py): MXA_FQXL_W4=0 the MXINT8-P
 // instantiations (launch_finish_qk_xl_w8), MXA_FQXL_W4=1 the MXINT4-P ones
-// (launch_finish_qk_xl_w4), so that the two build in parallel.
+// (launch_finish_qk_xl_w4), so that the two build in parallel.  A third compilation, MXA_FQXL_XDT=1
+// (MXINT8 P), holds the float16 / bfloat16 instantiations (launch_finish_qk_xl_x1: mxa_attention_dt).
 #include "mxa_finish_qk_xl.hpp"
 #include "mxa_launch.hpp"
 
 #ifndef MXA_FQXL_W4
 #define MXA_FQXL_W4 0
 #endif
-#if MXA_FQXL_W4
+#ifndef MXA_FQXL_XDT
+#define MXA_FQXL_XDT 0
+#endif
+#if MXA_FQXL_XDT
+#define MXA_FQXL_FN launch_finish_qk_xl_x1
+#elif MXA_FQXL_W4
 #define MXA_FQXL_FN launch_finish_qk_xl_w4
 #else
 #define MXA_FQXL_FN launch_finish_qk_xl_w8
@@ -17,6 +23,8 @@
 namespace mxa {
 
 constexpr bool kFqxlW4 = MXA_FQXL_W4 != 0;
+constexpr bool kFqxlXdt = MXA_FQXL_XDT != 0;
+static_assert(!(kFqxlW4 && kFqxlXdt), "MXINT4 P: float32 only");
 
 // the LDS of a workgroup is one chunk's tables whatever T and the number of waves are; the waves per
 // workgroup come from finish_tile_plan by the waves per SIMD the instantiation's registers allow
@@ -27,7 +35,7 @@ static int finish_qk_xl_plan(const Rows2Args& ra, int BH, int regs_waves_per_sim
 template <int NB, bool EXTRA>
 static int launch_finish_qk_xl_x(const Rows2Args& ra0, int BH, hipStream_t stream) {
   Rows2Args ra = ra0;
-  constexpr auto kernel = &finish_qk_xl_kernel<NB, kFqxlW4, EXTRA>;
+  constexpr auto kernel = &finish_qk_xl_kernel<NB + (kFqxlXdt ? kFqDtNB : 0), kFqxlW4, EXTRA>;
   const int rc = finish_qk_xl_plan(ra, BH, kernel_waves_per_simd<kernel>(), &ra.waves, &ra.rows_per_wg);
   if (rc) return rc;
   // the kernel's barriers need whole tiles of whole waves: 1 .. 8 waves, a workgroup's rows a multiple of the tile
@@ -41,7 +49,8 @@ static int launch_finish_qk_xl_nb(const Rows2Args& ra, int BH, hipStream_t strea
 }
 
 int MXA_FQXL_FN(const Rows2Args& ra, int BH, hipStream_t stream, bool plan) {
-  if (ra.s_dt != kF32 || ra.in_dt != kF32 || ra.xo_codes || !ra.dense) return MXA_ERR_UNSUPPORTED;
+  // (launch_rows chooses the unit by the call's dtypes; the plan pass runs before they are bound)
+  if ((!kFqxlXdt && (ra.s_dt != kF32 || ra.in_dt != kF32)) || ra.xo_codes || !ra.dense) return MXA_ERR_UNSUPPORTED;
   if (!xl_rows(ra.T) || ra.T > kXlRowsT || ra.ntb != (ra.T + 31) / 32 || ra.tpad != 32 * ra.ntb || ra.nbd < 1 || ra.nbd > 4 ||
       ra.D > 32 * ra.nbd)
     return MXA_ERR_UNSUPPORTED;

@@ -95,7 +95,9 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NB <= 2 && 
   constexpr int KS = KSL % kFin16LongKS;
   constexpr bool LONG = KSL % kFin16Bits4KS >= kFin16LongKS;
   constexpr bool W4 = KSL >= kFin16Bits4KS;
-  static_assert(!((LONG || W4) && XDT) && !(W4 && XO), "long rows, MXINT4 P: float32; MXINT4 P: no proj codes");
+  // (LONG with XDT, mxa_attention_dt: the block word in bm and p_code_word work on the kept slots wherever the
+  // K rows came from, and fin16_lds with long_k drops only the K tables, which this form never reads)
+  static_assert(!(W4 && XDT) && !(W4 && XO), "MXINT4 P: float32, no proj codes");
   constexpr bool kRound = XDT || EXTRA;
   const int sdt = XDT ? a.s_dt : (int)kF32, idt = XDT ? a.in_dt : (int)kF32;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];

@@ -19,7 +19,10 @@
 // scale, so a non-finite scale reaches every row's output column as in the reference's dense
 // 0 * NaN.  (At the Sigma shape 16 rows x 20 keys touch most of the 128 blocks anyway.)
 // A kernel of its own, so that no finish16_kernel instantiation's registers move (see there).
-// float32 only; P is MXINT8 or (W4) MXINT4.
+// P is MXINT8 or (W4) MXINT4.  float32, or (XDT, MXINT8 P: mxa_attention_dt) float16 / bfloat16 tensors or
+// scores with finish16_kernel's XDT rules: the dtype roundings at run time, P's shared exponents taken in the
+// score dtype, each chunk's bm holding the block word (es + 1024 and the flush flag) for p_code_word.  Block
+// scales are per block, so the chunking cannot change a code there either.
 #pragma once
 #include "mxa_finish16.hpp"
 
@@ -28,6 +31,7 @@ namespace mxa {
 constexpr int kXlChunkBlocks = 32;                      // MX blocks of P per chunk
 constexpr int kXlChunk = 32 * kXlChunkBlocks;           // keys per chunk
 constexpr int kXlVst = kXlChunk + 16;                   // the code tile's row stride (16 pad columns)
+constexpr int kFin16XlDtKS = 64;                        // finish16_xl_kernel's KSX of an XDT instantiation: KS + this
 
 // LDS: the V block scales as floats [ntb][D], then per wave the chunk's P code tile [16][kXlVst],
 // its block scales sP [32][16] (float) and block maxima / code multipliers bm [16][32] (u32)
@@ -46,10 +50,17 @@ __host__ __device__ inline Fin16XlLds fin16_xl_lds(int D, int ntb, int waves) {
 
 // NB: 32-blocks per head dim; KS: kept slots per lane (k <= 4 KS); EXTRA: a bias, the debug
 // true-score output or bfloatX rounding; W4: MXINT4 P
-template <int NB, int KS, bool EXTRA, bool W4>
-__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NB <= 2 && KS <= 12 ? kFin16Occ : (NB * KS <= 64 ? 3 : 2), 8))) void finish16_xl_kernel(Rows2Args a) {
+// XDT travels in the slot count, KSX = KS + kFin16XlDtKS, as LONG does in finish16_kernel: the float32
+// instantiations keep the names and the code they had.  Its occupancy targets are the float32 form's: the
+// run-time roundings sit outside the per-block P.V loop (the scores, the softmax and one code per slot and
+// chunk), so they add no registers that live across it
+template <int NB, int KSX, bool EXTRA, bool W4>
+__global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NB <= 2 && KSX % kFin16XlDtKS <= 12 ? kFin16Occ : (NB * (KSX % kFin16XlDtKS) <= 64 ? 3 : 2), 8))) void finish16_xl_kernel(Rows2Args a) {
+  constexpr int KS = KSX % kFin16XlDtKS;
+  constexpr bool XDT = KSX >= kFin16XlDtKS;
+  static_assert(!(W4 && XDT) && (!XDT || EXTRA), "MXINT4 P: float32; float16 / bfloat16 always round");
   constexpr bool kRound = EXTRA;
-  constexpr int sdt = kF32, idt = kF32;
+  const int sdt = XDT ? a.s_dt : (int)kF32, idt = XDT ? a.in_dt : (int)kF32;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int bh = blockIdx.x;
@@ -177,20 +188,22 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NB <= 2 && 
       }
       wave_lds_sync();
       // per block: the scale sP (NaN for a NaN block) and the code multiplier 2^-es (0 for a NaN
-      // or flushed block), finish16_kernel's rule
+      // or flushed block; XDT: the block word of p_code_word), finish16_kernel's rule
       for (int bk = ph; bk < kXlChunkBlocks; bk += 4) {
         int e_raw;
         const int es = scale_exponent_dt(bm[bk], 127, sdt, &e_raw);
         const bool fl = a.flush_p && !(e_raw != kExpNaN && e_raw > -127);
         sP[bk * kFin16 + pr] = scale_f(es == kExpNaN ? kExpNaN : es - kPUnit<W4>);
-        bm[bk] = __float_as_uint(es == kExpNaN || fl ? 0.0f : pow2f(-es));
+        if (XDT) bm[bk] = (es == kExpNaN ? 0u : (uint32_t)(es + 1024)) | (fl ? 0x10000u : 0u);
+        else bm[bk] = __float_as_uint(es == kExpNaN || fl ? 0.0f : pow2f(-es));
       }
       wave_lds_sync();
 #pragma unroll
       for (int t = 0; t < KS; ++t) {
         const bool in = on[t] && (ix[t] >> 5) - cb >= 0 && (ix[t] >> 5) - cb < kXlChunkBlocks;
         const uint32_t e = bm[(ix[t] >> 5) & (kXlChunkBlocks - 1)];
-        const int code = (int)p_code_bits_f32<W4>(v[t], __uint_as_float(e));
+        // (a slot outside the chunk codes against a block that is not its own: the result goes to the pad)
+        const int code = XDT ? p_code_word(v[t], e, sdt) : (int)p_code_bits_f32<W4>(v[t], __uint_as_float(e));
         ptile[pr * kXlVst + (in ? ix[t] & (kXlChunk - 1) : pad)] = (int8_t)code;
       }
       wave_lds_sync();

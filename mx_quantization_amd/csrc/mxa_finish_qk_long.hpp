@@ -1,6 +1,6 @@
 // finish_qk_kernel's tiled sibling for rows of 513 .. 1,024 keys (mxa_attention_full): the
 // top-k path with k > 64 and the dense branch (top_k=False), every key's score and P.V on
-// v_mfma_i32_16x16x32_i8, float32.
+// v_mfma_i32_16x16x32_i8; float32, or (XDT, mxa_attention_dt) float16 / bfloat16 tensors or scores.
 //
 // finish_qk_kernel (mxa_finish_qk.hpp) holds a row's scores in registers (T <= 256) and the
 // head's K and V^T codes in LDS; neither fits 1,024 keys.  The reference quantizes
@@ -32,6 +32,7 @@ namespace mxa {
 
 constexpr int kFqlT = 1024;           // the longest row
 constexpr int kFqlNTB = kFqlT / 32;   // its key blocks
+constexpr int kFqDtNB = 8;            // finish_qk_long_kernel's / finish_qk_xl_kernel's NBX of an XDT instantiation: NB + this
 
 // LDS per workgroup (nothing per wave), strides fixed: K exponents [NB][1024] (int16, key
 // order), the exact epilogue's key terms [3][1024] (int32: smallest block exponent, the
@@ -66,10 +67,19 @@ __host__ __device__ inline FqlLds fql_lds(int nb, int D) {
 
 // NB: 32-element blocks per head dim; W4: P is MXINT4 (finish_qk_kernel's W4); EXTRA: a bias,
 // the debug true-score output or bfloatX rounding
-template <int NB, bool W4, bool EXTRA>
+// XDT (MXINT8 P): finish_qk_kernel's XDT rules -- true_score rounds to the score dtype before and after the
+// scale, the bias add goes through the dtypes, p = round_dt(round_bfloat(.., sdt), sdt) (the reference's softmax
+// of a 16-bit tensor computes in float32 and rounds once), P's block exponents are taken in the dtype, the
+// codes by round_code at run time, the output rounded and stored in the dtype.  The three passes, the sum
+// chain and div_by_sum are the float32 form's.  It travels in the block count, NBX = NB + kFqDtNB, so that the
+// float32 instantiations keep their names and code (as LONG does in finish16_kernel)
+template <int NBX, bool W4, bool EXTRA>
 __global__ __launch_bounds__(512) MXA_FQL_ATTR void finish_qk_long_kernel(Rows2Args a) {
-  constexpr int sdt = (int)kF32, idt = (int)kF32;
-  constexpr bool kRound = EXTRA;
+  constexpr int NB = NBX % kFqDtNB;
+  constexpr bool XDT = NBX >= kFqDtNB;
+  static_assert(!(W4 && XDT), "MXINT4 P: float32");
+  const int sdt = XDT ? a.s_dt : (int)kF32, idt = XDT ? a.in_dt : (int)kF32;
+  constexpr bool kRound = XDT || EXTRA;
   constexpr int kes = kFqlT;
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -235,8 +245,10 @@ __global__ __launch_bounds__(512) MXA_FQL_ATTR void finish_qk_long_kernel(Rows2A
         if (es != kExpNaN) {
 #pragma unroll
           for (int j = 0; j < 8; ++j) {
+            uint32_t code;
             const float x = fl ? p[j] * 0.0f : p[j];
-            const uint32_t code = (uint32_t)p_code_bits_f32<W4>(x, pow2f(-es));
+            if (XDT) code = (uint32_t)(int)round_code(x, es, 8, kRoundNearest, sdt) & 0xFFu;
+            else code = (uint32_t)p_code_bits_f32<W4>(x, pow2f(-es));
             if (j < 4) lo |= code << (8 * j);
             else hi |= code << (8 * (j - 4));
           }

@@ -1,6 +1,7 @@
 // finish_qk_long_kernel's chunked sibling for DENSE rows of 1,025 .. 4,096 keys (mxa_attention_xl_full:
 // top_k=False at 1024 x 1024, MX_transformer_block.py:656, :704-705; MX_pixart_transformer_2d.py:214),
-// float32, every key's score and P.V on v_mfma_i32_16x16x32_i8.
+// every key's score and P.V on v_mfma_i32_16x16x32_i8; float32, or (XDT, mxa_attention_dt) float16 /
+// bfloat16 tensors or scores.
 //
 // finish_qk_long_kernel (mxa_finish_qk_long.hpp) keeps the exact epilogue's per-key terms of the WHOLE
 // row in LDS (fql_lds, strides fixed at 1,024 keys).  Stretched to 4,096 keys that is 114 KB at NB = 3,
@@ -33,10 +34,16 @@ namespace mxa {
 
 // NB: 32-element blocks per head dim; W4: P is MXINT4; EXTRA: a bias, the debug true-score output or
 // bfloatX rounding (finish_qk_long_kernel's)
-template <int NB, bool W4, bool EXTRA>
+// XDT (MXINT8 P, NBX = NB + kFqDtNB): finish_qk_long_kernel's XDT rules inside the lockstep walk.  The dtypes
+// are kernel arguments, so every branch on them is uniform over the workgroup, and none of them encloses a
+// barrier: stage() and the trip counts of rounds, passes, chunks and blocks do not read them
+template <int NBX, bool W4, bool EXTRA>
 __global__ __launch_bounds__(512) void finish_qk_xl_kernel(Rows2Args a) {
-  constexpr int sdt = (int)kF32, idt = (int)kF32;
-  constexpr bool kRound = EXTRA;
+  constexpr int NB = NBX % kFqDtNB;
+  constexpr bool XDT = NBX >= kFqDtNB;
+  static_assert(!(W4 && XDT), "MXINT4 P: float32");
+  const int sdt = XDT ? a.s_dt : (int)kF32, idt = XDT ? a.in_dt : (int)kF32;
+  constexpr bool kRound = XDT || EXTRA;
   constexpr int kes = kFqlT;  // keys per chunk = the LDS tables' key stride
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -223,8 +230,10 @@ __global__ __launch_bounds__(512) void finish_qk_xl_kernel(Rows2Args a) {
         if (es != kExpNaN) {
 #pragma unroll
           for (int j = 0; j < 8; ++j) {
+            uint32_t code;
             const float x = fl ? p[j] * 0.0f : p[j];
-            const uint32_t code = (uint32_t)p_code_bits_f32<W4>(x, pow2f(-es));
+            if (XDT) code = (uint32_t)(int)round_code(x, es, 8, kRoundNearest, sdt) & 0xFFu;
+            else code = (uint32_t)p_code_bits_f32<W4>(x, pow2f(-es));
             if (j < 4) lo |= code << (8 * j);
             else hi |= code << (8 * (j - 4));
           }

@@ -154,23 +154,26 @@ inline int launch_select_mode(const Rows2Args& ra, int mode, int BH, hipStream_t
 // bits: 8 or 4, P's element width; full: the entry point reaches finish_qk_long_kernel (mxa_attention_full);
 // block: it reaches the fused projections on rows over 512 keys too (the *_full fused blocks), where xo is
 // the LONG 16-row kernel's: MXINT8, k <= 32; xl: it reaches rows of 1,025 .. 4,096 keys (mxa_attention_xl);
-// xl_dense: on those rows the dense branch too (mxa_attention_xl_full)
-struct FinFacts { bool topk; int k, T, nbd; bool xo, xdt; int bits; bool full; bool block = false; bool xl = false; bool xl_dense = false; };
+// xl_dense: on those rows the dense branch too (mxa_attention_xl_full); dt: on rows over 512 keys float16 /
+// bfloat16 tensors or scores too, at MXINT8 (mxa_attention_dt)
+struct FinFacts { bool topk; int k, T, nbd; bool xo, xdt; int bits; bool full; bool block = false; bool xl = false; bool xl_dense = false; bool dt = false; };
 // kind: MXA_FIN_* (include/mxa.h); reads_mask: the kernel reads the selection's prune-mask words (the
 // caller's mask_out, else a workspace copy), not the kept indices; status: MXA_ERR_UNSUPPORTED where the
 // kind has no instantiation for the facts
 struct FinChoice { int kind; bool reads_mask; int status; };
 inline FinChoice finish_choice(const FinFacts& f) {
   const bool lng = long_rows(f.T), w4 = f.bits == 4, regs = f.T <= 256 && f.nbd <= 4;  // regs: a row's scores in registers
+  // float16 / bfloat16 on rows over 512 keys: the XDT forms of the long rows' four kernels, MXINT8 P, no proj codes
+  const bool ldt = f.dt && !w4 && !f.xo;
   FinChoice c{};
   if (f.xl && xl_rows(f.T) && f.topk && f.k <= 64) {  // the chunked 16-row kernel (mxa_finish16_xl.hpp):
-    c.kind = MXA_FIN_GATHER16_XL;                      // float32, top-k in partial_sort's regime
-    c.status = xl_rows_ok(f.T, f.k) && !f.xdt && !f.xo ? MXA_OK : MXA_ERR_UNSUPPORTED;
+    c.kind = MXA_FIN_GATHER16_XL;                      // top-k in partial_sort's regime
+    c.status = xl_rows_ok(f.T, f.k) && (!f.xdt || ldt) && !f.xo ? MXA_OK : MXA_ERR_UNSUPPORTED;
     return c;
   }
-  if (f.xl_dense && xl_rows(f.T) && !f.topk) {  // the chunked tiled MFMA kernel (mxa_finish_qk_xl.hpp): float32
+  if (f.xl_dense && xl_rows(f.T) && !f.topk) {  // the chunked tiled MFMA kernel (mxa_finish_qk_xl.hpp)
     c.kind = MXA_FIN_DENSE_MFMA_XL;
-    c.status = f.T <= kXlRowsT && f.nbd <= 4 && !f.xdt && !f.xo ? MXA_OK : MXA_ERR_UNSUPPORTED;
+    c.status = f.T <= kXlRowsT && f.nbd <= 4 && (!f.xdt || ldt) && !f.xo ? MXA_OK : MXA_ERR_UNSUPPORTED;
     return c;
   }
   if (f.full && lng && (!f.topk || f.k > 64))  // the tiled MFMA kernel (mxa_finish_qk_long.hpp)
@@ -185,7 +188,8 @@ inline FinChoice finish_choice(const FinFacts& f) {
   // long rows and MXINT4 P: float32 without the proj's codes (but the fused blocks' on the LONG 16-row
   // kernel at MXINT8), and not on the 32-row or the dense row kernel (a K table of <= 512 keys, MXINT8 P only)
   const bool lxo = f.block && lng && !w4 && c.kind == MXA_FIN_GATHER16;
-  if ((lng || w4) && (f.xdt || (f.xo && !lxo) || c.kind == MXA_FIN_GATHER32 || c.kind == MXA_FIN_DENSE_ROWS))
+  // (mxa_attention_dt lets the 16-bit dtypes through to the LONG 16-row kernel and finish_qk_long_kernel)
+  if ((lng || w4) && ((f.xdt && !(lng && ldt)) || (f.xo && !lxo) || c.kind == MXA_FIN_GATHER32 || c.kind == MXA_FIN_DENSE_ROWS))
     c.status = MXA_ERR_UNSUPPORTED;
   if (xl_rows(f.T)) c.status = MXA_ERR_UNSUPPORTED;  // (no other kernel serves rows over 1,024 keys)
   return c;
@@ -285,19 +289,23 @@ int launch_finish_qk_x0w4(const Rows2Args& ra, int BH, hipStream_t stream, bool 
 // its tiled sibling for rows of 513 .. 1,024 keys (mxa_fin_qkl.hip): float32, MXINT8 / MXINT4 P
 int launch_finish_qk_long_w8(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 int launch_finish_qk_long_w4(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
+int launch_finish_qk_long_x1(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);  // float16 / bfloat16, MXINT8 P
 // ... and that sibling's chunked form for dense rows of 1,025 .. 4,096 keys (mxa_fin_qkxl.hip)
 int launch_finish_qk_xl_w8(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 int launch_finish_qk_xl_w4(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
+int launch_finish_qk_xl_x1(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);  // float16 / bfloat16, MXINT8 P
 // the 16-row finishing kernel (mxa_fin16.hip): float32 (x0), float16 / bfloat16 (x1)
 int launch_finish16_x0(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 int launch_finish16_x1(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 int launch_finish16_l0(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);  // long rows, float32
+int launch_finish16_l1(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);  // long rows, float16 / bfloat16
 int launch_finish16_x0w4(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);  // float32, MXINT4 P
 int launch_finish16_l0w4(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);  // ... on long rows
 int launch_finish16_l0xo(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);  // long rows, the proj's codes
 // its chunked sibling for rows of 1,025 .. 4,096 keys (mxa_fin16_xl.hip): float32, MXINT8 / MXINT4 P
 int launch_finish16_xl_w8(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 int launch_finish16_xl_w4(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
+int launch_finish16_xl_x1(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);  // float16 / bfloat16, MXINT8 P
 // the 32-row finishing kernel for NB blocks per head dim (mxa_fin.hip parts 1..4)
 int launch_finish32_p1(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 int launch_finish32_p2(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);

@@ -8,10 +8,11 @@ MX_transformer_block.py:648-717): B = 2, H = 16, N = T = 1,024, D = 72, ex_pred;
 (self_top_k=False, exclude_timesteps, exclude_blocks) and k = 154, at widths 8 and 4.
 
     python tools/bench_long_dense.py [--steps 20] [--warmup 3] [--reps 3] [--cases dense,k154] [--widths 8,4] [--fused-only]
-                                     [--tokens 1024] [--batch 2]
+                                     [--tokens 1024] [--batch 2] [--dtype f32]
 
 --tokens 4096 --batch 1: PixArt-Sigma at 1024x1024, whose dense rows run on finish_qk_xl_kernel
 (mxa_attention_xl_full); the library has no k = 154 on such rows, so the case list is `dense` there.
+--dtype f16 / bf16: q, k, v in that dtype on both routes (mxa_attention_dt's 16-bit kernels; width 8 only).
 
 Both routes of every case are warmed up first; then per case `reps` repetitions alternate the two
 routes, each timed with device events around `steps` calls.  Prints per case the median and the
@@ -27,6 +28,7 @@ from ab_routes import M, agreement, alternate, chain, ms_fields
 
 H, D, MODE = 16, 72, "ex_pred"
 CASES = {"dense": 0, "k154": 154}
+DTYPES = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}
 
 
 def main():
@@ -39,12 +41,15 @@ def main():
     ap.add_argument("--fused-only", action="store_true")
     ap.add_argument("--tokens", type=int, default=1024)
     ap.add_argument("--batch", type=int, default=2)
+    ap.add_argument("--dtype", default="f32", choices=tuple(DTYPES))
     args = ap.parse_args()
+    if args.dtype != "f32":
+        args.widths = "8"
     B, N = args.batch, args.tokens
     cases = args.cases or (",".join(CASES) if N <= 1024 else "dense")
     dev = torch.device("cuda", 0)
     g = torch.Generator(device="cpu").manual_seed(0)
-    q, k, v = (torch.randn(B, H, N, D, generator=g).to(dev) for _ in range(3))
+    q, k, v = (torch.randn(B, H, N, D, generator=g).to(DTYPES[args.dtype]).to(dev) for _ in range(3))
     scale = D ** -0.5
 
     def fused(kt, bits):
@@ -61,7 +66,7 @@ def main():
     runs = [(name, CASES[name], int(w)) for name in cases.split(",") for w in args.widths.split(",")]
     for run, times in zip(runs, alternate(map(routes, runs), args.steps, args.warmup, args.reps)):
         name, kt, bits = run
-        line = {"shape": "pixart_self_512" if N == 1024 else f"pixart_self_{N}_tokens", "case": name, "elem_bits": bits, "B_H_N_T_D_k": (B, H, N, N, D, kt), "pred_mode": MODE,
+        line = {"shape": "pixart_self_512" if N == 1024 else f"pixart_self_{N}_tokens", "case": name, "elem_bits": bits, "dtype": args.dtype, "B_H_N_T_D_k": (B, H, N, N, D, kt), "pred_mode": MODE,
                 "steps": args.steps, "reps": args.reps, **ms_fields(times)}
         if not args.fused_only:
             line.update(agreement(*(fn() for fn in routes(run).values())))

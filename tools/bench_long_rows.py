@@ -6,9 +6,11 @@ N x T matrix (torch's CPU order), torch gather / softmax / scatter, mx.matmul (P
 as tests/glue_deit.py lays out DeiT's.  The PixArt-alpha 512x512 self-attention block
 (workloads/PixArt/models/MX_transformer_block.py:624-717): B = 2, H = 16, N = T = 1,024, D = 72,
 k = 20, ex_pred and MXINT4.  --tokens 4096 --batch 1: PixArt-Sigma at 1024x1024 (the chain's M.topk then runs
-mxa_topk_xl); --bits 4: Q, K, P and V at MXINT4 on both routes.
+mxa_topk_xl); --bits 4: Q, K, P and V at MXINT4 on both routes; --dtype f16 / bf16: q, k, v in that dtype on both
+routes (the reference's PixArt pipeline runs in float16; the fused call then takes mxa_attention_dt's 16-bit kernels).
 
     python tools/bench_long_rows.py [--steps 20] [--warmup 3] [--reps 3] [--fused-only] [--tokens 1024] [--batch 2] [--bits 8]
+                                    [--dtype f32]
 
 Both routes and both modes are warmed up first; then per mode `reps` repetitions alternate the
 two routes, each timed with device events around `steps` calls.  Prints per mode the median and
@@ -24,6 +26,7 @@ from ab_routes import M, agreement, alternate, chain, ms_fields
 
 H, D, K_TOP = 16, 72, 20
 MODES = ("ex_pred", "MXINT4")
+DTYPES = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}
 
 
 def main():
@@ -35,11 +38,12 @@ def main():
     ap.add_argument("--tokens", type=int, default=1024)
     ap.add_argument("--batch", type=int, default=2)
     ap.add_argument("--bits", type=int, default=8, choices=(8, 4))
+    ap.add_argument("--dtype", default="f32", choices=tuple(DTYPES))
     args = ap.parse_args()
     B, N = args.batch, args.tokens
     dev = torch.device("cuda", 0)
     g = torch.Generator(device="cpu").manual_seed(0)
-    q, k, v = (torch.randn(B, H, N, D, generator=g).to(dev) for _ in range(3))
+    q, k, v = (torch.randn(B, H, N, D, generator=g).to(DTYPES[args.dtype]).to(dev) for _ in range(3))
     scale = D ** -0.5
 
     def fused(mode):
@@ -52,7 +56,7 @@ def main():
         return r
 
     for mode, times in zip(MODES, alternate(map(routes, MODES), args.steps, args.warmup, args.reps)):
-        line = {"shape": "pixart_self_512" if N == 1024 else f"pixart_self_{N}_tokens","B_H_N_T_D_k": (B, H, N, N, D, K_TOP), "pred_mode": mode, "elem_bits": args.bits,
+        line = {"shape": "pixart_self_512" if N == 1024 else f"pixart_self_{N}_tokens","B_H_N_T_D_k": (B, H, N, N, D, K_TOP), "pred_mode": mode, "elem_bits": args.bits, "dtype": args.dtype,
                 "steps": args.steps, "reps": args.reps, **ms_fields(times)}
         if not args.fused_only:
             line.update(agreement(*(fn() for fn in routes(mode).values())))
