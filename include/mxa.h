@@ -157,6 +157,17 @@ int mxa_topk_xl(const void* vals, int64_t rows, int32_t n, int64_t ld, int32_t k
                 int64_t* out_idx, void* out_vals, uint32_t* out_mask, int32_t dtype, hipStream_t stream);
 
 /*
+ * mxa_topk_xl plus the rest of rows of 1,025 .. 4,096 values: every 0 <= k <= n.  Where torch takes
+ * std::nth_element + std::sort (k > 64 or k * 64 > n) libstdc++'s __introselect and __introsort_loop
+ * are replayed by one wave per row on a 64-bit mirror of the row in LDS, the partition window walked
+ * in chunks of 16 registers (the selection body of mxa_attention_nth).  The same arguments, dtypes
+ * and outputs.  Every call mxa_topk_xl accepts runs what that runs (n <= 1,024: mxa_topk).  k == 0
+ * keeps nothing, as in mxa_topk.  MXA_ERR_UNSUPPORTED: n > 4,096.
+ */
+int mxa_topk_xl_nth(const void* vals, int64_t rows, int32_t n, int64_t ld, int32_t k,
+                    int64_t* out_idx, void* out_vals, uint32_t* out_mask, int32_t dtype, hipStream_t stream);
+
+/*
  * mxa_topk with a device workspace (the same results): rows of <= 256 values go through
  * the packed 32-bit selection pass and the one-lane tail (the fused op's selection
  * engine), which stage per-row state in the workspace.  mxa_topk_workspace_bytes:
@@ -386,6 +397,29 @@ int mxa_attention_dt(const mxa_attn_params* p, int32_t elem_bits, hipStream_t st
 int mxa_attention_dt_finish_kernel(const mxa_attn_params* p, int32_t elem_bits);
 
 /*
+ * mxa_attention_dt plus, on rows of 1,025 .. 4,096 keys, the top-k branch with every 1 <= k_top <= T
+ * where torch's CPU topk takes std::nth_element + std::sort (k_top > 64 or k_top * 64 > T): the
+ * reference's default k_top = 20 below 1,280 keys, --k 30 below 1,920, and PixArt's self_k = 154 at
+ * 1024 x 1024 (workloads/PixArt/models/MX_transformer_block.py:648-717).  The same parameter
+ * struct, strides, outputs and workspace rules.
+ *   - every call mxa_attention_dt(p, elem_bits) accepts runs exactly what that runs: the same
+ *     kernels, bytes, statuses and workspace size;
+ *   - k_top <= 64: select_xl_nth_kernel (one wave per query row, the chunked wave top-k), then
+ *     finish16_xl_kernel as in mxa_attention_xl -- float32 at either width and, at elem_bits 8, the
+ *     float16 / bfloat16 forms of mxa_attention_dt;
+ *   - k_top > 64: select_xl_nth_kernel, then the masked form of finish_qk_xl_kernel, which reads the
+ *     selection's prune-mask words (mask_out, else a workspace region whose size does not depend on
+ *     mask_out) -- float32 at either width.
+ * MXA_ERR_UNSUPPORTED, before any HIP call: with T > 1,024 k_top > 64 with float16 / bfloat16
+ * tensors or scores, MXA_PRED_ELSA; T > 4,096.  No scores-only or fused-projection form.
+ * mxa_attention_nth_finish_kernel: the MXA_FIN_* kind of the call (no launch; the workspace may be
+ * null) -- MXA_FIN_GATHER16_XL for k_top <= 64, MXA_FIN_MFMA_XL for k_top > 64 on those rows.
+ */
+int64_t mxa_attention_nth_workspace_bytes(const mxa_attn_params* p, int32_t elem_bits);
+int mxa_attention_nth(const mxa_attn_params* p, int32_t elem_bits, hipStream_t stream);
+int mxa_attention_nth_finish_kernel(const mxa_attn_params* p, int32_t elem_bits);
+
+/*
  * Which kernels mxa_attention(p) runs (no launch; the workspace may be null):
  *   MXA_PATH_ROWS_SPLIT  selection kernel (scores + top-k) then finishing kernel
  *                        (gather, softmax, MX(P), P.V on int8 MFMA) -- top_k != 0
@@ -413,8 +447,11 @@ int mxa_attention_path(const mxa_attn_params* p);
  *   MXA_FIN_GATHER16_XL      finish16_xl_kernel: top-k with k <= 64 on rows over 1,024 keys
  * and by mxa_attention_xl_full_finish_kernel for mxa_attention_xl_full alone:
  *   MXA_FIN_DENSE_MFMA_XL    finish_qk_xl_kernel: top_k == 0 on rows over 1,024 keys
+ * and by mxa_attention_nth_finish_kernel for mxa_attention_nth alone:
+ *   MXA_FIN_MFMA_XL          finish_qk_xl_kernel, masked: top-k with k >= 65 on rows over 1,024 keys
  * or a negative MXA_ERR_* for invalid parameters.
  */
+#define MXA_FIN_MFMA_XL 10
 #define MXA_FIN_DENSE_MFMA_XL 9
 #define MXA_FIN_GATHER16_XL 8
 #define MXA_FIN_GATHER16 1

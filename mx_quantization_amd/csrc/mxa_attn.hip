@@ -119,8 +119,10 @@ ModeNeeds mode_needs(int mode) {
 // kReachXl (mxa_attention_xl) stands beside kReachBlock, not above it: kReachFull's calls plus the top-k
 // branch on rows of 1,025 .. kXlRowsT keys (xl_rows_ok), none of the fused projections there or on long rows.
 // kReachXlFull (mxa_attention_xl_full): kReachXl's calls plus the dense branch on those rows; kReachDt
-// (mxa_attention_dt): kReachXlFull's calls plus, on rows over 512 keys, float16 / bfloat16 tensors and scores
-enum Reach { kReachShort, kReachLong, kReachFull, kReachBlock, kReachXl, kReachXlFull, kReachDt };
+// (mxa_attention_dt): kReachXlFull's calls plus, on rows over 512 keys, float16 / bfloat16 tensors and scores;
+// kReachNth (mxa_attention_nth): kReachDt's calls plus, on rows of 1,025 .. kXlRowsT keys, the top-k branch
+// with every k_top outside partial_sort's regime (xl_rows_nth)
+enum Reach { kReachShort, kReachLong, kReachFull, kReachBlock, kReachXl, kReachXlFull, kReachDt, kReachNth };
 
 // the proj Linear's input comes MX-quantized out of the finishing kernel (MXINT8 only: at 4 bits the
 // fp32 rows go through the workspace and the row quantizer for every D; rows over 512 keys: from the LONG
@@ -154,7 +156,7 @@ struct AttnCall {
 FinFacts attn_fin_facts(const AttnCall& c, const mxa_attn_params* p) {
   return {p->top_k != 0, p->top_k ? p->k_top : 0, p->T, (p->D + 31) / 32, c.pj && proj_codes_direct(p, c.elem_bits, c.reach),
           p->dtype != MXA_DT_F32 || p->score_dtype > MXA_DT_F32, c.elem_bits, c.reach >= kReachFull, c.reach == kReachBlock,
-          c.reach >= kReachXl, c.reach >= kReachXlFull, c.reach >= kReachDt};
+          c.reach >= kReachXl, c.reach >= kReachXlFull, c.reach >= kReachDt, c.reach >= kReachNth};
 }
 
 // one side's (Q's or K's) row operands; null: the score mode does not read it
@@ -283,10 +285,10 @@ int attn_validate(const AttnCall& c) {
   if (!valid_bfloat(p->bfloat)) return MXA_ERR_ARG;
   if (p->T > (reach == kReachShort ? kShortRowsT : reach >= kReachXl ? kXlRowsT : kLongRowsT) || p->D > 32 * kMaxNB)
     return MXA_ERR_UNSUPPORTED;
-  // rows over 1,024 keys: the top-k branch in partial_sort's regime alone, and for kReachXlFull the dense
-  // branch (the rest of their refusals -- 16-bit dtypes, the fused projections -- are the long rows', below,
-  // and finish_choice's)
-  if (xl_rows(p->T) && (scores_only || (p->top_k ? !xl_rows_ok(p->T, p->k_top) : reach < kReachXlFull) ||
+  // rows over 1,024 keys: the top-k branch in partial_sort's regime alone (kReachNth: every k_top), and for
+  // kReachXlFull the dense branch (the rest of their refusals -- 16-bit dtypes, the fused projections -- are the
+  // long rows', below, and finish_choice's)
+  if (xl_rows(p->T) && (scores_only || (p->top_k ? !xl_rows_ok(p->T, p->k_top) && reach < kReachNth : reach < kReachXlFull) ||
                         (p->approx && p->pred_mode == MXA_PRED_ELSA)))
     return MXA_ERR_UNSUPPORTED;
   // rows over 512 keys: float32 (but for kReachDt), no fused projection but kReachBlock's qkv and proj Linears;
@@ -588,6 +590,7 @@ int attention_impl(const AttnCall& c) {
   // feasibility of the path's kernels (LDS budgets), before any pointer is bound
   // (rows over 512 keys: the one-wave-per-row selection kernel, mxa_select_long.hpp)
   auto select = [&](bool plan, const SideLane* side = nullptr) {
+    if (xl_rows(pp.T) && !xl_rows_ok(pp.T, pp.k_top)) return launch_select_xl_nth(r2, mode, BH, c.stream, plan);  // (mxa_select_xl_nth.hpp)
     if (xl_rows(pp.T)) return launch_select_xl(r2, mode, BH, c.stream, plan);  // (mxa_select_xl.hpp)
     return long_rows(pp.T) ? launch_select_long(r2, mode, BH, c.stream, plan) : launch_select(r2, mode, BH, c.stream, plan, side);
   };
@@ -792,6 +795,24 @@ extern "C" int mxa_attention_dt(const mxa_attn_params* p, int32_t elem_bits, hip
 extern "C" int mxa_attention_dt_finish_kernel(const mxa_attn_params* p, int32_t elem_bits) {
   int plan = -1, fin = -1;
   const int rc = attention_impl({.p = p, .reach = kReachDt, .plan = &plan, .fin = &fin, .elem_bits = elem_bits});
+  return rc ? rc : fin;
+}
+
+// mxa_attention_dt plus, on rows of 1,025 .. 4,096 keys, the top-k branch where torch's topk takes
+// std::nth_element + std::sort (k_top > 64 or k_top * 64 > T; MX_transformer_block.py:648-717 with self_k = 154
+// at 1024 x 1024, the default k_top = 20 below 1,280 keys): select_xl_nth_kernel, then finish16_xl_kernel
+// (k_top <= 64) or the masked finish_qk_xl_kernel (k_top > 64, float32)
+extern "C" int64_t mxa_attention_nth_workspace_bytes(const mxa_attn_params* p, int32_t elem_bits) {
+  return mx_width_ok(elem_bits) && attn_shape_ok(p) ? attn_workspace_total({.p = p, .reach = kReachNth}) : -1;
+}
+
+extern "C" int mxa_attention_nth(const mxa_attn_params* p, int32_t elem_bits, hipStream_t stream) {
+  return attention_impl({.p = p, .stream = stream, .reach = kReachNth, .elem_bits = elem_bits});
+}
+
+extern "C" int mxa_attention_nth_finish_kernel(const mxa_attn_params* p, int32_t elem_bits) {
+  int plan = -1, fin = -1;
+  const int rc = attention_impl({.p = p, .reach = kReachNth, .plan = &plan, .fin = &fin, .elem_bits = elem_bits});
   return rc ? rc : fin;
 }
 

@@ -127,6 +127,8 @@ int launch_rows(const Rows2Args& ra0, const FinFacts& f, bool true_mode, int S, 
     case MXA_FIN_DENSE_MFMA_XL:
       if (f.xdt) return launch_finish_qk_xl_x1(ra, BH, stream, plan);
       return w4 ? launch_finish_qk_xl_w4(ra, BH, stream, plan) : launch_finish_qk_xl_w8(ra, BH, stream, plan);
+    case MXA_FIN_MFMA_XL:  // (finish_choice: float32)
+      return w4 ? launch_finish_qk_xl_m4(ra, BH, stream, plan) : launch_finish_qk_xl_m8(ra, BH, stream, plan);
     case MXA_FIN_GATHER16_XL:
       if (f.xdt) return launch_finish16_xl_x1(ra, BH, stream, plan);
       return w4 ? launch_finish16_xl_w4(ra, BH, stream, plan) : launch_finish16_xl_w8(ra, BH, stream, plan);

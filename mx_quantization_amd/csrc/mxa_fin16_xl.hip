@@ -60,7 +60,8 @@ static int launch_finish16_xl_nb(const Rows2Args& ra, int BH, hipStream_t stream
 
 int MXA_F16XL_FN(const Rows2Args& ra, int BH, hipStream_t stream, bool plan) {
   // (launch_rows chooses the unit by the call's dtypes; the plan pass runs before they are bound)
-  if (!xl_rows_ok(ra.T, ra.k_top) || ra.xo_codes || (!kF16XlXdt && (ra.s_dt != kF32 || ra.in_dt != kF32))) return MXA_ERR_UNSUPPORTED;
+  // (any kept-index list of 1 .. 64 keys: finish_choice decides which k reach it -- mxa_attention_nth's every one)
+  if (!xl_rows(ra.T) || ra.T > kXlRowsT || ra.k_top < 1 || ra.k_top > 64 || ra.xo_codes || (!kF16XlXdt && (ra.s_dt != kF32 || ra.in_dt != kF32))) return MXA_ERR_UNSUPPORTED;
   if (plan) {
     int w, r;
     return finish16_xl_plan(ra, BH, 2, &w, &r);

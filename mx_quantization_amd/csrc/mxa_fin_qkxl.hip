@@ -3,6 +3,8 @@
 // instantiations (launch_finish_qk_xl_w8), MXA_FQXL_W4=1 the MXINT4-P ones
 // (launch_finish_qk_xl_w4), so that the two build in parallel.  A third compilation, MXA_FQXL_XDT=1
 // (MXINT8 P), holds the float16 / bfloat16 instantiations (launch_finish_qk_xl_x1: mxa_attention_dt).
+// MXA_FQXL_MASK=1 (with either MXA_FQXL_W4): the masked float32 instantiations of the top-k branch with
+// k_top > 64 (launch_finish_qk_xl_m8 / _m4: mxa_attention_nth), two more units.
 #include "mxa_finish_qk_xl.hpp"
 #include "mxa_launch.hpp"
 
@@ -12,7 +14,14 @@
 #ifndef MXA_FQXL_XDT
 #define MXA_FQXL_XDT 0
 #endif
-#if MXA_FQXL_XDT
+#ifndef MXA_FQXL_MASK
+#define MXA_FQXL_MASK 0
+#endif
+#if MXA_FQXL_MASK && MXA_FQXL_W4
+#define MXA_FQXL_FN launch_finish_qk_xl_m4
+#elif MXA_FQXL_MASK
+#define MXA_FQXL_FN launch_finish_qk_xl_m8
+#elif MXA_FQXL_XDT
 #define MXA_FQXL_FN launch_finish_qk_xl_x1
 #elif MXA_FQXL_W4
 #define MXA_FQXL_FN launch_finish_qk_xl_w4
@@ -24,7 +33,8 @@ namespace mxa {
 
 constexpr bool kFqxlW4 = MXA_FQXL_W4 != 0;
 constexpr bool kFqxlXdt = MXA_FQXL_XDT != 0;
-static_assert(!(kFqxlW4 && kFqxlXdt), "MXINT4 P: float32 only");
+constexpr bool kFqxlMask = MXA_FQXL_MASK != 0;
+static_assert(!(kFqxlW4 && kFqxlXdt) && !(kFqxlMask && kFqxlXdt), "MXINT4 P and the masked form: float32 only");
 
 // the LDS of a workgroup is one chunk's tables whatever T and the number of waves are; the waves per
 // workgroup come from finish_tile_plan by the waves per SIMD the instantiation's registers allow
@@ -35,7 +45,7 @@ static int finish_qk_xl_plan(const Rows2Args& ra, int BH, int regs_waves_per_sim
 template <int NB, bool EXTRA>
 static int launch_finish_qk_xl_x(const Rows2Args& ra0, int BH, hipStream_t stream) {
   Rows2Args ra = ra0;
-  constexpr auto kernel = &finish_qk_xl_kernel<NB + (kFqxlXdt ? kFqDtNB : 0), kFqxlW4, EXTRA>;
+  constexpr auto kernel = &finish_qk_xl_kernel<NB + (kFqxlXdt ? kFqDtNB : 0) + (kFqxlMask ? kFqXlMaskNB : 0), kFqxlW4, EXTRA>;
   const int rc = finish_qk_xl_plan(ra, BH, kernel_waves_per_simd<kernel>(), &ra.waves, &ra.rows_per_wg);
   if (rc) return rc;
   // the kernel's barriers need whole tiles of whole waves: 1 .. 8 waves, a workgroup's rows a multiple of the tile
@@ -50,7 +60,9 @@ static int launch_finish_qk_xl_nb(const Rows2Args& ra, int BH, hipStream_t strea
 
 int MXA_FQXL_FN(const Rows2Args& ra, int BH, hipStream_t stream, bool plan) {
   // (launch_rows chooses the unit by the call's dtypes; the plan pass runs before they are bound)
-  if ((!kFqxlXdt && (ra.s_dt != kF32 || ra.in_dt != kF32)) || ra.xo_codes || !ra.dense) return MXA_ERR_UNSUPPORTED;
+  // (the masked units: the top-k branch, whose mask words the selection wrote -- bound after the plan pass)
+  if ((!kFqxlXdt && (ra.s_dt != kF32 || ra.in_dt != kF32)) || ra.xo_codes || (ra.dense != 0) == kFqxlMask) return MXA_ERR_UNSUPPORTED;
+  if (kFqxlMask && !plan && !ra.mask_out) return MXA_ERR_ARG;
   if (!xl_rows(ra.T) || ra.T > kXlRowsT || ra.ntb != (ra.T + 31) / 32 || ra.tpad != 32 * ra.ntb || ra.nbd < 1 || ra.nbd > 4 ||
       ra.D > 32 * ra.nbd)
     return MXA_ERR_UNSUPPORTED;

@@ -25,7 +25,10 @@
 // fq_finish_score (bias, true_out), the K codes and the V^T codes are addressed by the key's place in
 // the row.  The K codes and V^T codes stay in the workspace (L2); sweep's loads run a pair of key
 // blocks ahead, across chunk borders too (a chunk holds an even number of blocks, so no pair straddles
-// one).  Dense only: the kept bits of a lane are "key < T".
+// one).  The dense form's kept bits of a lane are "key < T"; the MASKED form (k_top > 64 outside
+// partial_sort's regime, mxa_attention_nth: MXA_FIN_MFMA_XL) reads the selection's prune-mask words the way
+// finish_qk_long_kernel does, a block's byte of the row's word a pair of key blocks ahead with the K operands --
+// so a chunk's mask words travel with that chunk's per-key terms -- and everything else is the dense form's.
 // Reference: microxscaling/mx/matmul.py:68-76, :85-88.
 #pragma once
 #include "mxa_finish_qk_long.hpp"
@@ -37,10 +40,14 @@ namespace mxa {
 // XDT (MXINT8 P, NBX = NB + kFqDtNB): finish_qk_long_kernel's XDT rules inside the lockstep walk.  The dtypes
 // are kernel arguments, so every branch on them is uniform over the workgroup, and none of them encloses a
 // barrier: stage() and the trip counts of rounds, passes, chunks and blocks do not read them
+// MASKED (float32): NBX = NB + kFqXlMaskNB, as XDT an offset of the block count that the dense instantiations
+// do not use, so that they keep their names and code
+constexpr int kFqXlMaskNB = 16;
 template <int NBX, bool W4, bool EXTRA>
 __global__ __launch_bounds__(512) void finish_qk_xl_kernel(Rows2Args a) {
   constexpr int NB = NBX % kFqDtNB;
-  constexpr bool XDT = NBX >= kFqDtNB;
+  constexpr bool MASKED = NBX >= kFqXlMaskNB;
+  constexpr bool XDT = !MASKED && NBX >= kFqDtNB;
   static_assert(!(W4 && XDT), "MXINT4 P: float32");
   const int sdt = XDT ? a.s_dt : (int)kF32, idt = XDT ? a.in_dt : (int)kF32;
   constexpr bool kRound = XDT || EXTRA;
@@ -94,9 +101,11 @@ __global__ __launch_bounds__(512) void finish_qk_xl_kernel(Rows2Args a) {
     const int64_t brow = EXTRA && a.bias ? b_ * a.bs0 + h_ * a.bs1 + (int64_t)crow * a.bs2 : -1;
     const FqQuery<NB> Q = fq_load_query<NB>(a.qc, a.qsT, grow, g);
 
-    // the row's kept bits of keys 32 blk + 8 g .. + 7: every key < T
+    // the row's kept bits of keys 32 blk + 8 g .. + 7: every key < T (MASKED: the row's mask word of the block;
+    // a.ntb == ceil(T / 32) words per row, mxa_fin_qkxl.hip)
     auto kept_bits = [&](int blk) -> uint32_t {
       if (!valid || blk >= ntb) return 0u;
+      if constexpr (MASKED) return (a.mask_out[grow * ntb + blk] >> (8 * g)) & 0xFFu;
       return (1u << min(max(T - (32 * blk + 8 * g), 0), 8)) - 1u;
     };
     // key tile `tile`'s (of the row) A operands of this lane; a key >= T reads nothing and gives zero codes

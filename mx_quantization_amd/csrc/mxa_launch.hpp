@@ -83,6 +83,10 @@ inline bool long_rows(int T) { return T > kShortRowsT; }
 constexpr int kXlRowsT = 4096;
 inline bool xl_rows(int T) { return T > kLongRowsT; }
 inline bool xl_rows_ok(int T, int k) { return xl_rows(T) && T <= kXlRowsT && k >= 1 && k <= 64 && (int64_t)k * 64 <= T; }
+// ... and the rest of the top-k branch on those rows (mxa_attention_nth, mxa_topk_xl_nth): every 1 <= k <= T where
+// torch takes std::nth_element + std::sort -- the chunked wave top-k (mxa_select_xl_nth.hpp), then the same
+// 16-row kernel (k <= 64) or the masked form of the chunked MFMA kernel (k > 64, mxa_finish_qk_xl.hpp)
+inline bool xl_rows_nth(int T, int k) { return xl_rows(T) && T <= kXlRowsT && k >= 1 && k <= T && !xl_rows_ok(T, k); }
 // The side lane of a forked attention call (mxa_attn.hip, SideFork): the library's own stream beside the
 // caller's, joined before the finishing kernel.  `packed`: the event launch_select records behind the
 // packed pass
@@ -96,6 +100,8 @@ int launch_select(const Rows2Args& ra, int mode, int BH, hipStream_t stream, boo
 int launch_select_long(const Rows2Args& ra, int mode, int BH, hipStream_t stream, bool plan);
 // ... for rows of 1,025 .. 4,096 keys (mxa_sel_xl.hip)
 int launch_select_xl(const Rows2Args& ra, int mode, int BH, hipStream_t stream, bool plan);
+// ... outside partial_sort's regime (mxa_sel_xl_nth.hip)
+int launch_select_xl_nth(const Rows2Args& ra, int mode, int BH, hipStream_t stream, bool plan);
 // the one-lane tail's prefix (measured, DeiT-base: 48 positions 0.575-0.583 ms against 0.585-0.599
 // for 64 -- 12 KB of LDS per wave, 3 waves per SIMD instead of 2, outweighs the selection kernel's
 // extra step -- and 0.573-0.584 for 56; a 32-position prefix is slower: the selection kernel then
@@ -155,8 +161,9 @@ inline int launch_select_mode(const Rows2Args& ra, int mode, int BH, hipStream_t
 // block: it reaches the fused projections on rows over 512 keys too (the *_full fused blocks), where xo is
 // the LONG 16-row kernel's: MXINT8, k <= 32; xl: it reaches rows of 1,025 .. 4,096 keys (mxa_attention_xl);
 // xl_dense: on those rows the dense branch too (mxa_attention_xl_full); dt: on rows over 512 keys float16 /
-// bfloat16 tensors or scores too, at MXINT8 (mxa_attention_dt)
-struct FinFacts { bool topk; int k, T, nbd; bool xo, xdt; int bits; bool full; bool block = false; bool xl = false; bool xl_dense = false; bool dt = false; };
+// bfloat16 tensors or scores too, at MXINT8 (mxa_attention_dt); nth: on rows of 1,025 .. 4,096 keys every k_top
+// outside partial_sort's regime too (mxa_attention_nth)
+struct FinFacts { bool topk; int k, T, nbd; bool xo, xdt; int bits; bool full; bool block = false; bool xl = false; bool xl_dense = false; bool dt = false; bool nth = false; };
 // kind: MXA_FIN_* (include/mxa.h); reads_mask: the kernel reads the selection's prune-mask words (the
 // caller's mask_out, else a workspace copy), not the kept indices; status: MXA_ERR_UNSUPPORTED where the
 // kind has no instantiation for the facts
@@ -168,7 +175,13 @@ inline FinChoice finish_choice(const FinFacts& f) {
   FinChoice c{};
   if (f.xl && xl_rows(f.T) && f.topk && f.k <= 64) {  // the chunked 16-row kernel (mxa_finish16_xl.hpp):
     c.kind = MXA_FIN_GATHER16_XL;                      // top-k in partial_sort's regime
-    c.status = xl_rows_ok(f.T, f.k) && (!f.xdt || ldt) && !f.xo ? MXA_OK : MXA_ERR_UNSUPPORTED;
+    c.status = (xl_rows_ok(f.T, f.k) || (f.nth && xl_rows_nth(f.T, f.k))) && (!f.xdt || ldt) && !f.xo ? MXA_OK : MXA_ERR_UNSUPPORTED;
+    return c;
+  }
+  if (f.nth && xl_rows(f.T) && f.topk) {  // k > 64: the masked chunked MFMA kernel (mxa_finish_qk_xl.hpp), float32
+    c.kind = MXA_FIN_MFMA_XL;
+    c.reads_mask = true;
+    c.status = xl_rows_nth(f.T, f.k) && f.nbd <= 4 && !f.xdt && !f.xo ? MXA_OK : MXA_ERR_UNSUPPORTED;
     return c;
   }
   if (f.xl_dense && xl_rows(f.T) && !f.topk) {  // the chunked tiled MFMA kernel (mxa_finish_qk_xl.hpp)
@@ -294,6 +307,8 @@ int launch_finish_qk_long_x1(const Rows2Args& ra, int BH, hipStream_t stream, bo
 int launch_finish_qk_xl_w8(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 int launch_finish_qk_xl_w4(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 int launch_finish_qk_xl_x1(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);  // float16 / bfloat16, MXINT8 P
+int launch_finish_qk_xl_m8(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);  // the masked form (k_top > 64): float32
+int launch_finish_qk_xl_m4(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 // the 16-row finishing kernel (mxa_fin16.hip): float32 (x0), float16 / bfloat16 (x1)
 int launch_finish16_x0(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 int launch_finish16_x1(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
