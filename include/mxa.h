@@ -420,6 +420,28 @@ int mxa_attention_nth(const mxa_attn_params* p, int32_t elem_bits, hipStream_t s
 int mxa_attention_nth_finish_kernel(const mxa_attn_params* p, int32_t elem_bits);
 
 /*
+ * mxa_attention_nth plus, on rows of 1,025 .. 4,096 keys, k_top > 64 with float16 / bfloat16 tensors or a
+ * nonzero score_dtype: the reference runs PixArt-Sigma at 1024 x 1024 with torch_dtype=torch.float16 and
+ * self_k = 154 (workloads/PixArt/scripts/mx_inference.py:149-152, models/MX_transformer_block.py:648-717).
+ * The same parameter struct, strides, outputs and workspace rules.
+ *   - every call mxa_attention_nth(p, elem_bits) accepts runs exactly what that runs: the same kernels,
+ *     bytes, statuses and workspace size (every float32 call among them);
+ *   - at elem_bits 8 with 16-bit tensors or scores and 65 <= k_top <= 256: select_xl_nth_kernel, then
+ *     finish_gather_xl_kernel -- only the kept keys' scores, as finish16_xl_kernel computes them, with the
+ *     slots (key, 16-bit score, then p) in a per-wave LDS table instead of registers; it reads the kept
+ *     indices, so no mask words are reserved;
+ *   - with 256 < k_top <= T: select_xl_nth_kernel, then the masked form of finish_qk_xl_kernel with the
+ *     16-bit rules of mxa_attention_dt.
+ * MXA_ERR_UNSUPPORTED, before any HIP call: elem_bits 4 with such tensors or scores; with T > 1,024
+ * MXA_PRED_ELSA; T > 4,096.  No scores-only or fused-projection form.  mxa_attention_nth_dt_finish_kernel:
+ * the MXA_FIN_* kind of the call (no launch; the workspace may be null) -- MXA_FIN_GATHER_XL or
+ * MXA_FIN_MFMA_XL for those calls.
+ */
+int64_t mxa_attention_nth_dt_workspace_bytes(const mxa_attn_params* p, int32_t elem_bits);
+int mxa_attention_nth_dt(const mxa_attn_params* p, int32_t elem_bits, hipStream_t stream);
+int mxa_attention_nth_dt_finish_kernel(const mxa_attn_params* p, int32_t elem_bits);
+
+/*
  * Which kernels mxa_attention(p) runs (no launch; the workspace may be null):
  *   MXA_PATH_ROWS_SPLIT  selection kernel (scores + top-k) then finishing kernel
  *                        (gather, softmax, MX(P), P.V on int8 MFMA) -- top_k != 0
@@ -449,8 +471,13 @@ int mxa_attention_path(const mxa_attn_params* p);
  *   MXA_FIN_DENSE_MFMA_XL    finish_qk_xl_kernel: top_k == 0 on rows over 1,024 keys
  * and by mxa_attention_nth_finish_kernel for mxa_attention_nth alone:
  *   MXA_FIN_MFMA_XL          finish_qk_xl_kernel, masked: top-k with k >= 65 on rows over 1,024 keys
+ * and by mxa_attention_nth_dt_finish_kernel for mxa_attention_nth_dt alone:
+ *   MXA_FIN_GATHER_XL        finish_gather_xl_kernel: top-k with 65 <= k <= 256 on rows over 1,024 keys at
+ *                            float16 / bfloat16: kept-key QK^T on v_dot4 (the slots in LDS), P.V on
+ *                            v_mfma_i32_16x16x32_i8
  * or a negative MXA_ERR_* for invalid parameters.
  */
+#define MXA_FIN_GATHER_XL 11
 #define MXA_FIN_MFMA_XL 10
 #define MXA_FIN_DENSE_MFMA_XL 9
 #define MXA_FIN_GATHER16_XL 8

@@ -121,8 +121,9 @@ ModeNeeds mode_needs(int mode) {
 // kReachXlFull (mxa_attention_xl_full): kReachXl's calls plus the dense branch on those rows; kReachDt
 // (mxa_attention_dt): kReachXlFull's calls plus, on rows over 512 keys, float16 / bfloat16 tensors and scores;
 // kReachNth (mxa_attention_nth): kReachDt's calls plus, on rows of 1,025 .. kXlRowsT keys, the top-k branch
-// with every k_top outside partial_sort's regime (xl_rows_nth)
-enum Reach { kReachShort, kReachLong, kReachFull, kReachBlock, kReachXl, kReachXlFull, kReachDt, kReachNth };
+// with every k_top outside partial_sort's regime (xl_rows_nth); kReachNthDt (mxa_attention_nth_dt): kReachNth's
+// calls plus, on those rows, k_top > 64 with float16 / bfloat16 tensors or scores
+enum Reach { kReachShort, kReachLong, kReachFull, kReachBlock, kReachXl, kReachXlFull, kReachDt, kReachNth, kReachNthDt };
 
 // the proj Linear's input comes MX-quantized out of the finishing kernel (MXINT8 only: at 4 bits the
 // fp32 rows go through the workspace and the row quantizer for every D; rows over 512 keys: from the LONG
@@ -156,7 +157,7 @@ struct AttnCall {
 FinFacts attn_fin_facts(const AttnCall& c, const mxa_attn_params* p) {
   return {p->top_k != 0, p->top_k ? p->k_top : 0, p->T, (p->D + 31) / 32, c.pj && proj_codes_direct(p, c.elem_bits, c.reach),
           p->dtype != MXA_DT_F32 || p->score_dtype > MXA_DT_F32, c.elem_bits, c.reach >= kReachFull, c.reach == kReachBlock,
-          c.reach >= kReachXl, c.reach >= kReachXlFull, c.reach >= kReachDt, c.reach >= kReachNth};
+          c.reach >= kReachXl, c.reach >= kReachXlFull, c.reach >= kReachDt, c.reach >= kReachNth, c.reach >= kReachNthDt};
 }
 
 // one side's (Q's or K's) row operands; null: the score mode does not read it
@@ -813,6 +814,23 @@ extern "C" int mxa_attention_nth(const mxa_attn_params* p, int32_t elem_bits, hi
 extern "C" int mxa_attention_nth_finish_kernel(const mxa_attn_params* p, int32_t elem_bits) {
   int plan = -1, fin = -1;
   const int rc = attention_impl({.p = p, .reach = kReachNth, .plan = &plan, .fin = &fin, .elem_bits = elem_bits});
+  return rc ? rc : fin;
+}
+
+// mxa_attention_nth plus k_top > 64 on those rows with float16 / bfloat16 tensors or scores (PixArt-Sigma at
+// 1024 x 1024 with torch_dtype=torch.float16 and self_k = 154): select_xl_nth_kernel, then finish_gather_xl_kernel
+// (k_top <= 256, the kept keys' slots in LDS) or the masked finish_qk_xl_kernel's 16-bit form
+extern "C" int64_t mxa_attention_nth_dt_workspace_bytes(const mxa_attn_params* p, int32_t elem_bits) {
+  return mx_width_ok(elem_bits) && attn_shape_ok(p) ? attn_workspace_total({.p = p, .reach = kReachNthDt}) : -1;
+}
+
+extern "C" int mxa_attention_nth_dt(const mxa_attn_params* p, int32_t elem_bits, hipStream_t stream) {
+  return attention_impl({.p = p, .stream = stream, .reach = kReachNthDt, .elem_bits = elem_bits});
+}
+
+extern "C" int mxa_attention_nth_dt_finish_kernel(const mxa_attn_params* p, int32_t elem_bits) {
+  int plan = -1, fin = -1;
+  const int rc = attention_impl({.p = p, .reach = kReachNthDt, .plan = &plan, .fin = &fin, .elem_bits = elem_bits});
   return rc ? rc : fin;
 }
 

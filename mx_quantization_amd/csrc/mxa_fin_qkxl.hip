@@ -4,7 +4,8 @@
 // (launch_finish_qk_xl_w4), so that the two build in parallel.  A third compilation, MXA_FQXL_XDT=1
 // (MXINT8 P), holds the float16 / bfloat16 instantiations (launch_finish_qk_xl_x1: mxa_attention_dt).
 // MXA_FQXL_MASK=1 (with either MXA_FQXL_W4): the masked float32 instantiations of the top-k branch with
-// k_top > 64 (launch_finish_qk_xl_m8 / _m4: mxa_attention_nth), two more units.
+// k_top > 64 (launch_finish_qk_xl_m8 / _m4: mxa_attention_nth), two more units; MXA_FQXL_MASK=1 with
+// MXA_FQXL_XDT=1 the masked float16 / bfloat16 ones (launch_finish_qk_xl_mx: mxa_attention_nth_dt, k_top > 256).
 #include "mxa_finish_qk_xl.hpp"
 #include "mxa_launch.hpp"
 
@@ -17,7 +18,9 @@
 #ifndef MXA_FQXL_MASK
 #define MXA_FQXL_MASK 0
 #endif
-#if MXA_FQXL_MASK && MXA_FQXL_W4
+#if MXA_FQXL_MASK && MXA_FQXL_XDT
+#define MXA_FQXL_FN launch_finish_qk_xl_mx
+#elif MXA_FQXL_MASK && MXA_FQXL_W4
 #define MXA_FQXL_FN launch_finish_qk_xl_m4
 #elif MXA_FQXL_MASK
 #define MXA_FQXL_FN launch_finish_qk_xl_m8
@@ -34,7 +37,7 @@ namespace mxa {
 constexpr bool kFqxlW4 = MXA_FQXL_W4 != 0;
 constexpr bool kFqxlXdt = MXA_FQXL_XDT != 0;
 constexpr bool kFqxlMask = MXA_FQXL_MASK != 0;
-static_assert(!(kFqxlW4 && kFqxlXdt) && !(kFqxlMask && kFqxlXdt), "MXINT4 P and the masked form: float32 only");
+static_assert(!(kFqxlW4 && kFqxlXdt), "MXINT4 P: float32 only");
 
 // the LDS of a workgroup is one chunk's tables whatever T and the number of waves are; the waves per
 // workgroup come from finish_tile_plan by the waves per SIMD the instantiation's registers allow

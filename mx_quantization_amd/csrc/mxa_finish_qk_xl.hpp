@@ -42,12 +42,16 @@ namespace mxa {
 // barrier: stage() and the trip counts of rounds, passes, chunks and blocks do not read them
 // MASKED (float32): NBX = NB + kFqXlMaskNB, as XDT an offset of the block count that the dense instantiations
 // do not use, so that they keep their names and code
+// MASKED with XDT (MXINT8 P, k_top > kGxlMaxK at float16 / bfloat16, mxa_attention_nth_dt): both offsets, NBX = NB +
+// kFqDtNB + kFqXlMaskNB.  The mask words only choose which scores are -inf, and the XDT rules work on the scores
+// that remain, so the two forms meet without a line of their own
 constexpr int kFqXlMaskNB = 16;
 template <int NBX, bool W4, bool EXTRA>
 __global__ __launch_bounds__(512) void finish_qk_xl_kernel(Rows2Args a) {
   constexpr int NB = NBX % kFqDtNB;
   constexpr bool MASKED = NBX >= kFqXlMaskNB;
-  constexpr bool XDT = !MASKED && NBX >= kFqDtNB;
+  constexpr bool XDT = (NBX % kFqXlMaskNB) >= kFqDtNB;
+  static_assert(kFqXlMaskNB == 2 * kFqDtNB && NB >= 1 && NB <= 4 && NBX < 2 * kFqXlMaskNB, "NBX: NB + the two offsets");
   static_assert(!(W4 && XDT), "MXINT4 P: float32");
   const int sdt = XDT ? a.s_dt : (int)kF32, idt = XDT ? a.in_dt : (int)kF32;
   constexpr bool kRound = XDT || EXTRA;

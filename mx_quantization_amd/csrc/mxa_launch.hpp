@@ -155,6 +155,13 @@ inline int launch_select_mode(const Rows2Args& ra, int mode, int BH, hipStream_t
 #ifndef MXA_FQ_KMIN
 #define MXA_FQ_KMIN 65
 #endif
+// the largest k of the LDS-slot gather kernel (mxa_finish_gather_xl.hpp; its table holds 256 slots a row: the
+// threshold is the table's size, not a measurement).  MXA_GXL_MAXK: a tools-only build of a lower one, so that
+// a same-box A/B can send one k to either kernel
+#ifndef MXA_GXL_MAXK
+#define MXA_GXL_MAXK 256
+#endif
+constexpr int kGxlMaxK = MXA_GXL_MAXK;
 // topk, k (0 on the dense branch), xo: the finishing kernel writes the proj Linear's MX input codes
 // (the call's `direct`, known before any pointer is bound); xdt: float16 / bfloat16 inputs or scores;
 // bits: 8 or 4, P's element width; full: the entry point reaches finish_qk_long_kernel (mxa_attention_full);
@@ -162,8 +169,9 @@ inline int launch_select_mode(const Rows2Args& ra, int mode, int BH, hipStream_t
 // the LONG 16-row kernel's: MXINT8, k <= 32; xl: it reaches rows of 1,025 .. 4,096 keys (mxa_attention_xl);
 // xl_dense: on those rows the dense branch too (mxa_attention_xl_full); dt: on rows over 512 keys float16 /
 // bfloat16 tensors or scores too, at MXINT8 (mxa_attention_dt); nth: on rows of 1,025 .. 4,096 keys every k_top
-// outside partial_sort's regime too (mxa_attention_nth)
-struct FinFacts { bool topk; int k, T, nbd; bool xo, xdt; int bits; bool full; bool block = false; bool xl = false; bool xl_dense = false; bool dt = false; bool nth = false; };
+// outside partial_sort's regime too (mxa_attention_nth); nth_dt: there k_top > 64 at float16 / bfloat16 too
+// (mxa_attention_nth_dt)
+struct FinFacts { bool topk; int k, T, nbd; bool xo, xdt; int bits; bool full; bool block = false; bool xl = false; bool xl_dense = false; bool dt = false; bool nth = false; bool nth_dt = false; };
 // kind: MXA_FIN_* (include/mxa.h); reads_mask: the kernel reads the selection's prune-mask words (the
 // caller's mask_out, else a workspace copy), not the kept indices; status: MXA_ERR_UNSUPPORTED where the
 // kind has no instantiation for the facts
@@ -178,10 +186,18 @@ inline FinChoice finish_choice(const FinFacts& f) {
     c.status = (xl_rows_ok(f.T, f.k) || (f.nth && xl_rows_nth(f.T, f.k))) && (!f.xdt || ldt) && !f.xo ? MXA_OK : MXA_ERR_UNSUPPORTED;
     return c;
   }
+  // k > 64 at float16 / bfloat16 (MXINT8 P, no proj codes): up to kGxlMaxK kept keys the LDS-slot gather kernel
+  // (mxa_finish_gather_xl.hpp), which reads the kept indices; above it the masked MFMA kernel's XDT form, below
+  if (f.nth_dt && f.xdt && ldt && xl_rows_nth(f.T, f.k) && f.topk && f.k <= kGxlMaxK && f.nbd <= 4) {
+    c.kind = MXA_FIN_GATHER_XL;
+    c.status = MXA_OK;
+    return c;
+  }
   if (f.nth && xl_rows(f.T) && f.topk) {  // k > 64: the masked chunked MFMA kernel (mxa_finish_qk_xl.hpp), float32
     c.kind = MXA_FIN_MFMA_XL;
     c.reads_mask = true;
-    c.status = xl_rows_nth(f.T, f.k) && f.nbd <= 4 && !f.xdt && !f.xo ? MXA_OK : MXA_ERR_UNSUPPORTED;
+    // (float16 / bfloat16: mxa_attention_nth_dt alone)
+    c.status = xl_rows_nth(f.T, f.k) && f.nbd <= 4 && (!f.xdt || (f.nth_dt && ldt)) && !f.xo ? MXA_OK : MXA_ERR_UNSUPPORTED;
     return c;
   }
   if (f.xl_dense && xl_rows(f.T) && !f.topk) {  // the chunked tiled MFMA kernel (mxa_finish_qk_xl.hpp)
@@ -309,6 +325,7 @@ int launch_finish_qk_xl_w4(const Rows2Args& ra, int BH, hipStream_t stream, bool
 int launch_finish_qk_xl_x1(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);  // float16 / bfloat16, MXINT8 P
 int launch_finish_qk_xl_m8(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);  // the masked form (k_top > 64): float32
 int launch_finish_qk_xl_m4(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
+int launch_finish_qk_xl_mx(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);  // ... float16 / bfloat16, MXINT8 P
 // the 16-row finishing kernel (mxa_fin16.hip): float32 (x0), float16 / bfloat16 (x1)
 int launch_finish16_x0(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 int launch_finish16_x1(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
@@ -321,6 +338,8 @@ int launch_finish16_l0xo(const Rows2Args& ra, int BH, hipStream_t stream, bool p
 int launch_finish16_xl_w8(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 int launch_finish16_xl_w4(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 int launch_finish16_xl_x1(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);  // float16 / bfloat16, MXINT8 P
+// the LDS-slot gather kernel of those rows (mxa_fin_gxl.hip): 65 <= k <= 256, float16 / bfloat16, MXINT8 P
+int launch_finish_gather_xl(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 // the 32-row finishing kernel for NB blocks per head dim (mxa_fin.hip parts 1..4)
 int launch_finish32_p1(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 int launch_finish32_p2(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);

@@ -381,7 +381,7 @@ def mx_topk_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: 
                       return_scores: bool = False, out: Optional[torch.Tensor] = None,
                       return_mask: bool = False, elsa_proj: Optional[torch.Tensor] = None,
                       autocast: Optional[torch.dtype] = None, elem_bits: int = 8):
-    """The fused hot path (include/mxa.h mxa_attention_nth): q (B,H,N,D), k/v (B,H,T,D)
+    """The fused hot path (include/mxa.h mxa_attention_nth_dt): q (B,H,N,D), k/v (B,H,T,D)
     float32, float16 or bfloat16 (strided views of a packed qkv are fine; the ops follow
     the tensors' dtype as the reference's do).  autocast: the torch.autocast dtype the
     reference's matmuls would return (scores, P and out in it).  Returns (out (B,H,N,D),
@@ -393,11 +393,11 @@ def mx_topk_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: 
     elem_bits: 8, or 4 -- Q, K, P and V as MXINT4 and every approximator from the MXINT4 codes
     (the reference at a_elem_format = w_elem_format = "int4"; include/mxa.h mxa_attention_bits:
     float32, no autocast, no ELSA -- the library refuses those).
-    One route: mxa_attention_nth takes every call its siblings (mxa_attention, _long, _bits, _full, _xl,
-    _xl_full, _dt) take, on the same kernels; which kernel finishes a call is the library's decision.  Rows of
+    One route: mxa_attention_nth_dt takes every call its siblings (mxa_attention, _long, _bits, _full, _xl,
+    _xl_full, _dt, _nth) take, on the same kernels; which kernel finishes a call is the library's decision.  Rows of
     1,025 .. 4,096 keys: the top-k branch with every 1 <= k_top <= T, and the dense branch (top_k=False).
-    Float16 / bfloat16 tensors and autocast= work at every row length up to 4,096 keys at elem_bits 8, but
-    for k_top > 64 on rows over 1,024 keys (the library refuses the rest)."""
+    Float16 / bfloat16 tensors and autocast= work at every row length up to 4,096 keys and every k_top at
+    elem_bits 8 (the library refuses the rest)."""
     bits = _elem_bits(elem_bits)
     p, dev, (B, H, Nq, T, D), keep = _attn_params(q, k, v, scale, k_top, pred_mode, top_k, approx and top_k, bias,
                                                   flush_subnormals, bfloat, elsa_proj, autocast)
@@ -425,7 +425,7 @@ def mx_topk_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: 
         true_s = torch.empty((B, H, Nq, T), dtype=torch.float32, device=dev)
         pred_s = torch.full((B, H, Nq, T), float("nan"), dtype=torch.float32, device=dev)
         p.true_out, p.pred_out = true_s.data_ptr(), pred_s.data_ptr()
-    _call_with_workspace(lib().mxa_attention_nth_workspace_bytes, lib().mxa_attention_nth, "mxa_attention_nth", p, bits, dev=dev)
+    _call_with_workspace(lib().mxa_attention_nth_dt_workspace_bytes, lib().mxa_attention_nth_dt, "mxa_attention_nth_dt", p, bits, dev=dev)
     return (out, idx) + ((true_s, pred_s) if return_scores else ()) + ((mask,) if return_mask else ())
 
 
