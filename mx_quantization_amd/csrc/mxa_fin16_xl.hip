@@ -26,19 +26,14 @@ constexpr bool kF16XlW4 = MXA_F16XL_W4 != 0;
 constexpr bool kF16XlXdt = MXA_F16XL_XDT != 0;
 static_assert(!(kF16XlW4 && kF16XlXdt), "MXINT4 P: float32 only");
 
-// waves per workgroup by finish_tile_plan (mxa_launch.hpp) from the waves per SIMD the kernel's
-// registers allow
-static int finish16_xl_plan(const Rows2Args& ra, int BH, int regs_waves_per_simd, int* waves, int* rows_per_wg) {
-  auto lds = [&](int w) { return fin16_xl_lds(ra.D, ra.ntb, w).total; };
-  return finish_tile_plan(kFin16, ra.N, BH, lds, finish_wave_cap(regs_waves_per_simd), waves, rows_per_wg);
+// the LDS bytes of a workgroup of w waves
+static auto finish16_xl_lds_of(const Rows2Args& ra) {
+  return [D = ra.D, ntb = ra.ntb](int w) { return fin16_xl_lds(D, ntb, w).total; };
 }
 template <int NB, int KS, bool EXTRA>
-static int launch_finish16_xl_x(const Rows2Args& ra0, int BH, hipStream_t stream) {
-  Rows2Args ra = ra0;
+static int launch_finish16_xl_x(const Rows2Args& ra, int BH, hipStream_t stream) {
   constexpr auto kernel = &finish16_xl_kernel<NB, KS + (kF16XlXdt ? kFin16XlDtKS : 0), EXTRA, kF16XlW4>;
-  const int rc = finish16_xl_plan(ra, BH, kernel_waves_per_simd<kernel>(), &ra.waves, &ra.rows_per_wg);
-  if (rc) return rc;
-  return launch_finish_tiles<kernel>(ra, BH, fin16_xl_lds(ra.D, ra.ntb, ra.waves).total, stream);
+  return launch_finish_waves<kernel>(ra, kFin16, finish16_xl_lds_of(ra), BH, stream);
 }
 template <int NB>
 static int launch_finish16_xl_nb(const Rows2Args& ra, int BH, hipStream_t stream) {
@@ -64,7 +59,7 @@ int MXA_F16XL_FN(const Rows2Args& ra, int BH, hipStream_t stream, bool plan) {
   if (!xl_rows(ra.T) || ra.T > kXlRowsT || ra.k_top < 1 || ra.k_top > 64 || ra.xo_codes || (!kF16XlXdt && (ra.s_dt != kF32 || ra.in_dt != kF32))) return MXA_ERR_UNSUPPORTED;
   if (plan) {
     int w, r;
-    return finish16_xl_plan(ra, BH, 2, &w, &r);
+    return finish_tile_plan(kFin16, ra.N, BH, finish16_xl_lds_of(ra), finish_wave_cap(2), &w, &r);
   }
   return dispatch_nbd(ra.nbd, [&](auto nb) { return launch_finish16_xl_nb<decltype(nb)::value>(ra, BH, stream); });
 }

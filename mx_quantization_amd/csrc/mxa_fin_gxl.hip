@@ -7,32 +7,19 @@ namespace mxa {
 
 static_assert(kGxlMaxK <= kGxlSlots, "finish_choice sends no k past the slot table");
 
-// waves per workgroup by finish_tile_plan (mxa_launch.hpp) from the waves per SIMD the kernel's registers allow
-static int finish_gxl_plan(const Rows2Args& ra, int BH, int regs_waves_per_simd, int* waves, int* rows_per_wg) {
-  auto lds = [&](int w) { return gxl_lds(ra.D, ra.ntb, w).total; };
-  return finish_tile_plan(kFin16, ra.N, BH, lds, finish_wave_cap(regs_waves_per_simd), waves, rows_per_wg);
-}
-template <int NB>
-static int launch_finish_gxl_nb(const Rows2Args& ra0, int BH, hipStream_t stream) {
-  Rows2Args ra = ra0;
-  constexpr auto kernel = &finish_gather_xl_kernel<NB>;
-  const int rc = finish_gxl_plan(ra, BH, kernel_waves_per_simd<kernel>(), &ra.waves, &ra.rows_per_wg);
-  if (rc) return rc;
-  return launch_finish_tiles<kernel>(ra, BH, gxl_lds(ra.D, ra.ntb, ra.waves).total, stream);
-}
-
 int launch_finish_gather_xl(const Rows2Args& ra, int BH, hipStream_t stream, bool plan) {
   // the slot table holds kGxlSlots keys of 15 bits a row; the chunk walk needs whole 32-key blocks of a row of
   // 1,025 .. 4,096 keys.  (The plan pass runs before the dtypes are bound.)
   if (!xl_rows(ra.T) || ra.T > kXlRowsT || ra.k_top < 1 || ra.k_top > kGxlSlots || ra.k_top > ra.T || ra.xo_codes ||
       ra.ntb != (ra.T + 31) / 32 || ra.tpad != 32 * ra.ntb || ra.nbd < 1 || ra.nbd > 4 || ra.D > 32 * ra.nbd || ra.dpad != 32 * ra.nbd)
     return MXA_ERR_UNSUPPORTED;
+  auto lds = [&](int w) { return gxl_lds(ra.D, ra.ntb, w).total; };  // of a workgroup of w waves
   if (plan) {
     int w, r;
-    return finish_gxl_plan(ra, BH, 2, &w, &r);
+    return finish_tile_plan(kFin16, ra.N, BH, lds, finish_wave_cap(2), &w, &r);
   }
   if (ra.s_dt != kF16 && ra.s_dt != kBF16) return MXA_ERR_UNSUPPORTED;  // a slot's value has 16 bits
-  return dispatch_nbd(ra.nbd, [&](auto nb) { return launch_finish_gxl_nb<decltype(nb)::value>(ra, BH, stream); });
+  return dispatch_nbd(ra.nbd, [&](auto nb) { return launch_finish_waves<&finish_gather_xl_kernel<decltype(nb)::value>>(ra, kFin16, lds, BH, stream); });
 }
 
 }  // namespace mxa

@@ -39,26 +39,23 @@ constexpr bool kFqxlXdt = MXA_FQXL_XDT != 0;
 constexpr bool kFqxlMask = MXA_FQXL_MASK != 0;
 static_assert(!(kFqxlW4 && kFqxlXdt), "MXINT4 P: float32 only");
 
-// the LDS of a workgroup is one chunk's tables whatever T and the number of waves are; the waves per
-// workgroup come from finish_tile_plan by the waves per SIMD the instantiation's registers allow
-static int finish_qk_xl_plan(const Rows2Args& ra, int BH, int regs_waves_per_simd, int* waves, int* rows_per_wg) {
-  const size_t lds = fql_lds(ra.nbd, ra.D).total;
-  return finish_tile_plan(kFqRows, ra.N, BH, [lds](int) { return lds; }, finish_wave_cap(regs_waves_per_simd), waves, rows_per_wg);
-}
-template <int NB, bool EXTRA>
-static int launch_finish_qk_xl_x(const Rows2Args& ra0, int BH, hipStream_t stream) {
-  Rows2Args ra = ra0;
-  constexpr auto kernel = &finish_qk_xl_kernel<NB + (kFqxlXdt ? kFqDtNB : 0) + (kFqxlMask ? kFqXlMaskNB : 0), kFqxlW4, EXTRA>;
-  const int rc = finish_qk_xl_plan(ra, BH, kernel_waves_per_simd<kernel>(), &ra.waves, &ra.rows_per_wg);
+// One instantiation planned by finish_mfma_plan from its own registers (lds: one chunk's tables, fql_lds, whatever T
+// and the number of waves are), then launched.  The kernel's barriers need whole tiles of whole waves: 1 .. 8 waves,
+// a workgroup's rows a multiple of the tile.  finish_tile_plan gives nothing else; the test is a guard on that
+template <auto Kernel>
+static int launch_finish_qk_xl(Rows2Args ra, size_t lds, int BH, hipStream_t stream) {
+  const int rc = finish_mfma_plan(ra, kFqRows, lds, BH, kernel_waves_per_simd<Kernel>(), &ra.waves, &ra.rows_per_wg);
   if (rc) return rc;
-  // the kernel's barriers need whole tiles of whole waves: 1 .. 8 waves, a workgroup's rows a multiple of the tile
   if (ra.waves < 1 || ra.waves > 8 || ra.rows_per_wg <= 0 || ra.rows_per_wg % kFqRows) return MXA_ERR_LAUNCH;
-  return launch_finish_tiles<kernel>(ra, BH, fql_lds(NB, ra.D).total, stream);
+  return launch_finish_tiles<Kernel>(ra, BH, lds, stream);
 }
 template <int NB>
 static int launch_finish_qk_xl_nb(const Rows2Args& ra, int BH, hipStream_t stream) {
   if (ra.dpad != 32 * NB) return MXA_ERR_ARG;
-  return finish_mfma_extra(ra) ? launch_finish_qk_xl_x<NB, true>(ra, BH, stream) : launch_finish_qk_xl_x<NB, false>(ra, BH, stream);
+  const size_t lds = fql_lds(NB, ra.D).total;
+  constexpr int NBX = NB + (kFqxlXdt ? kFqDtNB : 0) + (kFqxlMask ? kFqXlMaskNB : 0);
+  if (finish_mfma_extra(ra)) return launch_finish_qk_xl<&finish_qk_xl_kernel<NBX, kFqxlW4, true>>(ra, lds, BH, stream);
+  return launch_finish_qk_xl<&finish_qk_xl_kernel<NBX, kFqxlW4, false>>(ra, lds, BH, stream);
 }
 
 int MXA_FQXL_FN(const Rows2Args& ra, int BH, hipStream_t stream, bool plan) {
@@ -71,7 +68,7 @@ int MXA_FQXL_FN(const Rows2Args& ra, int BH, hipStream_t stream, bool plan) {
     return MXA_ERR_UNSUPPORTED;
   if (plan) {
     int w, r;
-    return finish_qk_xl_plan(ra, BH, 2, &w, &r);
+    return finish_mfma_plan(ra, kFqRows, fql_lds(ra.nbd, ra.D).total, BH, 2, &w, &r);
   }
   return dispatch_nbd(ra.nbd, [&](auto nb) { return launch_finish_qk_xl_nb<decltype(nb)::value>(ra, BH, stream); });
 }

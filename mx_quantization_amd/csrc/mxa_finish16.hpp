@@ -73,6 +73,21 @@ __host__ __device__ inline Fin16Lds fin16_lds(int T, int D, int kst, int nbd, in
   return L;
 }
 
+// max / sum over the four lanes of a tile row (a quad): finish16_kernel, finish16_xl_kernel (mxa_finish16_xl.hpp) and
+// finish_gather_xl_kernel (mxa_finish_gather_xl.hpp)
+__device__ __forceinline__ float fin16_qmax(float x) {
+  uint32_t u = __float_as_uint(x);
+  auto op = [](uint32_t p, uint32_t q) { return __float_as_uint(fmaxf(__uint_as_float(p), __uint_as_float(q))); };
+  u = op(u, dpp_u32<0xB1>(u));
+  return __uint_as_float(op(u, dpp_u32<0x4E>(u)));
+}
+__device__ __forceinline__ float fin16_qsum(float x) {
+  uint32_t u = __float_as_uint(x);
+  auto op = [](uint32_t p, uint32_t q) { return __float_as_uint(__uint_as_float(p) + __uint_as_float(q)); };
+  u = op(u, dpp_u32<0xB1>(u));
+  return __uint_as_float(op(u, dpp_u32<0x4E>(u)));
+}
+
 // NB: 32-blocks per head dim; KS: kept slots per lane (k <= 4 KS); XDT: float16 / bfloat16
 // inputs or scores (the dtype roundings at run time); EXTRA: a bias, the debug true-score
 // output or bfloatX rounding (else the scores and P are plain float32); XO: the output rows
@@ -190,19 +205,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NB <= 2 && 
       v[t] = on[t] ? s : -INFINITY;
       mx = fmaxf(mx, v[t]);
     }
-    auto qmax = [](float x) {
-      uint32_t u = __float_as_uint(x);
-      auto op = [](uint32_t p, uint32_t q) { return __float_as_uint(fmaxf(__uint_as_float(p), __uint_as_float(q))); };
-      u = op(u, dpp_u32<0xB1>(u));
-      return __uint_as_float(op(u, dpp_u32<0x4E>(u)));
-    };
-    auto qsum = [](float x) {
-      uint32_t u = __float_as_uint(x);
-      auto op = [](uint32_t p, uint32_t q) { return __float_as_uint(__uint_as_float(p) + __uint_as_float(q)); };
-      u = op(u, dpp_u32<0xB1>(u));
-      return __uint_as_float(op(u, dpp_u32<0x4E>(u)));
-    };
-    mx = qmax(mx);
+    mx = fin16_qmax(mx);
     // exp(v - mx) as 2^((v - mx) log2 e) (the difference first: folding mx log2 e into an
     // fma loses the argument for large scores); an unused slot adds 0 (also where mx = -inf)
     float sum = 0.0f;
@@ -211,7 +214,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NB <= 2 && 
       v[t] = on[t] ? __builtin_amdgcn_exp2f((v[t] - mx) * 1.4426950408889634f) : 0.0f;
       sum += v[t];
     }
-    sum = qsum(sum);
+    sum = fin16_qsum(sum);
     const float rs = 1.0f / sum;
 #pragma unroll
     for (int t = 0; t < KS; ++t) {

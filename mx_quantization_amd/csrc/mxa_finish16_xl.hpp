@@ -144,26 +144,14 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(NB <= 2 && 
       v[t] = on[t] ? s : -INFINITY;
       mx = fmaxf(mx, v[t]);
     }
-    auto qmax = [](float x) {
-      uint32_t u = __float_as_uint(x);
-      auto op = [](uint32_t p, uint32_t q) { return __float_as_uint(fmaxf(__uint_as_float(p), __uint_as_float(q))); };
-      u = op(u, dpp_u32<0xB1>(u));
-      return __uint_as_float(op(u, dpp_u32<0x4E>(u)));
-    };
-    auto qsum = [](float x) {
-      uint32_t u = __float_as_uint(x);
-      auto op = [](uint32_t p, uint32_t q) { return __float_as_uint(__uint_as_float(p) + __uint_as_float(q)); };
-      u = op(u, dpp_u32<0xB1>(u));
-      return __uint_as_float(op(u, dpp_u32<0x4E>(u)));
-    };
-    mx = qmax(mx);
+    mx = fin16_qmax(mx);
     float sum = 0.0f;
 #pragma unroll
     for (int t = 0; t < KS; ++t) {
       v[t] = on[t] ? __builtin_amdgcn_exp2f((v[t] - mx) * 1.4426950408889634f) : 0.0f;
       sum += v[t];
     }
-    sum = qsum(sum);
+    sum = fin16_qsum(sum);
     const float rs = 1.0f / sum;
 #pragma unroll
     for (int t = 0; t < KS; ++t) {

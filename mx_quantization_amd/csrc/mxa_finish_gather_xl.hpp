@@ -136,19 +136,7 @@ __global__ __launch_bounds__(512) void finish_gather_xl_kernel(Rows2Args a) {
         }
       }
     }
-    auto qmax = [](float x) {
-      uint32_t u = __float_as_uint(x);
-      auto op = [](uint32_t p, uint32_t q) { return __float_as_uint(fmaxf(__uint_as_float(p), __uint_as_float(q))); };
-      u = op(u, dpp_u32<0xB1>(u));
-      return __uint_as_float(op(u, dpp_u32<0x4E>(u)));
-    };
-    auto qsum = [](float x) {
-      uint32_t u = __float_as_uint(x);
-      auto op = [](uint32_t p, uint32_t q) { return __float_as_uint(__uint_as_float(p) + __uint_as_float(q)); };
-      u = op(u, dpp_u32<0xB1>(u));
-      return __uint_as_float(op(u, dpp_u32<0x4E>(u)));
-    };
-    mx = qmax(mx);
+    mx = fin16_qmax(mx);
     // ---- pass 2: the sum, per lane in ascending slot order, then over the row's four lanes -----
     auto exp_of = [&](uint32_t w) { return __builtin_amdgcn_exp2f((gxl_value(w, sdt) - mx) * 1.4426950408889634f); };
     float sum = 0.0f;
@@ -156,7 +144,7 @@ __global__ __launch_bounds__(512) void finish_gather_xl_kernel(Rows2Args a) {
       const uint32_t w = slot[4 * t];
       sum += w & kGxlOff ? 0.0f : exp_of(w);
     }
-    sum = qsum(sum);
+    sum = fin16_qsum(sum);
     const float rs = 1.0f / sum;
 
     float acc[NDT][4];

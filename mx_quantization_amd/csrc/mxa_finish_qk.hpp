@@ -135,10 +135,10 @@ __device__ __forceinline__ float fq_exact(const int* I, const int* e) {
 // A part takes the fields of Rows2Args it needs by value, as the shared rules of mxa_finish.hpp do:
 // with a reference to the kernel's argument struct the spill counts of float16 / bfloat16
 // instantiations at the 128-VGPR cap rise.
-// Two steps stay written out in both kernels, because the register allocation of instantiations at
-// the 128-VGPR cap moved upward with them as functions (profiles/r12_fq_parts_resources.txt): the P
-// block coding (fq_umax4, p_block, the eight packed codes) and the output store.  Both kernels must
-// keep them the same text.
+// The P block coding (fq_umax4, p_block, the eight packed codes) stays written out in every kernel, and the
+// output store in finish_qk_kernel (the kernels of rows over 512 keys call fq_store_tile): as functions they
+// moved the register allocation of instantiations at the VGPR caps upward (profiles/r12_fq_parts_resources.txt,
+// profiles/r14_long_row_shared_steps_checks.txt).  The copies must keep the same text.
 
 // The exact epilogue's per-key terms of the head's keys [0, tpad): the K exponents tke [NB][KES]
 // (int16, key order) and tkx [3][KES] (the key's smallest block exponent, its blocks' offsets from
@@ -296,6 +296,22 @@ __device__ __forceinline__ void fq_pv_mfma(int64_t va, int64_t pc, float sP, con
   acc[1] = fmaf((float)c[1], sP * sv.y, acc[1]);
   acc[2] = fmaf((float)c[2], sP * sv.z, acc[2]);
   acc[3] = fmaf((float)c[3], sP * sv.w, acc[3]);
+}
+
+// The dense branch's kept bits of keys 32 blk + 8 g .. + 7: every key < T
+__device__ __forceinline__ uint32_t fq_dense_bits(int T, int blk, int g) { return (1u << min(max(T - (32 * blk + 8 * g), 0), 8)) - 1u; }
+
+// The tile's output row of the lane (element ob of out: its row's first), columns 16 u + 4 g + i < D from the
+// accumulators, rounded to the score dtype and bfloatX
+template <int NDT>
+__device__ __forceinline__ void fq_store_tile(void* out, int64_t ob, int D, int g, int bfloat, int sdt, const float (*acc)[4]) {
+#pragma unroll
+  for (int u = 0; u < NDT; ++u)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int dd = 16 * u + 4 * g + i;
+      if (dd < D) store_dt(out, ob + dd, round_bfloat(round_dt(acc[u][i], sdt), bfloat, kRoundNearest, 1, sdt), sdt);
+    }
 }
 
 // NB: 32-element blocks per head dim; NTB: key blocks the registers hold (T <= 32 NTB);

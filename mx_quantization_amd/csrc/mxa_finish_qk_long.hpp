@@ -57,6 +57,19 @@ __host__ __device__ inline FqlLds fql_lds(int nb, int D) {
   return L;
 }
 
+// ---- steps finish_qk_long_kernel and its chunked form finish_qk_xl_kernel (mxa_finish_qk_xl.hpp) share ----------
+// key tile `tile`'s A operands of lane (q, g) (row fq_key_of_row(16 tile + q) of the row's keys); a key >= T -- a
+// ragged last block, or a tile past the row -- reads nothing and gives zero codes
+template <int NB>
+__device__ __forceinline__ void fql_load_k(const int8_t* kc, int64_t kb, int T, int tile, int q, int g, int64_t* ka) {
+  const int akey = fq_key_of_row(16 * tile + q);
+#pragma unroll
+  for (int b = 0; b < NB; ++b) {
+    ka[b] = 0;
+    if (akey < T) ka[b] = *reinterpret_cast<const int64_t*>(kc + (kb + akey) * (32 * NB) + 32 * b + 8 * g);
+  }
+}
+
 // MXA_FQL_OCC: a tools-only build that asks the register allocator for that many waves per SIMD, for
 // same-box A/Bs (build_native defines); the product leaves the choice to the compiler
 #ifdef MXA_FQL_OCC
@@ -114,19 +127,10 @@ __global__ __launch_bounds__(512) MXA_FQL_ATTR void finish_qk_long_kernel(Rows2A
     // the row's kept bits of keys 32 blk + 8 g .. + 7 (the dense branch: every key < T)
     auto kept_bits = [&](int blk) -> uint32_t {
       if (!valid || blk >= ntb) return 0u;
-      if (a.dense) return (1u << min(max(T - (32 * blk + 8 * g), 0), 8)) - 1u;
+      if (a.dense) return fq_dense_bits(T, blk, g);
       return (a.mask_out[grow * ntw + blk] >> (8 * g)) & 0xFFu;
     };
-    // key tile `tile`'s A operands of this lane (row fq_key_of_row(16 tile + q)); a key >= T -- a
-    // ragged last block, or a tile past the row -- reads nothing and gives zero codes
-    auto load_k = [&](int tile, int64_t* ka) {
-      const int akey = fq_key_of_row(16 * tile + q);
-#pragma unroll
-      for (int b = 0; b < NB; ++b) {
-        ka[b] = 0;
-        if (akey < T) ka[b] = *reinterpret_cast<const int64_t*>(a.kc + (kb + akey) * (32 * NB) + 32 * b + 8 * g);
-      }
-    };
+    auto load_k = [&](int tile, int64_t* ka) { fql_load_k<NB>(a.kc, kb, T, tile, q, g, ka); };
     // the scores of the lane's keys 32 blk + 8 g + 4 t + i (i = 0..3) of key tile 2 blk + t from
     // its A operands ka, a dropped key -inf; first: the pass that writes the debug true scores
     auto scores = [&](int blk, int t, const int64_t* ka, uint32_t kbits, bool first, float* sv) {
@@ -259,16 +263,7 @@ __global__ __launch_bounds__(512) MXA_FQL_ATTR void finish_qk_long_kernel(Rows2A
         if (16 * u < D) fq_pv_mfma(va[u], pc, sP, tvs + (u * kFqlNTB + blk) * 16 + 4 * g, acc[u]);
     });
     // ---- the tile's output rows -------------------------------------------------------------
-    if (valid) {
-      const int64_t ob = b_ * a.os0 + h_ * a.os1 + (int64_t)r * a.os2;
-#pragma unroll
-      for (int u = 0; u < NDT; ++u)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int dd = 16 * u + 4 * g + i;
-          if (dd < D) store_dt(a.out, ob + dd, round_bfloat(round_dt(acc[u][i], sdt), a.bfloat, kRoundNearest, 1, sdt), sdt);
-        }
-    }
+    if (valid) fq_store_tile<NDT>(a.out, b_ * a.os0 + h_ * a.os1 + (int64_t)r * a.os2, D, g, a.bfloat, sdt, acc);
   }
 }
 

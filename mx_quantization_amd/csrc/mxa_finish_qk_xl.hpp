@@ -110,17 +110,9 @@ __global__ __launch_bounds__(512) void finish_qk_xl_kernel(Rows2Args a) {
     auto kept_bits = [&](int blk) -> uint32_t {
       if (!valid || blk >= ntb) return 0u;
       if constexpr (MASKED) return (a.mask_out[grow * ntb + blk] >> (8 * g)) & 0xFFu;
-      return (1u << min(max(T - (32 * blk + 8 * g), 0), 8)) - 1u;
+      return fq_dense_bits(T, blk, g);
     };
-    // key tile `tile`'s (of the row) A operands of this lane; a key >= T reads nothing and gives zero codes
-    auto load_k = [&](int tile, int64_t* ka) {
-      const int akey = fq_key_of_row(16 * tile + q);
-#pragma unroll
-      for (int b = 0; b < NB; ++b) {
-        ka[b] = 0;
-        if (akey < T) ka[b] = *reinterpret_cast<const int64_t*>(a.kc + (kb + akey) * (32 * NB) + 32 * b + 8 * g);
-      }
-    };
+    auto load_k = [&](int tile, int64_t* ka) { fql_load_k<NB>(a.kc, kb, T, tile, q, g, ka); };
     // the scores of the lane's keys 32 blk + 8 g + 4 t + i (i = 0..3) from key tile 2 blk + t's A
     // operands, a dropped key -inf; blk: the block's number in the row, cb: its chunk's first block
     auto scores = [&](int blk, int cb, int t, const int64_t* ka, uint32_t kbits, bool first, float* sv) {
@@ -257,16 +249,7 @@ __global__ __launch_bounds__(512) void finish_qk_xl_kernel(Rows2Args a) {
         if (16 * u < D) fq_pv_mfma(va[u], pc, sP, tvs + (u * kFqlNTB + (blk - cb)) * 16 + 4 * g, acc[u]);
     });
     // ---- the tile's output rows -------------------------------------------------------------
-    if (valid) {
-      const int64_t ob = b_ * a.os0 + h_ * a.os1 + (int64_t)r * a.os2;
-#pragma unroll
-      for (int u = 0; u < NDT; ++u)
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int dd = 16 * u + 4 * g + i;
-          if (dd < D) store_dt(a.out, ob + dd, round_bfloat(round_dt(acc[u][i], sdt), a.bfloat, kRoundNearest, 1, sdt), sdt);
-        }
-    }
+    if (valid) fq_store_tile<NDT>(a.out, b_ * a.os0 + h_ * a.os1 + (int64_t)r * a.os2, D, g, a.bfloat, sdt, acc);
   }
 }
 

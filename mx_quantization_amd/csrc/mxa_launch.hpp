@@ -284,8 +284,15 @@ inline int launch_finish_tiles(const Rows2Args& ra, int BH, size_t lds, hipStrea
   hipLaunchKernelGGL(Kernel, dim3((unsigned)BH, gy), dim3(64 * ra.waves), lds, stream, ra);
   return launch_status();
 }
+// one instantiation whose LDS grows with its waves (lds(w) bytes for a workgroup of w waves: mxa_fin16_xl.hip,
+// mxa_fin_gxl.hip), planned by its own registers, then launched
+template <auto Kernel, class LdsFn>
+inline int launch_finish_waves(Rows2Args ra, int tile_rows, LdsFn lds, int BH, hipStream_t stream) {
+  const int rc = finish_tile_plan(tile_rows, ra.N, BH, lds, finish_wave_cap(kernel_waves_per_simd<Kernel>()), &ra.waves, &ra.rows_per_wg);
+  return rc ? rc : launch_finish_tiles<Kernel>(ra, BH, lds(ra.waves), stream);
+}
 
-// ---- what the two MFMA finishing kernels' launches share (mxa_fin_qk.hip, mxa_fin_qkl.hip) ----
+// ---- what the MFMA finishing kernels' launches share (mxa_fin_qk.hip, mxa_fin_qkl.hip, mxa_fin_qkxl.hip) ----
 // their plan: tiles of tile_rows query rows, lds bytes of LDS per workgroup and none per wave
 inline int finish_mfma_plan(const Rows2Args& ra, int tile_rows, size_t lds, int BH, int regs_waves_per_simd, int* waves,
                             int* rows_per_wg) {
