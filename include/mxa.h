@@ -168,6 +168,16 @@ int mxa_topk_xl_nth(const void* vals, int64_t rows, int32_t n, int64_t ld, int32
                     int64_t* out_idx, void* out_vals, uint32_t* out_mask, int32_t dtype, hipStream_t stream);
 
 /*
+ * mxa_topk_xl_nth plus rows of 4,097 .. 16,384 values with 1 <= k <= 64 and k * 64 <= n (PixArt-Sigma's 2K
+ * rows: 16,384 keys at k = 20), where torch takes std::partial_sort: mxa_topk_xl's heap fed chunk by chunk
+ * from a 4 KB strip of order keys per wave (the selection body of mxa_attention_xxl), so no LDS area grows
+ * with n.  The same arguments, dtypes and outputs.  Every call mxa_topk_xl_nth accepts runs what that runs
+ * (n <= 4,096).  MXA_ERR_UNSUPPORTED: n > 16,384, and with n > 4,096 k == 0, k > 64 or k * 64 > n.
+ */
+int mxa_topk_xxl(const void* vals, int64_t rows, int32_t n, int64_t ld, int32_t k,
+                 int64_t* out_idx, void* out_vals, uint32_t* out_mask, int32_t dtype, hipStream_t stream);
+
+/*
  * mxa_topk with a device workspace (the same results): rows of <= 256 values go through
  * the packed 32-bit selection pass and the one-lane tail (the fused op's selection
  * engine), which stage per-row state in the workspace.  mxa_topk_workspace_bytes:
@@ -442,6 +452,28 @@ int mxa_attention_nth_dt(const mxa_attn_params* p, int32_t elem_bits, hipStream_
 int mxa_attention_nth_dt_finish_kernel(const mxa_attn_params* p, int32_t elem_bits);
 
 /*
+ * mxa_attention_nth_dt plus the top-k branch on rows of 4,097 .. 16,384 keys: PixArt-Sigma's 2K checkpoint
+ * runs self-attention on 128 x 128 = 16,384 latent tokens at D = 72 and self_k = 20
+ * (workloads/PixArt/models/MX_transformer_block.py:648-717).  The same parameter struct, strides, outputs
+ * and workspace rules.
+ *   - every call mxa_attention_nth_dt(p, elem_bits) accepts runs exactly what that runs: the same kernels,
+ *     bytes, statuses and workspace size;
+ *   - with 4,096 < T <= 16,384, top_k != 0, 1 <= k_top <= 64 and k_top * 64 <= T (torch's partial_sort
+ *     regime), float32 tensors and scores, elem_bits 8 and 4, a bias, the scores and the prune mask as on
+ *     shorter rows, every pred_mode but MXA_PRED_ELSA and approx == 0: select_xxl_kernel (the streaming
+ *     heap of mxa_attention_xl fed from a per-wave strip of one 1,024-key chunk, every key-side table read
+ *     through L2), then finish16_xxl_kernel (finish16_xl_kernel's tiles with V's block scales staged per
+ *     chunk, double-buffered: no LDS table grows with T).
+ * MXA_ERR_UNSUPPORTED, before any HIP call, with T > 4,096: top_k == 0, k_top > 64, k_top * 64 > T, float16
+ * / bfloat16 tensors or a nonzero score_dtype, MXA_PRED_ELSA, T > 16,384.  No scores-only or
+ * fused-projection form.  mxa_attention_xxl_finish_kernel: the MXA_FIN_* kind of the call (no launch; the
+ * workspace may be null) -- MXA_FIN_GATHER16_XXL on those rows.
+ */
+int64_t mxa_attention_xxl_workspace_bytes(const mxa_attn_params* p, int32_t elem_bits);
+int mxa_attention_xxl(const mxa_attn_params* p, int32_t elem_bits, hipStream_t stream);
+int mxa_attention_xxl_finish_kernel(const mxa_attn_params* p, int32_t elem_bits);
+
+/*
  * Which kernels mxa_attention(p) runs (no launch; the workspace may be null):
  *   MXA_PATH_ROWS_SPLIT  selection kernel (scores + top-k) then finishing kernel
  *                        (gather, softmax, MX(P), P.V on int8 MFMA) -- top_k != 0
@@ -475,8 +507,11 @@ int mxa_attention_path(const mxa_attn_params* p);
  *   MXA_FIN_GATHER_XL        finish_gather_xl_kernel: top-k with 65 <= k <= 256 on rows over 1,024 keys at
  *                            float16 / bfloat16: kept-key QK^T on v_dot4 (the slots in LDS), P.V on
  *                            v_mfma_i32_16x16x32_i8
+ * and by mxa_attention_xxl_finish_kernel for mxa_attention_xxl alone:
+ *   MXA_FIN_GATHER16_XXL     finish16_xxl_kernel: top-k with k <= 64 on rows over 4,096 keys
  * or a negative MXA_ERR_* for invalid parameters.
  */
+#define MXA_FIN_GATHER16_XXL 12
 #define MXA_FIN_GATHER_XL 11
 #define MXA_FIN_MFMA_XL 10
 #define MXA_FIN_DENSE_MFMA_XL 9

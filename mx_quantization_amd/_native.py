@@ -45,6 +45,8 @@ FIN_KERNELS_NTH = {10: ("finish_qk_xl_kernel (masked)", "v_mfma_i32_16x16x32_i8 
                         "v_mfma_i32_16x16x32_i8")}
 # mxa_attention_nth_dt_finish_kernel reports this one besides: float16 / bfloat16 with 65 <= k_top <= 256 on those rows
 FIN_KERNELS_NTH_DT = {11: ("finish_gather_xl_kernel", "v_dot4 (kept keys, slots in LDS)", "v_mfma_i32_16x16x32_i8")}
+# mxa_attention_xxl_finish_kernel reports this one besides: top-k on rows of 4,097 .. 16,384 keys
+FIN_KERNELS_XXL = {12: ("finish16_xxl_kernel", "v_dot4 (kept keys)", "v_mfma_i32_16x16x32_i8")}
 PRED_MODES = {"ex_pred": 0, "partial_Q": 1, "partial_K": 2, "MXINT4": 3, "two_step_leading_ones": 4,
               "true_ex": 5, "ELSA": 6}
 ROUND_MODES = {"nearest": 0, "floor": 1, "even": 2}
@@ -122,6 +124,10 @@ _SIGS = {
     "mxa_attention_nth_dt_workspace_bytes": (c_i64, [c_vp, c_i32]),
     "mxa_attention_nth_dt": (c_i32, [c_vp, c_i32, c_vp]),
     "mxa_attention_nth_dt_finish_kernel": (c_i32, [c_vp, c_i32]),
+    "mxa_topk_xxl": (c_i32, [c_vp, c_i64, c_i32, c_i64, c_i32, c_vp, c_vp, c_vp, c_i32, c_vp]),
+    "mxa_attention_xxl_workspace_bytes": (c_i64, [c_vp, c_i32]),
+    "mxa_attention_xxl": (c_i32, [c_vp, c_i32, c_vp]),
+    "mxa_attention_xxl_finish_kernel": (c_i32, [c_vp, c_i32]),
     "mxa_attention_xl_workspace_bytes": (c_i64, [c_vp, c_i32]),
     "mxa_attention_xl": (c_i32, [c_vp, c_i32, c_vp]),
     "mxa_attention_xl_finish_kernel": (c_i32, [c_vp, c_i32]),

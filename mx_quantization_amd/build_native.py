@@ -46,6 +46,11 @@ UNITS += [("mxa_fin_qkxl.hip", f"_m{8 - 4 * i}", ("MXA_FQXL_MASK=1", f"MXA_FQXL_
 # ... and there k_top > 64 at float16 / bfloat16 (mxa_attention_nth_dt): the LDS-slot gather kernel (k_top <= 256) and
 # the masked 16-bit form of the chunked MFMA kernel
 UNITS += [("mxa_fin_gxl.hip", "", ()), ("mxa_fin_qkxl.hip", "_mx", ("MXA_FQXL_MASK=1", "MXA_FQXL_XDT=1"))]
+# rows of 4,097 .. 16,384 keys (mxa_attention_xxl, mxa_topk_xxl): the chunk-fed streaming selection (the dispatcher +
+# mxa_topk_xxl, then one score mode each: MXA_SELXX_PART) and the 16-row finishing kernel with V's block scales staged
+# per chunk, at either P width (MXA_F16XXL_W4)
+UNITS += [("mxa_sel_xxl.hip", "", ("MXA_SELXX_PART=0",))] + [("mxa_sel_xxl.hip", f"_p{i}", (f"MXA_SELXX_PART={i}",)) for i in range(1, 6)]
+UNITS += [("mxa_fin16_xxl.hip", f"_w{8 - 4 * i}", (f"MXA_F16XXL_W4={i}",)) for i in range(2)]
 UNITS += [("mxa_proj.hip", "", ()), ("mxa_gemm.hip", "", ())]
 UNITS += [("mxa_proj4.hip", "", ())]  # the fused projections' MXINT4 kernels
 # the MLP's fc1 (the digit kernel's body with the GELU + quantizing epilogue) in a unit of its own
@@ -61,13 +66,14 @@ UNITS += [("mxa_fin_qkxl.hip", f"_w{8 - 4 * i}", (f"MXA_FQXL_W4={i}",)) for i in
 # (v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32); the older units keep the command lines their
 # measured code objects were built with
 NO_PK_F32 = ("-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops")
-UNIT_FLAGS = {"mxa_fin_qkxl.hip": NO_PK_F32, "mxa_sel_xl_nth.hip": NO_PK_F32, "mxa_fin_gxl.hip": NO_PK_F32}
+UNIT_FLAGS = {"mxa_fin_qkxl.hip": NO_PK_F32, "mxa_sel_xl_nth.hip": NO_PK_F32, "mxa_fin_gxl.hip": NO_PK_F32,
+              "mxa_sel_xxl.hip": NO_PK_F32, "mxa_fin16_xxl.hip": NO_PK_F32}
 # ... and so are the float16 / bfloat16 units of the other three long-row kernels (by source and suffix: the
 # float32 units of those sources are older)
 UNIT_FLAGS.update({(src, "_" + sfx): NO_PK_F32 for src, sfx in (("mxa_fin16.hip", "l1"), ("mxa_fin16_xl.hip", "x1"), ("mxa_fin_qkl.hip", "x1"))})
 SOURCES = sorted({u[0] for u in UNITS})
 HEADERS = ["mxa_common.hpp", "mxa_kernels.hpp", "mxa_prep.hpp", "mxa_proj.hpp", "mxa_proj_launch.hpp", "mxa_proj_args.hpp", "mxa_gemm_parts.hpp", "mxa_finish.hpp",
-           "mxa_order.hpp", "mxa_topk_grp.hpp", "mxa_topk_wave.hpp", "mxa_finish16.hpp", "mxa_finish_qk.hpp", "mxa_finish_qk_long.hpp", "mxa_finish_qk_xl.hpp", "mxa_tail.hpp", "mxa_gemm.hpp", "mxa_dot.hpp", "mxa_select.hpp", "mxa_select_long.hpp", "mxa_select_xl.hpp", "mxa_select_xl_nth.hpp", "mxa_topk_wave_xl.hpp", "mxa_finish16_xl.hpp", "mxa_finish_gather_xl.hpp", "mxa_rows2.hpp", "mxa_modes.hpp", "mxa_launch.hpp", "mxa_act.hpp", "mxa_mlp.hpp",
+           "mxa_order.hpp", "mxa_topk_grp.hpp", "mxa_topk_wave.hpp", "mxa_finish16.hpp", "mxa_finish_qk.hpp", "mxa_finish_qk_long.hpp", "mxa_finish_qk_xl.hpp", "mxa_tail.hpp", "mxa_gemm.hpp", "mxa_dot.hpp", "mxa_select.hpp", "mxa_select_long.hpp", "mxa_select_xl.hpp", "mxa_select_xl_nth.hpp", "mxa_topk_wave_xl.hpp", "mxa_finish16_xl.hpp", "mxa_finish_gather_xl.hpp", "mxa_select_xxl.hpp", "mxa_finish16_xxl.hpp", "mxa_rows2.hpp", "mxa_modes.hpp", "mxa_launch.hpp", "mxa_act.hpp", "mxa_mlp.hpp",
            "../../include/mxa.h"]
 ARCH = os.environ.get("MXA_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

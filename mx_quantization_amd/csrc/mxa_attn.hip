@@ -10,6 +10,10 @@
 //                               mxa_attention_xl on rows of 1,025 .. 4,096 keys (top-k, k * 64 <= T): the
 //                               streaming heap selection (mxa_select_xl.hpp), then the keys in chunks of 1,024
 //                               (mxa_finish16_xl.hpp)
+//   select_xxl_kernel / finish16_xxl_kernel
+//                               mxa_attention_xxl on rows of 4,097 .. 16,384 keys (top-k, k * 64 <= T): the same heap
+//                               fed chunk by chunk from a 4 KB strip (mxa_select_xxl.hpp), then the 16-row kernel with
+//                               V's block scales staged per chunk (mxa_finish16_xxl.hpp)
 //   select_long_kernel          rows of 513 .. 1,024 keys (mxa_attention_long): one wave per query
 //                               row, the scores into the wave top-k's mirror (mxa_select_long.hpp);
 //                               finish16_kernel then reads the kept keys from the workspace
@@ -122,8 +126,10 @@ ModeNeeds mode_needs(int mode) {
 // (mxa_attention_dt): kReachXlFull's calls plus, on rows over 512 keys, float16 / bfloat16 tensors and scores;
 // kReachNth (mxa_attention_nth): kReachDt's calls plus, on rows of 1,025 .. kXlRowsT keys, the top-k branch
 // with every k_top outside partial_sort's regime (xl_rows_nth); kReachNthDt (mxa_attention_nth_dt): kReachNth's
-// calls plus, on those rows, k_top > 64 with float16 / bfloat16 tensors or scores
-enum Reach { kReachShort, kReachLong, kReachFull, kReachBlock, kReachXl, kReachXlFull, kReachDt, kReachNth, kReachNthDt };
+// calls plus, on those rows, k_top > 64 with float16 / bfloat16 tensors or scores; kReachXxl (mxa_attention_xxl):
+// kReachNthDt's calls plus the float32 top-k branch in partial_sort's regime on rows of 4,097 .. kXxlRowsT keys
+// (xxl_rows_ok)
+enum Reach { kReachShort, kReachLong, kReachFull, kReachBlock, kReachXl, kReachXlFull, kReachDt, kReachNth, kReachNthDt, kReachXxl };
 
 // the proj Linear's input comes MX-quantized out of the finishing kernel (MXINT8 only: at 4 bits the
 // fp32 rows go through the workspace and the row quantizer for every D; rows over 512 keys: from the LONG
@@ -157,7 +163,8 @@ struct AttnCall {
 FinFacts attn_fin_facts(const AttnCall& c, const mxa_attn_params* p) {
   return {p->top_k != 0, p->top_k ? p->k_top : 0, p->T, (p->D + 31) / 32, c.pj && proj_codes_direct(p, c.elem_bits, c.reach),
           p->dtype != MXA_DT_F32 || p->score_dtype > MXA_DT_F32, c.elem_bits, c.reach >= kReachFull, c.reach == kReachBlock,
-          c.reach >= kReachXl, c.reach >= kReachXlFull, c.reach >= kReachDt, c.reach >= kReachNth, c.reach >= kReachNthDt};
+          c.reach >= kReachXl, c.reach >= kReachXlFull, c.reach >= kReachDt, c.reach >= kReachNth, c.reach >= kReachNthDt,
+          c.reach >= kReachXxl};
 }
 
 // one side's (Q's or K's) row operands; null: the score mode does not read it
@@ -284,7 +291,8 @@ int attn_validate(const AttnCall& c) {
       (p->pred_mode == MXA_PRED_EXION || p->pred_mode == MXA_PRED_TRUE_EX || p->pred_mode == MXA_PRED_ELSA))
     return MXA_ERR_UNSUPPORTED;
   if (!valid_bfloat(p->bfloat)) return MXA_ERR_ARG;
-  if (p->T > (reach == kReachShort ? kShortRowsT : reach >= kReachXl ? kXlRowsT : kLongRowsT) || p->D > 32 * kMaxNB)
+  if (p->T > (reach == kReachShort ? kShortRowsT : reach >= kReachXxl ? kXxlRowsT : reach >= kReachXl ? kXlRowsT : kLongRowsT) ||
+      p->D > 32 * kMaxNB)
     return MXA_ERR_UNSUPPORTED;
   // rows over 1,024 keys: the top-k branch in partial_sort's regime alone (kReachNth: every k_top), and for
   // kReachXlFull the dense branch (the rest of their refusals -- 16-bit dtypes, the fused projections -- are the
@@ -295,6 +303,9 @@ int attn_validate(const AttnCall& c) {
   // rows over 512 keys: float32 (but for kReachDt), no fused projection but kReachBlock's qkv and proj Linears;
   // MXINT4: float32, and the approximators of exponent_approximation (ELSA's hashes would need the width too)
   const bool xdt = p->dtype != MXA_DT_F32 || p->score_dtype > MXA_DT_F32;
+  // rows over 4,096 keys (kReachXxl alone passed the bound): the float32 top-k branch in partial_sort's regime and
+  // nothing else -- not the dense branch, another k_top, a 16-bit dtype or a fused projection
+  if (xxl_rows(p->T) && (!p->top_k || !xxl_rows_ok(p->T, p->k_top) || xdt || xq || xc || pj)) return MXA_ERR_UNSUPPORTED;
   if ((long_rows(p->T) && (xc || ((xq || pj) && reach != kReachBlock) || (xdt && reach < kReachDt))) || (elem_bits == 4 && xdt))
     return MXA_ERR_UNSUPPORTED;
   if (elem_bits == 4 && p->approx && p->pred_mode == MXA_PRED_ELSA) return MXA_ERR_UNSUPPORTED;
@@ -591,6 +602,7 @@ int attention_impl(const AttnCall& c) {
   // feasibility of the path's kernels (LDS budgets), before any pointer is bound
   // (rows over 512 keys: the one-wave-per-row selection kernel, mxa_select_long.hpp)
   auto select = [&](bool plan, const SideLane* side = nullptr) {
+    if (xxl_rows(pp.T)) return launch_select_xxl(r2, mode, BH, c.stream, plan);  // (mxa_select_xxl.hpp)
     if (xl_rows(pp.T) && !xl_rows_ok(pp.T, pp.k_top)) return launch_select_xl_nth(r2, mode, BH, c.stream, plan);  // (mxa_select_xl_nth.hpp)
     if (xl_rows(pp.T)) return launch_select_xl(r2, mode, BH, c.stream, plan);  // (mxa_select_xl.hpp)
     return long_rows(pp.T) ? launch_select_long(r2, mode, BH, c.stream, plan) : launch_select(r2, mode, BH, c.stream, plan, side);
@@ -831,6 +843,23 @@ extern "C" int mxa_attention_nth_dt(const mxa_attn_params* p, int32_t elem_bits,
 extern "C" int mxa_attention_nth_dt_finish_kernel(const mxa_attn_params* p, int32_t elem_bits) {
   int plan = -1, fin = -1;
   const int rc = attention_impl({.p = p, .reach = kReachNthDt, .plan = &plan, .fin = &fin, .elem_bits = elem_bits});
+  return rc ? rc : fin;
+}
+
+// mxa_attention_nth_dt plus the top-k branch on rows of 4,097 .. 16,384 keys with k_top <= 64 and k_top * 64 <= T,
+// float32 (MX_transformer_block.py:648-717 on PixArt-Sigma's 2K checkpoint: 128 x 128 latent tokens, self_k = 20):
+// select_xxl_kernel, finish16_xxl_kernel
+extern "C" int64_t mxa_attention_xxl_workspace_bytes(const mxa_attn_params* p, int32_t elem_bits) {
+  return mx_width_ok(elem_bits) && attn_shape_ok(p) ? attn_workspace_total({.p = p, .reach = kReachXxl}) : -1;
+}
+
+extern "C" int mxa_attention_xxl(const mxa_attn_params* p, int32_t elem_bits, hipStream_t stream) {
+  return attention_impl({.p = p, .stream = stream, .reach = kReachXxl, .elem_bits = elem_bits});
+}
+
+extern "C" int mxa_attention_xxl_finish_kernel(const mxa_attn_params* p, int32_t elem_bits) {
+  int plan = -1, fin = -1;
+  const int rc = attention_impl({.p = p, .reach = kReachXxl, .plan = &plan, .fin = &fin, .elem_bits = elem_bits});
   return rc ? rc : fin;
 }
 

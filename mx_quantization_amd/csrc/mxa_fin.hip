@@ -1,7 +1,7 @@
 // Row-kernel launches.  launch_rows switches once on the kind finish_choice (mxa_launch.hpp)
 // gives for the call and hands over to that kernel's launcher: the MFMA finishing kernels
 // (mxa_fin_qk.hip, mxa_fin_qkl.hip, mxa_fin_qkxl.hip), the 16-row gather kernels (mxa_fin16.hip, mxa_fin16_xl.hip,
-// mxa_fin_gxl.hip), and the two
+// mxa_fin16_xxl.hip, mxa_fin_gxl.hip), and the two
 // launched from this file: the 32-row gather kernel (mxa_finish.hpp) and the dense branch's
 // v_dot4 row kernel (mxa_rows2.hpp).
 #include "mxa_finish.hpp"
@@ -133,6 +133,8 @@ int launch_rows(const Rows2Args& ra0, const FinFacts& f, bool true_mode, int S, 
       return w4 ? launch_finish_qk_xl_m4(ra, BH, stream, plan) : launch_finish_qk_xl_m8(ra, BH, stream, plan);
     case MXA_FIN_GATHER_XL:  // (finish_choice: float16 / bfloat16, MXINT8)
       return launch_finish_gather_xl(ra, BH, stream, plan);
+    case MXA_FIN_GATHER16_XXL:  // (finish_choice: float32)
+      return w4 ? launch_finish16_xxl_w4(ra, BH, stream, plan) : launch_finish16_xxl_w8(ra, BH, stream, plan);
     case MXA_FIN_GATHER16_XL:
       if (f.xdt) return launch_finish16_xl_x1(ra, BH, stream, plan);
       return w4 ? launch_finish16_xl_w4(ra, BH, stream, plan) : launch_finish16_xl_w8(ra, BH, stream, plan);

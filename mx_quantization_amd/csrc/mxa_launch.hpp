@@ -87,6 +87,12 @@ inline bool xl_rows_ok(int T, int k) { return xl_rows(T) && T <= kXlRowsT && k >
 // torch takes std::nth_element + std::sort -- the chunked wave top-k (mxa_select_xl_nth.hpp), then the same
 // 16-row kernel (k <= 64) or the masked form of the chunked MFMA kernel (k > 64, mxa_finish_qk_xl.hpp)
 inline bool xl_rows_nth(int T, int k) { return xl_rows(T) && T <= kXlRowsT && k >= 1 && k <= T && !xl_rows_ok(T, k); }
+// rows of 4,097 .. 16,384 keys (mxa_attention_xxl, mxa_topk_xxl; PixArt-Sigma's 2K checkpoint: 128 x 128 latent
+// tokens): the top-k branch in partial_sort's regime alone -- the selection that walks the row in chunks of 1,024
+// keys (mxa_select_xxl.hpp) and the 16-row finishing kernel whose LDS does not grow with T (mxa_finish16_xxl.hpp)
+constexpr int kXxlRowsT = 16384;
+inline bool xxl_rows(int T) { return T > kXlRowsT; }
+inline bool xxl_rows_ok(int T, int k) { return xxl_rows(T) && T <= kXxlRowsT && k >= 1 && k <= 64 && (int64_t)k * 64 <= T; }
 // The side lane of a forked attention call (mxa_attn.hip, SideFork): the library's own stream beside the
 // caller's, joined before the finishing kernel.  `packed`: the event launch_select records behind the
 // packed pass
@@ -102,6 +108,8 @@ int launch_select_long(const Rows2Args& ra, int mode, int BH, hipStream_t stream
 int launch_select_xl(const Rows2Args& ra, int mode, int BH, hipStream_t stream, bool plan);
 // ... outside partial_sort's regime (mxa_sel_xl_nth.hip)
 int launch_select_xl_nth(const Rows2Args& ra, int mode, int BH, hipStream_t stream, bool plan);
+// ... for rows of 4,097 .. 16,384 keys (mxa_sel_xxl.hip)
+int launch_select_xxl(const Rows2Args& ra, int mode, int BH, hipStream_t stream, bool plan);
 // the one-lane tail's prefix (measured, DeiT-base: 48 positions 0.575-0.583 ms against 0.585-0.599
 // for 64 -- 12 KB of LDS per wave, 3 waves per SIMD instead of 2, outweighs the selection kernel's
 // extra step -- and 0.573-0.584 for 56; a 32-position prefix is slower: the selection kernel then
@@ -170,8 +178,8 @@ constexpr int kGxlMaxK = MXA_GXL_MAXK;
 // xl_dense: on those rows the dense branch too (mxa_attention_xl_full); dt: on rows over 512 keys float16 /
 // bfloat16 tensors or scores too, at MXINT8 (mxa_attention_dt); nth: on rows of 1,025 .. 4,096 keys every k_top
 // outside partial_sort's regime too (mxa_attention_nth); nth_dt: there k_top > 64 at float16 / bfloat16 too
-// (mxa_attention_nth_dt)
-struct FinFacts { bool topk; int k, T, nbd; bool xo, xdt; int bits; bool full; bool block = false; bool xl = false; bool xl_dense = false; bool dt = false; bool nth = false; bool nth_dt = false; };
+// (mxa_attention_nth_dt); xxl: it reaches the top-k branch on rows of 4,097 .. 16,384 keys (mxa_attention_xxl)
+struct FinFacts { bool topk; int k, T, nbd; bool xo, xdt; int bits; bool full; bool block = false; bool xl = false; bool xl_dense = false; bool dt = false; bool nth = false; bool nth_dt = false; bool xxl = false; };
 // kind: MXA_FIN_* (include/mxa.h); reads_mask: the kernel reads the selection's prune-mask words (the
 // caller's mask_out, else a workspace copy), not the kept indices; status: MXA_ERR_UNSUPPORTED where the
 // kind has no instantiation for the facts
@@ -181,6 +189,11 @@ inline FinChoice finish_choice(const FinFacts& f) {
   // float16 / bfloat16 on rows over 512 keys: the XDT forms of the long rows' four kernels, MXINT8 P, no proj codes
   const bool ldt = f.dt && !w4 && !f.xo;
   FinChoice c{};
+  if (f.xxl && f.topk && xxl_rows_ok(f.T, f.k)) {  // rows of 4,097 .. 16,384 keys (mxa_finish16_xxl.hpp): float32,
+    c.kind = MXA_FIN_GATHER16_XXL;                  // no proj codes; every other call on such rows is refused below
+    c.status = !f.xdt && !f.xo ? MXA_OK : MXA_ERR_UNSUPPORTED;
+    return c;
+  }
   if (f.xl && xl_rows(f.T) && f.topk && f.k <= 64) {  // the chunked 16-row kernel (mxa_finish16_xl.hpp):
     c.kind = MXA_FIN_GATHER16_XL;                      // top-k in partial_sort's regime
     c.status = (xl_rows_ok(f.T, f.k) || (f.nth && xl_rows_nth(f.T, f.k))) && (!f.xdt || ldt) && !f.xo ? MXA_OK : MXA_ERR_UNSUPPORTED;
@@ -347,6 +360,10 @@ int launch_finish16_xl_w4(const Rows2Args& ra, int BH, hipStream_t stream, bool 
 int launch_finish16_xl_x1(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);  // float16 / bfloat16, MXINT8 P
 // the LDS-slot gather kernel of those rows (mxa_fin_gxl.hip): 65 <= k <= 256, float16 / bfloat16, MXINT8 P
 int launch_finish_gather_xl(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
+// the chunked 16-row kernel's sibling for rows of 4,097 .. 16,384 keys, whose V block scales are staged per
+// chunk (mxa_fin16_xxl.hip): float32, MXINT8 / MXINT4 P
+int launch_finish16_xxl_w8(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
+int launch_finish16_xxl_w4(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 // the 32-row finishing kernel for NB blocks per head dim (mxa_fin.hip parts 1..4)
 int launch_finish32_p1(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);
 int launch_finish32_p2(const Rows2Args& ra, int BH, hipStream_t stream, bool plan);

@@ -16,8 +16,9 @@ the given modules to `TORCH`: a namespace that forwards every attribute to torch
 
 Covered: device tensors of float32 / float16 / bfloat16, the last dim, largest=True,
 sorted=True (the only form the modules use), up to 4,096 columns and every k (include/mxa.h
-mxa_topk_xl_nth: the PixArt 1024x1024 self-attention rows; longer rows raise NativeError,
-MXA_ERR_UNSUPPORTED).  Other forms (largest=False,
+mxa_topk_xl_nth: the PixArt 1024x1024 self-attention rows), and 4,097..16,384 columns with k <= 64 and
+k * 64 <= n (mxa_topk_xxl: the 2K checkpoint's rows); anything longer, or another k there, raises NativeError
+(MXA_ERR_UNSUPPORTED).  Other forms (largest=False,
 sorted=False, another dim, CPU tensors) are torch's own topk, unchanged.
 """
 from __future__ import annotations

@@ -166,7 +166,9 @@ def topk(vals: torch.Tensor, k: int, return_mask: bool = False, packed: bool = T
     pack) packed=False runs the 64-bit pass alone: DeiT-base-sized random rows 0.79 ms
     against 1.05 ms through the packed attempt (profiles/r06v1_ab_topk_fp32.txt).
     Rows of 1,025 .. 4,096 values: mxa_topk_xl_nth -- the streaming heap selection where torch takes
-    std::partial_sort (k <= 64, k * 64 <= n), the chunked one-wave-per-row introselect for every other k."""
+    std::partial_sort (k <= 64, k * 64 <= n), the chunked one-wave-per-row introselect for every other k.
+    Rows of 4,097 .. 16,384 values: mxa_topk_xxl -- that heap fed chunk by chunk, in partial_sort's regime alone
+    (the library refuses every other k there, and longer rows)."""
     dev = require_device(vals)
     dt = _dt(vals, "vals")
     vals = vals.contiguous()
@@ -179,9 +181,10 @@ def topk(vals: torch.Tensor, k: int, return_mask: bool = False, packed: bool = T
         # the workspace path (rows of <= 256 values: the fused op's packed selection pass
         # and one-lane tail); 0 bytes: mxa_topk alone
         mp = mask.data_ptr() if return_mask else None
-        if n > 1024:  # include/mxa.h mxa_topk_xl_nth
-            check(lib().mxa_topk_xl_nth(vals.data_ptr(), rows, n, n, k, idx.data_ptr(), out.data_ptr(), mp, dt,
-                                        stream_ptr(dev)), "mxa_topk_xl_nth")
+        if n > 1024:  # include/mxa.h mxa_topk_xl_nth; rows over 4,096 values: mxa_topk_xxl
+            name = "mxa_topk_xxl" if n > 4096 else "mxa_topk_xl_nth"
+            check(getattr(lib(), name)(vals.data_ptr(), rows, n, n, k, idx.data_ptr(), out.data_ptr(), mp, dt,
+                                       stream_ptr(dev)), name)
             return (out, idx, mask) if return_mask else (out, idx)
         if not packed:  # the 64-bit pass alone
             check(lib().mxa_topk(vals.data_ptr(), rows, n, n, k, idx.data_ptr(), out.data_ptr(), mp, dt,
@@ -381,7 +384,7 @@ def mx_topk_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: 
                       return_scores: bool = False, out: Optional[torch.Tensor] = None,
                       return_mask: bool = False, elsa_proj: Optional[torch.Tensor] = None,
                       autocast: Optional[torch.dtype] = None, elem_bits: int = 8):
-    """The fused hot path (include/mxa.h mxa_attention_nth_dt): q (B,H,N,D), k/v (B,H,T,D)
+    """The fused hot path (include/mxa.h mxa_attention_xxl): q (B,H,N,D), k/v (B,H,T,D)
     float32, float16 or bfloat16 (strided views of a packed qkv are fine; the ops follow
     the tensors' dtype as the reference's do).  autocast: the torch.autocast dtype the
     reference's matmuls would return (scores, P and out in it).  Returns (out (B,H,N,D),
@@ -393,11 +396,12 @@ def mx_topk_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: 
     elem_bits: 8, or 4 -- Q, K, P and V as MXINT4 and every approximator from the MXINT4 codes
     (the reference at a_elem_format = w_elem_format = "int4"; include/mxa.h mxa_attention_bits:
     float32, no autocast, no ELSA -- the library refuses those).
-    One route: mxa_attention_nth_dt takes every call its siblings (mxa_attention, _long, _bits, _full, _xl,
-    _xl_full, _dt, _nth) take, on the same kernels; which kernel finishes a call is the library's decision.  Rows of
-    1,025 .. 4,096 keys: the top-k branch with every 1 <= k_top <= T, and the dense branch (top_k=False).
+    One route: mxa_attention_xxl takes every call its siblings (mxa_attention, _long, _bits, _full, _xl,
+    _xl_full, _dt, _nth, _nth_dt) take, on the same kernels; which kernel finishes a call is the library's decision.
+    Rows of 1,025 .. 4,096 keys: the top-k branch with every 1 <= k_top <= T, and the dense branch (top_k=False).
     Float16 / bfloat16 tensors and autocast= work at every row length up to 4,096 keys and every k_top at
-    elem_bits 8 (the library refuses the rest)."""
+    elem_bits 8 (the library refuses the rest).  Rows of 4,097 .. 16,384 keys (PixArt-Sigma's 2K checkpoint): the
+    float32 top-k branch with k_top <= 64 and k_top * 64 <= T, at either width; everything else there is refused."""
     bits = _elem_bits(elem_bits)
     p, dev, (B, H, Nq, T, D), keep = _attn_params(q, k, v, scale, k_top, pred_mode, top_k, approx and top_k, bias,
                                                   flush_subnormals, bfloat, elsa_proj, autocast)
@@ -425,7 +429,7 @@ def mx_topk_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, scale: 
         true_s = torch.empty((B, H, Nq, T), dtype=torch.float32, device=dev)
         pred_s = torch.full((B, H, Nq, T), float("nan"), dtype=torch.float32, device=dev)
         p.true_out, p.pred_out = true_s.data_ptr(), pred_s.data_ptr()
-    _call_with_workspace(lib().mxa_attention_nth_dt_workspace_bytes, lib().mxa_attention_nth_dt, "mxa_attention_nth_dt", p, bits, dev=dev)
+    _call_with_workspace(lib().mxa_attention_xxl_workspace_bytes, lib().mxa_attention_xxl, "mxa_attention_xxl", p, bits, dev=dev)
     return (out, idx) + ((true_s, pred_s) if return_scores else ()) + ((mask,) if return_mask else ())
 
 
